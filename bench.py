@@ -15,8 +15,14 @@ Per-GPU work is fixed (weak scaling): the batch is cut on shape boundaries and t
 the scorer responses over RCCL (the batch-mean score of nets/model.py:146 couples the shapes of a
 batch).  --exchange allgather (default; the form BASELINE.json north_star names) also all-gathers the
 final view descriptors so every rank pools all shapes; --exchange scores stops at the scorer
-responses and every rank pools the shapes it owns.  With --other-exchange (always over gloo) an N > 1
-line times BOTH and reports the other one under "other_exchange".
+responses and every rank pools the shapes it owns.  With --other-exchange (with --full, always over gloo) an
+N > 1 line times BOTH and reports the other one under "other_exchange".
+
+A plain run does only what the headline figure needs: set up, tune the tiles in-process, warm up, time
+--steps steps, print the line.  --full adds everything else the line can carry: the per-launch roofline
+and its rocprofv3 traffic children, the exact-fp32-MFMA twin, the CPU baseline, the training line's
+family rooflines and, N > 1, the other exchange / gather / overlap forms.  --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy (float32; rank 0's arrays).
 
 Prints ONE JSON line on rank 0.
 """
@@ -70,7 +76,8 @@ def parse():
     ap.add_argument("--no-other-exchange", action="store_true", help="N > 1: time only --exchange")
     ap.add_argument("--other-exchange", action="store_true",
                     help="N > 1 over RCCL: also time the other exchange form and the other gather mode (extra timed loops after "
-                         "the one the line's `value` comes from; always on over gloo, where the control flow is what is tested)")
+                         "the one the line's `value` comes from; with --full always on over gloo, where the control flow is what "
+                         "is tested)")
     ap.add_argument("--gather", default="collective", choices=["collective", "direct"],
                     help="N > 1: how a gather travels — 'collective' = RCCL all_gather_into_tensor (the library picks ring / "
                          "tree), 'direct' = one point-to-point send to and receive from EVERY peer (each xGMI link carries "
@@ -113,7 +120,14 @@ def parse():
     ap.add_argument("--storage", default=None, choices=["f32", "bf16", "f16"],
                     help="activation/filter storage type (default: the preset's own: c2 f32 = the bench line, "
                          "c3/c4 bf16, c5 f16; forward only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (+ rocprofv3 traffic children), "
+                         "exact-fp32-MFMA twin, CPU baseline, training family rooflines, N > 1 other exchange forms")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, rank 0, <= 64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.storage is None:
         a.storage = PRESET_STORAGE[a.preset]
     if a.storage != "f32":
@@ -259,6 +273,24 @@ def cpu_baseline(P, Hd, seconds):
                       "configs[0] as written (2 shapes x 6 views), each reference-shaped (V sequential backbone calls at "
                       "batch 2 + grouping head) and folded (one backbone call); %.1f s of CPU time in all"
                       % (BACKBONE, H, W, V, time.time() - t_all)}
+
+
+DUMP_BYTES = 64 << 20                           # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every named tensor as <path>/<name>.npy, float32 (float64 stays float64).  A tensor larger than
+    its share of DUMP_BYTES is written as a fixed sample of its flattened form: the sorted, de-duplicated draws of
+    numpy.random.RandomState(0).randint(0, size, share // itemsize), the same elements on every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.unique(np.random.RandomState(0).randint(0, a.size, share // a.itemsize))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -527,11 +559,15 @@ def train_main(a, world, rank, dev, traffic=None):
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        sh.train_step(x, labels, lr=1e-6)
+        loss = sh.train_step(x, labels, lr=1e-6)
     barrier()
     dt = time.perf_counter() - t0
     if a.pmc_child:
         return
+    if a.dump_outputs and rank == 0:
+        # the step's loss and logits, and the parameters it updated (all of them, in name order, flattened)
+        dump_outputs(a.dump_outputs, {"loss": loss, "logits": eng.logits, "params": torch.cat(
+            [eng.params[k].reshape(-1).float() for k in sorted(eng.params)])})
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -542,7 +578,7 @@ def train_main(a, world, rank, dev, traffic=None):
         ms = dt / a.steps * 1e3
         flops = 3.0 * sum(op.get("flops", 0) for op in eng.plan.ops) * world
         roof = {}
-        if world == 1 and not a.no_roofline:
+        if world == 1 and a.full and not a.no_roofline:
             roof = {"roofline": train_roofline(eng, x, labels, a.storage, traffic)}
         print(json.dumps({**{
             "metric": "views/sec (training step)", "value": round(views_per_step / (ms * 1e-3), 1), "unit": "views/s",
@@ -578,7 +614,7 @@ def main():
     # N = 1: tile tuning and the HBM-traffic PMC passes run as CHILDREN before this process touches the GPU
     traffic = None
     tmp_tiles = None
-    want_traffic = (world == 1 and not a.pmc_child and not a.train and not a.no_roofline and not a.no_traffic
+    want_traffic = (world == 1 and a.full and not a.pmc_child and not a.train and not a.no_roofline and not a.no_traffic
                     and not a.graph)
     if want_traffic:
         if not (a.tile_cache and os.path.exists(a.tile_cache)):
@@ -600,7 +636,7 @@ def main():
         else:
             traffic = {"note": "traffic not measured: no tile table from the tuning child"}
 
-    if world == 1 and a.train and not a.pmc_child and not a.no_roofline and not a.no_traffic:
+    if world == 1 and a.train and a.full and not a.pmc_child and not a.no_roofline and not a.no_traffic:
         traffic = measure_traffic_train(a)                  # (children; this process has not touched the GPU yet)
 
     assert torch.cuda.is_available(), "bench.py needs a HIP device"
@@ -666,7 +702,8 @@ def main():
         return
 
     def timed(step):
-        """W untimed steps, then exactly K steps between two barrier + synchronize pairs; MAX over the ranks."""
+        """W untimed steps, then exactly K steps between two barrier + synchronize pairs; MAX over the ranks.
+        Returns (seconds, what the last timed step returned)."""
         for _ in range(a.warmup):
             step()
         if getattr(step, "flush", None):
@@ -674,16 +711,16 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step()
+            out = step()
         if getattr(step, "flush", None):
-            step.flush()                                    # the overlapped exchange's last head belongs to the timed steps
+            out = step.flush()                              # the overlapped exchange's last head belongs to the timed steps
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return dt, out
 
     def step():
         return sh.forward(x, check=False)
@@ -692,16 +729,18 @@ def main():
     if a.graph:
         assert world == 1, "--graph is a single-GPU option"
         step = eng.capture(x)
-    dt = timed(step)
+    dt, last = timed(step)
     eng.check_status()
     if a.pmc_child:
         return
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(zip(("scores", "shape_descriptor", "logits"), last)))
     other = other_g = None
     # (the driver's scaling run gets the ONE measurement it asks for: nothing after it can cost it the line)
-    if world > 1 and not a.no_other_exchange and (a.other_exchange or a.backend == "gloo"):
+    if world > 1 and not a.no_other_exchange and (a.other_exchange or (a.full and a.backend == "gloo")):
         name = "scores" if a.exchange == "allgather" else "allgather"
         sh2 = ShardedGVCNN(eng, exchange=name, gather_mode=a.gather)
-        dt2 = timed(lambda: sh2.forward(x, check=False))
+        dt2, _ = timed(lambda: sh2.forward(x, check=False))
         other = (name, dt2)
         if a.exchange == "allgather":                       # the same exchange, the other way of moving it
             gname = "direct" if a.gather == "collective" else "collective"
@@ -709,7 +748,7 @@ def main():
             step3 = lambda: sh3.forward(x, check=False)     # noqa: E731
             if sh3.overlap:
                 step3.flush = sh3.flush
-            other_g = (gname, timed(step3))
+            other_g = (gname, timed(step3)[0])
 
     # what every rank ran on / with (gathered outside the timed region)
     rank_facts = None
@@ -722,12 +761,12 @@ def main():
                 "tile_table": hashlib.sha1(json.dumps(tiles).encode()).hexdigest()[:12]}
         rank_facts = [None] * world
         dist.all_gather_object(rank_facts, mine)
-        if sh.overlap and not a.no_other_exchange:
+        if sh.overlap and not a.no_other_exchange and (a.full or a.other_exchange):
             # the same exchange with call-by-call semantics (every forward returns its own result): the 1 -> N ratio can be
             # read on either; a failure here must not cost the line above
             try:
                 sh_cc = ShardedGVCNN(eng, exchange=a.exchange, overlap=False, gather_mode=a.gather)
-                other_ov = timed(lambda: sh_cc.forward(x, check=False))
+                other_ov = timed(lambda: sh_cc.forward(x, check=False))[0]
             except Exception as e:                          # noqa: BLE001
                 other_ov = None
                 sys.stderr.write("bench.py: call-by-call re-run failed: %r\n" % (e,))
@@ -789,7 +828,7 @@ def main():
                                        "unit": "views/s", "ms_per_step": round(ms3, 3)}
         step_tflops = eng.plan.total_flops / (ms * 1e-3) / 1e12
         out["step_tflops_per_gpu"] = round(step_tflops, 2)
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             out["roofline"] = roofline(eng, x.view(N * V, H, W, 3), a.math, traffic=traffic)
         out["config"]["math"] = a.math + ": " + MATH[a.math][2]
         out["config"]["branch_lanes"] = eng.plan.lanes_used if not a.no_lanes else 1
@@ -800,7 +839,7 @@ def main():
             out["config"]["tiles"] = ("measured per launch: warm repeats shortlist four, timed in sequence the launch keeps "
                                       "the fastest (%d launches left their warm-repeat choice)" % eng.plan.autotune_moved)
 
-        if world == 1 and a.math != "f32" and not a.no_exact:
+        if world == 1 and a.full and a.math != "f32" and not a.no_exact:
             # the same step on the exact fp32 MFMA path, for reference (short run, same inputs)
             e32 = gv.GVCNN(BACKBONE, N, V, H, W, C, G, device=dev, num_bins=G, math="f32", lanes=not a.no_lanes)
             e32.plan.bind(P)
@@ -821,7 +860,7 @@ def main():
                                      "roofline_frac": r32["frac"], "achieved_tflops": r32["achieved"],
                                      "max_rel_diff_shape_descriptor_vs_default_math": dS}
             del e32
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(P, Hd, a.cpu_seconds)
     if world > 1:
         dist.barrier()

@@ -53,3 +53,25 @@ def test_launcher_command_is_the_contract_form(monkeypatch):
     assert cmd[cmd.index("--nproc-per-node") + 1] == "4" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "4", "--steps", "3"] and cmd[-5].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_dump_outputs_float32_within_budget_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: 16-bit tensors widen to float32, float64 stays, small tensors are written whole, and a tensor
+    over its share of the byte budget becomes the same seeded sample of its elements on every call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("gv_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4096)
+    big = torch.arange(10000, dtype=torch.float32)
+    arrays = {"small": torch.tensor([[1.5, -2.0]], dtype=torch.bfloat16), "wide": torch.ones(3, dtype=torch.float64),
+              "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    small, wide = np.load(str(tmp_path / "a" / "small.npy")), np.load(str(tmp_path / "a" / "wide.npy"))
+    assert small.dtype == np.float32 and small.tolist() == [[1.5, -2.0]]
+    assert wide.dtype == np.float64 and wide.tolist() == [1.0, 1.0, 1.0]
+    s1, s2 = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert s1.dtype == np.float32 and 0 < s1.nbytes <= 4096 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and set(s1.tolist()) <= set(big.tolist())     # distinct elements, in order

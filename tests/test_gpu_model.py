@@ -264,7 +264,7 @@ def test_bench_two_rank_control_flow_on_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--same-device", "--steps", "2", "--warmup", "1", "--shapes", "2", "--no-roofline"]
+           "--same-device", "--steps", "2", "--warmup", "1", "--shapes", "2", "--no-roofline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -293,7 +293,7 @@ def test_bench_eight_rank_control_flow_of_the_8gpu_configs(preset, V, hw, esz):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     # c4 with the tile tuning the driver's run has (ONE tuning, by rank 0, its table broadcast); c5 with default tiles
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--same-device", "--preset",
-           preset, "--steps", "1", "--warmup", "1", "--shapes", "4", "--no-roofline", "--no-lanes"] + \
+           preset, "--steps", "1", "--warmup", "1", "--shapes", "4", "--no-roofline", "--no-lanes", "--full"] + \
           ([] if preset == "c4" else ["--no-tune"])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -495,7 +495,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--shapes", "2",
-                          "--cpu-seconds", "2"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -513,6 +513,35 @@ def test_bench_line_contract():
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     c = j["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0 and isinstance(c["sample"], str)
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline figure only, over exactly --steps timed steps, and --dump-outputs
+    writes what the last timed step returned: scores, shape descriptor and logits of the bench's own seeded batch,
+    float32, equal (1e-3) to the same forward run here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--shapes", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"] == "views/sec" and j["unit"] == "views/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["steps"] == 3 and j["warmup"] == 1 and abs(j["value"] - 2 * 12 / (j["ms_per_step"] * 1e-3)) < 0.01 * j["value"]
+    assert not {"roofline", "exact_f32_mfma", "cpu_baseline"} & set(j)
+    got = {n: np.load(os.path.join(str(tmp_path), n + ".npy")) for n in ("scores", "shape_descriptor", "logits")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    eng, _, _ = make_engine("inception_v3", 2, 12, 224, 224, 10, 7, num_bins=7, math="bf16x3")
+    scores, S, logits = eng.forward(views(2, 12, 224, 224).to(DEV))
+    torch.cuda.synchronize()
+    assert got["shape_descriptor"].shape == tuple(S.shape) and got["logits"].shape == tuple(logits.shape)
+    assert_close(got["scores"], scores.cpu().numpy())
+    assert_close(got["shape_descriptor"], S.cpu().numpy())
+    assert_close(got["logits"], logits.cpu().numpy())
 
 
 def test_roofline_timing_is_in_sequence_and_the_training_line_has_a_roofline():
@@ -533,7 +562,7 @@ def test_roofline_timing_is_in_sequence_and_the_training_line_has_a_roofline():
     assert 0.5 * whole <= sum(each) <= 3.0 * whole + 1.0, (sum(each), whole)     # (event pairs add a little per op)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--train", "--preset", "c3", "--steps", "2",
-                          "--warmup", "1", "--shapes", "2", "--no-traffic"], capture_output=True, text=True, timeout=900,
+                          "--warmup", "1", "--shapes", "2", "--no-traffic", "--full"], capture_output=True, text=True, timeout=900,
                          cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])

@@ -11,7 +11,7 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 bash $R/tools/profile_round.sh $TAG > $O/profile_round.log 2>&1
 cd $R
-python3 bench.py --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
+python3 bench.py --full --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
 python3 tools/step_times.py --tune > $O/step_times_train_c3_bf16.txt 2>&1
 python3 tools/step_times.py --tune --backbone resnet_v2_50 > $O/step_times_train_c4_bf16.txt 2>&1
 python3 tools/seq_vs_warm.py --preset c3 > $O/seq_vs_warm_c3.txt 2>&1

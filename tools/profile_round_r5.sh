@@ -12,8 +12,8 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 bash $R/tools/profile_round.sh $TAG > $O/profile_round.log 2>&1
 cd $R
-python3 bench.py --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
-bash tools/ws_bench_ab.sh "c2 c3 c5 c4" > $O/ws_plan_ab.txt 2>&1
+python3 bench.py --full --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
+OUT=$O/ab bash tools/ws_bench_ab.sh "c2 c3 c5 c4" > $O/ws_plan_ab.txt 2>&1
 python3 tools/seq_vs_warm.py --preset c3 > $O/seq_vs_warm_c3.txt 2>&1
 python3 tools/seq_vs_warm.py --preset c5 > $O/seq_vs_warm_c5.txt 2>&1
 python3 tools/ws_probe.py bf16 both > $O/ws_probe.txt 2>&1

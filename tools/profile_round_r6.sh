@@ -17,14 +17,14 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 bash $R/tools/profile_round.sh $TAG > $O/profile_round.log 2>&1
 cd $R
-python3 bench.py --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
+python3 bench.py --full --train --preset c4 > $O/bench_train_c4_bf16.json 2>> $O/bench.err
 {
 for mode in separate chain units_everywhere default; do
   unset GV_NO_CHAIN GV_NO_UNIT GV_UNIT_ALL
   [ $mode = separate ] && export GV_NO_CHAIN=1
   [ $mode = chain ] && export GV_NO_UNIT=1
   [ $mode = units_everywhere ] && export GV_UNIT_ALL=1
-  python3 bench.py --preset c4 --no-cpu-baseline --no-traffic --no-exact > $O/ab_c4_$mode.json 2> $O/ab_c4_$mode.err
+  python3 bench.py --full --preset c4 --no-cpu-baseline --no-traffic --no-exact > $O/ab_c4_$mode.json 2> $O/ab_c4_$mode.err
   python3 - <<PY
 import json
 d=json.loads(open("$O/ab_c4_$mode.json").read().strip().splitlines()[-1])
@@ -47,8 +47,8 @@ bash tools/pmc_bench.sh gpurun_out/pmc_${TAG}_c2 > /dev/null 2>&1
 bash tools/pmc_bench.sh gpurun_out/pmc_${TAG}_c4 --preset c4 > /dev/null 2>&1
 python3 tools/traffic_per_launch.py gpurun_out/pmc_${TAG}_c2 --preset c2 --trace $O/kt/kt_kernel_trace.csv > $O/traffic_per_launch_c2.txt 2>&1
 python3 tools/traffic_per_launch.py gpurun_out/pmc_${TAG}_c4 --preset c4 > $O/traffic_per_launch_c4.txt 2>&1
-bash tools/r6_poolact.sh > $O/pool_act_ab.log 2>&1; cp gpurun_out/r6/pool_act_ab.txt $O/pool_act_ab.txt
-bash tools/r6_proj.sh > $O/proj_ab.log 2>&1; cp gpurun_out/r6/proj_ab.txt $O/proj_ab.txt
+OUT=$O/r6 bash tools/r6_poolact.sh > $O/pool_act_ab.log 2>&1; cp $O/r6/pool_act_ab.txt $O/pool_act_ab.txt
+OUT=$O/r6 bash tools/r6_proj.sh > $O/proj_ab.log 2>&1; cp $O/r6/proj_ab.txt $O/proj_ab.txt
 [ -x gvcnn-tf_amd/build/fetch_calib ] && bash tools/r6_calib.sh calib-only > $O/fetch_calib.log 2>&1 && cp gpurun_out/r6/fetch_calib.txt $O/fetch_calib.txt
 python3 tools/step_times.py --backbone resnet_v2_50 --tune > $O/step_times_train_c4_bf16.txt 2>&1
 python3 tools/step_times.py --tune > $O/step_times_train_c3_bf16.txt 2>&1
