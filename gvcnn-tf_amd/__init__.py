@@ -14,6 +14,9 @@ from . import backbones, params  # noqa: E402
 from . import model  # noqa: E402
 from .model import (AUTO_REUSE, GVCNN, basic, configure, group_fusion, group_scheme, group_weight,  # noqa: E402,F401
                     grouping_module, gvcnn, gvcnn_fused, view_pooling)
+from . import retrieval  # noqa: E402
+from .retrieval import ShapeIndex  # noqa: E402,F401
 
 __all__ = ["GVCNN", "gvcnn", "basic", "group_scheme", "group_weight", "view_pooling", "group_fusion",
-           "grouping_module", "gvcnn_fused", "configure", "AUTO_REUSE", "backbones", "params", "model"]
+           "grouping_module", "gvcnn_fused", "configure", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
+           "ShapeIndex"]

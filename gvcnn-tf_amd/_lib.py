@@ -27,6 +27,9 @@ GV_OK, GV_E_BADARG, GV_E_UNSUPPORTED, GV_E_ALIGN, GV_E_PLAN = 0, -1, -2, -3, -4
 GV_VIEWPOOL_MAX, GV_VIEWPOOL_MEAN = 0, 1
 GV_ORDER_SHAPE_MAJOR, GV_ORDER_VIEW_MAJOR = 0, 1
 GV_WEIGHT_COUNT, GV_WEIGHT_MEAN_SCORE = 0, 1
+GV_METRIC_L2, GV_METRIC_COSINE = 0, 1
+GV_KNN_MAX_K = 256
+GV_RETR_AP_MAX_NDB = 16384
 GV_ABI_VERSION = 1
 
 
@@ -108,6 +111,11 @@ SIGNATURES = {
     "gv_preprocess_views": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gv_png_unfilter": (C.c_int, [_P, _I, _I, _I, _P]),
     "gv_eval_metrics": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "gv_retr_prepare": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "gv_knn_workspace_bytes": (_L, [_I, _I, _I]),
+    "gv_knn_search": (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P]),
+    "gv_retr_ap_workspace_bytes": (_L, [_I, _I]),
+    "gv_retr_average_precision": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -461,6 +461,15 @@ class GVCNN:
                                     self.logits.data_ptr(), _st()), "gv_dense_fwd")
         return S, self.logits
 
+    def embed(self, views, check=True, basic=False):
+        """The shape descriptor retrieval ranks on: forward (forward_basic when basic=True), then a copy of `gap`
+        ([N, C] fp32, the vector the classifier's Dense layer reads, nets/model.py:163-164)."""
+        if basic:
+            self.forward_basic(views)
+        else:
+            self.forward(views, check=check)
+        return self.gap.clone()
+
 
 # ------------------------------------------------------------------------------------------------
 # reference-shaped functional entry points with a variable store (AUTO_REUSE semantics)

@@ -379,6 +379,43 @@ int gv_png_unfilter(const uint8_t* raw, int32_t h, int32_t rowbytes, int32_t bpp
 int gv_eval_metrics(const float* logits, const int64_t* labels, int32_t n, int32_t c, int64_t* prediction,
                     int32_t* confusion, int32_t* correct, void* stream);
 
+/* ---- shape retrieval on the shape descriptor (the fp32 GAP vector [N, C] of nets/model.py:163) ---------------------
+ * An index is n descriptors prepared by gv_retr_prepare into `dtype` storage [n, ld] plus their squared norms.
+ * Ranking order of every function: the 64-bit key (distance, row id) — ascending distance, equal distances by the lower
+ * id.  The distance of a pair does not depend on where it sits in a tile or a chunk: db_chunk changes speed only, and
+ * the results are bitwise identical for every valid chunk size.
+ * Argument errors: GV_E_BADARG for a NULL required pointer, a size <= 0, ld < d, k outside [1, GV_KNN_MAX_K], an
+ * unknown metric, a workspace smaller than the *_workspace_bytes answer, a db_chunk that is not a positive multiple of
+ * 256; GV_E_UNSUPPORTED for an unknown dtype or an AP database above GV_RETR_AP_MAX_NDB rows; GV_E_ALIGN for
+ * ld % 64 != 0 or a storage / workspace pointer that is not 16-byte aligned.  All checked before any HIP call. */
+#define GV_METRIC_L2 0        /* squared Euclidean distance, clamped at 0 */
+#define GV_METRIC_COSINE 1    /* 1 - cosine similarity (rows normalised by gv_retr_prepare) */
+#define GV_KNN_MAX_K 256
+#define GV_RETR_AP_MAX_NDB 16384
+/* x [n, d] fp32 (row stride x_ld) -> y [n, ld] in `dtype` (columns d..ld-1 zero; GV_METRIC_COSINE: each row scaled to
+ * unit L2 norm first, a zero row stays zero) and sqnorm [n] = |y row|^2 of the values as stored (after rounding). */
+int gv_retr_prepare(const float* x, int32_t n, int32_t d, int32_t x_ld, int32_t metric, int32_t dtype,
+                    void* y, int32_t ld, float* sqnorm, void* stream);
+/* Workspace of gv_knn_search: a [nq, db_chunk] fp32 distance tile and the running k best of every query. */
+int64_t gv_knn_workspace_bytes(int32_t nq, int32_t db_chunk, int32_t k);
+/* k nearest database rows of every query (both prepared with the same metric / dtype / ld): dist [nq, k] fp32 and
+ * idx [nq, k] int64, ascending by (distance, id); a query with fewer than k candidates is padded with id -1 / +inf.
+ * exclude [nq] (NULL: none): a value in [0, ndb) drops that row from the query's ranking (leave-self-out). */
+int gv_knn_search(const void* q, const float* q_sqnorm, int32_t nq, const void* db, const float* db_sqnorm,
+                  int32_t ndb, int32_t d, int32_t ld, int32_t metric, int32_t dtype, int32_t k,
+                  const int64_t* exclude, int32_t db_chunk, float* dist, int64_t* idx,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+/* Workspace of gv_retr_average_precision (GV_E_UNSUPPORTED above GV_RETR_AP_MAX_NDB). */
+int64_t gv_retr_ap_workspace_bytes(int32_t nq, int32_t ndb);
+/* ap [nq] fp32: average precision of each query over the FULL ranking of the database (same order, same exclusion),
+ * AP = (1/R) sum_{j=1..R} j / rank_j with R relevant rows (db_labels == q_labels), accumulated in fp64.  A query with a
+ * label < 0, or with no relevant row left after exclusion, gets NaN; a database row with a label < 0 is ranked but never
+ * relevant.  ndb <= GV_RETR_AP_MAX_NDB (a whole-row sort in LDS). */
+int gv_retr_average_precision(const void* q, const float* q_sqnorm, const int64_t* q_labels, int32_t nq,
+                              const void* db, const float* db_sqnorm, const int64_t* db_labels, int32_t ndb,
+                              int32_t d, int32_t ld, int32_t metric, int32_t dtype, const int64_t* exclude,
+                              float* ap, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
  * consumers (an Inception block input, a ResNet shortcut) sums their gradients.
