@@ -16,7 +16,10 @@ from .model import (AUTO_REUSE, GVCNN, basic, configure, group_fusion, group_sch
                     grouping_module, gvcnn, gvcnn_fused, view_pooling)
 from . import retrieval  # noqa: E402
 from .retrieval import ShapeIndex  # noqa: E402,F401
+from . import render  # noqa: E402
+from .render import MeshBatch, ViewRenderer, load_obj, load_off, pack_meshes, random_rotations  # noqa: E402,F401
 
 __all__ = ["GVCNN", "gvcnn", "basic", "group_scheme", "group_weight", "view_pooling", "group_fusion",
            "grouping_module", "gvcnn_fused", "configure", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
-           "ShapeIndex"]
+           "ShapeIndex", "render", "MeshBatch", "ViewRenderer", "load_off", "load_obj", "pack_meshes",
+           "random_rotations"]

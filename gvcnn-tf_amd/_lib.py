@@ -30,6 +30,10 @@ GV_WEIGHT_COUNT, GV_WEIGHT_MEAN_SCORE = 0, 1
 GV_METRIC_L2, GV_METRIC_COSINE = 0, 1
 GV_KNN_MAX_K = 256
 GV_RETR_AP_MAX_NDB = 16384
+GV_RENDER_PERSPECTIVE, GV_RENDER_TWO_SIDED = 1, 2
+GV_RENDER_OUT_F32_QUANTIZED, GV_RENDER_OUT_F32, GV_RENDER_OUT_U8 = 0, 1, 2
+GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RENDER_TOO_LARGE, GV_RENDER_BAD_OFFSETS = \
+    0, 1, 2, 3, 4, 5
 GV_ABI_VERSION = 1
 
 
@@ -77,6 +81,13 @@ class BnStats(C.Structure):
                 ("seg", BnStatsSeg * 8)]
 
 
+class RenderDesc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("num_views", C.c_int32), ("flags", C.c_int32),
+                ("fit", C.c_float), ("proj_scale", C.c_float), ("persp_dist", C.c_float), ("depth_a", C.c_float),
+                ("depth_b", C.c_float), ("ambient", C.c_float), ("light", C.c_float * 3), ("color", C.c_float * 3),
+                ("background", C.c_float * 3)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nb", "ih", "iw", "c", "x_ld", "kh", "kw", "stride", "pad_t", "pad_l",
@@ -116,6 +127,11 @@ SIGNATURES = {
     "gv_knn_search": (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P]),
     "gv_retr_ap_workspace_bytes": (_L, [_I, _I]),
     "gv_retr_average_precision": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "gv_render_workspace_bytes": (_L, [_I, _I, _I, _I, _L]),
+    "gv_render_prepare": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _P, _P]),
+    "gv_render_bins_bytes": (_L, [_L]),
+    "gv_render_draw": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L, _I,
+                                 _P, _P, _P, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -470,6 +470,34 @@ class GVCNN:
             self.forward(views, check=check)
         return self.gap.clone()
 
+    # -- meshes in (render.py): render into an engine-owned view buffer, then the view entry points ---------------
+    def _render_meshes(self, batch, renderer, rotations):
+        from . import render as _render
+        if renderer is None:
+            renderer = getattr(self, "_renderer", None)
+            if renderer is None:
+                renderer = self._renderer = _render.ViewRenderer(self.V, self.H, self.W, device=self.device)
+        elif (renderer.V, renderer.H, renderer.W) != (self.V, self.H, self.W):
+            raise ValueError("the renderer makes %s views, the engine takes %s"
+                             % ((renderer.V, renderer.H, renderer.W), (self.V, self.H, self.W)))
+        n = len(batch)
+        if n != self.N:
+            raise ValueError("the batch holds %d meshes, the engine was built for %d" % (n, self.N))
+        if getattr(self, "_mesh_views", None) is None:
+            self._mesh_views = torch.empty((self.N, self.V, self.H, self.W, 3), dtype=torch.float32,
+                                           device=self.device)
+        return renderer.render(batch, rotations=rotations, out=self._mesh_views, quantize=True)
+
+    def forward_meshes(self, batch, renderer=None, rotations=None, check=True):
+        """forward() on the views of N meshes rendered on the device (render.ViewRenderer; default: V x H x W of this
+        engine, the reference's cameras).  batch: a render.MeshBatch or a list of (verts, tris).  One host read per
+        batch (the size of the tile lists), so this call is not captured into a graph; capture() stays on forward."""
+        return self.forward(self._render_meshes(batch, renderer, rotations), check=check)
+
+    def embed_meshes(self, batch, renderer=None, rotations=None, check=True, basic=False):
+        """embed() on the rendered views of N meshes (see forward_meshes)."""
+        return self.embed(self._render_meshes(batch, renderer, rotations), check=check, basic=basic)
+
 
 # ------------------------------------------------------------------------------------------------
 # reference-shaped functional entry points with a variable store (AUTO_REUSE semantics)

@@ -1,0 +1,476 @@
+"""Meshes in: render a batch of triangle meshes into the backbone's input views on the device.
+
+    verts, tris = load_off("chair_0001.off")
+    batch = MeshBatch([(verts, tris), ...], device)              # uploaded once
+    r = ViewRenderer(12, 224, 224)                               # obj2png.py's cameras: azimuth 30*(i+1), elevation 30
+    views = r.render(batch)                                      # [N, 12, 224, 224, 3] fp32 in [-0.5, 0.5]
+    views = r.render(batch, rotations=random_rotations(len(batch), "z", seed))   # augmentation
+
+The rasteriser is csrc/render.hip; its contract (written out in include/gvcnn_hip.h, "meshes in") makes every pixel
+reproducible bit for bit:
+  - per mesh, fp32 with every step rounded: c = bbox midpoint, r = max |v - c| (correctly rounded sqrt),
+    u = (v - c) * (fit / r); optional rotation w = M u ([N, 3, 3] fp32 rotation matrices, checked on the host);
+  - cameras as matplotlib's view_init(elev, azim) with +z up, looking at the origin; C_v [3, 3] (rows right, up,
+    forward) built in float64 on the host and rounded to fp32.  fov = 0: orthographic, the unit sphere on the shorter
+    image side; fov > 0: perspective with the eye at 1/sin(fov/2), the unit sphere tangent to the frustum;
+  - screen coordinates snapped to 1/256 pixel (round to nearest even), pixel centres at (i + 0.5, j + 0.5), row 0 on
+    top; integer edge functions with the top-left rule (top and left edges own the pixel centres on them); 24-bit
+    depth affine in screen space; the pixel keeps the smallest (depth << 32 | triangle id), so equal depths go to the
+    lower id and scheduling never matters;
+  - flat shading by the world-space face normal n = (w1-w0) x (w2-w0) and the light l: s = n.l / |n|,
+    f = ambient + (1 - ambient) * (s + 1) / 2 (matplotlib's _shade_colors with ambient 0.3; two_sided: |s|),
+    colour = color * f on a background colour;
+  - uint8 = floor(c * 255 + 0.5); quantize=True gives fma(uint8, 1/255, -0.5), rounded once (what the record pipeline's
+    gv_preprocess_views computes from a PNG, so a render equals its own PNG round trip); quantize=False gives c - 0.5.
+The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
+(31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import model as _model
+
+MAX_SIDE = 512
+MAX_VIEWS = 64
+MAX_TRIS = 1 << 24
+DEFAULT_COLOR = (31 / 255.0, 119 / 255.0, 180 / 255.0)         # matplotlib C0
+DEFAULT_BACKGROUND = (1.0, 1.0, 1.0)
+DEFAULT_MAX_WORKSPACE = 2 << 30
+ROTATION_TOL = 1e-4                                           # |M M^T - I| bound of a rotation matrix
+STATUS = {_lib.GV_RENDER_OK: "ok", _lib.GV_RENDER_EMPTY: "empty", _lib.GV_RENDER_ZERO_RADIUS: "zero radius",
+          _lib.GV_RENDER_NONFINITE: "non-finite radius", _lib.GV_RENDER_TOO_LARGE: "more than 2^24 triangles",
+          _lib.GV_RENDER_BAD_OFFSETS: "bad offsets"}
+
+
+def light_direction(azdeg=225.0, altdeg=19.4712):
+    """matplotlib.colors.LightSource(azdeg, altdeg).direction, float64."""
+    az, alt = math.radians(90.0 - azdeg), math.radians(altdeg)
+    return (math.cos(az) * math.cos(alt), math.sin(az) * math.cos(alt), math.sin(alt))
+
+
+DEFAULT_LIGHT = light_direction()
+
+
+def _device(device=None):
+    """The device with its index resolved ('cuda' -> 'cuda:<current>'), so two spellings of one device compare equal."""
+    d = _model._dev(device)
+    if d.type == "cuda" and d.index is None:
+        d = torch.device("cuda", torch.cuda.current_device())
+    return d
+
+
+def check_rotations(rotations, n=None):
+    """rotations [n, 3, 3] -> float32 numpy, checked on the host: finite, orthonormal (max |M M^T - I| <= 1e-4) and
+    det > 0.  The contract's bounds (every vertex inside the unit sphere, in front of a perspective eye) hold only for
+    rotations; ValueError otherwise.  A device tensor is copied to the host for the check (one read)."""
+    r = rotations.detach().cpu().numpy() if torch.is_tensor(rotations) else np.asarray(rotations)
+    if r.ndim != 3 or r.shape[1:] != (3, 3) or (n is not None and r.shape[0] != n):
+        raise ValueError("rotations must be [%s, 3, 3], got %s" % ("n" if n is None else n, r.shape))
+    r = r.astype(np.float32)
+    m = r.astype(np.float64)
+    if not np.isfinite(m).all():
+        raise ValueError("rotations must be finite")
+    err = np.abs(m @ m.transpose(0, 2, 1) - np.eye(3)).max() if len(m) else 0.0
+    if err > ROTATION_TOL or (len(m) and np.linalg.det(m).min() <= 0):
+        raise ValueError("rotations must be rotation matrices (orthonormal, det +1): max |M M^T - I| = %.3g" % err)
+    return r
+
+
+# ---- mesh files ------------------------------------------------------------------------------------------------------
+def _fan(poly):
+    return [(poly[0], poly[i], poly[i + 1]) for i in range(1, len(poly) - 1)]
+
+
+def _finish(verts, tris, what):
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("%s: a face index is outside [0, %d)" % (what, len(v)))
+    return v, t.astype(np.int32)
+
+
+def _lines(text):
+    for line in text.splitlines():
+        line = line.split("#", 1)[0].strip()
+        if line:
+            yield line
+
+
+def parse_off(text, what="OFF"):
+    """OFF text -> (verts float32 [nv, 3], tris int32 [nt, 3]).  ModelNet quirks: 'OFF' glued to the counts
+    ('OFF1234 5678 0'), comments, blank lines, polygons (fan-triangulated), colour tokens after a face."""
+    toks = _lines(text)
+    try:
+        head = next(toks)
+    except StopIteration:
+        raise ValueError("%s: empty file" % what)
+    if not head.startswith("OFF"):
+        raise ValueError("%s: no OFF header" % what)
+    rest = head[3:].split()
+    if not rest:
+        try:
+            rest = next(toks).split()
+        except StopIteration:
+            raise ValueError("%s: truncated (no counts)" % what)
+    try:
+        nv, nf = int(rest[0]), int(rest[1])
+    except (IndexError, ValueError):
+        raise ValueError("%s: bad counts line" % what)
+    if nv < 0 or nf < 0:
+        raise ValueError("%s: negative counts" % what)
+    verts, tris = [], []
+    try:
+        for _ in range(nv):
+            p = next(toks).split()
+            if len(p) < 3:
+                raise ValueError("%s: a vertex line has fewer than 3 values" % what)
+            verts.append([float(p[0]), float(p[1]), float(p[2])])
+        for _ in range(nf):
+            p = next(toks).split()
+            k = int(p[0])
+            if k < 3 or len(p) < 1 + k:
+                raise ValueError("%s: a face line is short" % what)
+            poly = [int(x) for x in p[1:1 + k]]              # anything after: colour tokens
+            if min(poly) < 0 or max(poly) >= nv:
+                raise ValueError("%s: a face index is outside [0, %d)" % (what, nv))
+            tris.extend(_fan(poly))
+    except StopIteration:
+        raise ValueError("%s: truncated (expected %d vertices and %d faces)" % (what, nv, nf))
+    return _finish(verts, tris, what)
+
+
+def parse_obj(text, what="OBJ"):
+    """OBJ text -> (verts, tris): 'v x y z', 'f a b c ...' with a, a/b, a/b/c or a//c, 1-based or negative (relative)
+    indices; polygons are fan-triangulated (ObjFile.QuadToTria does the same for quads)."""
+    verts, tris = [], []
+    for line in _lines(text):
+        p = line.split()
+        if p[0] == "v":
+            if len(p) < 4:
+                raise ValueError("%s: a vertex line has fewer than 3 values" % what)
+            verts.append([float(p[1]), float(p[2]), float(p[3])])
+        elif p[0] == "f":
+            if len(p) < 4:
+                raise ValueError("%s: a face has fewer than 3 vertices" % what)
+            poly = []
+            for tok in p[1:]:
+                i = int(tok.split("/")[0])
+                j = i - 1 if i > 0 else len(verts) + i
+                if i == 0 or not 0 <= j < len(verts):
+                    raise ValueError("%s: face index %d is outside the %d vertices read so far" % (what, i, len(verts)))
+                poly.append(j)
+            tris.extend(_fan(poly))
+    return _finish(verts, tris, what)
+
+
+def load_off(path):
+    with open(path) as f:
+        return parse_off(f.read(), str(path))
+
+
+def load_obj(path):
+    with open(path) as f:
+        return parse_obj(f.read(), str(path))
+
+
+def load_mesh(path):
+    p = str(path).lower()
+    if p.endswith(".off"):
+        return load_off(path)
+    if p.endswith(".obj"):
+        return load_obj(path)
+    raise ValueError("unknown mesh format: %s" % path)
+
+
+# ---- packing -------------------------------------------------------------------------------------------------------
+def pack_meshes(meshes):
+    """[(verts [nv, 3], tris [nt, 3]), ...] -> dict of host arrays: verts float32 [sum nv, 3], tris int32 [sum nt, 3]
+    (local indices), vert_offsets / tri_offsets int64 [N + 1].  Every mesh is checked here, before any upload:
+    finite vertices, integer indices in [0, nv), at most 2^24 triangles."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("no meshes")
+    vs, ts = [], []
+    for i, m in enumerate(meshes):
+        try:
+            v, t = m
+        except (TypeError, ValueError):
+            raise ValueError("mesh %d is not a (verts, tris) pair" % i)
+        v = np.asarray(v)
+        t = np.asarray(t)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("mesh %d: verts must be [nv, 3], got %s" % (i, v.shape))
+        if t.size == 0:
+            t = t.reshape(0, 3)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("mesh %d: tris must be [nt, 3], got %s" % (i, t.shape))
+        if t.size and not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("mesh %d: tris must be integers" % i)
+        with np.errstate(over="ignore"):
+            v = v.astype(np.float32)
+        if not np.isfinite(v).all():
+            raise ValueError("mesh %d: non-finite vertex" % i)
+        if t.size and (t.min() < 0 or t.max() >= len(v)):
+            raise ValueError("mesh %d: a triangle index is outside [0, %d)" % (i, len(v)))
+        if len(t) > MAX_TRIS:
+            raise ValueError("mesh %d: %d triangles (at most 2^24)" % (i, len(t)))
+        vs.append(v)
+        ts.append(t.astype(np.int32))
+    vo = np.zeros(len(meshes) + 1, np.int64)
+    to = np.zeros(len(meshes) + 1, np.int64)
+    vo[1:] = np.cumsum([len(v) for v in vs])
+    to[1:] = np.cumsum([len(t) for t in ts])
+    return {"verts": np.concatenate(vs).reshape(-1, 3), "tris": np.concatenate(ts).reshape(-1, 3),
+            "vert_offsets": vo, "tri_offsets": to}
+
+
+class MeshBatch:
+    """Meshes packed and uploaded once (a dataset held on the device can be re-rendered every epoch)."""
+
+    def __init__(self, meshes, device=None):
+        p = pack_meshes(meshes)
+        self.device = _device(device)
+        self.n = len(p["vert_offsets"]) - 1
+        self.vert_offsets_host, self.tri_offsets_host = p["vert_offsets"], p["tri_offsets"]
+        self.num_tris = np.diff(p["tri_offsets"])
+        # one element at least: an empty tensor has no address to hand to the library
+        v = p["verts"] if len(p["verts"]) else np.zeros((1, 3), np.float32)
+        t = p["tris"] if len(p["tris"]) else np.zeros((1, 3), np.int32)
+        self.verts = torch.from_numpy(np.ascontiguousarray(v)).to(self.device)
+        self.tris = torch.from_numpy(np.ascontiguousarray(t)).to(self.device)
+        self.vert_offsets = torch.from_numpy(p["vert_offsets"]).to(self.device)
+        self.tri_offsets = torch.from_numpy(p["tri_offsets"]).to(self.device)
+
+    def __len__(self):
+        return self.n
+
+    def group(self, a, b):
+        """The C-ABI arguments of meshes [a, b): pointers into the packed arrays (no copy)."""
+        vo, to = self.vert_offsets_host, self.tri_offsets_host
+        return (self.verts.data_ptr() + int(vo[a]) * 12, self.vert_offsets.data_ptr() + a * 8,
+                self.tris.data_ptr() + int(to[a]) * 12, self.tri_offsets.data_ptr() + a * 8, b - a,
+                int(vo[b] - vo[a]), int(to[b] - to[a]), int(self.num_tris[a:b].max()))
+
+
+def random_rotations(n, mode="z", seed=0):
+    """[n, 3, 3] float32 rotation matrices, built in float64 from np.random.RandomState(seed) and rounded once.
+    mode 'z': about the up axis by a uniform angle; 'so3': uniform over all rotations (unit quaternions)."""
+    rng = np.random.RandomState(seed)
+    if mode == "z":
+        a = rng.uniform(0.0, 2.0 * np.pi, size=n)
+        c, s = np.cos(a), np.sin(a)
+        R = np.zeros((n, 3, 3))
+        R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1], R[:, 2, 2] = c, -s, s, c, 1.0
+    elif mode == "so3":
+        q = rng.normal(size=(n, 4))
+        q /= np.linalg.norm(q, axis=1, keepdims=True)
+        w, x, y, z = q.T
+        R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                      2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                      2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=1).reshape(n, 3, 3)
+    else:
+        raise ValueError("mode must be 'z' or 'so3', not %r" % (mode,))
+    return R.astype(np.float32)
+
+
+def icosphere(subdivisions=0):
+    """(verts, tris) of the unit icosphere: 20 * 4^subdivisions outward-wound faces (synthetic test and benchmark
+    meshes)."""
+    t = (1.0 + 5 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+         (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10),
+         (8, 6, 7), (9, 8, 1)]
+    verts = [np.array(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(subdivisions):
+        mid, nf = {}, []
+
+        def m(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                p = verts[a] + verts[b]
+                verts.append(p / np.linalg.norm(p))
+                mid[k] = len(verts) - 1
+            return mid[k]
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    return np.array(verts, np.float32), np.array(f, np.int32)
+
+
+def default_azimuths(num_views):
+    """a_i = (i + 1) * 360 / V: obj2png.py's azim * (i + 1) (V = 8, azim = 45)."""
+    return [(i + 1) * 360.0 / num_views for i in range(num_views)]
+
+
+def camera_matrices(elevation, azimuths):
+    """[V, 3, 3] float32: rows right, up, forward (eye -> origin) of matplotlib's view_init(elev, azim), +z up."""
+    azimuths = list(azimuths)
+    el = np.broadcast_to(np.asarray(elevation, np.float64), (len(azimuths),))
+    C = np.zeros((len(azimuths), 3, 3))
+    for i, (e, a) in enumerate(zip(el, azimuths)):
+        e, a = math.radians(float(e)), math.radians(float(a))
+        eye = np.array([math.cos(e) * math.cos(a), math.cos(e) * math.sin(a), math.sin(e)])
+        f = -eye
+        r = np.array([-math.sin(a), math.cos(a), 0.0])
+        u = np.cross(r, f)
+        C[i] = np.stack([r, u, f])
+    return C.astype(np.float32)
+
+
+def projection(height, width, fov):
+    """(flags bit, proj_scale, persp_dist, depth_a, depth_b) in float64 (the descriptor rounds them to fp32)."""
+    half = min(height, width) / 2.0
+    if fov == 0:
+        return 0, half, 0.0, 0.0, 0.0
+    t = math.radians(fov) / 2.0
+    D = 1.0 / math.sin(t)
+    return _lib.GV_RENDER_PERSPECTIVE, half / math.tan(t), D, (D + 1.0) / 2.0, (D * D - 1.0) / 2.0
+
+
+class ViewRenderer:
+    """V views of H x W per mesh (rendering contract: the module docstring).  elevation: degrees, one for all views or
+    one per view; azimuths: degrees (default (i + 1) * 360 / V); fov: 0 (orthographic) or a perspective field of view
+    in degrees, (0, 120]; fit: the normalised radius in (0, 1]; color / background: RGB in [0, 1]; light: a direction
+    (normalised here); max_workspace_bytes: a batch whose workspace or tile lists would pass it is rendered in groups of
+    meshes, with identical results."""
+
+    def __init__(self, num_views, height, width, elevation=30.0, azimuths=None, fov=0.0, fit=0.9,
+                 color=DEFAULT_COLOR, background=DEFAULT_BACKGROUND, light=DEFAULT_LIGHT, ambient=0.3,
+                 two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE):
+        if not 1 <= int(num_views) <= MAX_VIEWS:
+            raise ValueError("num_views must be in [1, %d]" % MAX_VIEWS)
+        if not (1 <= int(height) <= MAX_SIDE and 1 <= int(width) <= MAX_SIDE):
+            raise ValueError("height and width must be in [1, %d]" % MAX_SIDE)
+        if not 0.0 < fit <= 1.0:
+            raise ValueError("fit must be in (0, 1]")
+        if not 0.0 <= ambient <= 1.0:
+            raise ValueError("ambient must be in [0, 1]")
+        if not (fov == 0 or 0.0 < fov <= 120.0):
+            raise ValueError("fov must be 0 (orthographic) or in (0, 120] degrees")
+        self.lib = _lib.load()
+        self.V, self.H, self.W = int(num_views), int(height), int(width)
+        self.azimuths = default_azimuths(self.V) if azimuths is None else [float(a) for a in azimuths]
+        if len(self.azimuths) != self.V:
+            raise ValueError("azimuths must hold num_views values")
+        self.elevation = elevation
+        self.device = _device(device)
+        self.cameras_host = camera_matrices(elevation, self.azimuths)
+        lt = np.asarray(light, np.float64)
+        if lt.shape != (3,) or not np.isfinite(lt).all() or not np.linalg.norm(lt) > 0:
+            raise ValueError("light must be a nonzero 3-vector")
+        lt = lt / np.linalg.norm(lt)
+        flags, k, D, a, b = projection(self.H, self.W, fov)
+        d = _lib.RenderDesc()
+        d.height, d.width, d.num_views = self.H, self.W, self.V
+        d.flags = flags | (_lib.GV_RENDER_TWO_SIDED if two_sided else 0)
+        d.fit, d.proj_scale, d.persp_dist, d.depth_a, d.depth_b, d.ambient = fit, k, D, a, b, ambient
+        for dst, src in ((d.light, lt), (d.color, color), (d.background, background)):
+            src = np.asarray(src, np.float64)
+            if src.shape != (3,) or not np.isfinite(src).all():
+                raise ValueError("color, background and light are RGB / xyz triples")
+            for i in range(3):
+                dst[i] = float(src[i])
+        self.desc = d
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        self.cameras = torch.from_numpy(self.cameras_host).to(self.device)
+        self.status = None
+
+    def descriptor(self):
+        """The descriptor's fields as Python values (fp32-rounded), for an oracle."""
+        d = self.desc
+        return {"height": d.height, "width": d.width, "num_views": d.num_views, "flags": d.flags, "fit": d.fit,
+                "proj_scale": d.proj_scale, "persp_dist": d.persp_dist, "depth_a": d.depth_a, "depth_b": d.depth_b,
+                "ambient": d.ambient, "light": list(d.light), "color": list(d.color),
+                "background": list(d.background), "cameras": self.cameras_host.copy()}
+
+    def _rotations(self, rotations, n):
+        if rotations is None:
+            return None
+        return torch.from_numpy(check_rotations(rotations, n)).to(self.device)
+
+    def _batch(self, batch):
+        if not isinstance(batch, MeshBatch):
+            batch = MeshBatch(batch, self.device)
+        elif batch.device != self.device:
+            raise ValueError("the batch lives on %s, the renderer on %s" % (batch.device, self.device))
+        return batch
+
+    def _draw(self, batch, a, b, rot, output, out, face_id, depth, status):
+        """Render meshes [a, b) into out[a:b] (and the buffers); halves the group when its tile lists would pass the
+        workspace cap."""
+        lib, d = self.lib, self.desc
+        args = batch.group(a, b)
+        n, total_tris = args[4], args[6]
+        ws_bytes = lib.gv_render_workspace_bytes(n, self.V, self.H, self.W, total_tris)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_render_workspace_bytes")
+        if ws_bytes > self.max_workspace_bytes and n > 1:
+            h = (a + b) // 2
+            self._draw(batch, a, h, rot, output, out, face_id, depth, status)
+            self._draw(batch, h, b, rot, output, out, face_id, depth, status)
+            return
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        info = torch.empty(1 + (n + 1) // 2, dtype=torch.int64, device=self.device)     # pair total, then status
+        st_dev = info[1:].view(torch.int32)
+        rp = None if rot is None else rot.data_ptr() + a * 36
+        _lib.check(lib.gv_render_prepare(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
+                                         info.data_ptr(), st_dev.data_ptr(), _model._st()), "gv_render_prepare")
+        host = info.cpu().numpy()                                        # the one host read of a render
+        total = int(host[0])
+        status[a:b] = host[1:].view(np.int32)[:n]
+        bins_bytes = lib.gv_render_bins_bytes(total)
+        _lib.check(bins_bytes if bins_bytes < 0 else 0, "gv_render_bins_bytes")
+        if ws_bytes + bins_bytes > self.max_workspace_bytes and n > 1:
+            del ws, info
+            h = (a + b) // 2
+            self._draw(batch, a, h, rot, output, out, face_id, depth, status)
+            self._draw(batch, h, b, rot, output, out, face_id, depth, status)
+            return
+        bins = torch.empty(bins_bytes, dtype=torch.uint8, device=self.device)
+        img = self.V * self.H * self.W
+        esz = 1 if output == _lib.GV_RENDER_OUT_U8 else 4
+        _lib.check(lib.gv_render_draw(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
+                                      bins.data_ptr(), bins_bytes, total, output, out.data_ptr() + a * img * 3 * esz,
+                                      None if face_id is None else face_id.data_ptr() + a * img * 4,
+                                      None if depth is None else depth.data_ptr() + a * img * 4, _model._st()),
+                   "gv_render_draw")
+
+    def _render(self, batch, rotations, out, output, return_buffers):
+        with torch.cuda.device(self.device):
+            batch = self._batch(batch)
+            n = batch.n
+            rot = self._rotations(rotations, n)
+            shape = (n, self.V, self.H, self.W, 3)
+            dt = torch.uint8 if output == _lib.GV_RENDER_OUT_U8 else torch.float32
+            if out is None:
+                out = torch.empty(shape, dtype=dt, device=self.device)
+            elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous()
+                  or _device(out.device) != self.device):
+                raise ValueError("out must be a contiguous %s tensor %s on %s" % (dt, shape, self.device))
+            face_id = depth = None
+            if return_buffers:
+                face_id = torch.empty(shape[:4], dtype=torch.int32, device=self.device)
+                depth = torch.empty(shape[:4], dtype=torch.int32, device=self.device)   # uint32 bits
+            status = np.zeros(n, np.int32)
+            self._draw(batch, 0, n, rot, output, out, face_id, depth, status)
+            self.status = status
+            if return_buffers:
+                return out, face_id, depth
+            return out
+
+    def render(self, batch, rotations=None, out=None, quantize=True, return_buffers=False):
+        """views fp32 [N, V, H, W, 3] on the device (and (face_id int32, depth) [N, V, H, W] with return_buffers; depth
+        is an int32 tensor holding the uint32 values, -1 = 0xFFFFFFFF = background).  batch: a MeshBatch or a list of
+        (verts, tris).  rotations: [N, 3, 3] rotation matrices (check_rotations) or None; pass them as a host array to
+        keep to one host read (the tile-list size) per mesh group."""
+        output = _lib.GV_RENDER_OUT_F32_QUANTIZED if quantize else _lib.GV_RENDER_OUT_F32
+        return self._render(batch, rotations, out, output, return_buffers)
+
+    def render_uint8(self, batch, rotations=None, out=None, return_buffers=False):
+        """views uint8 [N, V, H, W, 3] on the device (what a PNG of the render holds)."""
+        return self._render(batch, rotations, out, _lib.GV_RENDER_OUT_U8, return_buffers)

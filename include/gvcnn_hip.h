@@ -416,6 +416,84 @@ int gv_retr_average_precision(const void* q, const float* q_sqnorm, const int64_
                               int32_t d, int32_t ld, int32_t metric, int32_t dtype, const int64_t* exclude,
                               float* ap, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- meshes in: multi-view rasteriser (replaces the reference's offline off2obj -> obj2png -> TFRecord chain) -------
+ * Turns N triangle meshes into the backbone's input views [N, V, H, W, 3].  Results are defined bit for bit (every
+ * fp32 step below is rounded on its own; the kernels are compiled with FMA contraction off):
+ *  - meshes: fp32 vertices [sum nv, 3] and int32 triangles [sum nt, 3] of LOCAL vertex indices, concatenated; int64
+ *    vert_offsets / tri_offsets [N+1] (offsets[0] need not be 0: mesh m is rows offsets[m]-offsets[0] ..
+ *    offsets[m+1]-offsets[0] of the arrays passed, so a group of meshes is a pointer into the offsets).  The triangle
+ *    index within its mesh is its id.  A triangle with an index outside [0, nv) is dropped.
+ *  - normalisation, per mesh, fp32, every step rounded (no FMA): c = (min + max) * 0.5 per axis,
+ *    r = sqrt(max_i ((dx*dx + dy*dy) + dz*dz)) with d = v - c, u = (v - c) * (fit / r).  Status GV_RENDER_*.
+ *  - rotation (rotations [N,3,3] row-major, NULL = identity): w = M u, w_i = (M_i0*u0 + M_i1*u1) + M_i2*u2.  M must
+ *    be a rotation (orthonormal, det +1; the Python layer checks this); any other M gives unspecified pictures (memory
+ *    stays in bounds).
+ *  - cameras [V,3,3] (rows: right, up, forward = from the eye to the origin), computed on the host in float64 from
+ *    matplotlib's view_init(elev, azim) with +z up and rounded to fp32: q = C_v w (same sum order).
+ *  - projection: orthographic: sx = W/2 + q0*k, sy = H/2 - q1*k, t = (q2 + 1) * 0.5 with k = proj_scale (min(H,W)/2);
+ *    GV_RENDER_PERSPECTIVE: z = q2 + D, sx = W/2 + (q0*k)/z, sy = H/2 - (q1*k)/z, t = a - b/z with D = persp_dist
+ *    = 1/sin(fov/2), k = min(H,W)/2 / tan(fov/2), a = depth_a = (D+1)/2, b = depth_b = (D*D-1)/2 (all computed on the
+ *    host in float64, rounded to fp32).  X = rint(clamp(sx*256, +-2^18)) (round to nearest even), Y likewise; pixel
+ *    (i, j) has its centre at (256 i + 128, 256 j + 128); row 0 is the top row.  Z = rint(clamp(t, 0, 1) * (2^24-1)).
+ *  - coverage, int64 on the snapped coordinates: a zero-area triangle is dropped, a negative one is re-oriented
+ *    (vertices 1 and 2 swapped).  E_ab(P) = (Xb-Xa)*(Py-Ya) - (Yb-Ya)*(Px-Xa); weights e0 = E_12, e1 = E_20, e2 = E_01.
+ *    Covered: every e > 0, or e == 0 on an edge a -> b that owns its centres.  Top-left rule: positive area in this
+ *    y-down frame is clockwise on screen, so top edges (dy == 0, dx > 0) and left edges (dy < 0) own: a square with
+ *    corners on centres covers its top row and left column, not its bottom row and right column, and two triangles on
+ *    either side of a shared edge never both cover a centre.  Depth Z = (e0*Z0 + e1*Z1 + e2*Z2) div (e0 + e1 + e2),
+ *    unsigned 64-bit; the clamp keeps the numerator below 2^62.  The pixel keeps the smallest key (Z << 32) | id: equal depths go to the lower id.
+ *  - shading, per triangle from its winding: n = (w1-w0) x (w2-w0), s = (n.l) / sqrt(n.n) (0 when n.n == 0),
+ *    f = ambient + (1-ambient) * h with h = (s+1)*0.5, or |s| with GV_RENDER_TWO_SIDED; colour = color * f, and
+ *    background where nothing covers the pixel.
+ *  - output: GV_RENDER_OUT_U8 u8 = clamp(floor(c*255 + 0.5), 0, 255); GV_RENDER_OUT_F32_QUANTIZED fma(u8, 1/255, -0.5)
+ *    rounded once (what gv_preprocess_views computes from 8-bit views: a render equals its own PNG round trip);
+ *    GV_RENDER_OUT_F32 c - 0.5.
+ *    face_id int32 [N,V,H,W] (-1 background) and depth uint32 [N,V,H,W] (Z, 0xFFFFFFFF background) are optional.
+ * Sequence: ws = workspace_bytes(...); prepare(...) writes *pair_total and status[N] (device memory); the host reads the
+ * total; bins = bins_bytes(total) bytes; draw(...) writes the views.  Bitwise deterministic for any batch split or
+ * mesh order.  Limits: H, W <= 512, V <= 64, N <= 65535, max_tris (the largest nt of the batch: it sizes the grid)
+ * <= 2^24 (GV_E_UNSUPPORTED beyond).  Argument errors (GV_E_BADARG before any HIP call): a NULL required pointer, a
+ * size <= 0, fit outside (0, 1], ambient outside [0, 1], a non-finite colour / light / projection constant, D <= 1,
+ * unknown flags or output, a workspace / bins buffer smaller than the size query's answer; GV_E_ALIGN for a
+ * workspace / bins pointer that is not 16-byte aligned or a 4-byte output that is not 4-byte aligned. */
+#define GV_RENDER_PERSPECTIVE 1       /* gv_render_desc.flags */
+#define GV_RENDER_TWO_SIDED 2
+#define GV_RENDER_OUT_F32_QUANTIZED 0 /* output selectors */
+#define GV_RENDER_OUT_F32 1
+#define GV_RENDER_OUT_U8 2
+#define GV_RENDER_OK 0                /* per-mesh status: rendered */
+#define GV_RENDER_EMPTY 1             /* no triangles or no vertices: background */
+#define GV_RENDER_ZERO_RADIUS 2       /* every vertex at one point: background */
+#define GV_RENDER_NONFINITE 3         /* radius or scale not finite: background */
+#define GV_RENDER_TOO_LARGE 4         /* more than 2^24 triangles: background */
+#define GV_RENDER_BAD_OFFSETS 5       /* offsets decreasing or beyond total_verts / total_tris: background */
+typedef struct gv_render_desc {
+    int32_t height, width, num_views, flags;
+    float fit;                        /* (0, 1] */
+    float proj_scale;                 /* k */
+    float persp_dist, depth_a, depth_b; /* D, a, b (perspective only) */
+    float ambient;
+    float light[3];
+    float color[3];
+    float background[3];
+} gv_render_desc;
+/* Bytes of the size-determined workspace (16-byte aligned; total_tris = tri_offsets[N] - tri_offsets[0]). */
+int64_t gv_render_workspace_bytes(int32_t n, int32_t num_views, int32_t height, int32_t width, int64_t total_tris);
+/* Normalise, set up and count the (triangle, view, tile) pairs: *pair_total (int64, device) and status [N] (device). */
+int gv_render_prepare(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
+                      int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
+                      const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes,
+                      int64_t* pair_total, int32_t* status, void* stream);
+/* Bytes of the tile lists for `total` pairs. */
+int64_t gv_render_bins_bytes(int64_t total);
+/* Scatter, raster and resolve with the workspace of the prepare call on the same arguments; out [N,V,H,W,3] as
+ * `output` selects; face_id / depth nullable. */
+int gv_render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
+                   int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
+                   const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
+                   int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth,
+                   void* stream);
+
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
  * consumers (an Inception block input, a ResNet shortcut) sums their gradients.

@@ -1,0 +1,66 @@
+"""ModelNet meshes -> GZIP TFRecords of rendered views, on the device (replaces the reference's off2obj.py ->
+obj2png.py -> create_modelnet_tf_record.py chain).
+
+    python tools/render_modelnet.py --src ModelNet40 --split train --out modelnet40_train.tfrecord --views 12 --size 224
+
+Walks SRC/<class>/<split>/*.off in sorted order; the label of a shape is the index of its class directory among the
+sorted class directories (create_modelnet_tf_record.py's convention).  Meshes are rendered `--batch` at a time with
+render.ViewRenderer (uint8, the reference's cameras and shading) and written as tf.Example records of V PNGs that
+records.ViewBatcher reads.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def find_shapes(src, split):
+    classes = sorted(d for d in os.listdir(src) if os.path.isdir(os.path.join(src, d)))
+    shapes = []
+    for label, cls in enumerate(classes):
+        d = os.path.join(src, cls, split)
+        if os.path.isdir(d):
+            shapes += [(os.path.join(d, f), label) for f in sorted(os.listdir(d)) if f.lower().endswith(".off")]
+    return classes, shapes
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--src", required=True, help="ModelNet root: <class>/<split>/*.off")
+    ap.add_argument("--split", default="train")
+    ap.add_argument("--out", required=True, help="GZIP TFRecord file to write")
+    ap.add_argument("--views", type=int, default=12)
+    ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--elevation", type=float, default=30.0)
+    ap.add_argument("--fov", type=float, default=0.0)
+    ap.add_argument("--batch", type=int, default=32, help="meshes per device render")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    import torch
+    import gvcnn_tf_amd as gv
+    from gvcnn_tf_amd import records, render
+
+    classes, shapes = find_shapes(a.src, a.split)
+    if not shapes:
+        raise SystemExit("no %s/*.off files under %s" % (a.split, a.src))
+    dev = torch.device(a.device)
+    r = render.ViewRenderer(a.views, a.size, a.size, elevation=a.elevation, fov=a.fov, device=dev)
+
+    def examples():
+        for b0 in range(0, len(shapes), a.batch):
+            part = shapes[b0:b0 + a.batch]
+            views = r.render_uint8([render.load_off(p) for p, _ in part]).cpu().numpy()
+            for (p, label), st, v in zip(part, r.status, views):
+                if st != gv._lib.GV_RENDER_OK:
+                    print("warning: %s renders as background (%s)" % (p, render.STATUS.get(int(st), st)),
+                          file=sys.stderr)
+                yield records.make_example([records.encode_png(v[i]) for i in range(a.views)], label)
+    records.write_tfrecords(a.out, examples())
+    print("%d shapes of %d classes -> %s" % (len(shapes), len(classes), a.out))
+
+
+if __name__ == "__main__":
+    main()
