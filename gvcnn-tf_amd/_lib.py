@@ -30,6 +30,7 @@ GV_WEIGHT_COUNT, GV_WEIGHT_MEAN_SCORE = 0, 1
 GV_METRIC_L2, GV_METRIC_COSINE = 0, 1
 GV_KNN_MAX_K = 256
 GV_RETR_AP_MAX_NDB = 16384
+GV_METRIC_MAX_RANK, GV_METRIC_MAX_BATCH = 256, 16384
 GV_RENDER_PERSPECTIVE, GV_RENDER_TWO_SIDED = 1, 2
 GV_RENDER_OUT_F32_QUANTIZED, GV_RENDER_OUT_F32, GV_RENDER_OUT_U8 = 0, 1, 2
 GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RENDER_TOO_LARGE, GV_RENDER_BAD_OFFSETS = \
@@ -127,6 +128,11 @@ SIGNATURES = {
     "gv_knn_search": (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P]),
     "gv_retr_ap_workspace_bytes": (_L, [_I, _I]),
     "gv_retr_average_precision": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "gv_metric_project": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P]),
+    "gv_metric_pair_workspace_bytes": (_L, [_I, _I]),
+    "gv_metric_pair_grad": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _L, _P]),
+    "gv_metric_wgrad_workspace_bytes": (_L, [_I, _I, _I]),
+    "gv_metric_wgrad": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _P]),
     "gv_render_workspace_bytes": (_L, [_I, _I, _I, _I, _L]),
     "gv_render_prepare": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _P, _P]),
     "gv_render_bins_bytes": (_L, [_L]),

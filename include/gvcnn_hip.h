@@ -416,6 +416,44 @@ int gv_retr_average_precision(const void* q, const float* q_sqnorm, const int64_
                               int32_t d, int32_t ld, int32_t metric, int32_t dtype, const int64_t* exclude,
                               float* ap, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- learned retrieval metric: low-rank Mahalanobis projection (the paper's second retrieval number) ---------------
+ * W [r, d] fp32 and a scalar threshold b, z_i = W x_i.  Over the pairs i < j of a batch whose labels are both >= 0 (P
+ * pairs), y = +1 for equal labels and -1 otherwise, c = pos_weight for y = +1 and 1 otherwise,
+ * d_ij = max(0, |z_i|^2 + |z_j|^2 - 2 z_i.z_j):
+ *     L = (1/P) sum c_ij max(0, 1 - y_ij (b - d_ij));   a pair is ACTIVE when 1 - y_ij (b - d_ij) > 0 (strictly);
+ *     a_ij = c_ij y_ij [active];   dL/dz_i = (2/P) ((sum_j a_ij) z_i - sum_j a_ij z_j);   dL/db = -(1/P) sum_{i<j} a_ij.
+ * All storage is fp32 and every product runs on the exact fp32 MFMA; every reduction has a fixed order (no
+ * floating-point atomics): the same inputs give the same bits every run.  rl = r rounded up to 64.
+ * Argument errors: GV_E_BADARG for a NULL required pointer, a size <= 0, a row stride below its row length, an rl
+ * that is not r rounded up to 64, a workspace smaller than the *_workspace_bytes answer; GV_E_UNSUPPORTED for
+ * r > GV_METRIC_MAX_RANK or n > GV_METRIC_MAX_BATCH (pair / wgrad); GV_E_ALIGN for a row stride that is not a multiple
+ * of 4 or a pointer that is not 16-byte aligned.  All checked before any HIP call. */
+#define GV_METRIC_MAX_RANK 256
+#define GV_METRIC_MAX_BATCH 16384
+/* z [n, rl] = x [n, d] (row stride x_ld) W^T (w [r, d], row stride w_ld), columns r..rl-1 written as zero, and
+ * sqnorm [n] = |z row|^2 summed from the stored values.  Any n > 0. */
+int gv_metric_project(const float* x, int32_t n, int32_t d, int32_t x_ld, const float* w, int32_t r, int32_t w_ld,
+                      float* z, int32_t rl, float* sqnorm, void* stream);
+/* Workspace of gv_metric_pair_grad: per-slice partial row sums and per-workgroup statistics, linear in n. */
+int64_t gv_metric_pair_workspace_bytes(int32_t n, int32_t r);
+/* One pass over all pairs of the batch, nothing n x n leaves the compute unit.  z / sqnorm as gv_metric_project wrote
+ * them, labels int64 [n] (a label < 0 takes part in no pair), b a DEVICE scalar.  Writes
+ * dz_unnorm [n, rl] = 2 ((sum_j a_ij) z_i - sum_j a_ij z_j)  (not divided by P; pad columns zero) and
+ * stats fp64 [5] = {sum_{i<j} c h, P, active pairs, sum_{i<j} a_ij, sum_{i<j} d_ij}: the per-pair fp32 values are
+ * summed in fp64, the counts in integers. */
+int gv_metric_pair_grad(const float* z, const float* sqnorm, const int64_t* labels, int32_t n, int32_t r, int32_t rl,
+                        const float* b, float pos_weight, float* dz_unnorm, double* stats, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* Workspace of gv_metric_wgrad: one image of the gradient per slice of the batch axis. */
+int64_t gv_metric_wgrad_workspace_bytes(int32_t n, int32_t d, int32_t r);
+/* grad [r * ld + 1]: dL/dW [r, ld] = (dz_unnorm^T x) / P (columns d..ld-1 zero), then dL/db = -(sum a) / P as the last
+ * element; P and sum a are read from stats ON THE DEVICE (P = 0: all zeros).  The batch axis is split over workgroups
+ * and the slices are added in index order.  loss (NULL: not wanted): a device scalar that receives stats[0] / P
+ * (P = 0: 0). */
+int gv_metric_wgrad(const float* dz_unnorm, int32_t n, int32_t r, int32_t rl, const float* x, int32_t d, int32_t x_ld,
+                    const double* stats, float* grad, int32_t ld, float* loss, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* ---- meshes in: multi-view rasteriser (replaces the reference's offline off2obj -> obj2png -> TFRecord chain) -------
  * Turns N triangle meshes into the backbone's input views [N, V, H, W, 3].  Results are defined bit for bit (every
  * fp32 step below is rounded on its own; the kernels are compiled with FMA contraction off):
