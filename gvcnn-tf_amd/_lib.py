@@ -138,6 +138,10 @@ SIGNATURES = {
     "gv_render_bins_bytes": (_L, [_L]),
     "gv_render_draw": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L, _I,
                                  _P, _P, _P, _P]),
+    "gv_render_prepare_ss": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _P, _I,
+                                       _P]),
+    "gv_render_draw_ss": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L, _I,
+                                    _P, _P, _P, _I, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

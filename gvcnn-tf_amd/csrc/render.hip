@@ -18,6 +18,11 @@
 //                                          streamed through LDS 256 setups at a time; each pixel keeps the smallest
 //                                          64-bit key (Z << 32 | triangle id) in a register and writes its outputs once.
 //
+// gv_render_prepare_ss / gv_render_draw_ss: the same launches with S x S samples per pixel (S = 1 << LS = 1, 2, 4; LS is a
+// template parameter of tri_setup, bin_kernel and raster_kernel; LS = 0 is the code behind the original pair).  The
+// triangle's box is taken over the sample grid, so binning depends on S; a raster thread still owns one pixel and keeps
+// its S * S keys in registers, and resolves them to the pixel in the same launch.
+//
 // No thread walks more than one tile's pixels: a triangle that covers the whole screen sits in every tile list it
 // touches and each tile's threads test it against their own pixel.  The triangle setup is a pure function of (mesh,
 // view, triangle), recomputed where needed (count, scatter, raster), so the bins hold 4-byte ids only.
@@ -133,7 +138,9 @@ __device__ __forceinline__ bool load_tri(const Args& a, int m, int t, const floa
     return true;
 }
 
-// setup of triangle t of mesh m in view v: false when it covers no pixel centre (zero area, off screen, bad index)
+// setup of triangle t of mesh m in view v with S = 1 << LS samples per pixel and axis: false when its box holds no
+// sample (zero area, off screen, bad index).  px0..py1 is the pixel range of the sample box.
+template <int LS>
 __device__ bool tri_setup(const Args& a, int m, int v, int t, Tri& T) {
     const float *p0, *p1, *p2;
     if (!load_tri(a, m, t, p0, p1, p2)) return false;
@@ -158,12 +165,15 @@ __device__ bool tri_setup(const Args& a, int m, int v, int t, Tri& T) {
     T.area = area;
     const int xmin = min(T.x0, min(T.x1, T.x2)), xmax = max(T.x0, max(T.x1, T.x2));
     const int ymin = min(T.y0, min(T.y1, T.y2)), ymax = max(T.y0, max(T.y1, T.y2));
-    // pixel centres 256 i + 128 inside [min, max]
-    T.px0 = max((xmin + 127) >> 8, 0);
-    T.px1 = min((xmax - 128) >> 8, a.W - 1);
-    T.py0 = max((ymin + 127) >> 8, 0);
-    T.py1 = min((ymax - 128) >> 8, a.H - 1);
-    return T.px0 <= T.px1 && T.py0 <= T.py1;
+    // samples step * g + step / 2 inside [min, max], step = 256 >> LS (LS = 0: the pixel centres 256 i + 128)
+    constexpr int LG = 8 - LS, HALF = 128 >> LS;
+    const int gx0 = max((xmin + HALF - 1) >> LG, 0), gx1 = min((xmax - HALF) >> LG, (a.W << LS) - 1);
+    const int gy0 = max((ymin + HALF - 1) >> LG, 0), gy1 = min((ymax - HALF) >> LG, (a.H << LS) - 1);
+    T.px0 = gx0 >> LS;
+    T.px1 = gx1 >> LS;
+    T.py0 = gy0 >> LS;
+    T.py1 = gy1 >> LS;
+    return gx0 <= gx1 && gy0 <= gy1;
 }
 
 // flat shading factor of a triangle (winding-defined world normal)
@@ -251,7 +261,7 @@ __global__ __launch_bounds__(RT) void normalise_kernel(const float* __restrict__
 }
 
 // ---- binning: count (SCATTER = false) and scatter (SCATTER = true) --------------------------------------------------
-template <bool SCATTER>
+template <bool SCATTER, int LS>
 __global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_count, long long* __restrict__ image_total,
                                                  float* __restrict__ shade, float3 light, float ambient, int two_sided,
                                                  const long long* __restrict__ tile_start, int* __restrict__ tile_fill,
@@ -276,7 +286,7 @@ __global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_
                                                                     p0, p1, p2, light, ambient, two_sided);
             }
             Tri q;
-            if (!tri_setup(a, m, v, t, q)) continue;
+            if (!tri_setup<LS>(a, m, v, t, q)) continue;
             for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
                 for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) atomicAdd(&s_cnt[ty * a.tiles_x + tx], 1);
         }
@@ -305,7 +315,7 @@ __global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_
             __syncthreads();
             for (int t = c0 + tid; t < min(c0 + CHUNK, nt); t += RT) {
                 Tri q;
-                if (!tri_setup(a, m, v, t, q)) continue;
+                if (!tri_setup<LS>(a, m, v, t, q)) continue;
                 for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
                     for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) {
                         const int i = ty * a.tiles_x + tx;
@@ -369,8 +379,9 @@ struct LTri {                                                    // one setup in
     int bx, by;                                                  // px0 | px1 << 16, py0 | py1 << 16
     int id;                                                      // triangle id | owned-edge bits << 24
     long long area;
-    int pad0, pad1;
+    double inv;                                                  // 1 / area, rounded once (S > 1 only)
 };
+static_assert(sizeof(LTri) == 64, "one setup is 64 bytes of LDS");
 
 // the top-left rule.  Positive area in the y-down frame means clockwise on screen: a top edge runs left to right
 // (dy == 0, dx > 0) and a left edge runs upwards (dy < 0); those edges own the pixel centres on them
@@ -382,21 +393,28 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
     return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
 }
 
-template <int OUT>
+// S = 1 << LS samples per pixel and axis.  The thread of pixel (px, py) holds the S * S keys of its samples (b rows,
+// a columns, key b * S + a) in registers: every index into best[] below is a compile-time constant of a fully unrolled
+// loop.  The edge functions are affine, so they are evaluated once per triangle at sample (0, 0) and stepped by the
+// exact 64-bit increments d/dx = -(by - ay) * step, d/dy = (bx - ax) * step.
+template <int OUT, int LS>
 __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restrict__ shade,
                                                     const int* __restrict__ tile_count,
                                                     const long long* __restrict__ tile_start,
                                                     const int* __restrict__ bins, long long cap, float3 color,
                                                     float3 background, void* __restrict__ out, int* __restrict__ face_id,
                                                     unsigned* __restrict__ depth) {
+    constexpr int S = 1 << LS, NS = S * S, STEP = 256 >> LS;
     __shared__ LTri s_tri[RT];
     const int T = a.tiles_x * a.tiles_y;
     const int tile = blockIdx.x, v = blockIdx.y, m = blockIdx.z, tid = threadIdx.x;
     const long long img = (long long)m * a.V + v;
     const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
     const int px = tx * TS + (tid & (TS - 1)), py = ty * TS + (tid >> 4);
-    const int PX = px * 256 + 128, PY = py * 256 + 128;
-    u64 best = BG_KEY;
+    const int PX = px * 256 + STEP / 2, PY = py * 256 + STEP / 2;   // sample (0, 0)
+    u64 best[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) best[s] = BG_KEY;
     if (a.xf[m].status == GV_RENDER_OK) {
         const long long start = tile_start[img * T + tile];
         const long long end = min(start + (long long)tile_count[img * T + tile], cap);
@@ -406,7 +424,7 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
                 const int t = bins[c0 + tid];
                 Tri q;
                 LTri& L = s_tri[tid];
-                if (tri_setup(a, m, v, t, q)) {
+                if (tri_setup<LS>(a, m, v, t, q)) {
                     L.x0 = q.x0; L.y0 = q.y0; L.x1 = q.x1; L.y1 = q.y1; L.x2 = q.x2; L.y2 = q.y2;
                     L.z0 = q.z0; L.z1 = q.z1; L.z2 = q.z2;
                     L.bx = q.px0 | (q.px1 << 16);
@@ -414,6 +432,7 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
                     L.id = t | (owns(q.x1, q.y1, q.x2, q.y2) << 24) | (owns(q.x2, q.y2, q.x0, q.y0) << 25) |
                            (owns(q.x0, q.y0, q.x1, q.y1) << 26);
                     L.area = q.area;
+                    if constexpr (LS > 0) L.inv = 1.0 / (double)q.area;      // area < 2^38: exact in a double
                 } else {
                     L.bx = 1;                                    // empty range: px0 = 1 > px1 = 0
                     L.by = 0;
@@ -426,41 +445,90 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
                 const long long e0 = edge(L.x1, L.y1, L.x2, L.y2, PX, PY);
                 const long long e1 = edge(L.x2, L.y2, L.x0, L.y0, PX, PY);
                 const long long e2 = edge(L.x0, L.y0, L.x1, L.y1, PX, PY);
-                const bool in = (e0 > 0 || (e0 == 0 && (L.id >> 24 & 1))) && (e1 > 0 || (e1 == 0 && (L.id >> 25 & 1))) &&
-                                (e2 > 0 || (e2 == 0 && (L.id >> 26 & 1)));
-                if (!in) continue;
-                const u64 num = (u64)e0 * L.z0 + (u64)e1 * L.z1 + (u64)e2 * L.z2;
-                // exact early-out: Z = num div area >= bestZ + 1 exactly when num >= (bestZ + 1) * area (< 2^62)
-                if (best != BG_KEY && num >= ((best >> 32) + 1) * (u64)L.area) continue;
-                const u64 Z = num / (u64)L.area;
-                const u64 key = (Z << 32) | (unsigned)(L.id & 0xffffff);
-                best = key < best ? key : best;
+                if constexpr (LS == 0) {
+                    const bool in = (e0 > 0 || (e0 == 0 && (L.id >> 24 & 1))) && (e1 > 0 || (e1 == 0 && (L.id >> 25 & 1))) &&
+                                    (e2 > 0 || (e2 == 0 && (L.id >> 26 & 1)));
+                    if (!in) continue;
+                    const u64 num = (u64)e0 * L.z0 + (u64)e1 * L.z1 + (u64)e2 * L.z2;
+                    // exact early-out: Z = num div area >= bestZ + 1 exactly when num >= (bestZ + 1) * area (< 2^62)
+                    if (best[0] != BG_KEY && num >= ((best[0] >> 32) + 1) * (u64)L.area) continue;
+                    const u64 Z = num / (u64)L.area;
+                    const u64 key = (Z << 32) | (unsigned)(L.id & 0xffffff);
+                    best[0] = key < best[0] ? key : best[0];
+                } else {
+                    const long long dx0 = -(long long)(L.y2 - L.y1) * STEP, dy0 = (long long)(L.x2 - L.x1) * STEP;
+                    const long long dx1 = -(long long)(L.y0 - L.y2) * STEP, dy1 = (long long)(L.x0 - L.x2) * STEP;
+                    const long long dx2 = -(long long)(L.y1 - L.y0) * STEP, dy2 = (long long)(L.x1 - L.x0) * STEP;
+                    // an affine function has its maximum over the pixel's samples at a corner: below zero there, the
+                    // edge excludes every sample
+                    if (e0 + (S - 1) * (max(dx0, 0ll) + max(dy0, 0ll)) < 0 || e1 + (S - 1) * (max(dx1, 0ll) + max(dy1, 0ll)) < 0 ||
+                        e2 + (S - 1) * (max(dx2, 0ll) + max(dy2, 0ll)) < 0)
+                        continue;
+                    const int o0 = L.id >> 24 & 1, o1 = L.id >> 25 & 1, o2 = L.id >> 26 & 1;
+                    const unsigned z0 = L.z0, z1 = L.z1, z2 = L.z2, id = (unsigned)(L.id & 0xffffff);
+                    const u64 area = (u64)L.area;
+                    const double inv = L.inv;
+#pragma unroll
+                    for (int b = 0; b < S; ++b)
+#pragma unroll
+                        for (int c = 0; c < S; ++c) {
+                            const long long f0 = e0 + b * dy0 + c * dx0, f1 = e1 + b * dy1 + c * dx1;
+                            const long long f2 = e2 + b * dy2 + c * dx2;
+                            const bool in = (f0 > 0 || (f0 == 0 && o0)) && (f1 > 0 || (f1 == 0 && o1)) &&
+                                            (f2 > 0 || (f2 == 0 && o2));
+                            if (!in) continue;
+                            const u64 num = (u64)f0 * z0 + (u64)f1 * z1 + (u64)f2 * z2;
+                            const u64 old = best[b * S + c];
+                            // the same exact early-out, per sample
+                            if (old != BG_KEY && num >= ((old >> 32) + 1) * area) continue;
+                            // Z = num div area without the 64-bit division: num < 2^62 and 1 / area carry a relative
+                            // error of 2^-53 each, their product one more, and Z < 2^24, so the estimate is within
+                            // 2^-27 of num / area and its floor within 1 of Z; the exact remainder settles it
+                            u64 Z = (u64)(unsigned)((double)num * inv);
+                            const long long rem = (long long)(num - Z * area);
+                            if (rem < 0) --Z;
+                            else if ((u64)rem >= area) ++Z;
+                            const u64 key = (Z << 32) | id;
+                            best[b * S + c] = key < old ? key : old;
+                        }
+                }
             }
             __syncthreads();
         }
     }
     if (px >= a.W || py >= a.H) return;
     const size_t p = ((size_t)img * a.H + py) * a.W + px;
-    float c0 = background.x, c1 = background.y, c2 = background.z;
-    if (best != BG_KEY) {
-        const int id = (int)(best & 0xffffffffu);
-        const float f = shade[a.toff[m] - a.toff[0] + id];
-        c0 = mul_rn(color.x, f);
-        c1 = mul_rn(color.y, f);
-        c2 = mul_rn(color.z, f);
+    // resolve: u8 per sample and channel, summed exactly; fp32 colours added in row-major sample order
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    unsigned sum[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float cs[3] = {background.x, background.y, background.z};
+        if (best[s] != BG_KEY) {
+            const int id = (int)(best[s] & 0xffffffffu);
+            const float f = shade[a.toff[m] - a.toff[0] + id];
+            cs[0] = mul_rn(color.x, f);
+            cs[1] = mul_rn(color.y, f);
+            cs[2] = mul_rn(color.z, f);
+        }
+        if (face_id || depth) {
+            const size_t q = ((size_t)img * (a.H << LS) + (py << LS) + s / S) * (a.W << LS) + (px << LS) + s % S;
+            if (face_id) face_id[q] = best[s] == BG_KEY ? -1 : (int)(best[s] & 0xffffffffu);
+            if (depth) depth[q] = best[s] == BG_KEY ? 0xFFFFFFFFu : (unsigned)(best[s] >> 32);
+        }
+        for (int c = 0; c < 3; ++c) {
+            if (OUT == GV_RENDER_OUT_F32)
+                acc[c] = s == 0 ? cs[c] : add_rn(acc[c], cs[c]);
+            else
+                sum[c] += (unsigned)(unsigned char)fminf(fmaxf(floorf(add_rn(mul_rn(cs[c], 255.0f), 0.5f)), 0.0f), 255.0f);
+        }
     }
-    if (face_id) face_id[p] = best == BG_KEY ? -1 : (int)(best & 0xffffffffu);
-    if (depth) depth[p] = best == BG_KEY ? 0xFFFFFFFFu : (unsigned)(best >> 32);
     if (OUT == GV_RENDER_OUT_F32) {
         float* o = static_cast<float*>(out) + p * 3;
-        o[0] = add_rn(c0, -0.5f);
-        o[1] = add_rn(c1, -0.5f);
-        o[2] = add_rn(c2, -0.5f);
+        for (int c = 0; c < 3; ++c) o[c] = add_rn(LS ? mul_rn(acc[c], 1.0f / NS) : acc[c], -0.5f);
     } else {
-        const float cs[3] = {c0, c1, c2};
         unsigned char u[3];
-        for (int c = 0; c < 3; ++c)
-            u[c] = (unsigned char)fminf(fmaxf(floorf(add_rn(mul_rn(cs[c], 255.0f), 0.5f)), 0.0f), 255.0f);
+        for (int c = 0; c < 3; ++c) u[c] = (unsigned char)((sum[c] + NS / 2) >> (2 * LS));
         if (OUT == GV_RENDER_OUT_U8) {
             unsigned char* o = static_cast<unsigned char*>(out) + p * 3;
             o[0] = u[0];
@@ -550,6 +618,123 @@ dim3 bin_grid(int32_t max_tris, int32_t v, int32_t n) {
     return dim3((unsigned)chunks, (unsigned)v, (unsigned)n);
 }
 
+// samples per pixel and axis -> log2 (0, 1, 2); -1 for a power of two above 4 (GV_E_UNSUPPORTED once the shared checks
+// have passed); false for anything else (GV_E_BADARG)
+bool sample_shift(int32_t samples, int* ls) {
+    if (samples <= 0 || (samples & (samples - 1))) return false;
+    *ls = samples == 1 ? 0 : samples == 2 ? 1 : samples == 4 ? 2 : -1;
+    return true;
+}
+
+template <int LS>
+void launch_count(dim3 grid, hipStream_t st, const Args& a, int* tile_count, long long* image_total, float* shade,
+                  const gv_render_desc* d) {
+    hipLaunchKernelGGL((bin_kernel<false, LS>), grid, dim3(RT), 0, st, a, tile_count, image_total, shade,
+                       make_float3(d->light[0], d->light[1], d->light[2]), d->ambient,
+                       (d->flags & GV_RENDER_TWO_SIDED) ? 1 : 0, nullptr, nullptr, nullptr, 0ll);
+}
+
+template <int LS>
+int launch_draw(dim3 bgrid, dim3 grid, hipStream_t st, const Args& a, const float* shade, const int* tc,
+                const long long* ts, int* tile_fill, int* bins, long long cap, const gv_render_desc* d, int32_t output,
+                void* out, int32_t* face_id, uint32_t* depth) {
+    hipLaunchKernelGGL((bin_kernel<true, LS>), bgrid, dim3(RT), 0, st, a, nullptr, nullptr, nullptr,
+                       make_float3(0.f, 0.f, 0.f), 0.f, 0, ts, tile_fill, bins, cap);
+    GV_LAUNCH_CHECK();
+    const float3 color = make_float3(d->color[0], d->color[1], d->color[2]);
+    const float3 bg = make_float3(d->background[0], d->background[1], d->background[2]);
+    const int* b = bins;
+    if (output == GV_RENDER_OUT_F32_QUANTIZED)
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32_QUANTIZED, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b,
+                           cap, color, bg, out, face_id, depth);
+    else if (output == GV_RENDER_OUT_F32)
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color,
+                           bg, out, face_id, depth);
+    else
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_U8, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color,
+                           bg, out, face_id, depth);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+
+int render_prepare(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
+                   int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
+                   const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes,
+                   int64_t* pair_total, int32_t* status, int ls, void* stream) {
+    if (!pair_total || !status) return GV_E_BADARG;
+    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
+                                cameras, workspace, workspace_bytes);
+    if (rc != GV_OK) return rc;
+    if (ls < 0) return GV_E_UNSUPPORTED;
+    const hipStream_t st = (hipStream_t)stream;
+    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    char* ws = static_cast<char*>(workspace);
+    MeshXf* xf = reinterpret_cast<MeshXf*>(ws + L.xf);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
+    const int T = a.tiles_x * a.tiles_y;
+    const long long nimg = (long long)n * desc->num_views;
+    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_count, 0, (size_t)nimg * T * 4, st));
+    GV_HIP_CHECK(hipMemsetAsync(ws + L.image_total, 0, (size_t)nimg * 8, st));
+    hipLaunchKernelGGL(normalise_kernel, dim3(n), dim3(RT), 0, st, verts, (const long long*)vert_offsets,
+                       (const long long*)tri_offsets, (long long)total_verts, (long long)total_tris, desc->fit, xf,
+                       status);
+    GV_LAUNCH_CHECK();
+    const dim3 grid = bin_grid(max_tris, desc->num_views, n);
+    int* tc = reinterpret_cast<int*>(ws + L.tile_count);
+    long long* it = reinterpret_cast<long long*>(ws + L.image_total);
+    float* shade = reinterpret_cast<float*>(ws + L.shade);
+    if (ls == 0) launch_count<0>(grid, st, a, tc, it, shade, desc);
+    else if (ls == 1) launch_count<1>(grid, st, a, tc, it, shade, desc);
+    else launch_count<2>(grid, st, a, tc, it, shade, desc);
+    GV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_images_kernel, dim3(1), dim3(SCAN_T), 0, st,
+                       reinterpret_cast<const long long*>(ws + L.image_total), nimg,
+                       reinterpret_cast<long long*>(ws + L.image_base), (long long*)pair_total);
+    GV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)nimg), dim3(SCAN_T), 0, st,
+                       reinterpret_cast<const int*>(ws + L.tile_count),
+                       reinterpret_cast<const long long*>(ws + L.image_base), T,
+                       reinterpret_cast<long long*>(ws + L.tile_start));
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+
+int render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
+                int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
+                const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
+                int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth, int ls,
+                void* stream) {
+    if (!bins || !out || total < 0) return GV_E_BADARG;
+    if (output != GV_RENDER_OUT_F32_QUANTIZED && output != GV_RENDER_OUT_F32 && output != GV_RENDER_OUT_U8)
+        return GV_E_BADARG;
+    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
+                                cameras, workspace, workspace_bytes);
+    if (rc != GV_OK) return rc;
+    if (ls < 0) return GV_E_UNSUPPORTED;
+    if (bins_bytes < gv_render_bins_bytes(total)) return GV_E_BADARG;
+    if (!gv_aligned16(bins) || (output != GV_RENDER_OUT_U8 && ((uintptr_t)out & 3u))) return GV_E_ALIGN;
+    if (((uintptr_t)face_id & 3u) || ((uintptr_t)depth & 3u)) return GV_E_ALIGN;
+    const hipStream_t st = (hipStream_t)stream;
+    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    char* ws = static_cast<char*>(workspace);
+    const MeshXf* xf = reinterpret_cast<const MeshXf*>(ws + L.xf);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
+    const int T = a.tiles_x * a.tiles_y;
+    const long long nimg = (long long)n * desc->num_views;
+    const long long cap = bins_bytes / 4;
+    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_fill, 0, (size_t)nimg * T * 4, st));
+    const dim3 bgrid = bin_grid(max_tris, desc->num_views, n);
+    const dim3 grid((unsigned)T, (unsigned)desc->num_views, (unsigned)n);
+    const float* shade = reinterpret_cast<const float*>(ws + L.shade);
+    const int* tc = reinterpret_cast<const int*>(ws + L.tile_count);
+    const long long* ts = reinterpret_cast<const long long*>(ws + L.tile_start);
+    int* tf = reinterpret_cast<int*>(ws + L.tile_fill);
+    int* b = static_cast<int*>(bins);
+    if (ls == 0) return launch_draw<0>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
+    if (ls == 1) return launch_draw<1>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
+    return launch_draw<2>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
+}
+
 }  // namespace
 
 extern "C" int64_t gv_render_workspace_bytes(int32_t n, int32_t num_views, int32_t height, int32_t width,
@@ -569,38 +754,8 @@ extern "C" int gv_render_prepare(const float* verts, const int64_t* vert_offsets
                                  int32_t max_tris, const gv_render_desc* desc, const float* cameras,
                                  const float* rotations, void* workspace, int64_t workspace_bytes, int64_t* pair_total,
                                  int32_t* status, void* stream) {
-    if (!pair_total || !status) return GV_E_BADARG;
-    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
-                                cameras, workspace, workspace_bytes);
-    if (rc != GV_OK) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
-    char* ws = static_cast<char*>(workspace);
-    MeshXf* xf = reinterpret_cast<MeshXf*>(ws + L.xf);
-    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_count, 0, (size_t)nimg * T * 4, st));
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.image_total, 0, (size_t)nimg * 8, st));
-    hipLaunchKernelGGL(normalise_kernel, dim3(n), dim3(RT), 0, st, verts, (const long long*)vert_offsets,
-                       (const long long*)tri_offsets, (long long)total_verts, (long long)total_tris, desc->fit, xf,
-                       status);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bin_kernel<false>, bin_grid(max_tris, desc->num_views, n), dim3(RT), 0, st, a,
-                       reinterpret_cast<int*>(ws + L.tile_count), reinterpret_cast<long long*>(ws + L.image_total),
-                       reinterpret_cast<float*>(ws + L.shade), make_float3(desc->light[0], desc->light[1], desc->light[2]),
-                       desc->ambient, (desc->flags & GV_RENDER_TWO_SIDED) ? 1 : 0, nullptr, nullptr, nullptr, 0ll);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_images_kernel, dim3(1), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const long long*>(ws + L.image_total), nimg,
-                       reinterpret_cast<long long*>(ws + L.image_base), (long long*)pair_total);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)nimg), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const int*>(ws + L.tile_count),
-                       reinterpret_cast<const long long*>(ws + L.image_base), T,
-                       reinterpret_cast<long long*>(ws + L.tile_start));
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return render_prepare(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                          rotations, workspace, workspace_bytes, pair_total, status, 0, stream);
 }
 
 extern "C" int gv_render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
@@ -608,44 +763,32 @@ extern "C" int gv_render_draw(const float* verts, const int64_t* vert_offsets, c
                               int32_t max_tris, const gv_render_desc* desc, const float* cameras, const float* rotations,
                               void* workspace, int64_t workspace_bytes, void* bins, int64_t bins_bytes, int64_t total,
                               int32_t output, void* out, int32_t* face_id, uint32_t* depth, void* stream) {
-    if (!bins || !out || total < 0) return GV_E_BADARG;
-    if (output != GV_RENDER_OUT_F32_QUANTIZED && output != GV_RENDER_OUT_F32 && output != GV_RENDER_OUT_U8)
-        return GV_E_BADARG;
-    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
-                                cameras, workspace, workspace_bytes);
-    if (rc != GV_OK) return rc;
-    if (bins_bytes < gv_render_bins_bytes(total)) return GV_E_BADARG;
-    if (!gv_aligned16(bins) || (output != GV_RENDER_OUT_U8 && ((uintptr_t)out & 3u))) return GV_E_ALIGN;
-    if (((uintptr_t)face_id & 3u) || ((uintptr_t)depth & 3u)) return GV_E_ALIGN;
-    const hipStream_t st = (hipStream_t)stream;
-    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
-    char* ws = static_cast<char*>(workspace);
-    const MeshXf* xf = reinterpret_cast<const MeshXf*>(ws + L.xf);
-    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
-    const long long cap = bins_bytes / 4;
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_fill, 0, (size_t)nimg * T * 4, st));
-    hipLaunchKernelGGL(bin_kernel<true>, bin_grid(max_tris, desc->num_views, n), dim3(RT), 0, st, a, nullptr, nullptr,
-                       nullptr, make_float3(0.f, 0.f, 0.f), 0.f, 0, reinterpret_cast<const long long*>(ws + L.tile_start),
-                       reinterpret_cast<int*>(ws + L.tile_fill), static_cast<int*>(bins), cap);
-    GV_LAUNCH_CHECK();
-    const float3 color = make_float3(desc->color[0], desc->color[1], desc->color[2]);
-    const float3 bg = make_float3(desc->background[0], desc->background[1], desc->background[2]);
-    const dim3 grid((unsigned)T, (unsigned)desc->num_views, (unsigned)n);
-    const float* shade = reinterpret_cast<const float*>(ws + L.shade);
-    const int* tc = reinterpret_cast<const int*>(ws + L.tile_count);
-    const long long* ts = reinterpret_cast<const long long*>(ws + L.tile_start);
-    const int* b = static_cast<const int*>(bins);
-    if (output == GV_RENDER_OUT_F32_QUANTIZED)
-        hipLaunchKernelGGL(raster_kernel<GV_RENDER_OUT_F32_QUANTIZED>, grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap,
-                           color, bg, out, face_id, depth);
-    else if (output == GV_RENDER_OUT_F32)
-        hipLaunchKernelGGL(raster_kernel<GV_RENDER_OUT_F32>, grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color, bg,
-                           out, face_id, depth);
-    else
-        hipLaunchKernelGGL(raster_kernel<GV_RENDER_OUT_U8>, grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color, bg,
-                           out, face_id, depth);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return render_draw(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                       rotations, workspace, workspace_bytes, bins, bins_bytes, total, output, out, face_id, depth, 0,
+                       stream);
+}
+
+// the same pair with S x S samples per pixel (S = samples: 1, 2 or 4)
+extern "C" int gv_render_prepare_ss(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                                    const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                                    int32_t max_tris, const gv_render_desc* desc, const float* cameras,
+                                    const float* rotations, void* workspace, int64_t workspace_bytes,
+                                    int64_t* pair_total, int32_t* status, int32_t samples, void* stream) {
+    int ls = 0;
+    if (!sample_shift(samples, &ls)) return GV_E_BADARG;
+    return render_prepare(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                          rotations, workspace, workspace_bytes, pair_total, status, ls, stream);
+}
+
+extern "C" int gv_render_draw_ss(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                                 const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                                 int32_t max_tris, const gv_render_desc* desc, const float* cameras,
+                                 const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
+                                 int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id,
+                                 uint32_t* depth, int32_t samples, void* stream) {
+    int ls = 0;
+    if (!sample_shift(samples, &ls)) return GV_E_BADARG;
+    return render_draw(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                       rotations, workspace, workspace_bytes, bins, bins_bytes, total, output, out, face_id, depth, ls,
+                       stream);
 }

@@ -21,7 +21,10 @@ reproducible bit for bit:
     f = ambient + (1 - ambient) * (s + 1) / 2 (matplotlib's _shade_colors with ambient 0.3; two_sided: |s|),
     colour = color * f on a background colour;
   - uint8 = floor(c * 255 + 0.5); quantize=True gives fma(uint8, 1/255, -0.5), rounded once (what the record pipeline's
-    gv_preprocess_views computes from a PNG, so a render equals its own PNG round trip); quantize=False gives c - 0.5.
+    gv_preprocess_views computes from a PNG, so a render equals its own PNG round trip); quantize=False gives c - 0.5;
+  - samples=S (1, 2 or 4): S x S coverage and depth samples per pixel on a regular grid ((256 / S) * a + 128 / S in
+    1/256 pixel), each treated as a pixel centre above and resolved in the same launch: the uint8 pixel is the rounded
+    mean of the samples' uint8 values, the unquantised one the mean of their colours added in row-major order, - 0.5.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
@@ -338,11 +341,12 @@ class ViewRenderer:
     one per view; azimuths: degrees (default (i + 1) * 360 / V); fov: 0 (orthographic) or a perspective field of view
     in degrees, (0, 120]; fit: the normalised radius in (0, 1]; color / background: RGB in [0, 1]; light: a direction
     (normalised here); max_workspace_bytes: a batch whose workspace or tile lists would pass it is rendered in groups of
-    meshes, with identical results."""
+    meshes, with identical results; samples: 1, 2 or 4 coverage samples per pixel and axis (anti-aliasing; 1 is one sample
+    at the pixel centre)."""
 
     def __init__(self, num_views, height, width, elevation=30.0, azimuths=None, fov=0.0, fit=0.9,
                  color=DEFAULT_COLOR, background=DEFAULT_BACKGROUND, light=DEFAULT_LIGHT, ambient=0.3,
-                 two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE):
+                 two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE, samples=1):
         if not 1 <= int(num_views) <= MAX_VIEWS:
             raise ValueError("num_views must be in [1, %d]" % MAX_VIEWS)
         if not (1 <= int(height) <= MAX_SIDE and 1 <= int(width) <= MAX_SIDE):
@@ -353,6 +357,10 @@ class ViewRenderer:
             raise ValueError("ambient must be in [0, 1]")
         if not (fov == 0 or 0.0 < fov <= 120.0):
             raise ValueError("fov must be 0 (orthographic) or in (0, 120] degrees")
+        if samples not in (1, 2, 4):
+            raise ValueError("samples must be 1, 2 or 4")
+        self.samples = int(samples)
+        self._ss = self.samples > 1                      # through gv_render_*_ss (samples = 1: the original pair)
         self.lib = _lib.load()
         self.V, self.H, self.W = int(num_views), int(height), int(width)
         self.azimuths = default_azimuths(self.V) if azimuths is None else [float(a) for a in azimuths]
@@ -387,7 +395,7 @@ class ViewRenderer:
         return {"height": d.height, "width": d.width, "num_views": d.num_views, "flags": d.flags, "fit": d.fit,
                 "proj_scale": d.proj_scale, "persp_dist": d.persp_dist, "depth_a": d.depth_a, "depth_b": d.depth_b,
                 "ambient": d.ambient, "light": list(d.light), "color": list(d.color),
-                "background": list(d.background), "cameras": self.cameras_host.copy()}
+                "background": list(d.background), "cameras": self.cameras_host.copy(), "samples": self.samples}
 
     def _rotations(self, rotations, n):
         if rotations is None:
@@ -418,8 +426,14 @@ class ViewRenderer:
         info = torch.empty(1 + (n + 1) // 2, dtype=torch.int64, device=self.device)     # pair total, then status
         st_dev = info[1:].view(torch.int32)
         rp = None if rot is None else rot.data_ptr() + a * 36
-        _lib.check(lib.gv_render_prepare(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
-                                         info.data_ptr(), st_dev.data_ptr(), _model._st()), "gv_render_prepare")
+        S = self.samples
+        if not self._ss:
+            rc = lib.gv_render_prepare(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, info.data_ptr(),
+                                       st_dev.data_ptr(), _model._st())
+        else:
+            rc = lib.gv_render_prepare_ss(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
+                                          info.data_ptr(), st_dev.data_ptr(), S, _model._st())
+        _lib.check(rc, "gv_render_prepare")
         host = info.cpu().numpy()                                        # the one host read of a render
         total = int(host[0])
         status[a:b] = host[1:].view(np.int32)[:n]
@@ -434,11 +448,15 @@ class ViewRenderer:
         bins = torch.empty(bins_bytes, dtype=torch.uint8, device=self.device)
         img = self.V * self.H * self.W
         esz = 1 if output == _lib.GV_RENDER_OUT_U8 else 4
-        _lib.check(lib.gv_render_draw(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
-                                      bins.data_ptr(), bins_bytes, total, output, out.data_ptr() + a * img * 3 * esz,
-                                      None if face_id is None else face_id.data_ptr() + a * img * 4,
-                                      None if depth is None else depth.data_ptr() + a * img * 4, _model._st()),
-                   "gv_render_draw")
+        tail = (d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, bins.data_ptr(), bins_bytes, total, output,
+                out.data_ptr() + a * img * 3 * esz,
+                None if face_id is None else face_id.data_ptr() + a * img * S * S * 4,        # the sample grid
+                None if depth is None else depth.data_ptr() + a * img * S * S * 4)
+        if not self._ss:
+            rc = lib.gv_render_draw(*args, *tail, _model._st())
+        else:
+            rc = lib.gv_render_draw_ss(*args, *tail, S, _model._st())
+        _lib.check(rc, "gv_render_draw")
 
     def _render(self, batch, rotations, out, output, return_buffers):
         with torch.cuda.device(self.device):
@@ -454,8 +472,9 @@ class ViewRenderer:
                 raise ValueError("out must be a contiguous %s tensor %s on %s" % (dt, shape, self.device))
             face_id = depth = None
             if return_buffers:
-                face_id = torch.empty(shape[:4], dtype=torch.int32, device=self.device)
-                depth = torch.empty(shape[:4], dtype=torch.int32, device=self.device)   # uint32 bits
+                grid = (n, self.V, self.samples * self.H, self.samples * self.W)        # one entry per sample
+                face_id = torch.empty(grid, dtype=torch.int32, device=self.device)
+                depth = torch.empty(grid, dtype=torch.int32, device=self.device)        # uint32 bits
             status = np.zeros(n, np.int32)
             self._draw(batch, 0, n, rot, output, out, face_id, depth, status)
             self.status = status
@@ -464,10 +483,11 @@ class ViewRenderer:
             return out
 
     def render(self, batch, rotations=None, out=None, quantize=True, return_buffers=False):
-        """views fp32 [N, V, H, W, 3] on the device (and (face_id int32, depth) [N, V, H, W] with return_buffers; depth
-        is an int32 tensor holding the uint32 values, -1 = 0xFFFFFFFF = background).  batch: a MeshBatch or a list of
-        (verts, tris).  rotations: [N, 3, 3] rotation matrices (check_rotations) or None; pass them as a host array to
-        keep to one host read (the tile-list size) per mesh group."""
+        """views fp32 [N, V, H, W, 3] on the device (and (face_id int32, depth) [N, V, S*H, S*W] with return_buffers, one
+        entry per sample, S = samples; depth is an int32 tensor holding the uint32 values, -1 = 0xFFFFFFFF =
+        background).  batch: a MeshBatch or a list of (verts, tris).  rotations: [N, 3, 3] rotation matrices
+        (check_rotations) or None; pass them as a host array to keep to one host read (the tile-list size) per mesh
+        group."""
         output = _lib.GV_RENDER_OUT_F32_QUANTIZED if quantize else _lib.GV_RENDER_OUT_F32
         return self._render(batch, rotations, out, output, return_buffers)
 

@@ -531,6 +531,40 @@ int gv_render_draw(const float* verts, const int64_t* vert_offsets, const int32_
                    const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
                    int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth,
                    void* stream);
+/* Anti-aliased renders: the same pair with S x S coverage and depth samples per pixel, S = samples in {1, 2, 4}, kept
+ * in registers and resolved to one pixel in the same launch.  Everything up to the snapped vertices and the shading
+ * factor is unchanged.
+ *  - sample positions: step = 256 / S; sample (a, b) of pixel (i, j), a, b in [0, S), sits at x = 256 i + step*a + step/2,
+ *    y = 256 j + step*b + step/2: integers on the vertices' grid (S = 2: offsets 64, 192; S = 4: 32, 96, 160, 224; S = 1:
+ *    the pixel centre).
+ *  - coverage and depth: every sample is treated exactly as a pixel centre above (integer edge functions at the sample,
+ *    top-left rule, Z = (e0*Z0 + e1*Z1 + e2*Z2) div area, smallest key (Z << 32) | id).  Coordinates are not rescaled:
+ *    the 2^62 bound holds as it stands.
+ *  - binning: with g = S*i + a the sample index along an axis, a triangle's sample box is
+ *    g0 = max((min + step/2 - 1) >> log2(step), 0) .. g1 = min((max - step/2) >> log2(step), S*W - 1) (rows likewise, with
+ *    H); it is dropped when g0 > g1 and belongs to the tiles of pixels g0 / S .. g1 / S (S = 1: (min + 127) >> 8 ..
+ *    (max - 128) >> 8).  The tile lists therefore depend on S: draw_ss must be given the samples of the prepare_ss that
+ *    filled the workspace.
+ *  - resolve: sample colour c_s = background, or color * f of its triangle.  GV_RENDER_OUT_U8: u8_s = clamp(floor(c_s*255
+ *    + 0.5), 0, 255) per sample and channel, pixel = (sum_s u8_s + S*S/2) div (S*S), exact integers;
+ *    GV_RENDER_OUT_F32_QUANTIZED: fma(pixel u8, 1/255, -0.5) (still its own PNG round trip); GV_RENDER_OUT_F32: per
+ *    channel the c_s added in row-major sample order (b outer, a inner), one rounding per add, times 1/(S*S) (exact), plus
+ *    -0.5 (S = 1: c - 0.5).
+ *  - face_id / depth, when requested, are on the sample grid: [N, V, S*H, S*W], sample (a, b) of pixel (i, j) at row
+ *    S*j + b, column S*i + a; background -1 / 0xFFFFFFFF.
+ * Status codes, gv_render_workspace_bytes and gv_render_bins_bytes (with the pair total of prepare_ss) are unchanged.
+ * samples <= 0 or not a power of two: GV_E_BADARG; a power of two above 4: GV_E_UNSUPPORTED; every other rejection as in
+ * the pair above.  samples = 1 gives bitwise the results of the pair above. */
+int gv_render_prepare_ss(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                         const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                         int32_t max_tris, const gv_render_desc* desc, const float* cameras, const float* rotations,
+                         void* workspace, int64_t workspace_bytes, int64_t* pair_total, int32_t* status, int32_t samples,
+                         void* stream);
+int gv_render_draw_ss(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
+                      int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
+                      const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
+                      int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth,
+                      int32_t samples, void* stream);
 
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several

@@ -1,12 +1,16 @@
 """Rasteriser throughput on seeded synthetic meshes; prints one JSON line.
 
-    python tools/render_bench.py [--forward c4|c2] [--steps 20] [--warmup 5]
+    python tools/render_bench.py [--forward c4|c2] [--samples 1,2,4] [--pool-baseline] [--steps 20] [--warmup 5]
 
 Cases: icospheres of 80, 1 280, 20 480 and 327 680 faces and a giant/tiny mix (two screen-size triangles + 20 000
 small ones), N = 32 meshes x V = 12 views at 224^2 and 299^2, each mesh under its own random rotation.  Per case: ms per
 batch (device events around the whole render: prepare, the one host read of the tile-list size, draw; after warm-up),
 meshes/s, views/s and triangle-views/s.  --forward c4 (bf16 ResNet-v2-50) or c2 (fp32 Inception-v3): the GVCNN
-forward time of the same views, so the render cost reads against what it feeds.
+forward time of the same views, so the render cost reads against what it feeds.  --samples: the anti-aliased renders
+(S x S samples per pixel resolved in the rasteriser), one case per S, each with the device time of its prepare and draw
+calls (events around the two C-ABI calls; the rest of "ms" is the host read between them).  --pool-baseline: next to
+every S = 2 case whose doubled side the rasteriser takes (<= 512), what one sample per pixel can do: render at 2H x 2W
+and average-pool in torch.
 """
 import argparse
 import json
@@ -46,6 +50,47 @@ def timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+class SplitTimer:
+    """Stands in for the library of a ViewRenderer: device events around every prepare and every draw call."""
+
+    def __init__(self, lib):
+        self.lib, self.events = lib, {"prepare": [], "draw": []}
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+        kind = "prepare" if name.startswith("gv_render_prepare") else "draw" if name.startswith("gv_render_draw") else None
+        if kind is None:
+            return fn
+
+        def call(*args):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            rc = fn(*args)
+            b.record()
+            self.events[kind].append((a, b))
+            return rc
+        return call
+
+    def ms(self, kind, steps):
+        """device ms per render of the calls of `kind` (after a synchronize)."""
+        return sum(a.elapsed_time(b) for a, b in self.events[kind]) / steps
+
+
+def timed_split(r, fn, steps, warmup):
+    """(ms, prepare ms, draw ms) per render: the whole render as `timed` measures it, then the two calls' own times in
+    a second pass (the extra events stay out of the first)."""
+    ms = timed(fn, steps, warmup)
+    lib = r.lib
+    r.lib = t = SplitTimer(lib)
+    try:
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+    finally:
+        r.lib = lib
+    return ms, t.ms("prepare", steps), t.ms("draw", steps)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--forward", choices=sorted(FORWARD))
@@ -54,6 +99,11 @@ def main(argv=None):
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--views", type=int, default=12)
     ap.add_argument("--sizes", default="224,299")
+    ap.add_argument("--samples", default="1", help="samples per pixel and axis, comma separated (1, 2, 4)")
+    ap.add_argument("--pool-baseline", action="store_true",
+                    help="next to S = 2: one sample per pixel at twice the side, then avg_pool2d")
+    ap.add_argument("--meshes", default="", help="comma separated subset of the mesh names (default: all)")
+    ap.add_argument("--table", action="store_true", help="a plain-text table of the cases in front of the JSON line")
     a = ap.parse_args(argv)
     import gvcnn_tf_amd as gv
     from gvcnn_tf_amd import render as R
@@ -62,19 +112,39 @@ def main(argv=None):
     N, V = a.n, a.views
     meshes = {"ico80": R.icosphere(1), "ico1k": R.icosphere(3), "ico20k": R.icosphere(5), "ico330k": R.icosphere(7),
               "giant_tiny": giant_tiny()}
+    if a.meshes:
+        meshes = {k: meshes[k] for k in a.meshes.split(",")}
     rots = R.random_rotations(N, "so3", seed=0)
+    samples = [int(s) for s in a.samples.split(",")]
     cases = []
     for size in [int(s) for s in a.sizes.split(",")]:
-        r = R.ViewRenderer(V, size, size, device=dev)
         out = torch.empty((N, V, size, size, 3), dtype=torch.float32, device=dev)
-        for name, m in meshes.items():
-            batch = R.MeshBatch([m] * N, dev)
-            ms = timed(lambda: r.render(batch, rotations=rots, out=out), a.steps, a.warmup)
-            case = {"mesh": name, "faces": int(len(m[1])), "size": size, "N": N, "V": V, "ms": round(ms, 4),
-                    "meshes_per_s": round(N / ms * 1e3, 1), "views_per_s": round(N * V / ms * 1e3, 1),
-                    "tri_views_per_s": float("%.4g" % (N * V * len(m[1]) / ms * 1e3))}
-            cases.append(case)
-            del batch
+        for S in samples:
+            r = R.ViewRenderer(V, size, size, device=dev, samples=S)
+            for name, m in meshes.items():
+                batch = R.MeshBatch([m] * N, dev)
+                ms, prep, draw = timed_split(r, lambda: r.render(batch, rotations=rots, out=out), a.steps, a.warmup)
+                case = {"mesh": name, "faces": int(len(m[1])), "size": size, "samples": S, "N": N, "V": V,
+                        "ms": round(ms, 4), "prepare_ms": round(prep, 4), "draw_ms": round(draw, 4),
+                        "meshes_per_s": round(N / ms * 1e3, 1), "views_per_s": round(N * V / ms * 1e3, 1),
+                        "tri_views_per_s": float("%.4g" % (N * V * len(m[1]) / ms * 1e3))}
+                cases.append(case)
+                if a.pool_baseline and S == 2 and 2 * size <= R.MAX_SIDE:
+                    big = R.ViewRenderer(V, 2 * size, 2 * size, device=dev)
+                    wide = torch.empty((N, V, 2 * size, 2 * size, 3), dtype=torch.float32, device=dev)
+
+                    def pooled():
+                        big.render(batch, rotations=rots, out=wide, quantize=False)
+                        x = wide.view(N * V, 2 * size, 2 * size, 3).permute(0, 3, 1, 2)       # NCHW view of NHWC
+                        y = torch.nn.functional.avg_pool2d(x, 2)
+                        out.view(N * V, size, size, 3).copy_(y.permute(0, 2, 3, 1))
+                    ms = timed(pooled, a.steps, a.warmup)
+                    cases.append({"mesh": name, "faces": int(len(m[1])), "size": size, "samples": 1,
+                                  "baseline": "render at %d^2 + avg_pool2d(2)" % (2 * size), "N": N, "V": V,
+                                  "ms": round(ms, 4), "meshes_per_s": round(N / ms * 1e3, 1),
+                                  "views_per_s": round(N * V / ms * 1e3, 1)})
+                    del big, wide
+                del batch
         if a.forward:
             backbone, storage = FORWARD[a.forward]
             eng = gv.GVCNN(backbone, N, V, size, size, 40, 10, device=dev, storage=storage)
@@ -83,6 +153,14 @@ def main(argv=None):
                           "ms": round(ms, 4), "views_per_s": round(N * V / ms * 1e3, 1)})
             del eng
             torch.cuda.empty_cache()
+    if a.table:
+        print("%-11s %7s %5s %2s  %9s %10s %9s  %s" % ("mesh", "faces", "size", "S", "ms/batch", "prepare ms", "draw ms", ""))
+        for c in cases:
+            if "mesh" in c:
+                print("%-11s %7d %5d %2d  %9.3f %10s %9s  %s" % (
+                    c["mesh"], c["faces"], c["size"], c["samples"], c["ms"],
+                    "%.3f" % c["prepare_ms"] if "prepare_ms" in c else "-",
+                    "%.3f" % c["draw_ms"] if "draw_ms" in c else "-", c.get("baseline", "")))
     print(json.dumps({"metric": "render_ms_per_batch", "unit": "ms", "cases": cases}))
 
 

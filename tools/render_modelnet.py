@@ -1,7 +1,7 @@
 """ModelNet meshes -> GZIP TFRecords of rendered views, on the device (replaces the reference's off2obj.py ->
 obj2png.py -> create_modelnet_tf_record.py chain).
 
-    python tools/render_modelnet.py --src ModelNet40 --split train --out modelnet40_train.tfrecord --views 12 --size 224
+    python tools/render_modelnet.py --src ModelNet40 --split train --out modelnet40_train.tfrecord --views 12 --size 224 [--samples 4]
 
 Walks SRC/<class>/<split>/*.off in sorted order; the label of a shape is the index of its class directory among the
 sorted class directories (create_modelnet_tf_record.py's convention).  Meshes are rendered `--batch` at a time with
@@ -36,6 +36,8 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--elevation", type=float, default=30.0)
     ap.add_argument("--fov", type=float, default=0.0)
+    ap.add_argument("--samples", type=int, default=1, choices=(1, 2, 4),
+                    help="coverage samples per pixel and axis (anti-aliasing inside the rasteriser)")
     ap.add_argument("--batch", type=int, default=32, help="meshes per device render")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -47,7 +49,8 @@ def main(argv=None):
     if not shapes:
         raise SystemExit("no %s/*.off files under %s" % (a.split, a.src))
     dev = torch.device(a.device)
-    r = render.ViewRenderer(a.views, a.size, a.size, elevation=a.elevation, fov=a.fov, device=dev)
+    r = render.ViewRenderer(a.views, a.size, a.size, elevation=a.elevation, fov=a.fov, device=dev,
+                            samples=a.samples)
 
     def examples():
         for b0 in range(0, len(shapes), a.batch):
