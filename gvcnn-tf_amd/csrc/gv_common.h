@@ -79,6 +79,13 @@ __device__ __forceinline__ int gv_div(int m, const GvFastDiv& f) {
 
 static inline int gv_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline bool gv_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// rows of p (stride ld elements) can be walked in 16-byte accesses of n elements; nullptr: an operand that is not used
+static inline bool gv_vec_ok(const void* p, int ld, int n) { return p == nullptr || (gv_aligned16(p) && ld % n == 0); }
+// workgroups of 256 threads for a grid-stride loop over `total` items
+static inline unsigned gv_grid_for(int64_t total) {
+    const int64_t b = (total + 255) / 256, cap = 256 * 16;
+    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
+}
 
 // ---- where a filter-gradient launch puts its partial tiles ------------------------------------------------------
 // A filter gradient splits the pixel axis over workgroups ("slices"); every slice produces a partial of each

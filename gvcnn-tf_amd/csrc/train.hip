@@ -133,8 +133,6 @@ void launch_grouped_sums(dim3 grid, hipStream_t st, bool vec, const float* z, in
                            nb, hw, c, G, acc, scale, shift);
 }
 
-inline bool vec_ok(const void* p, int ld) { return p == nullptr || ((((uintptr_t)p) & 15u) == 0 && (ld & 3) == 0); }
-
 // mean/var (biased) + folded scale/shift per (group, channel)
 __global__ void bn_finalize_grouped(const double* __restrict__ acc, int G, int c, const int* __restrict__ counts,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -492,12 +490,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const float* __restrict__ 
     }
 }
 
-inline unsigned grid_for(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    const int64_t cap = 256 * 16;
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
 
 // Storage-typed loads of the filter-gradient kernels: S = float, __bf16 or _Float16 in HBM, fp32 in registers.
 template <typename S>
@@ -797,27 +789,46 @@ extern "C" int gv_bn_update_moving_batched(const gv_bn_moving_job* jobs_dev, int
     return GV_OK;
 }
 
-extern "C" int gv_bn_sums_grouped(const float* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
-                                  int32_t num_groups, double* accum, void* stream) {
+// ---- the HBM-bound ops of the training step: one implementation per op -----------------------------------------------
+// The storage-typed `_t` entry point (dtype GV_F32 | GV_BF16 | GV_F16, for some ops with GV_ACCUM_* bits OR-ed in) is the
+// implementation: it checks the arguments, clears the accumulator, picks the pixel splits and calls gvlp:: (the streaming
+// kernels of train_lp.hip, instantiated for every storage type).  A GV_F32 shape that gvlp:: declines runs the scalar
+// fp32 kernel of this file; a 16-bit one has its scalar kernel behind gvlp::.  The fp32 entry point passes GV_F32.
+static inline bool storage_type(int dtype) { return dtype == GV_F32 || dtype == GV_BF16 || dtype == GV_F16; }
+
+// pixel splits of a sums launch: 2048 pixels per workgroup on the big layers, but at least ~1024 workgroups in total
+// (down to 128 pixels per workgroup) on the small, latency-bound ones
+static inline int sums_splits(int64_t npix, int cap, int c = 64, int G = 1) {
+    int64_t splits = (npix + 2047) / 2048;
+    const int64_t want = 1024 / ((int64_t)((c + 63) / 64) * G) + 1, most = (npix + 127) / 128;
+    if (splits < want) splits = want < most ? want : most;
+    return (int)(splits > cap ? cap : (splits < 1 ? 1 : splits));
+}
+
+extern "C" int gv_bn_sums_grouped_t(const void* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
+                                    int32_t num_groups, double* accum, int32_t dtype, void* stream) {
+    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;          // the caller keeps a pre-zeroed accumulator per layer
+    dtype &= ~GV_ACCUM_ZEROED;
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!z || !accum) return GV_E_BADARG;
     if (nb <= 0 || hw <= 0 || c <= 0 || z_ld < c || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    const int64_t npix = (int64_t)(nb / num_groups) * hw;
-    int splits = (int)((npix + 2047) / 2048);
-    {   // at least ~1024 workgroups on the small late layers (latency-bound), down to 128 pixels per workgroup
-        const int64_t want = 1024 / ((int64_t)((c + 63) / 64) * num_groups) + 1, most = (npix + 127) / 128;
-        if (splits < want) splits = (int)(want < most ? want : most);
-    }
-    if (splits > 256) splits = 256;
-    // (the streaming kernels of train_lp.hip, instantiated for fp32, when the shape is 16-byte vectorisable)
-    if (gvlp::grouped_sums(GV_F32, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb, hw, c,
-                           num_groups, splits, accum, st) == GV_OK)
-        return GV_OK;
-    launch_grouped_sums<0>(dim3((c + 63) / 64, splits, num_groups), st, (c & 3) == 0 && vec_ok(z, z_ld), z, z_ld,
+    if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
+        GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
+    const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
+    const int rc = gvlp::grouped_sums(dtype, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb,
+                                      hw, c, num_groups, splits, accum, st);
+    if (rc == GV_OK || dtype != GV_F32) return rc;
+    const float* zf = (const float*)z;
+    launch_grouped_sums<0>(dim3((c + 63) / 64, splits, num_groups), st, (c & 3) == 0 && gv_vec_ok(zf, z_ld, 4), zf, z_ld,
                            nullptr, 0, nullptr, 0, nullptr, nullptr, nb, hw, c, num_groups, accum);
     GV_LAUNCH_CHECK();
     return GV_OK;
+}
+
+extern "C" int gv_bn_sums_grouped(const float* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
+                                  int32_t num_groups, double* accum, void* stream) {
+    return gv_bn_sums_grouped_t(z, nb, hw, c, z_ld, num_groups, accum, GV_F32, stream);
 }
 
 extern "C" int gv_bn_finalize_grouped(const double* accum, int32_t c, int32_t num_groups, const int32_t* counts,
@@ -840,75 +851,106 @@ extern "C" int gv_bn_stats_grouped(const float* z, int32_t nb, int32_t hw, int32
     return gv_bn_finalize_grouped(accum, c, num_groups, counts, gamma, beta, eps, mean, var, inv, scale, shift, stream);
 }
 
-extern "C" int gv_scale_shift_act_grouped(const float* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
-                                          const float* scale, const float* shift, int32_t num_groups,
-                                          int32_t relu, float* y, int32_t y_ld, void* stream) {
+extern "C" int gv_scale_shift_act_grouped_t(const void* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
+                                            const float* scale, const float* shift, int32_t num_groups,
+                                            int32_t relu, void* y, int32_t y_ld, int32_t dtype, void* stream) {
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!x || !y || !scale || !shift || nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0)
         return GV_E_BADARG;
-    if ((c & 3) || (x_ld & 3) || (y_ld & 3) || !gv_aligned16(x) || !gv_aligned16(y) || !gv_aligned16(scale) ||
-        !gv_aligned16(shift))
+    // (the scalar fp32 kernel works in float4 as well; the 16-bit one takes any shape)
+    if (dtype == GV_F32 && ((c & 3) || (x_ld & 3) || (y_ld & 3) || !gv_aligned16(x) || !gv_aligned16(y) ||
+                            !gv_aligned16(scale) || !gv_aligned16(shift)))
         return GV_E_ALIGN;
-    if (gvlp::scale_shift_act_grouped(GV_F32, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld,
-                                      (hipStream_t)stream) == GV_OK)
-        return GV_OK;
-    hipLaunchKernelGGL(scale_shift_act_grouped_f32, dim3(grid_for((int64_t)nb * hw * (c / 4))), dim3(256), 0,
-                       (hipStream_t)stream, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = gvlp::scale_shift_act_grouped(dtype, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, st);
+    if (rc == GV_OK || dtype != GV_F32) return rc;
+    hipLaunchKernelGGL(scale_shift_act_grouped_f32, dim3(gv_grid_for((int64_t)nb * hw * (c / 4))), dim3(256), 0, st,
+                       (const float*)x, nb, hw, c, x_ld, scale, shift, num_groups, relu, (float*)y, y_ld);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
 
-static int bn_bwd_sums_f32(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld, const float* z, int32_t z_ld,
-                           const float* mean, const float* inv, int32_t nb, int32_t hw, int32_t c, int32_t num_groups,
-                           double* accum, const float* scale, const float* shift, void* stream);
+extern "C" int gv_scale_shift_act_grouped(const float* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
+                                          const float* scale, const float* shift, int32_t num_groups,
+                                          int32_t relu, float* y, int32_t y_ld, void* stream) {
+    return gv_scale_shift_act_grouped_t(x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, GV_F32, stream);
+}
+
+extern "C" int gv_bn_finalize_apply_grouped_t(const double* accum, const int32_t* counts, const float* gamma,
+                                              const float* beta, float eps, const void* x, int32_t nb, int32_t hw,
+                                              int32_t c, int32_t x_ld, int32_t num_groups, int32_t relu, void* y,
+                                              int32_t y_ld, float* mean, float* var, float* inv, float* scale,
+                                              float* shift, int32_t dtype, void* stream) {
+    if (!accum || !counts || !beta || !x || !y || !mean || !var || !inv || !scale || !shift) return GV_E_BADARG;
+    if (nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0) return GV_E_BADARG;
+    // one fused launch where the shape streams; else the two ops (which also reject an unknown dtype)
+    int rc = gvlp::bn_finalize_apply_grouped(dtype, accum, counts, gamma, beta, eps, x, nb, hw, c, x_ld, num_groups, relu,
+                                             y, y_ld, mean, var, inv, scale, shift, (hipStream_t)stream);
+    if (rc != GV_E_UNSUPPORTED) return rc;
+    rc = gv_bn_finalize_grouped(accum, c, num_groups, counts, gamma, beta, eps, mean, var, inv, scale, shift, stream);
+    if (rc != GV_OK) return rc;
+    return gv_scale_shift_act_grouped_t(x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, dtype, stream);
+}
+
+// scale / shift (both or neither): the ReLU mask is recomputed from z when y was not kept
+extern "C" int gv_bn_relu_bwd_sums_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
+                                             const void* z, int32_t z_ld, const float* mean, const float* inv,
+                                             int32_t nb, int32_t hw, int32_t c, int32_t num_groups, double* accum,
+                                             const float* scale, const float* shift, int32_t dtype, void* stream) {
+    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;
+    dtype &= ~GV_ACCUM_ZEROED;
+    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!dy || !z || !mean || !inv || !accum) return GV_E_BADARG;
+    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
+        GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
+    const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
+    const int rc = gvlp::grouped_sums(dtype, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c,
+                                      num_groups, splits, accum, st);
+    if (rc == GV_OK || dtype != GV_F32) return rc;
+    const float *zf = (const float*)z, *df = (const float*)dy, *yf = (const float*)y;
+    launch_grouped_sums<1>(dim3((c + 63) / 64, splits, num_groups), st,
+                           (c & 3) == 0 && gv_vec_ok(zf, z_ld, 4) && gv_vec_ok(df, dy_ld, 4) && gv_vec_ok(yf, y_ld, 4), zf,
+                           z_ld, df, dy_ld, yf, y_ld, mean, inv, nb, hw, c, num_groups, accum, scale, shift);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
 
 extern "C" int gv_bn_relu_bwd_sums_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
                                            const float* z, int32_t z_ld, const float* mean, const float* inv,
                                            int32_t nb, int32_t hw, int32_t c, int32_t num_groups, double* accum,
                                            void* stream) {
-    return bn_bwd_sums_f32(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, nb, hw, c, num_groups, accum, nullptr, nullptr, stream);
+    return gv_bn_relu_bwd_sums_grouped_t(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, nb, hw, c, num_groups, accum, nullptr,
+                                         nullptr, GV_F32, stream);
 }
 
-static int bn_bwd_sums_f32(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld, const float* z, int32_t z_ld,
-                           const float* mean, const float* inv, int32_t nb, int32_t hw, int32_t c, int32_t num_groups,
-                           double* accum, const float* scale, const float* shift, void* stream) {
-    if (!dy || !z || !mean || !inv || !accum) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    const int64_t npix = (int64_t)(nb / num_groups) * hw;
-    int splits = (int)((npix + 2047) / 2048);
-    {   // at least ~1024 workgroups on the small late layers (latency-bound), down to 128 pixels per workgroup
-        const int64_t want = 1024 / ((int64_t)((c + 63) / 64) * num_groups) + 1, most = (npix + 127) / 128;
-        if (splits < want) splits = (int)(want < most ? want : most);
-    }
-    if (splits > 256) splits = 256;
-    if (gvlp::grouped_sums(GV_F32, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c, num_groups, splits,
-                           accum, st) == GV_OK)
-        return GV_OK;
-    launch_grouped_sums<1>(dim3((c + 63) / 64, splits, num_groups), st,
-                           (c & 3) == 0 && vec_ok(z, z_ld) && vec_ok(dy, dy_ld) && vec_ok(y, y_ld), z, z_ld, dy, dy_ld, y,
-                           y_ld, mean, inv, nb, hw, c, num_groups, accum, scale, shift);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-static int bn_bwd_apply_f32(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld, const float* z, int32_t z_ld,
-                            const float* mean, const float* inv, const float* gamma, const int32_t* counts, int32_t nb,
-                            int32_t hw, int32_t c, int32_t num_groups, const double* accum, float* dz, int32_t dz_ld,
-                            float* dbeta, float* dgamma, const float* scale, const float* shift, int accumulate,
-                            void* stream) {
+extern "C" int gv_bn_relu_bwd_apply_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
+                                              const void* z, int32_t z_ld, const float* mean, const float* inv,
+                                              const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
+                                              int32_t c, int32_t num_groups, const double* accum, void* dz,
+                                              int32_t dz_ld, float* dbeta, float* dgamma, const float* scale,
+                                              const float* shift, int32_t accumulate, int32_t dtype, void* stream) {
+    const int raw_z = (dtype & GV_ACCUM_RAW_Z) ? 1 : 0;          // (sum g*z accumulators: 16-bit storage only)
+    dtype &= ~GV_ACCUM_RAW_Z;
+    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
+    if (!storage_type(dtype) || (raw_z && dtype == GV_F32)) return GV_E_UNSUPPORTED;
     if (!dy || !z || !mean || !inv || !counts || !accum || !dz) return GV_E_BADARG;
     if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    {
-        bool done = false;
-        if (gvlp::bn_bwd_apply_grouped(GV_F32, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale, shift,
-                                       accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done, st) == GV_OK)
-            return GV_OK;
+    bool done = false;                                           // (the streaming kernel also sums dbeta / dgamma)
+    int rc = gvlp::bn_bwd_apply_grouped(dtype, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale, shift,
+                                        accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done, st, raw_z);
+    if (rc != GV_OK && dtype == GV_F32) {
+        hipLaunchKernelGGL(bn_bwd_apply_grouped_f32, dim3(gv_grid_for((int64_t)nb * hw * c)), dim3(256), 0, st,
+                           (const float*)dy, dy_ld, (const float*)y, y_ld, (const float*)z, z_ld, mean, inv, gamma, accum,
+                           counts, nb, hw, c, num_groups, (float*)dz, dz_ld, scale, shift, accumulate);
+        rc = GV_OK;
+        done = false;                                            // (the scalar kernel leaves dbeta / dgamma to bn_param_grads)
     }
-    hipLaunchKernelGGL(bn_bwd_apply_grouped_f32, dim3(grid_for((int64_t)nb * hw * c)), dim3(256), 0, st, dy, dy_ld,
-                       y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, nb, hw, c, num_groups, dz, dz_ld, scale, shift, accumulate);
-    if (dbeta || dgamma)
+    if (rc != GV_OK) return rc;
+    if ((dbeta || dgamma) && !done)
         hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, num_groups, c, dbeta,
                            dgamma);
     GV_LAUNCH_CHECK();
@@ -920,8 +962,8 @@ extern "C" int gv_bn_relu_bwd_apply_grouped(const float* dy, int32_t dy_ld, cons
                                             const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
                                             int32_t c, int32_t num_groups, const double* accum, float* dz,
                                             int32_t dz_ld, float* dbeta, float* dgamma, void* stream) {
-    return bn_bwd_apply_f32(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, counts, nb, hw, c, num_groups, accum, dz, dz_ld,
-                            dbeta, dgamma, nullptr, nullptr, 1, stream);
+    return gv_bn_relu_bwd_apply_grouped_t(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, counts, nb, hw, c, num_groups,
+                                          accum, dz, dz_ld, dbeta, dgamma, nullptr, nullptr, 1, GV_F32, stream);
 }
 
 extern "C" int gv_bn_relu_bwd_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
@@ -948,27 +990,48 @@ extern "C" int gv_scale(float* x, int64_t n, float s, void* stream) {
     return GV_OK;
 }
 
+extern "C" int gv_accumulate_t(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int64_t npix, int32_t c,
+                               int32_t dtype, void* stream) {
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!src || !dst || npix <= 0 || c <= 0 || src_ld < c || dst_ld < c) return GV_E_BADARG;
+    if (dtype != GV_F32) return gvlp::accumulate(dtype, src, src_ld, dst, dst_ld, npix, c, (hipStream_t)stream);
+    hipLaunchKernelGGL(accumulate_f32, dim3(gv_grid_for(npix * c)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
+                       src_ld, (float*)dst, dst_ld, npix, c);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+
 extern "C" int gv_accumulate(const float* src, int32_t src_ld, float* dst, int32_t dst_ld, int64_t npix,
                              int32_t c, void* stream) {
-    if (!src || !dst || npix <= 0 || c <= 0 || src_ld < c || dst_ld < c) return GV_E_BADARG;
-    hipLaunchKernelGGL(accumulate_f32, dim3(grid_for(npix * c)), dim3(256), 0, (hipStream_t)stream, src, src_ld,
-                       dst, dst_ld, npix, c);
+    return gv_accumulate_t(src, src_ld, dst, dst_ld, npix, c, GV_F32, stream);
+}
+
+extern "C" int gv_bias_grad_t(const void* dz, int32_t dz_ld, int64_t npix, int32_t c, double* accum, float* dbias,
+                              int32_t dtype, void* stream) {
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!dz || !accum || !dbias || npix <= 0 || c <= 0 || dz_ld < c || npix > 0x7fffffff) return GV_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)c, st));
+    if (dtype == GV_F32) {
+        // the split count decides the last bits of the sums, so fp32 keeps the rule it has always had: 2048 pixels per
+        // workgroup, without the "at least ~1024 workgroups" term of sums_splits
+        const int most = gv_ceil_div(npix, 2048), splits = most < 1024 ? most : 1024;
+        const float* df = (const float*)dz;
+        launch_grouped_sums<2>(dim3((c + 63) / 64, splits, 1), st, (c & 3) == 0 && gv_vec_ok(df, dz_ld, 4), nullptr, 0, df,
+                               dz_ld, nullptr, 0, nullptr, nullptr, (int)npix, 1, c, 1, accum);
+    } else {
+        const int rc = gvlp::grouped_sums(dtype, 2, nullptr, 0, dz, dz_ld, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                          (int)npix, 1, c, 1, sums_splits(npix, 1024), accum, st);
+        if (rc != GV_OK) return rc;
+    }
+    hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, 1, c, dbias, (float*)nullptr);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
 
 extern "C" int gv_bias_grad(const float* dz, int32_t dz_ld, int64_t npix, int32_t c, double* accum,
                             float* dbias, void* stream) {
-    if (!dz || !accum || !dbias || npix <= 0 || c <= 0 || dz_ld < c || npix > 0x7fffffff) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)c, st));
-    int splits = (int)((npix + 2047) / 2048);
-    if (splits > 1024) splits = 1024;
-    launch_grouped_sums<2>(dim3((c + 63) / 64, splits, 1), st, (c & 3) == 0 && vec_ok(dz, dz_ld), nullptr, 0, dz, dz_ld,
-                           nullptr, 0, nullptr, nullptr, (int)npix, 1, c, 1, accum);
-    hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, 1, c, dbias, (float*)nullptr);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_bias_grad_t(dz, dz_ld, npix, c, accum, dbias, GV_F32, stream);
 }
 
 static int g_pool_scatter = 0;
@@ -985,7 +1048,7 @@ extern "C" int gv_pool2d_bwd(const gv_pool_desc* d, const void* x, const void* d
         return gvlp::pool2d_bwd(d, x, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
     if (d->dtype != GV_F32) return GV_E_UNSUPPORTED;
     if (d->mode & GV_POOL_BWD_STORE) return GV_E_UNSUPPORTED;    // the scatter kernel only adds
-    hipLaunchKernelGGL(pool2d_bwd_f32, dim3(grid_for((int64_t)d->nb * d->oh * d->ow * d->c)), dim3(256), 0,
+    hipLaunchKernelGGL(pool2d_bwd_f32, dim3(gv_grid_for((int64_t)d->nb * d->oh * d->ow * d->c)), dim3(256), 0,
                        (hipStream_t)stream, (const float*)x, d->x_ld, (const float*)dy, dy_ld, d->nb, d->ih, d->iw, d->c,
                        d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, mode, (float*)dx, dx_ld);
     GV_LAUNCH_CHECK();
@@ -1039,18 +1102,24 @@ extern "C" int gv_pool2d_bwd_argmax(const gv_pool_desc* d, const uint8_t* argmax
     return gvlp::pool2d_bwd_argmax(d, argmax, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
 }
 
-static int pool_fuse_bwd_launch(const float* F, const float* dS, int32_t num_views, int32_t num_shapes, int64_t E,
-                                int64_t view_stride, int64_t shape_stride, const int32_t* scheme, int32_t num_groups,
-                                const float* weight, int32_t mode, float* dF, void* stream, int64_t scheme_stride,
-                                int64_t weight_stride) {
+// per_shape: every shape has its own scheme ([num_groups][num_views]) and weights ([num_groups]); else one for the batch
+extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t num_views, int32_t num_shapes,
+                                       int64_t E, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
+                                       int32_t num_groups, const float* weight, int32_t mode, void* dF,
+                                       int32_t per_shape, int32_t dtype, void* stream) {
+    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!F || !dS || !scheme || !weight || !dF) return GV_E_BADARG;
     if (num_views <= 0 || num_shapes <= 0 || E <= 0 || num_groups <= 0) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
+    const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
+    if (dtype != GV_F32)
+        return gvlp::view_pool_fuse_bwd(dtype, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme,
+                                        num_groups, weight, mode, dF, (hipStream_t)stream, ss, ws);
     int64_t bx = (E + 255) / 256;
     if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(view_pool_fuse_bwd_f32, dim3((unsigned)bx, (unsigned)num_shapes), dim3(256), 0,
-                       (hipStream_t)stream, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme,
-                       num_groups, weight, mode, dF, scheme_stride, weight_stride);
+                       (hipStream_t)stream, (const float*)F, dS, num_views, num_shapes, E, view_stride, shape_stride,
+                       scheme, num_groups, weight, mode, (float*)dF, ss, ws);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
@@ -1059,22 +1128,22 @@ extern "C" int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t nu
                                      int64_t E, int64_t view_stride, int64_t shape_stride,
                                      const int32_t* scheme, int32_t num_groups, const float* weight,
                                      int32_t mode, float* dF, void* stream) {
-    return pool_fuse_bwd_launch(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
-                                mode, dF, stream, 0, 0);
+    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
+                                   mode, dF, 0, GV_F32, stream);
 }
 
 extern "C" int gv_view_pool_fuse_bwd_per_shape(const float* F, const float* dS, int32_t num_views,
                                                int32_t num_shapes, int64_t E, int64_t view_stride,
                                                int64_t shape_stride, const int32_t* scheme, int32_t num_groups,
                                                const float* weight, int32_t mode, float* dF, void* stream) {
-    return pool_fuse_bwd_launch(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
-                                mode, dF, stream, (int64_t)num_groups * num_views, num_groups);
+    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
+                                   mode, dF, 1, GV_F32, stream);
 }
 
 extern "C" int gv_global_avg_pool_bwd(const float* dgap, int32_t nb, int32_t hw, int32_t c, float* dx,
                                       int32_t dx_ld, void* stream) {
     if (!dgap || !dx || nb <= 0 || hw <= 0 || c <= 0 || dx_ld < c) return GV_E_BADARG;
-    hipLaunchKernelGGL(global_avg_pool_bwd_f32, dim3(grid_for((int64_t)nb * hw * c)), dim3(256), 0,
+    hipLaunchKernelGGL(global_avg_pool_bwd_f32, dim3(gv_grid_for((int64_t)nb * hw * c)), dim3(256), 0,
                        (hipStream_t)stream, dgap, nb, hw, c, dx, dx_ld);
     GV_LAUNCH_CHECK();
     return GV_OK;
@@ -1278,154 +1347,4 @@ extern "C" int gv_conv2d_wgrad_ws(const gv_conv_desc* d, const void* x, const vo
     if (!workspace || workspace_bytes < 0 || !gv_aligned16(workspace)) return GV_E_BADARG;
     return wgrad_dispatch(d, x, dz, dz_ld, GvDw{dw_hwio, (float*)workspace, 0, (size_t)workspace_bytes},
                           (hipStream_t)stream);
-}
-
-// ---- storage-typed forms (16-bit training step; GV_F32 forwards to the fp32 entry points) ---------------------------
-static inline bool lp_type(int dtype) { return dtype == GV_BF16 || dtype == GV_F16; }
-
-// pixel splits of a sums launch: 2048 pixels per workgroup on the big layers, but at least ~1024 workgroups in total
-// (down to 128 pixels per workgroup) on the small, latency-bound ones
-static inline int sums_splits(int64_t npix, int cap, int c = 64, int G = 1) {
-    int64_t splits = (npix + 2047) / 2048;
-    const int64_t want = 1024 / ((int64_t)((c + 63) / 64) * G) + 1, most = (npix + 127) / 128;
-    if (splits < want) splits = want < most ? want : most;
-    return (int)(splits > cap ? cap : (splits < 1 ? 1 : splits));
-}
-
-extern "C" int gv_bn_sums_grouped_t(const void* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
-                                    int32_t num_groups, double* accum, int32_t dtype, void* stream) {
-    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;          // the caller keeps a pre-zeroed accumulator per layer
-    dtype &= ~GV_ACCUM_ZEROED;
-    if (dtype == GV_F32) return gv_bn_sums_grouped((const float*)z, nb, hw, c, z_ld, num_groups, accum, stream);
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!z || !accum) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || z_ld < c || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (!zeroed) GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    return gvlp::grouped_sums(dtype, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb, hw, c,
-                              num_groups, sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups), accum, st);
-}
-
-extern "C" int gv_scale_shift_act_grouped_t(const void* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
-                                            const float* scale, const float* shift, int32_t num_groups,
-                                            int32_t relu, void* y, int32_t y_ld, int32_t dtype, void* stream) {
-    if (dtype == GV_F32)
-        return gv_scale_shift_act_grouped((const float*)x, nb, hw, c, x_ld, scale, shift, num_groups, relu, (float*)y,
-                                          y_ld, stream);
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!x || !y || !scale || !shift || nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0)
-        return GV_E_BADARG;
-    return gvlp::scale_shift_act_grouped(dtype, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld,
-                                         (hipStream_t)stream);
-}
-
-extern "C" int gv_bn_finalize_apply_grouped_t(const double* accum, const int32_t* counts, const float* gamma,
-                                              const float* beta, float eps, const void* x, int32_t nb, int32_t hw,
-                                              int32_t c, int32_t x_ld, int32_t num_groups, int32_t relu, void* y,
-                                              int32_t y_ld, float* mean, float* var, float* inv, float* scale,
-                                              float* shift, int32_t dtype, void* stream) {
-    if (!accum || !counts || !beta || !x || !y || !mean || !var || !inv || !scale || !shift) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0) return GV_E_BADARG;
-    if (lp_type(dtype) || dtype == GV_F32) {
-        const int rc = gvlp::bn_finalize_apply_grouped(dtype, accum, counts, gamma, beta, eps, x, nb, hw, c, x_ld,
-                                                       num_groups, relu, y, y_ld, mean, var, inv, scale, shift,
-                                                       (hipStream_t)stream);
-        if (rc != GV_E_UNSUPPORTED) return rc;
-    }
-    const int rc = gv_bn_finalize_grouped(accum, c, num_groups, counts, gamma, beta, eps, mean, var, inv, scale, shift,
-                                          stream);
-    if (rc != GV_OK) return rc;
-    return gv_scale_shift_act_grouped_t(x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, dtype, stream);
-}
-
-extern "C" int gv_bn_relu_bwd_sums_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
-                                             const void* z, int32_t z_ld, const float* mean, const float* inv,
-                                             int32_t nb, int32_t hw, int32_t c, int32_t num_groups, double* accum,
-                                             const float* scale, const float* shift, int32_t dtype, void* stream) {
-    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;
-    dtype &= ~GV_ACCUM_ZEROED;
-    if (dtype == GV_F32) {
-        if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-        return bn_bwd_sums_f32((const float*)dy, dy_ld, (const float*)y, y_ld, (const float*)z, z_ld, mean, inv, nb, hw, c,
-                               num_groups, accum, scale, shift, stream);
-    }
-    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!dy || !z || !mean || !inv || !accum) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (!zeroed) GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    return gvlp::grouped_sums(dtype, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c, num_groups,
-                              sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups), accum, st);
-}
-
-extern "C" int gv_bn_relu_bwd_apply_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
-                                              const void* z, int32_t z_ld, const float* mean, const float* inv,
-                                              const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
-                                              int32_t c, int32_t num_groups, const double* accum, void* dz,
-                                              int32_t dz_ld, float* dbeta, float* dgamma, const float* scale,
-                                              const float* shift, int32_t accumulate, int32_t dtype, void* stream) {
-    const int raw_z = (dtype & GV_ACCUM_RAW_Z) ? 1 : 0;
-    dtype &= ~GV_ACCUM_RAW_Z;
-    if (dtype == GV_F32) {
-        if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-        if (raw_z) return GV_E_UNSUPPORTED;
-        return bn_bwd_apply_f32((const float*)dy, dy_ld, (const float*)y, y_ld, (const float*)z, z_ld, mean, inv, gamma,
-                                counts, nb, hw, c, num_groups, accum, (float*)dz, dz_ld, dbeta, dgamma, scale, shift,
-                                accumulate, stream);
-    }
-    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!dy || !z || !mean || !inv || !counts || !accum || !dz) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    bool done = false;                                           // (the streaming kernel also sums dbeta / dgamma)
-    const int rc = gvlp::bn_bwd_apply_grouped(dtype, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale,
-                                              shift, accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done,
-                                              st, raw_z);
-    if (rc != GV_OK) return rc;
-    if ((dbeta || dgamma) && !done)
-        hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, num_groups, c, dbeta,
-                           dgamma);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-extern "C" int gv_accumulate_t(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int64_t npix, int32_t c,
-                               int32_t dtype, void* stream) {
-    if (dtype == GV_F32) return gv_accumulate((const float*)src, src_ld, (float*)dst, dst_ld, npix, c, stream);
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!src || !dst || npix <= 0 || c <= 0 || src_ld < c || dst_ld < c) return GV_E_BADARG;
-    return gvlp::accumulate(dtype, src, src_ld, dst, dst_ld, npix, c, (hipStream_t)stream);
-}
-
-extern "C" int gv_bias_grad_t(const void* dz, int32_t dz_ld, int64_t npix, int32_t c, double* accum, float* dbias,
-                              int32_t dtype, void* stream) {
-    if (dtype == GV_F32) return gv_bias_grad((const float*)dz, dz_ld, npix, c, accum, dbias, stream);
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!dz || !accum || !dbias || npix <= 0 || c <= 0 || dz_ld < c || npix > 0x7fffffff) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)c, st));
-    const int rc = gvlp::grouped_sums(dtype, 2, nullptr, 0, dz, dz_ld, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                      (int)npix, 1, c, 1, sums_splits(npix, 1024), accum, st);
-    if (rc != GV_OK) return rc;
-    hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, 1, c, dbias, (float*)nullptr);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t num_views, int32_t num_shapes,
-                                       int64_t E, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
-                                       int32_t num_groups, const float* weight, int32_t mode, void* dF,
-                                       int32_t per_shape, int32_t dtype, void* stream) {
-    const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
-    if (dtype == GV_F32)
-        return pool_fuse_bwd_launch((const float*)F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme,
-                                    num_groups, weight, mode, (float*)dF, stream, ss, ws);
-    if (!lp_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!F || !dS || !scheme || !weight || !dF) return GV_E_BADARG;
-    if (num_views <= 0 || num_shapes <= 0 || E <= 0 || num_groups <= 0) return GV_E_BADARG;
-    if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
-    return gvlp::view_pool_fuse_bwd(dtype, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme,
-                                    num_groups, weight, mode, dF, (hipStream_t)stream, ss, ws);
 }

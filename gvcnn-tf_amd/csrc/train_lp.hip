@@ -23,12 +23,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-inline unsigned grid_for(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    const int64_t cap = 256 * 16;
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
 // dst[p][c] += src[p][c]
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void accumulate_lp(const unsigned short* __restrict__ src, int src_ld,
@@ -1364,39 +1358,86 @@ __global__ __launch_bounds__(256) void conv_wgrad_strip_lp(const unsigned short*
     }
 }
 
-inline bool vec8(const void* p, int ld) { return p == nullptr || (gv_aligned16(p) && (ld % 8) == 0); }
-inline bool vec4(const void* p, int ld) { return p == nullptr || (gv_aligned16(p) && (ld % 4) == 0); }
+// ---- launchers of the streaming kernels: one body for every storage type ---------------------------------------------
+// E is the element type in HBM (float, or unsigned short for the 16-bit types) and T the type it stands for (float,
+// __bf16, _Float16): GV_ST_DISPATCH below.  A shape the streaming kernels cannot take runs the scalar 16-bit kernel;
+// on fp32 storage the launcher answers GV_E_UNSUPPORTED and the caller (train.hip) launches its scalar fp32 kernel.
+// every operand (nullptr: not used) can be walked in 16-byte quads (4 fp32 or 8 16-bit channels) ...
+inline bool stream_vec_ok(size_t elem_bytes, int c, const void* p0, int ld0, const void* p1, int ld1,
+                          const void* p2 = nullptr, int ld2 = 0, const void* p3 = nullptr, int ld3 = 0) {
+    const int ne = (int)(16 / elem_bytes);
+    return c % ne == 0 && gv_vec_ok(p0, ld0, ne) && gv_vec_ok(p1, ld1, ne) && gv_vec_ok(p2, ld2, ne) && gv_vec_ok(p3, ld3, ne);
+}
+// ... and a group's pixel index fits the int the streaming kernels count in
+inline bool stream_pix_ok(int nb, int hw, int G) { return (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll; }
 
-template <typename T>
-int sums_t(int mode, const unsigned short* z, int z_ld, const unsigned short* dy, int dy_ld, const unsigned short* y,
-           int y_ld, const float* mean, const float* inv, const float* scale, const float* shift, int nb, int hw, int c,
-           int G, int splits, double* acc, hipStream_t st) {
-    const bool v = (c % 8 == 0) && vec8(z, z_ld) && vec8(dy, dy_ld) && vec8(y, y_ld);
+template <typename E, typename T>
+int sums_t(int mode, const E* z, int z_ld, const E* dy, int dy_ld, const E* y, int y_ld, const float* mean,
+           const float* inv, const float* scale, const float* shift, int nb, int hw, int c, int G, int splits, double* acc,
+           hipStream_t st) {
+    const bool v = stream_vec_ok(sizeof(E), c, z, z_ld, dy, dy_ld, y, y_ld);
     const dim3 grid((c + 63) / 64, splits, G);
-    if (v && (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll) {
-#define GV_SUMS8(MODE)                                                                                               \
-        hipLaunchKernelGGL((grouped_sums_v8<unsigned short, T, MODE>), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, \
-                           shift, nb, hw, c, G, acc)
-        if (mode == 0) GV_SUMS8(0);
-        else if (mode == 1) GV_SUMS8(1);
-        else GV_SUMS8(2);
-#undef GV_SUMS8
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-#define GV_SUMS(MODE)                                                                                                \
-    do {                                                                                                             \
-        if (v)                                                                                                       \
-            hipLaunchKernelGGL((grouped_sums_lp<T, MODE, 8>), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, \
-                               inv, scale, shift, nb, hw, c, G, acc);                                                              \
-        else                                                                                                         \
-            hipLaunchKernelGGL((grouped_sums_lp<T, MODE, 1>), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, \
-                               inv, scale, shift, nb, hw, c, G, acc);                                                              \
+    const bool stream = v && stream_pix_ok(nb, hw, G);
+#define GV_SUMS_LAUNCH(...)                                                                                           \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, \
+                       c, G, acc)
+#define GV_SUMS(MODE)                                                                                                 \
+    do {                                                                                                              \
+        if (stream) GV_SUMS_LAUNCH(grouped_sums_v8<E, T, MODE>);                                                      \
+        else if constexpr (sizeof(E) != 2) return GV_E_UNSUPPORTED;                                                   \
+        else if (v) GV_SUMS_LAUNCH(grouped_sums_lp<T, MODE, 8>);                                                      \
+        else GV_SUMS_LAUNCH(grouped_sums_lp<T, MODE, 1>);                                                             \
     } while (0)
     if (mode == 0) GV_SUMS(0);
     else if (mode == 1) GV_SUMS(1);
     else GV_SUMS(2);
 #undef GV_SUMS
+#undef GV_SUMS_LAUNCH
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+
+// The arguments of bn_stream_v8 by name; what a launch does not use stays null.
+struct StreamArgs {
+    const void *x = nullptr, *dy = nullptr, *yact = nullptr;     // forward: x;  backward: z, dy and the kept activation
+    int x_ld = 0, dy_ld = 0, y_ld = 0;                           // (nullptr: the ReLU mask is recomputed from scale / shift)
+    const float *p0 = nullptr, *p1 = nullptr;                    // forward: scale, shift;  backward: mean, inv
+    const float* gamma = nullptr;
+    const double* acc = nullptr;
+    const int* counts = nullptr;
+    const float *scale = nullptr, *shift = nullptr;
+    int accumulate = 0, nb = 0, hw = 0, c = 0, G = 0;
+    int flag = 0;                                                // forward: relu;  backward: raw_z
+    void* out = nullptr;
+    int out_ld = 0;
+    BnExtra ex{};
+};
+
+// A BatchNorm apply, forward or backward: the streaming kernel when the operands allow it (*streamed says so), else the
+// scalar 16-bit kernel where `scalar_ok`, else GV_E_UNSUPPORTED and nothing launched.
+template <typename E, typename T, bool BWD>
+int launch_bn_stream(const StreamArgs& a, bool scalar_ok, bool* streamed, hipStream_t st) {
+    const bool v = stream_vec_ok(sizeof(E), a.c, a.x, a.x_ld, a.dy, a.dy_ld, a.yact, a.y_ld, a.out, a.out_ld) &&
+                   stream_pix_ok(a.nb, a.hw, a.G);
+    if (streamed) *streamed = v;
+    if (v) {
+        hipLaunchKernelGGL((bn_stream_v8<E, T, BWD>), dim3((a.c + 63) / 64, stream_splits(a.nb, a.hw, a.G, a.c), a.G),
+                           dim3(256), 0, st, (const E*)a.x, a.x_ld, (const E*)a.dy, a.dy_ld, (const E*)a.yact, a.y_ld, a.p0,
+                           a.p1, a.gamma, a.acc, a.counts, a.scale, a.shift, a.accumulate, a.nb, a.hw, a.c, a.G, a.flag,
+                           (E*)a.out, a.out_ld, a.ex);
+    } else if constexpr (sizeof(E) != 2) {
+        return GV_E_UNSUPPORTED;
+    } else {
+        if (!scalar_ok) return GV_E_UNSUPPORTED;
+        const dim3 grid(gv_grid_for((int64_t)a.nb * a.hw * a.c));
+        if constexpr (BWD)
+            hipLaunchKernelGGL((bn_bwd_apply_grouped_lp<T, 1>), grid, dim3(256), 0, st, (const E*)a.dy, a.dy_ld,
+                               (const E*)a.yact, a.y_ld, (const E*)a.x, a.x_ld, a.p0, a.p1, a.gamma, a.acc, a.counts, a.scale,
+                               a.shift, a.accumulate, a.nb, a.hw, a.c, a.G, (E*)a.out, a.out_ld);
+        else
+            hipLaunchKernelGGL((scale_shift_act_grouped_lp<T, 1>), grid, dim3(256), 0, st, (const E*)a.x, a.nb, a.hw, a.c,
+                               a.x_ld, a.p0, a.p1, a.G, a.flag, (E*)a.out, a.out_ld);
+    }
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
@@ -1798,16 +1839,25 @@ namespace gvlp {
         return GV_E_UNSUPPORTED;                          \
     } while (0)
 
+// every storage type: E the element type in HBM, T the type it stands for
+#define GV_ST_DISPATCH(dtype, CALL)                                                   \
+    do {                                                                              \
+        if ((dtype) == GV_F32) { using E = float; using T = float; CALL; }            \
+        if ((dtype) == GV_BF16) { using E = unsigned short; using T = __bf16; CALL; } \
+        if ((dtype) == GV_F16) { using E = unsigned short; using T = _Float16; CALL; } \
+        return GV_E_UNSUPPORTED;                                                      \
+    } while (0)
+
 int accumulate(int dtype, const void* src, int src_ld, void* dst, int dst_ld, int64_t npix, int c, hipStream_t st) {
     const unsigned short* s = (const unsigned short*)src;
     unsigned short* d = (unsigned short*)dst;
-    const bool v = (c % 8 == 0) && vec8(s, src_ld) && vec8(d, dst_ld);
+    const bool v = stream_vec_ok(2, c, s, src_ld, d, dst_ld);
     GV_LP_DISPATCH(dtype, {
         if (v)
-            hipLaunchKernelGGL((accumulate_lp<T, 8>), dim3(grid_for(npix * (c / 8))), dim3(256), 0, st, s, src_ld, d,
+            hipLaunchKernelGGL((accumulate_lp<T, 8>), dim3(gv_grid_for(npix * (c / 8))), dim3(256), 0, st, s, src_ld, d,
                                dst_ld, npix, c);
         else
-            hipLaunchKernelGGL((accumulate_lp<T, 1>), dim3(grid_for(npix * c)), dim3(256), 0, st, s, src_ld, d, dst_ld,
+            hipLaunchKernelGGL((accumulate_lp<T, 1>), dim3(gv_grid_for(npix * c)), dim3(256), 0, st, s, src_ld, d, dst_ld,
                                npix, c);
         GV_LAUNCH_CHECK();
         return GV_OK;
@@ -1817,128 +1867,44 @@ int accumulate(int dtype, const void* src, int src_ld, void* dst, int dst_ld, in
 int grouped_sums(int dtype, int mode, const void* z, int z_ld, const void* dy, int dy_ld, const void* y, int y_ld,
                  const float* mean, const float* inv, const float* scale, const float* shift, int nb, int hw, int c,
                  int G, int splits, double* acc, hipStream_t st) {
-    if (dtype == GV_F32) {                                       // the same streaming kernels on fp32 storage (4 per quad)
-        if (!((c % 4 == 0) && vec4(z, z_ld) && vec4(dy, dy_ld) && vec4(y, y_ld) &&
-              (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll))
-            return GV_E_UNSUPPORTED;
-        const dim3 grid((c + 63) / 64, splits, G);
-        const float *zf = (const float*)z, *df = (const float*)dy, *yf = (const float*)y;
-#define GV_SUMS32(MODE)                                                                                              \
-        hipLaunchKernelGGL((grouped_sums_v8<float, float, MODE>), grid, dim3(256), 0, st, zf, z_ld, df, dy_ld, yf, y_ld,   \
-                           mean, inv, scale, shift, nb, hw, c, G, acc)
-        if (mode == 0) GV_SUMS32(0);
-        else if (mode == 1) GV_SUMS32(1);
-        else GV_SUMS32(2);
-#undef GV_SUMS32
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    GV_LP_DISPATCH(dtype, return sums_t<T>(mode, (const unsigned short*)z, z_ld, (const unsigned short*)dy, dy_ld,
-                                           (const unsigned short*)y, y_ld, mean, inv, scale, shift, nb, hw, c, G, splits,
-                                           acc, st));
+    GV_ST_DISPATCH(dtype, return (sums_t<E, T>(mode, (const E*)z, z_ld, (const E*)dy, dy_ld, (const E*)y, y_ld, mean, inv,
+                                               scale, shift, nb, hw, c, G, splits, acc, st)));
 }
 
 int scale_shift_act_grouped(int dtype, const void* x, int nb, int hw, int c, int x_ld, const float* scale,
                             const float* shift, int G, int relu, void* y, int y_ld, hipStream_t st) {
-    if (dtype == GV_F32) {
-        if (!((c % 4 == 0) && vec4(x, x_ld) && vec4(y, y_ld) && (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll))
-            return GV_E_UNSUPPORTED;
-        hipLaunchKernelGGL((bn_stream_v8<float, float, false>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0,
-                           st, (const float*)x, x_ld, (const float*)nullptr, 0, (const float*)nullptr, 0, scale, shift,
-                           (const float*)nullptr, (const double*)nullptr, (const int*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, 0, nb, hw, c, G, relu, (float*)y, y_ld, BnExtra{});
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    const unsigned short* xs = (const unsigned short*)x;
-    unsigned short* ys = (unsigned short*)y;
-    const bool v = (c % 8 == 0) && vec8(xs, x_ld) && vec8(ys, y_ld) && (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll;
-    GV_LP_DISPATCH(dtype, {
-        if (v)
-            hipLaunchKernelGGL((bn_stream_v8<unsigned short, T, false>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0, st,
-                               xs, x_ld, (const unsigned short*)nullptr, 0, (const unsigned short*)nullptr, 0, scale, shift,
-                               (const float*)nullptr, (const double*)nullptr, (const int*)nullptr, (const float*)nullptr,
-                               (const float*)nullptr, 0, nb, hw, c, G, relu, ys, y_ld, BnExtra{});
-        else
-            hipLaunchKernelGGL((scale_shift_act_grouped_lp<T, 1>), dim3(grid_for((int64_t)nb * hw * c)), dim3(256), 0, st,
-                               xs, nb, hw, c, x_ld, scale, shift, G, relu, ys, y_ld);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    });
+    StreamArgs a;
+    a.x = x; a.x_ld = x_ld; a.p0 = scale; a.p1 = shift;
+    a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = relu; a.out = y; a.out_ld = y_ld;
+    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, false>(a, true, nullptr, st)));
 }
 
 // Fused finalize + apply (forward).  Returns GV_E_UNSUPPORTED when the shape needs the separate kernels.
 int bn_finalize_apply_grouped(int dtype, const double* acc, const int* counts, const float* gamma, const float* beta,
                               float eps, const void* x, int nb, int hw, int c, int x_ld, int G, int relu, void* y,
                               int y_ld, float* mean, float* var, float* inv, float* scale, float* shift, hipStream_t st) {
-    BnExtra ex{};
-    ex.fin_acc = acc; ex.beta = beta; ex.eps = eps;
-    ex.mean = mean; ex.var = var; ex.inv = inv; ex.scale_out = scale; ex.shift_out = shift;
-    if (dtype == GV_F32) {
-        if (!((c % 4 == 0) && vec4(x, x_ld) && vec4(y, y_ld) && (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll))
-            return GV_E_UNSUPPORTED;
-        hipLaunchKernelGGL((bn_stream_v8<float, float, false>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0,
-                           st, (const float*)x, x_ld, (const float*)nullptr, 0, (const float*)nullptr, 0,
-                           (const float*)nullptr, (const float*)nullptr, gamma, (const double*)nullptr, counts,
-                           (const float*)nullptr, (const float*)nullptr, 0, nb, hw, c, G, relu, (float*)y, y_ld, ex);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    const unsigned short* xs = (const unsigned short*)x;
-    unsigned short* ys = (unsigned short*)y;
-    const bool v = (c % 8 == 0) && vec8(xs, x_ld) && vec8(ys, y_ld) && (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll;
-    if (!v) return GV_E_UNSUPPORTED;
-    GV_LP_DISPATCH(dtype, {
-        hipLaunchKernelGGL((bn_stream_v8<unsigned short, T, false>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0, st, xs,
-                           x_ld, (const unsigned short*)nullptr, 0, (const unsigned short*)nullptr, 0, (const float*)nullptr,
-                           (const float*)nullptr, gamma, (const double*)nullptr, counts, (const float*)nullptr,
-                           (const float*)nullptr, 0, nb, hw, c, G, relu, ys, y_ld, ex);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    });
+    StreamArgs a;
+    a.x = x; a.x_ld = x_ld; a.gamma = gamma; a.counts = counts;
+    a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = relu; a.out = y; a.out_ld = y_ld;
+    a.ex.fin_acc = acc; a.ex.beta = beta; a.ex.eps = eps;
+    a.ex.mean = mean; a.ex.var = var; a.ex.inv = inv; a.ex.scale_out = scale; a.ex.shift_out = shift;
+    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, false>(a, false, nullptr, st)));
 }
 
+// *param_grads_done: the streaming kernel ran, which also sums dbeta / dgamma; else the caller launches bn_param_grads.
+// raw_z (sum g*z accumulators, 16-bit storage): only the streaming kernel converts them.
 int bn_bwd_apply_grouped(int dtype, const void* dy, int dy_ld, const void* y, int y_ld, const void* z, int z_ld,
                          const float* mean, const float* inv, const float* gamma, const double* acc, const int* counts,
                          const float* scale, const float* shift, int accumulate, int nb, int hw, int c, int G, void* dz,
                          int dz_ld, float* dbeta, float* dgamma, bool* param_grads_done, hipStream_t st, int raw_z) {
-    if (dtype == GV_F32) {
-        *param_grads_done = false;
-        if (raw_z) return GV_E_UNSUPPORTED;
-        if (!((c % 4 == 0) && vec4(dy, dy_ld) && vec4(y, y_ld) && vec4(z, z_ld) && vec4(dz, dz_ld) &&
-              (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll))
-            return GV_E_UNSUPPORTED;
-        BnExtra ex32{};
-        ex32.dbeta = dbeta; ex32.dgamma = dgamma;
-        *param_grads_done = true;
-        hipLaunchKernelGGL((bn_stream_v8<float, float, true>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0,
-                           st, (const float*)z, z_ld, (const float*)dy, dy_ld, (const float*)y, y_ld, mean, inv, gamma, acc,
-                           counts, scale, shift, accumulate, nb, hw, c, G, 0, (float*)dz, dz_ld, ex32);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    const unsigned short* a = (const unsigned short*)dy;
-    const unsigned short* b = (const unsigned short*)y;
-    const unsigned short* zz = (const unsigned short*)z;
-    unsigned short* o = (unsigned short*)dz;
-    const bool v = (c % 8 == 0) && vec8(a, dy_ld) && vec8(b, y_ld) && vec8(zz, z_ld) && vec8(o, dz_ld) &&
-                   (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll;
-    BnExtra ex{};
-    ex.dbeta = dbeta; ex.dgamma = dgamma;
-    *param_grads_done = v;
-    if (raw_z && !v) return GV_E_UNSUPPORTED;                    // (sum g*z accumulators: the streaming kernel converts them)
-    GV_LP_DISPATCH(dtype, {
-        if (v)
-            hipLaunchKernelGGL((bn_stream_v8<unsigned short, T, true>), dim3((c + 63) / 64, stream_splits(nb, hw, G, c), G), dim3(256), 0, st,
-                               zz, z_ld, a, dy_ld, b, y_ld, mean, inv, gamma, acc, counts, scale, shift, accumulate, nb, hw, c,
-                               G, raw_z ? 1 : 0, o, dz_ld, ex);
-        else
-            hipLaunchKernelGGL((bn_bwd_apply_grouped_lp<T, 1>), dim3(grid_for((int64_t)nb * hw * c)), dim3(256), 0, st, a,
-                               dy_ld, b, y_ld, zz, z_ld, mean, inv, gamma, acc, counts, scale, shift, accumulate, nb, hw, c, G,
-                               o, dz_ld);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    });
+    *param_grads_done = false;
+    if (raw_z && dtype == GV_F32) return GV_E_UNSUPPORTED;
+    StreamArgs a;
+    a.x = z; a.x_ld = z_ld; a.dy = dy; a.dy_ld = dy_ld; a.yact = y; a.y_ld = y_ld; a.p0 = mean; a.p1 = inv;
+    a.gamma = gamma; a.acc = acc; a.counts = counts; a.scale = scale; a.shift = shift; a.accumulate = accumulate;
+    a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = raw_z ? 1 : 0; a.out = dz; a.out_ld = dz_ld;
+    a.ex.dbeta = dbeta; a.ex.dgamma = dgamma;
+    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, true>(a, !raw_z, param_grads_done, st)));
 }
 
 int pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int dy_ld, void* dx, int dx_ld, hipStream_t st) {
@@ -1951,10 +1917,10 @@ int pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int dy_ld, 
 #define GV_POOL_BWD(E, T, VEC, XS, G_, O_)                                                                              \
     do {                                                                                                                \
         if (m3s2g && VEC > 1)                                                                                           \
-            hipLaunchKernelGGL((maxpool3s2_bwd_lp<E, T, VEC>), dim3(grid_for(nblk2 * (d->c / VEC))), dim3(256), 0, st, XS, \
+            hipLaunchKernelGGL((maxpool3s2_bwd_lp<E, T, VEC>), dim3(gv_grid_for(nblk2 * (d->c / VEC))), dim3(256), 0, st, XS, \
                                d->x_ld, G_, dy_ld, d->nb, d->ih, d->iw, d->c, d->oh, d->ow, store, O_, dx_ld);          \
         else                                                                                                            \
-            hipLaunchKernelGGL((pool2d_bwd_lp<E, T, VEC>), dim3(grid_for(npix * (d->c / VEC))), dim3(256), 0, st, XS,      \
+            hipLaunchKernelGGL((pool2d_bwd_lp<E, T, VEC>), dim3(gv_grid_for(npix * (d->c / VEC))), dim3(256), 0, st, XS,      \
                                d->x_ld, G_, dy_ld, d->nb, d->ih, d->iw, d->c, d->kh, d->kw, d->stride, d->pad_t,        \
                                d->pad_l, d->oh, d->ow, mode, store, O_, dx_ld);                                         \
         GV_LAUNCH_CHECK();                                                                                              \
@@ -1972,7 +1938,7 @@ int pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int dy_ld, 
     const unsigned short* xs = (const unsigned short*)x;
     const unsigned short* g = (const unsigned short*)dy;
     unsigned short* o = (unsigned short*)dx;
-    const bool v = (d->c % 8 == 0) && vec8(xs, d->x_ld) && vec8(g, dy_ld) && vec8(o, dx_ld);
+    const bool v = (d->c % 8 == 0) && gv_vec_ok(xs, d->x_ld, 8) && gv_vec_ok(g, dy_ld, 8) && gv_vec_ok(o, dx_ld, 8);
     GV_LP_DISPATCH(d->dtype, {
         if (v) GV_POOL_BWD(unsigned short, T, 8, xs, g, o);
         GV_POOL_BWD(unsigned short, T, 1, xs, g, o);
@@ -1985,7 +1951,7 @@ int pool2d_fwd_argmax(const gv_pool_desc* d, const void* x, void* y, unsigned ch
     const int64_t opix = (int64_t)d->nb * d->oh * d->ow;
 #define GV_AMAX_F(E, T, VEC, XS, YS)                                                                                        \
     do {                                                                                                                    \
-        hipLaunchKernelGGL((maxpool_argmax_fwd<E, T, VEC>), dim3(grid_for(opix * (d->c / VEC))), dim3(256), 0, st, XS, d->x_ld, \
+        hipLaunchKernelGGL((maxpool_argmax_fwd<E, T, VEC>), dim3(gv_grid_for(opix * (d->c / VEC))), dim3(256), 0, st, XS, d->x_ld, \
                            d->nb, d->ih, d->iw, d->c, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, YS, d->y_ld, \
                            arg);                                                                                            \
         GV_LAUNCH_CHECK();                                                                                                  \
@@ -2001,7 +1967,7 @@ int pool2d_fwd_argmax(const gv_pool_desc* d, const void* x, void* y, unsigned ch
     }
     const unsigned short* xs = (const unsigned short*)x;
     unsigned short* ys = (unsigned short*)y;
-    const bool v = (d->c % 8 == 0) && vec8(xs, d->x_ld) && vec8(ys, d->y_ld) && (((uintptr_t)arg) & 7) == 0;
+    const bool v = (d->c % 8 == 0) && gv_vec_ok(xs, d->x_ld, 8) && gv_vec_ok(ys, d->y_ld, 8) && (((uintptr_t)arg) & 7) == 0;
     GV_LP_DISPATCH(d->dtype, {
         if (v) GV_AMAX_F(unsigned short, T, 8, xs, ys);
         GV_AMAX_F(unsigned short, T, 1, xs, ys);
@@ -2029,10 +1995,10 @@ int pool2d_bwd_argmax(const gv_pool_desc* d, const unsigned char* arg, const voi
 #define GV_AMAX_B(E, T, VEC, G_, O_)                                                                                        \
     do {                                                                                                                    \
         if (m3s2)                                                                                                           \
-            hipLaunchKernelGGL((maxpool3s2_argmax_bwd<E, T, VEC>), dim3(grid_for(nblk2 * (d->c / VEC))), dim3(256), 0, st, arg, \
+            hipLaunchKernelGGL((maxpool3s2_argmax_bwd<E, T, VEC>), dim3(gv_grid_for(nblk2 * (d->c / VEC))), dim3(256), 0, st, arg, \
                                G_, dy_ld, d->nb, d->ih, d->iw, d->c, d->oh, d->ow, store, O_, dx_ld, bn);                   \
         else                                                                                                                \
-            hipLaunchKernelGGL((maxpool_argmax_bwd<E, T, VEC>), dim3(grid_for(npix * (d->c / VEC))), dim3(256), 0, st, arg, G_, \
+            hipLaunchKernelGGL((maxpool_argmax_bwd<E, T, VEC>), dim3(gv_grid_for(npix * (d->c / VEC))), dim3(256), 0, st, arg, G_, \
                                dy_ld, d->nb, d->ih, d->iw, d->c, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, \
                                store, O_, dx_ld);                                                                           \
         GV_LAUNCH_CHECK();                                                                                                  \
@@ -2048,7 +2014,7 @@ int pool2d_bwd_argmax(const gv_pool_desc* d, const unsigned char* arg, const voi
     }
     const unsigned short* g = (const unsigned short*)dy;
     unsigned short* o = (unsigned short*)dx;
-    const bool v = (d->c % 8 == 0) && vec8(g, dy_ld) && vec8(o, dx_ld) && (((uintptr_t)arg) & 7) == 0;
+    const bool v = (d->c % 8 == 0) && gv_vec_ok(g, dy_ld, 8) && gv_vec_ok(o, dx_ld, 8) && (((uintptr_t)arg) & 7) == 0;
     GV_LP_DISPATCH(d->dtype, {
         if (v) GV_AMAX_B(unsigned short, T, 8, g, o);
         GV_AMAX_B(unsigned short, T, 1, g, o);
