@@ -1011,32 +1011,14 @@ int launch_halo_x3(const ConvArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)(a.nb * tiles_x * nct));
     const bool plain = a.cout % 32 == 0 && a.y_ld % 4 == 0 && ((((uintptr_t)a.y) & 15) == 0) && a.res == nullptr &&
                        (uint64_t)a.M * a.y_ld * 4 < 0xffffffffull;
-#define GV_HALO_LAUNCH(B, P, W)                                                                                     \
-    {                                                                                                               \
-        const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_x3<B, P, W>), 160 * 1024);                                   \
-        if (!ok) return GV_E_UNSUPPORTED;                                                                           \
-        hipLaunchKernelGGL((conv3x3_halo_x3<B, P, W>), grid, dim3(256), lds, st, a);                                \
-        GV_LAUNCH_CHECK();                                                                                          \
-        return GV_OK;                                                                                               \
-    }
-#define GV_HALO_K32(B, P)                                                                                           \
-    {                                                                                                               \
-        const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_x3_k32<B, P>), 160 * 1024);                                   \
-        if (!ok) return GV_E_UNSUPPORTED;                                                                           \
-        hipLaunchKernelGGL((conv3x3_halo_x3_k32<B, P>), grid, dim3(256), lds32, st, a);                             \
-        GV_LAUNCH_CHECK();                                                                                          \
-        return GV_OK;                                                                                               \
-    }
+#define GV_HALO_LAUNCH(B, P, W) return gv_launch<conv3x3_halo_x3<B, P, W>>(grid, dim3(256), lds, st, a);
+#define GV_HALO_K32(B, P) return gv_launch<conv3x3_halo_x3_k32<B, P>>(grid, dim3(256), lds32, st, a);
     const size_t lds32 = (size_t)10 * 32 * 192 + 4 * 32 * 36 * 4 + 32 * (9 * 192 + 32);
     if (a.pool) {                                     // conv -> max pool 3x3 / 2 VALID: the 30-pixel strip form only
         if (rw != 1 || a.pool != 1 || a.res != nullptr || a.cout % 4 != 0) return GV_E_UNSUPPORTED;
         const dim3 pgrid((unsigned)(a.nb * ((a.pw + 13) / 14) * nct));
         const size_t ldsp = lds32 + (size_t)10 * 14 * 32 * 4;
-        const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_x3_k32<0, false, true>), 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-        hipLaunchKernelGGL((conv3x3_halo_x3_k32<0, false, true>), pgrid, dim3(256), ldsp, st, a);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
+        return gv_launch<conv3x3_halo_x3_k32<0, false, true>>(pgrid, dim3(256), ldsp, st, a);
     }
     if (rw == 1 && !(a.dbg & 8)) {                    // (debug bit 8: the 32x32x16 form, for A/B timing)
         if (a.dbg & (4 | 16 | 32)) {
@@ -1223,13 +1205,7 @@ int launch_stem_x3_one(const ConvArgs& a, hipStream_t st) {
     constexpr int KR = KW == 3 ? 16 : 24, NG = (KW * KR / 8 + 1) / 2 * 2, PR = 3 * 2 + KW + 1, PC = 31 * 2 + KW;
     constexpr int PITCH = (PC * 3 * 2 + 16 + 3) / 4 * 4;
     const size_t lds = (size_t)3 * PR * PITCH + 4 * 32 * 36 * 4 + (size_t)3 * 32 * TN * (NG * 16 + 16);
-    if (lds > 64 * 1024) {
-        const bool ok = GV_BIG_LDS_OK((&conv_stem_patch_x3<TN, KW>), 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL((conv_stem_patch_x3<TN, KW>), dim3((unsigned)(a.nb * ((a.ow + 31) / 32))), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_stem_patch_x3<TN, KW>>(dim3((unsigned)(a.nb * ((a.ow + 31) / 32))), dim3(256), lds, st, a);
 }
 
 int launch_stem_x3(const ConvArgs& a, hipStream_t st) {
@@ -1256,40 +1232,24 @@ __global__ void pack_filter_bf16s(const float* __restrict__ w, int K, int ktiles
     }
 }
 
-struct TileCfg { int bm, bn; };
-constexpr TileCfg kTiles[] = {{128, 128}, {128, 64}, {64, 64}, {128, 96}, {64, 128}, {128, 32},
-                              {256, 128}, {128, 256}, {256, 64},    // these three: 8 waves
-                              {128, 192}, {64, 192}};               // one n-tile for the many 192-channel layers
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// the register-staged tiles (launch_np): 128 x 128, 128 x 64, 64 x 64, 128 x 96, 64 x 128, 128 x 32, then 256 x 128, 128 x 256,
+// 256 x 64 (these three: 8 waves), then 128 x 192, 64 x 192 (one n-tile for the many 192-channel layers)
+constexpr int kNumTiles = 11;
 
 template <int WM, int WN, int TM, int TN, int NP>
 int launch_cfg(const ConvArgs& a0, bool generic, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     ConvArgs a = a0;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int tiles_m = gv_ceil_div(a.M, BM);
-    const int64_t nwg = (int64_t)tiles_m * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     size_t lds = (size_t)(2 * BM + 2 * BN) * (NP * 32 + 16) + (generic ? (size_t)a.Kpad * 8 : 0);
     if (a.y_p3 | a.y2_p3) {
         const size_t epi = (size_t)(WM * WN) * X3EpiGeom<TN>::BYTES;
         lds = lds > epi ? lds : epi;
     }
-    if (generic) {
-        if (lds > 64 * 1024) {
-            const bool ok = GV_BIG_LDS_OK((&conv_igemm_bf16s<WM, WN, TM, TN, NP, true>), 160 * 1024);
-            if (!ok) return GV_E_UNSUPPORTED;
-        }
-        hipLaunchKernelGGL((conv_igemm_bf16s<WM, WN, TM, TN, NP, true>), dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
-    } else {
-        if (lds > 64 * 1024) {
-            const bool ok = GV_BIG_LDS_OK((&conv_igemm_bf16s<WM, WN, TM, TN, NP, false>), 160 * 1024);
-            if (!ok) return GV_E_UNSUPPORTED;
-        }
-        hipLaunchKernelGGL((conv_igemm_bf16s<WM, WN, TM, TN, NP, false>), dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
-    }
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    const dim3 grid((unsigned)nwg), block(WM * WN * 64);
+    return generic ? gv_launch<conv_igemm_bf16s<WM, WN, TM, TN, NP, true>>(grid, block, lds, st, a)
+                   : gv_launch<conv_igemm_bf16s<WM, WN, TM, TN, NP, false>>(grid, block, lds, st, a);
 }
 
 template <int NP>
@@ -1314,9 +1274,7 @@ int launch_np(int cfg, const ConvArgs& a, bool generic, hipStream_t st) {
 
 namespace gvconv {
 
-// + the halo-tiled stem kernel (3 planes only) + the wave-specialised kernel's GEMM mode (conv_ws_x3.hip; 3 planes only)
-int bf16s_num_cfgs() { return kNumTiles + 1 + wsg_x3_num_cfgs(); }
-int bf16s_special_cfg() { return kNumTiles; }
+int bf16s_staged_num_cfgs() { return kNumTiles; }
 
 // the 3-channel stems: square 3x3 or 7x7 window, stride 2, <= 64 output channels, plain epilogue
 bool bf16s_stem_ok(int planes, const ConvArgs& a) {
@@ -1333,45 +1291,35 @@ bool bf16s_halo_ok(int planes, const ConvArgs& a, bool generic) {
 }
 
 // GV_CONV_MAXPOOL3S2 on fp32 storage: the halo kernel's class in its 30-pixel strip form, VALID pool, no residual
-bool bf16s_halo_pool_ok(int planes, const ConvArgs& a, bool generic) {
+static bool bf16s_halo_pool_ok(int planes, const ConvArgs& a, bool generic) {
     return a.pool == 1 && bf16s_halo_ok(planes, a, generic) && a.res == nullptr && a.cout % 4 == 0 && a.oh >= 3 && a.ow >= 3 &&
            !(gv_ceil_div(a.ow, 16) * 16 * 5 <= gv_ceil_div(a.ow, 30) * 32 * 4);
 }
 
-int bf16s_pick_tile(int /*planes*/, int M, int N, int /*K*/) {
-    int best = 0;
-    double best_cost = 1e30;
-    const int order[] = {0, 3, 1, 5};                 // 128 x {128, 96, 64, 32}
-    const double pen[] = {1.00, 1.02, 1.05, 1.20};
-    for (int t = 0; t < 4; ++t) {
-        const int bn = kTiles[order[t]].bn;
-        const double cost = (double)gv_ceil_div(N, bn) * bn * pen[t];
-        if (cost < best_cost) { best_cost = cost; best = order[t]; }
-    }
-    const int64_t blocks = (int64_t)gv_ceil_div(M, 128) * gv_ceil_div(N, kTiles[best].bn);
-    if (blocks < 1024) {
-        if (kTiles[best].bn == 128) best = 4;
-        else if (kTiles[best].bn == 64) best = 2;
-    }
-    return best;
-}
-
-int bf16s_launch(int planes, int cfg, const ConvArgs& a0, bool generic, hipStream_t st) {
+// the kernels here run 16-deep k-tiles
+static ConvArgs with_ktiles(const ConvArgs& a0) {
     ConvArgs a = a0;
     a.Kpad = (a.K + KT - 1) / KT * KT;
     a.ktiles = a.Kpad / KT;
-    if (cfg == kNumTiles) {
-        if (a.pool) return bf16s_halo_pool_ok(planes, a, generic) ? launch_halo_x3(a, st) : GV_E_UNSUPPORTED;
-        if (bf16s_stem_ok(planes, a)) return launch_stem_x3(a, st);
-        return bf16s_halo_ok(planes, a, generic) ? launch_halo_x3(a, st) : GV_E_UNSUPPORTED;
-    }
-    if (cfg > kNumTiles) return planes == 3 && !generic ? wsg_x3_launch(cfg - kNumTiles - 1, a0, st) : GV_E_UNSUPPORTED;
+    return a;
+}
+
+int bf16s_staged_launch(int planes, int cfg, const ConvArgs& a0, bool generic, hipStream_t st) {
+    const ConvArgs a = with_ktiles(a0);
     switch (planes) {
         case 3: return launch_np<3>(cfg, a, generic, st);
         case 2: return launch_np<2>(cfg, a, generic, st);
         case 1: return launch_np<1>(cfg, a, generic, st);
     }
     return GV_E_UNSUPPORTED;
+}
+
+// the halo-tiled kernel and the strip kernel of the 3-channel stems (3 planes only)
+int bf16s_special_launch(int planes, const ConvArgs& a0, bool generic, hipStream_t st) {
+    const ConvArgs a = with_ktiles(a0);
+    if (a.pool) return bf16s_halo_pool_ok(planes, a, generic) ? launch_halo_x3(a, st) : GV_E_UNSUPPORTED;
+    if (bf16s_stem_ok(planes, a)) return launch_stem_x3(a, st);
+    return bf16s_halo_ok(planes, a, generic) ? launch_halo_x3(a, st) : GV_E_UNSUPPORTED;
 }
 
 int64_t bf16s_packed_bytes(int kh, int kw, int cin, int cout, int planes) {
@@ -1386,13 +1334,11 @@ int bf16s_pack_filter(const float* w_hwio, int kh, int kw, int cin, int cout, in
     const int64_t total = (int64_t)cout * ktiles * KT;
     const dim3 grid((unsigned)gv_ceil_div(total, 256));
     switch (planes) {
-        case 3: hipLaunchKernelGGL(pack_filter_bf16s<3>, grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out); break;
-        case 2: hipLaunchKernelGGL(pack_filter_bf16s<2>, grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out); break;
-        case 1: hipLaunchKernelGGL(pack_filter_bf16s<1>, grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out); break;
-        default: return GV_E_UNSUPPORTED;
+        case 3: return gv_launch<pack_filter_bf16s<3>>(grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out);
+        case 2: return gv_launch<pack_filter_bf16s<2>>(grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out);
+        case 1: return gv_launch<pack_filter_bf16s<1>>(grid, dim3(256), 0, st, w_hwio, K, ktiles, cout, (unsigned short*)out);
     }
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return GV_E_UNSUPPORTED;
 }
 
 }  // namespace gvconv

@@ -507,15 +507,8 @@ int launch_chain(const ChainArgs& a, hipStream_t st) {
     using G = ChainGeom<D, KX>;
     constexpr int lds = G::template lds_bytes<NW>() - (TAIL ? G::NR * G::W1C : 0);
     static_assert(lds <= 160 * 1024, "one workgroup's LDS");
-    auto kern = &conv_chain_lp<T, D, NW, RVS, FRONT, TAIL, KX>;
-    if (lds > 64 * 1024) {
-        const bool ok = GV_BIG_LDS_OK(kern, lds);
-        if (!ok) return GV_E_UNSUPPORTED;
-    }
     const int nwg = gv_ceil_div(a.M, NW * 32);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NW * 64), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_chain_lp<T, D, NW, RVS, FRONT, TAIL, KX>>(dim3((unsigned)nwg), dim3(NW * 64), lds, st, a);
 }
 
 template <typename T>
@@ -579,9 +572,7 @@ int chain_tail_launch(int dtype, const ConvArgs& a, hipStream_t st) {
     c.relu2 = 1;
     c.dbg = g_chain_debug;
     c.w0 = nullptr; c.sc0 = c.sh0 = nullptr; c.zeros = nullptr; c.ih = c.iw = 0;
-    if (dtype == GV_BF16) return launch_tail_d<__bf16>(a.cout, c, st);
-    if (dtype == GV_F16) return launch_tail_d<_Float16>(a.cout, c, st);
-    return GV_E_UNSUPPORTED;
+    GV_LP_DISPATCH(dtype, return launch_tail_d<T>(a.cout, c, st));
 }
 
 }  // namespace gvconv

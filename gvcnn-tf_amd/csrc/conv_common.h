@@ -1,6 +1,8 @@
-// Shared pieces of the two implicit-GEMM convolution kernels (conv_igemm.hip: fp32 MFMA;
-// conv_bf16s.hip: fp32 data split into bf16 planes on the bf16 MFMA).
+// Shared pieces of the implicit-GEMM convolution kernels (the conv_*.hip files): the launch arguments, the fp32 epilogue,
+// the host helpers every launcher uses, and what each kernel family exports to the tile tables of conv_igemm.hip.
 #pragma once
+#include <cstdlib>
+
 #include "gv_common.h"
 #include "conv_stats.h"
 
@@ -106,53 +108,87 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x16 (&
     }
 }
 
-// conv_bf16s.hip
-int bf16s_num_cfgs();
-int bf16s_special_cfg();        // the halo-tiled / strip stem kernels
-int bf16s_pick_tile(int planes, int M, int N, int K);
+// ---- host helpers of the launchers ------------------------------------------------------------------------------------
+// The 1-D grid of bm x bn output tiles (n-tiles fastest): sets a.tiles_n and returns the workgroup count, -1 where it does
+// not fit a grid dimension.
+inline int64_t conv_grid(ConvArgs& a, int bm, int bn) {
+    a.tiles_n = gv_ceil_div(a.cout, bn);
+    const int64_t nwg = (int64_t)gv_ceil_div(a.M, bm) * a.tiles_n;
+    return nwg > 0x7fffffff ? -1 : nwg;
+}
+
+// GV_NO_WS=1: every wave-specialised tile declines (A/B of whole plans: the autotuner then never sees these tiles)
+inline bool ws_disabled() {
+    static const bool off = getenv("GV_NO_WS") != nullptr;
+    return off;
+}
+
+// Default choice of the register-staged kernels of conv_lp.hip and conv_bf16s.hip when the descriptor does not name a tile
+// (plans normally carry a measured one).  Their first six tiles are the same shapes: 0 = 128 x 128, 1 = 128 x 64,
+// 2 = 64 x 64, 3 = 128 x 96, 4 = 64 x 128, 5 = 128 x 32.  Least padded N first, then the larger tile.
+inline int staged_pick_tile(int M, int N) {
+    int best = 0, best_bn = 128;
+    double best_cost = 1e30;
+    const int order[] = {0, 3, 1, 5}, bns[] = {128, 96, 64, 32};
+    const double pen[] = {1.00, 1.02, 1.05, 1.20};
+    for (int t = 0; t < 4; ++t) {
+        const double cost = (double)gv_ceil_div(N, bns[t]) * bns[t] * pen[t];
+        if (cost < best_cost) { best_cost = cost; best = order[t]; best_bn = bns[t]; }
+    }
+    const int64_t blocks = (int64_t)gv_ceil_div(M, 128) * gv_ceil_div(N, best_bn);
+    if (blocks < 1024) {                              // small problems: halve BM so the grid covers the chip
+        if (best_bn == 128) best = 4;
+        else if (best_bn == 64) best = 2;
+    }
+    return best;
+}
+
+// ---- the kernel families ------------------------------------------------------------------------------------------------
+// A family exports how many tile configurations it has and how to launch its i-th; where its configurations sit among the
+// tile indices of a storage form is the business of the tables in conv_igemm.hip alone.
+
+// conv_bf16s.hip (fp32 storage, math on 1 ... 3 bf16 planes): the register-staged tiles, and the halo-tiled / strip stem kernels
+int bf16s_staged_num_cfgs();
+int bf16s_staged_launch(int planes, int cfg, const ConvArgs& a, bool generic, hipStream_t st);
+int bf16s_special_launch(int planes, const ConvArgs& a, bool generic, hipStream_t st);
 bool bf16s_halo_ok(int planes, const ConvArgs& a, bool generic);
-bool bf16s_halo_pool_ok(int planes, const ConvArgs& a, bool generic);   // GV_CONV_MAXPOOL3S2 on fp32 storage
 bool bf16s_stem_ok(int planes, const ConvArgs& a);
-int bf16s_launch(int planes, int cfg, const ConvArgs& a, bool generic, hipStream_t st);
 int bf16s_pack_filter(const float* w_hwio, int kh, int kw, int cin, int cout, int planes, void* out,
                       hipStream_t st);
 int64_t bf16s_packed_bytes(int kh, int kw, int cin, int cout, int planes);
 
-
-// conv_lp.hip (16-bit storage)
-int lp_num_cfgs();
-int lp_pick_tile(int M, int N, int K);
+// conv_lp.hip (16-bit storage): the register-staged tiles, and the strip / halo kernels of the stem layers
+int lp_staged_num_cfgs();
+int lp_staged_launch(int dtype, int cfg, const ConvArgs& a, bool generic, bool xf32, hipStream_t st);
+int lp_special_launch(int dtype, const ConvArgs& a, bool generic, bool xf32, hipStream_t st);
 bool lp_xpre_cfg_ok(int cfg);   // register-staged tiles instantiated with the pre-activation-on-load loader
 int lp_xpre_pick(int M, int N);
 bool lp_halo_ok(const ConvArgs& a, bool generic);
-bool lp_halo_pool_ok(const ConvArgs& a, bool generic);   // GV_CONV_MAXPOOL3S2
-bool lp_stem_pool_ok(const ConvArgs& a, bool xf32);       // GV_CONV_MAXPOOL3S2 / GV_CONV_MAXPOOL3S2_SAME
 bool lp_stem_ok(const ConvArgs& a, bool xf32);
-int lp_launch(int dtype, int cfg, const ConvArgs& a, bool generic, bool xf32, hipStream_t st);
 int lp_pack_filter(const float* w_hwio, int kh, int kw, int cin, int cout, int dtype, void* out, hipStream_t st);
 int64_t lp_packed_bytes(int kh, int kw, int cin, int cout);
 int lp_pack_filters_batched(const gv_pack_job* jobs_dev, const int* block_job_dev, int nblocks, int dtype, hipStream_t st);
-int lp_special_cfg();           // the strip / halo kernels of the stem layers
 
-// conv_dma.hip (LDS-DMA loader; extra tile configurations of the 16-bit storage path)
+// conv_dma.hip (LDS-DMA loader): tiles of the 16-bit storage path ...
 int dma_lp_num_cfgs();
-bool dma_lp_ok(const ConvArgs& a, bool generic, bool xf32);
+bool dma_lp_ok(const ConvArgs& a, bool generic, bool xf32);   // (the wave-specialised kernel's class as well)
 int dma_lp_launch(int dtype, int cfg, const ConvArgs& a, hipStream_t st);
 const void* dma_zero_page();   // one zero page per device for padding taps / rows past the end
-// conv_chain.hip: the conv1-behind-a-pre-activation class of gv_conv2d_fwd_xpre (1x1, cin = 4 * cout) as a streaming launch
-bool chain_tail_ok(const ConvArgs& a);
-int chain_tail_launch(int dtype, const ConvArgs& a, hipStream_t st);
-// conv_ws.hip (wave-specialised kernel: loader waves + MFMA consumer waves; configurations follow the LDS-DMA tiles)
-int ws_lp_num_cfgs();
-int ws_lp_launch(int dtype, int cfg, const ConvArgs& a, hipStream_t st);
-// fp32 values stored as three bf16 planes ("P3": [pixel][channel/16][plane][16]), GV_MATH_BF16X3
+// ... and of fp32 values stored as three bf16 planes ("P3": [pixel][channel/16][plane][16]), GV_MATH_BF16X3
 int dma_x3_num_cfgs();
 bool dma_x3_ok(const ConvArgs& a);
 int dma_x3_launch(int cfg, const ConvArgs& a, hipStream_t st);
-// conv_ws_x3.hip (the wave-specialised strip kernel on three-plane input; configurations follow the LDS-DMA tiles)
+// conv_chain.hip: the conv1-behind-a-pre-activation class of gv_conv2d_fwd_xpre (1x1, cin = 4 * cout) as a streaming launch
+bool chain_tail_ok(const ConvArgs& a);
+int chain_tail_launch(int dtype, const ConvArgs& a, hipStream_t st);
+// conv_ws.hip (wave-specialised kernel on 16-bit storage: loader waves + MFMA consumer waves)
+int ws_lp_num_cfgs();
+int ws_lp_launch(int dtype, int cfg, const ConvArgs& a, hipStream_t st);
+// conv_ws_x3.hip (the wave-specialised kernel on three bf16 planes): the strip mode on three-plane input ...
 int ws_x3_num_cfgs();
 int ws_x3_launch(int cfg, const ConvArgs& a, hipStream_t st);
-int wsg_x3_num_cfgs();          // its GEMM mode on plain fp32 input: configurations behind conv_bf16s.hip's (after the special one)
+// ... and the GEMM mode on plain fp32 input
+int wsg_x3_num_cfgs();
 int wsg_x3_launch(int cfg, const ConvArgs& a, hipStream_t st);
 
 }  // namespace gvconv

@@ -719,9 +719,8 @@ int launch_dma(const ConvArgs& a0, hipStream_t st) {
     ConvArgs a = a0;
     a.Kpad = (a.K + G::KT - 1) / G::KT * G::KT;
     a.ktiles = a.Kpad / G::KT;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int64_t nwg = (int64_t)gv_ceil_div(a.M, BM) * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     a.zeros = zero_page_for_current_device();
     if (!a.zeros) return GV_E_UNSUPPORTED;
     a.korder = (a.kh * a.kw > 1 && a.kh * a.kw <= 32 && a.kw < 32 && a.cin % G::KT == 0 && a.dil_shift == 0 && !(a.dbg & 128)) ? 1 : 0;   // dbg 128: tap-major (A/B)
@@ -732,32 +731,16 @@ int launch_dma(const ConvArgs& a0, hipStream_t st) {
     size_t lds = (size_t)dma_ss_off<NP, WM, WN, TM, TN, ST, EPI, KTX>() +
                  (dma_use_ss<NP, WM, WN, TM, TN, ST, EPI, KTX>() ? 4 * BN * sizeof(float) : 0);
     auto go = [&](auto mode) -> int {                              // (one instantiation, and one attribute cache, per kernel)
-        auto kern = &conv_dma<T, NP, WM, WN, TM, TN, ST, EPI, decltype(mode)::value, KTX>;
         if (lds > 160 * 1024) return GV_E_UNSUPPORTED;
-        if (lds > 64 * 1024) {
-            const bool ok = GV_BIG_LDS_OK(kern, 160 * 1024);
-            if (!ok) return GV_E_UNSUPPORTED;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
+        return gv_launch<conv_dma<T, NP, WM, WN, TM, TN, ST, EPI, decltype(mode)::value, KTX>>(dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
     };
     if (a.st.mode != gvconv::STAT_OFF) {                           // BatchNorm sums in the epilogue (conv_stats.h)
         if constexpr (EPI == 0 && NP == 1) {
             if (!gvconv::stat_tile_ok(a.st, BM, a.cout, TM * 32)) return GV_E_UNSUPPORTED;
-            a.st.slots = gvconv::stat_rows(BM, a.st.hw, a.st.G);
-            a.st.fold = gvconv::stat_slots(BM, a.st.hw) > a.st.G ? 1 : 0;
-            // the tables live in the ring the epilogue has freed, behind the waves' staging blocks, where they fit in
-            // front of the epilogue's constants; else behind everything (more LDS per workgroup)
-            const size_t tab = gvconv::stat_lds_bytes(a.st.mode, a.st.slots, BN);
+            // the tables live in the ring the epilogue has freed (conv_stats.h: stat_place)
             constexpr size_t epi_b = (size_t)WM * WN * EpiGeom<TN>::BYTES, ss_off = dma_ss_off<NP, WM, WN, TM, TN, ST, EPI, KTX>();
             constexpr size_t late = dma_late_ss<NP, WM, WN, TM, TN, ST, EPI, KTX>() ? (size_t)16 * BN : 0;   // (the late constants table)
-            if (epi_b + late + tab <= ss_off) {
-                a.st.lds_off = (int)(epi_b + late);
-            } else {
-                a.st.lds_off = (int)((lds + 15) / 16 * 16);
-                lds = (size_t)a.st.lds_off + tab;
-            }
+            lds = gvconv::stat_place(a.st, BM, BN, epi_b + late, ss_off, lds);
             if (a.st.mode == gvconv::STAT_FWD) return go(std::integral_constant<int, gvconv::STAT_FWD>{});
             return go(std::integral_constant<int, gvconv::STAT_BWD>{});
         } else {
@@ -850,18 +833,14 @@ namespace gvconv {
 
 const void* dma_zero_page() { return zero_page_for_current_device(); }   // (wgrad_dma.hip shares it)
 
-constexpr int kDmaX3Tiles = 19;
-int dma_x3_num_cfgs() { return kDmaX3Tiles + ws_x3_num_cfgs(); }   // + the wave-specialised kernel's tiles (conv_ws_x3.hip)
+int dma_x3_num_cfgs() { return 19; }
 
 // P3 input: whole 16-channel groups inside one filter tap
 bool dma_x3_ok(const ConvArgs& a) { return a.cin % 16 == 0 && a.x_ld % 16 == 0; }
 
-int dma_x3_launch(int cfg, const ConvArgs& a, hipStream_t st) {
-    return cfg >= kDmaX3Tiles ? ws_x3_launch(cfg - kDmaX3Tiles, a, st) : launch_dma_x3(cfg, a, st);
-}
+int dma_x3_launch(int cfg, const ConvArgs& a, hipStream_t st) { return launch_dma_x3(cfg, a, st); }
 
-constexpr int kDmaLpTiles = 25;
-int dma_lp_num_cfgs() { return kDmaLpTiles + ws_lp_num_cfgs(); }   // + the wave-specialised kernel's tiles (conv_ws.hip)
+int dma_lp_num_cfgs() { return 25; }
 
 // the DMA loader's layer class: whole 8-channel chunks inside one filter tap, 16-byte aligned pixels, 16-bit input
 bool dma_lp_ok(const ConvArgs& a, bool generic, bool xf32) {
@@ -869,10 +848,7 @@ bool dma_lp_ok(const ConvArgs& a, bool generic, bool xf32) {
 }
 
 int dma_lp_launch(int dtype, int cfg, const ConvArgs& a, hipStream_t st) {
-    if (cfg >= kDmaLpTiles) return ws_lp_launch(dtype, cfg - kDmaLpTiles, a, st);
-    if (dtype == GV_BF16) return launch_dma_lp<__bf16>(cfg, a, st);
-    if (dtype == GV_F16) return launch_dma_lp<_Float16>(cfg, a, st);
-    return GV_E_UNSUPPORTED;
+    GV_LP_DISPATCH(dtype, return launch_dma_lp<T>(cfg, a, st));
 }
 
 }  // namespace gvconv

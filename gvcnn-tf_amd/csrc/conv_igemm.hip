@@ -293,25 +293,14 @@ template <int WM, int WN, int TM, int TN, int NCH>
 int launch_cfg(const ConvArgs& a0, bool generic, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     ConvArgs a = a0;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
     a.ktiles = a.Kpad / (CH * NCH);
-    const int tiles_m = gv_ceil_div(a.M, BM);
-    const int64_t nwg = (int64_t)tiles_m * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     const size_t lds = (size_t)(2 * BM + 2 * BN) * (CH * NCH + 4) * sizeof(float);
     if constexpr (NCH == 1) {
-        if (generic) {
-            hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, 1, true>), dim3((unsigned)nwg), dim3(256), lds, st, a);
-            GV_LAUNCH_CHECK();
-            return GV_OK;
-        }
+        if (generic) return gv_launch<conv_igemm_f32<WM, WN, TM, TN, 1, true>>(dim3((unsigned)nwg), dim3(256), lds, st, a);
     }
-    if (lds > 64 * 1024) {
-        if (!GV_BIG_LDS_OK((&conv_igemm_f32<WM, WN, TM, TN, NCH, false>), 160 * 1024)) return GV_E_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, NCH, false>), dim3((unsigned)nwg), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_igemm_f32<WM, WN, TM, TN, NCH, false>>(dim3((unsigned)nwg), dim3(256), lds, st, a);
 }
 
 int launch_tile(int cfg, const ConvArgs& a, bool generic, hipStream_t st) {
@@ -354,15 +343,7 @@ int pick_tile(int M, int N, int K) {
     return best;
 }
 
-}  // namespace
-
-extern "C" void gv_conv2d_set_tile_override(int cfg) { g_tile_override = cfg; }
-extern "C" void gv_conv2d_set_debug(int bits) { g_debug = bits; }
-#ifdef GV_PHASE_TIMES
-unsigned long long* g_phase_buf = nullptr;
-extern "C" void gv_conv2d_set_phase_buffer(void* p) { g_phase_buf = (unsigned long long*)p; }
-#endif
-static int planes_of(int math_mode) {
+int planes_of(int math_mode) {
     switch (math_mode) {
         case GV_MATH_F32: return 0;
         case GV_MATH_BF16X3: return 3;
@@ -372,18 +353,120 @@ static int planes_of(int math_mode) {
     return -1;
 }
 
+// ---- the tile tables ----------------------------------------------------------------------------------------------------
+// A tile index (gv_conv_desc::tile_cfg - 1, gv_conv2d_set_tile_override) names one kernel configuration of a storage form.
+// A form's table is the list of its kernel families IN ORDER, each with as many indices as it has configurations; this is
+// the one place that says which index is whose.  Plans, tile caches, tools and tests hold indices as numbers: append tiles
+// to the last family or families to a table, never reorder.
+enum Form { FORM_LP, FORM_X3IN, FORM_PLANES, FORM_F32 };
+enum Family {
+    LP_STAGED, LP_SPECIAL, LP_DMA, LP_WS,            // 16-bit storage (conv_lp, conv_dma, conv_ws)
+    X3IN_DMA, X3IN_WS,                               // three-plane input (conv_dma, conv_ws_x3)
+    PLANES_STAGED, PLANES_SPECIAL, PLANES_WSG,       // fp32 storage, math on bf16 planes (conv_bf16s, conv_ws_x3)
+    F32_STAGED,                                      // exact fp32 (this file)
+    NO_FAMILY
+};
+struct FamilyRange { Family fam; int count; };
+struct TileTable { int nfam; FamilyRange fam[4]; };
+struct TileRef { Family fam; int local; };           // configuration `local` of family `fam`
+
+TileTable tile_table(Form form) {
+    using namespace gvconv;
+    switch (form) {
+        case FORM_LP:                                // register-staged tiles, the strip / halo slot, LDS-DMA, wave-specialised
+            return {4, {{LP_STAGED, lp_staged_num_cfgs()}, {LP_SPECIAL, 1}, {LP_DMA, dma_lp_num_cfgs()}, {LP_WS, ws_lp_num_cfgs()}}};
+        case FORM_X3IN:                              // LDS-DMA tiles, the wave-specialised strip kernel
+            return {2, {{X3IN_DMA, dma_x3_num_cfgs()}, {X3IN_WS, ws_x3_num_cfgs()}}};
+        case FORM_PLANES:                            // register-staged tiles, the halo / stem slot, the wave-specialised GEMM mode
+            return {3, {{PLANES_STAGED, bf16s_staged_num_cfgs()}, {PLANES_SPECIAL, 1}, {PLANES_WSG, wsg_x3_num_cfgs()}}};
+        case FORM_F32: break;
+    }
+    return {1, {{F32_STAGED, kNumTiles}}};
+}
+
+int table_size(Form form) {
+    const TileTable t = tile_table(form);
+    int n = 0;
+    for (int i = 0; i < t.nfam; ++i) n += t.fam[i].count;
+    return n;
+}
+
+// global index -> (family, local index); NO_FAMILY outside the table
+TileRef tile_lookup(Form form, int cfg) {
+    const TileTable t = tile_table(form);
+    for (int i = 0; i < t.nfam && cfg >= 0; ++i) {
+        if (cfg < t.fam[i].count) return {t.fam[i].fam, cfg};
+        cfg -= t.fam[i].count;
+    }
+    return {NO_FAMILY, 0};
+}
+
+// the first index of a family
+int family_first(Form form, Family fam) {
+    const TileTable t = tile_table(form);
+    int first = 0;
+    for (int i = 0; i < t.nfam && t.fam[i].fam != fam; ++i) first += t.fam[i].count;
+    return first;
+}
+
+int launch_lp_tile(int dtype, int cfg, ConvArgs a, bool generic, bool xf32, hipStream_t st) {
+    using namespace gvconv;
+    const TileRef t = tile_lookup(FORM_LP, cfg);
+    a.ktiles = a.Kpad / 32;                          // (32-deep k-tiles; the families with another depth set their own)
+    if (a.pool && t.fam != LP_SPECIAL) return GV_E_UNSUPPORTED;    // conv -> max pool: the strip / halo kernels only
+    switch (t.fam) {
+        case LP_STAGED: return lp_staged_launch(dtype, t.local, a, generic, xf32, st);
+        case LP_SPECIAL: return lp_special_launch(dtype, a, generic, xf32, st);
+        case LP_DMA: return dma_lp_ok(a, generic, xf32) ? dma_lp_launch(dtype, t.local, a, st) : GV_E_UNSUPPORTED;
+        case LP_WS: return dma_lp_ok(a, generic, xf32) ? ws_lp_launch(dtype, t.local, a, st) : GV_E_UNSUPPORTED;
+        default: return GV_E_UNSUPPORTED;
+    }
+}
+
+int launch_x3in_tile(int cfg, const ConvArgs& a, hipStream_t st) {
+    const TileRef t = tile_lookup(FORM_X3IN, cfg);
+    switch (t.fam) {
+        case X3IN_DMA: return gvconv::dma_x3_launch(t.local, a, st);
+        case X3IN_WS: return gvconv::ws_x3_launch(t.local, a, st);
+        default: return GV_E_UNSUPPORTED;
+    }
+}
+
+int launch_planes_tile(int planes, int cfg, const ConvArgs& a, bool generic, hipStream_t st) {
+    const TileRef t = tile_lookup(FORM_PLANES, cfg);
+    switch (t.fam) {
+        case PLANES_STAGED: return gvconv::bf16s_staged_launch(planes, t.local, a, generic, st);
+        case PLANES_SPECIAL: return gvconv::bf16s_special_launch(planes, a, generic, st);
+        case PLANES_WSG: return planes == 3 && !generic ? gvconv::wsg_x3_launch(t.local, a, st) : GV_E_UNSUPPORTED;
+        default: return GV_E_UNSUPPORTED;
+    }
+}
+
+int launch_f32_tile(int cfg, const ConvArgs& a, bool generic, hipStream_t st) {
+    const TileRef t = tile_lookup(FORM_F32, cfg);
+    return t.fam == F32_STAGED ? launch_tile(t.local, a, generic, st) : GV_E_UNSUPPORTED;
+}
+
+}  // namespace
+
+extern "C" void gv_conv2d_set_tile_override(int cfg) { g_tile_override = cfg; }
+extern "C" void gv_conv2d_set_debug(int bits) { g_debug = bits; }
+#ifdef GV_PHASE_TIMES
+unsigned long long* g_phase_buf = nullptr;
+extern "C" void gv_conv2d_set_phase_buffer(void* p) { g_phase_buf = (unsigned long long*)p; }
+#endif
+
 // index of the strip / halo kernels of the stem layers among the tile configurations (16-bit storage: math_mode -1)
 extern "C" int gv_conv2d_special_tile_cfg(int32_t math_mode) {
-    if (math_mode == -1) return gvconv::lp_special_cfg();
-    const int np = planes_of(math_mode);
-    return np <= 0 ? GV_E_BADARG : gvconv::bf16s_special_cfg();
+    if (math_mode == -1) return family_first(FORM_LP, LP_SPECIAL);
+    return planes_of(math_mode) <= 0 ? GV_E_BADARG : family_first(FORM_PLANES, PLANES_SPECIAL);
 }
 
 extern "C" int gv_conv2d_num_tile_cfgs(int32_t math_mode) {
-    if (math_mode == -1) return gvconv::lp_num_cfgs();     // the 16-bit storage kernels
-    if (math_mode == -3) return gvconv::dma_x3_num_cfgs();  // three-plane input (GV_CONV_X_P3)
+    if (math_mode == -1) return table_size(FORM_LP);       // the 16-bit storage kernels
+    if (math_mode == -3) return table_size(FORM_X3IN);     // three-plane input (GV_CONV_X_P3)
     const int np = planes_of(math_mode);
-    return np < 0 ? GV_E_BADARG : (np == 0 ? kNumTiles : gvconv::bf16s_num_cfgs());
+    return np < 0 ? GV_E_BADARG : table_size(np == 0 ? FORM_F32 : FORM_PLANES);
 }
 
 extern "C" int64_t gv_packed_filter_bytes(int32_t kh, int32_t kw, int32_t cin, int32_t cout,
@@ -424,58 +507,49 @@ extern "C" int gv_pack_filters_batched(const gv_pack_job* jobs_dev, int32_t num_
     return gvconv::lp_pack_filters_batched(jobs_dev, block_job_dev, num_blocks, dtype, (hipStream_t)stream);
 }
 
-static int conv2d_fwd_impl(const gv_conv_desc* d, const void* x, const float* xscale, const float* xshift,
-                           const void* w_packed, const float* scale, const float* shift, const void* residual,
-                           void* y, void* y2, const float* scale2, const float* shift2, void* stream,
-                           const gv_bn_stats* stats = nullptr);
+// ---- gv_conv2d_fwd / _xpre / _bnstats: one launch, in named steps -------------------------------------------------------
+namespace {
 
-extern "C" int gv_conv2d_fwd(const gv_conv_desc* d, const void* x, const void* w_packed,
-                             const float* scale, const float* shift, const void* residual,
-                             void* y, void* y2, const float* scale2, const float* shift2,
-                             void* stream) {
-    return conv2d_fwd_impl(d, x, nullptr, nullptr, w_packed, scale, shift, residual, y, y2, scale2, shift2, stream);
-}
+struct ConvCall {                                        // what the three entry points pass in
+    const gv_conv_desc* d;
+    const void* x;
+    const float *xscale, *xshift;
+    const void* w_packed;
+    const float *scale, *shift;
+    const void* residual;
+    void *y, *y2;
+    const float *scale2, *shift2;
+    const gv_bn_stats* stats;
+    hipStream_t st;
+};
+struct ConvKind {                                        // what the descriptor checks find out
+    bool lp;                                             // 16-bit storage
+    int np;                                              // bf16 planes of the math (16-bit storage: 1; exact fp32: 0)
+    Form form;                                           // whose tile table tile_cfg indexes
+};
 
-extern "C" int gv_conv2d_fwd_xpre(const gv_conv_desc* d, const void* x, const float* xscale, const float* xshift,
-                                  const void* w_packed, const float* scale, const float* shift,
-                                  const void* residual, void* y, void* y2, const float* scale2,
-                                  const float* shift2, void* stream) {
-    if (!xscale || !xshift) return GV_E_BADARG;
-    return conv2d_fwd_impl(d, x, xscale, xshift, w_packed, scale, shift, residual, y, y2, scale2, shift2, stream);
-}
-
-extern "C" int gv_conv2d_fwd_bnstats(const gv_conv_desc* d, const void* x, const void* w_packed, const float* scale,
-                                     const float* shift, const void* residual, void* y, const gv_bn_stats* stats,
-                                     void* stream) {
-    if (!stats) return GV_E_BADARG;
-    return conv2d_fwd_impl(d, x, nullptr, nullptr, w_packed, scale, shift, residual, y, nullptr, nullptr, nullptr, stream, stats);
-}
-
-static int conv2d_fwd_impl(const gv_conv_desc* d, const void* x, const float* xscale, const float* xshift,
-                           const void* w_packed, const float* scale, const float* shift, const void* residual,
-                           void* y, void* y2, const float* scale2, const float* shift2, void* stream,
-                           const gv_bn_stats* stats) {
-    if (!d || !x || !w_packed || !scale || !shift || !y) return GV_E_BADARG;
+// Step 1: everything that can be said from the descriptor and the pointers alone.
+int check_desc(const ConvCall& c, ConvKind* kind) {
+    const gv_conv_desc* d = c.d;
+    if (!d || !c.x || !c.w_packed || !c.scale || !c.shift || !c.y) return GV_E_BADARG;
     if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->cin <= 0 || d->cout <= 0 || d->kh <= 0 ||
         d->kw <= 0 || d->stride <= 0 || d->oh <= 0 || d->ow <= 0 || d->pad_t < 0 || d->pad_l < 0)
         return GV_E_BADARG;
     const bool split = (d->flags & GV_CONV_SPLIT) != 0;
     if (split) {
-        if (!y2 || d->split_col <= 0 || d->split_col >= d->cout) return GV_E_BADARG;
+        if (!c.y2 || d->split_col <= 0 || d->split_col >= d->cout) return GV_E_BADARG;
         if (d->y_ld < d->split_col || d->y2_ld < d->cout - d->split_col) return GV_E_BADARG;
     } else {
         if (d->y_ld < d->cout) return GV_E_BADARG;
-        if (y2 && (!scale2 || !shift2 || d->y2_ld < d->cout)) return GV_E_BADARG;
+        if (c.y2 && (!c.scale2 || !c.shift2 || d->y2_ld < d->cout)) return GV_E_BADARG;
     }
     if (d->x_ld < d->cin) return GV_E_BADARG;
-    if (residual && d->res_ld < d->cout) return GV_E_BADARG;
+    if (c.residual && d->res_ld < d->cout) return GV_E_BADARG;
     // the window of the last output must start inside the padded input
-    {
-        // (a data-gradient launch may legitimately have output rows no window reaches: they get zeros)
-        if (d->in_dilation != 2 && d->y_step != 2 && ((d->oh - 1) * d->stride - d->pad_t >= d->ih ||
-                                    (d->ow - 1) * d->stride - d->pad_l >= d->iw))
-            return GV_E_BADARG;
-    }
+    // (a data-gradient launch may legitimately have output rows no window reaches: they get zeros)
+    if (d->in_dilation != 2 && d->y_step != 2 && ((d->oh - 1) * d->stride - d->pad_t >= d->ih ||
+                                                  (d->ow - 1) * d->stride - d->pad_l >= d->iw))
+        return GV_E_BADARG;
     const bool lp = d->dtype == GV_BF16 || d->dtype == GV_F16;
     if (d->dtype != GV_F32 && !lp) return GV_E_UNSUPPORTED;
     if ((d->flags & GV_CONV_X_F32) && !lp) return GV_E_BADARG;
@@ -487,36 +561,49 @@ static int conv2d_fwd_impl(const gv_conv_desc* d, const void* x, const float* xs
     if (y2p3 && !split) return GV_E_BADARG;
     if (yp3 || y2p3) {
         // whole 16-channel groups per destination, 8-column chunks in the staged epilogue, no second activation
-        if (d->cout % 8 != 0 || (y2 && !split) || (residual && d->res_ld % 4 != 0)) return GV_E_UNSUPPORTED;
+        if (d->cout % 8 != 0 || (c.y2 && !split) || (c.residual && d->res_ld % 4 != 0)) return GV_E_UNSUPPORTED;
         if (yp3 && (d->y_ld % 16 != 0 || (split ? d->split_col : d->cout) % 16 != 0)) return GV_E_UNSUPPORTED;
         if (y2p3 && (d->y2_ld % 16 != 0 || (d->cout - d->split_col) % 16 != 0 || d->split_col % 8 != 0)) return GV_E_UNSUPPORTED;
-        if (!yp3 && (d->y_ld % 4 != 0 || !gv_aligned16(y))) return GV_E_ALIGN;
-        if (split && !y2p3 && (d->y2_ld % 4 != 0 || !gv_aligned16(y2))) return GV_E_ALIGN;
+        if (!yp3 && (d->y_ld % 4 != 0 || !gv_aligned16(c.y))) return GV_E_ALIGN;
+        if (split && !y2p3 && (d->y2_ld % 4 != 0 || !gv_aligned16(c.y2))) return GV_E_ALIGN;
         if (split && d->split_col % 8 != 0) return GV_E_UNSUPPORTED;
     }
-    const int ncfg = lp ? gvconv::lp_num_cfgs()
-                        : (xp3 ? gvconv::dma_x3_num_cfgs() : (np == 0 ? kNumTiles : gvconv::bf16s_num_cfgs()));
-    if (d->tile_cfg < 0 || d->tile_cfg > ncfg) return GV_E_BADARG;
-    const int64_t M64 = (int64_t)d->nb * d->oh * d->ow;
-    if (M64 > 0x7fffffff || (int64_t)d->nb * d->ih * d->iw > 0x7fffffff) return GV_E_UNSUPPORTED;
-    if (!gv_aligned16(w_packed)) return GV_E_ALIGN;
+    *kind = {lp, np, lp ? FORM_LP : (xp3 ? FORM_X3IN : (np == 0 ? FORM_F32 : FORM_PLANES))};
+    if (d->tile_cfg < 0 || d->tile_cfg > table_size(kind->form)) return GV_E_BADARG;
+    if ((int64_t)d->nb * d->oh * d->ow > 0x7fffffff || (int64_t)d->nb * d->ih * d->iw > 0x7fffffff) return GV_E_UNSUPPORTED;
+    if (!gv_aligned16(c.w_packed)) return GV_E_ALIGN;
+    if (d->relu_cols < 0) return GV_E_BADARG;
+    if (d->in_dilation != 0 && d->in_dilation != 1 && d->in_dilation != 2) return GV_E_BADARG;
+    const bool dilated = d->in_dilation == 2;
+    if (dilated && (np == 0 || (d->cin % CH != 0) || d->stride != 1)) return GV_E_UNSUPPORTED;
+    if (d->y_step != 0) {
+        // one parity class of a stride-2 data gradient: stride-1 launch whose output rows land on every second pixel
+        if (d->y_step != 2 || d->y_py < 0 || d->y_py > 1 || d->y_px < 0 || d->y_px > 1) return GV_E_BADARG;
+        if (2 * (d->oh - 1) + d->y_py >= d->y_ih || 2 * (d->ow - 1) + d->y_px >= d->y_iw) return GV_E_BADARG;
+        if (!lp || split || c.y2 || d->stride != 1 || dilated) return GV_E_UNSUPPORTED;
+        if ((int64_t)d->nb * d->y_ih * d->y_iw > 0x7fffffff) return GV_E_UNSUPPORTED;
+    }
+    return GV_OK;
+}
 
+// Step 2: the launch arguments of a checked descriptor (the families fill in tiles_n, ktiles and their own fields).
+ConvArgs make_args(const ConvCall& c) {
+    const gv_conv_desc* d = c.d;
     ConvArgs a;
-    a.x = (const float*)x; a.w = w_packed; a.scale = scale; a.shift = shift;
-    a.res = (const float*)residual; a.y = (float*)y; a.y2 = (float*)y2;
-    a.scale2 = scale2; a.shift2 = shift2;
-    a.xscale = xscale; a.xshift = xshift;
+    a.x = (const float*)c.x; a.w = c.w_packed; a.scale = c.scale; a.shift = c.shift;
+    a.res = (const float*)c.residual; a.y = (float*)c.y; a.y2 = (float*)c.y2;
+    a.scale2 = c.scale2; a.shift2 = c.shift2;
+    a.xscale = c.xscale; a.xshift = c.xshift;
     a.nb = d->nb; a.ih = d->ih; a.iw = d->iw; a.cin = d->cin; a.x_ld = d->x_ld;
     a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l;
     a.oh = d->oh; a.ow = d->ow; a.cout = d->cout; a.y_ld = d->y_ld; a.res_ld = d->res_ld;
     a.y2_ld = d->y2_ld;
-    a.M = (int)M64; a.K = d->kh * d->kw * d->cin;
+    a.M = (int)((int64_t)d->nb * d->oh * d->ow); a.K = d->kh * d->kw * d->cin;
     a.Kpad = (a.K + KPAD_ALIGN - 1) / KPAD_ALIGN * KPAD_ALIGN;
     a.ktiles = 0;
     a.relu = (d->flags & GV_CONV_RELU) ? 1 : 0;
     a.relu2 = (d->flags & GV_CONV_RELU2) ? 1 : 0;
-    a.split = split ? d->split_col : 0;
-    if (d->relu_cols < 0) return GV_E_BADARG;
+    a.split = (d->flags & GV_CONV_SPLIT) ? d->split_col : 0;
     a.relu_limit = d->relu_cols > 0 ? d->relu_cols : 0x7fffffff;
     a.tiles_n = 0;
     a.dbg = g_debug;
@@ -526,129 +613,161 @@ static int conv2d_fwd_impl(const gv_conv_desc* d, const void* x, const float* xs
     a.zeros = nullptr;
     a.y_p3 = (d->flags & GV_CONV_Y_P3) ? 1 : 0;
     a.y2_p3 = (d->flags & GV_CONV_Y2_P3) ? 1 : 0;
-    if (d->in_dilation != 0 && d->in_dilation != 1 && d->in_dilation != 2) return GV_E_BADARG;
     a.dil_shift = d->in_dilation == 2 ? 1 : 0;
-    if (a.dil_shift && (np == 0 || (d->cin % CH != 0) || d->stride != 1)) return GV_E_UNSUPPORTED;
-    if (d->y_step != 0) {
-        // one parity class of a stride-2 data gradient: stride-1 launch whose output rows land on every second pixel
-        if (d->y_step != 2 || d->y_py < 0 || d->y_py > 1 || d->y_px < 0 || d->y_px > 1) return GV_E_BADARG;
-        if (2 * (d->oh - 1) + d->y_py >= d->y_ih || 2 * (d->ow - 1) + d->y_px >= d->y_iw) return GV_E_BADARG;
-        if (!lp || split || y2 || d->stride != 1 || a.dil_shift) return GV_E_UNSUPPORTED;
-        if ((int64_t)d->nb * d->y_ih * d->y_iw > 0x7fffffff) return GV_E_UNSUPPORTED;
-        a.y_step = 2; a.y_py = d->y_py; a.y_px = d->y_px; a.y_ih = d->y_ih; a.y_iw = d->y_iw;
-    }
+    if (d->y_step != 0) { a.y_step = 2; a.y_py = d->y_py; a.y_px = d->y_px; a.y_ih = d->y_ih; a.y_iw = d->y_iw; }
     // exact m / (oh*ow) and rem / ow by multiplication: the loaders' row -> (image, y, x) walk (four 32-bit divisions per
     // lane of every workgroup's prologue otherwise, ~35 instructions each) and the parity-class epilogue
     a.y_div_img = gv_fast_div(d->oh * d->ow);
     a.y_div_row = gv_fast_div(d->ow);
-    if (stats) {
-        // BatchNorm sums in the epilogue: 16-bit storage, one plain destination (the sums are those of the stored values)
-        if (stats->mode != GV_BN_STATS_FWD && stats->mode != GV_BN_STATS_BWD) return GV_E_BADARG;
-        if (stats->groups <= 0 || stats->nseg <= 0 || stats->nseg > GV_BN_STATS_MAX_SEG) return GV_E_BADARG;
-        if (!lp || split || y2 || (d->flags & (GV_CONV_RELU | GV_CONV_RELU2))) return GV_E_UNSUPPORTED;
-        // whole 16-byte chunks of 8 channels everywhere (the lean epilogue of the instantiations that fold the sums)
-        if (d->cout % 8 != 0 || d->y_ld % 8 != 0 || !gv_aligned16(y) || (residual && (d->res_ld % 8 != 0 || !gv_aligned16(residual))))
-            return GV_E_UNSUPPORTED;
-        a.st.mode = stats->mode == GV_BN_STATS_FWD ? gvconv::STAT_FWD : gvconv::STAT_BWD;
-        a.st.hw = d->oh * d->ow;
-        a.st.G = stats->groups;
-        a.st.nseg = stats->nseg;
-        a.st.hw_magic = a.st.hw > 1 ? (unsigned)((0x100000000ull + (unsigned)a.st.hw - 1) / (unsigned)a.st.hw) : 0u;
-        a.st.lds_off = a.st.slots = a.st.fold = a.st.pad_ = 0;
-        a.st.dbg = g_debug;
-        for (int i = 0; i < stats->nseg; ++i) {
-            const gv_bn_stats_seg& g = stats->seg[i];
-            if (g.c0 < 0 || g.c1 <= g.c0 || g.c1 > d->cout) return GV_E_BADARG;
-            if (stats->mode == GV_BN_STATS_BWD && g.acc && (!g.z || g.z_ld < g.c1 - g.c0 || (g.scale == nullptr) != (g.shift == nullptr)))
-                return GV_E_BADARG;
-            if (stats->mode == GV_BN_STATS_BWD && g.acc && (g.z_ld % 8 != 0 || !gv_aligned16(g.z))) return GV_E_ALIGN;
-            a.st.seg[i].c0 = g.c0; a.st.seg[i].c1 = g.c1; a.st.seg[i].z_ld = g.z_ld; a.st.seg[i].pad_ = 0;
-            a.st.seg[i].z = (const unsigned short*)g.z; a.st.seg[i].scale = g.scale; a.st.seg[i].shift = g.shift;
-            a.st.seg[i].acc = g.acc;
-        }
-    }
+    return a;
+}
 
-    if (d->flags & (GV_CONV_MAXPOOL3S2 | GV_CONV_MAXPOOL3S2_SAME)) {
-        // conv -> max_pool2d 3x3 / 2 in one launch: y is the pooled tensor (the halo / stem strip kernels' classes only)
-        const bool same = (d->flags & GV_CONV_MAXPOOL3S2_SAME) != 0;
-        if (same && (d->flags & GV_CONV_MAXPOOL3S2)) return GV_E_BADARG;
-        // (fp32 storage: three-plane math, the VALID pool behind the halo kernel's class — checked below)
-        if ((!lp && (np != 3 || same || xp3 || yp3)) || split || y2 || residual || stats || xscale || d->y_step != 0 || a.dil_shift ||
-            d->oh < 3 || d->ow < 3)
-            return GV_E_UNSUPPORTED;
-        if (same && ((d->oh | d->ow) & 1)) return GV_E_UNSUPPORTED;          // TF's SAME pads (0, 1) on an even map only
-        a.pool = same ? 2 : 1;
-        a.ph = same ? d->oh / 2 : (d->oh - 3) / 2 + 1;
-        a.pw = same ? d->ow / 2 : (d->ow - 3) / 2 + 1;
-        // GV_CONV_POOL_ACT2: the pooled tensor leaves as act2(pool * scale2 + shift2) (16-bit storage, the stem strip kernel)
-        if (d->flags & GV_CONV_POOL_ACT2) {
-            if (!scale2 || !shift2) return GV_E_BADARG;
-            if (!lp) return GV_E_UNSUPPORTED;
-        } else {
-            a.scale2 = a.shift2 = nullptr;
-        }
-    } else if (d->flags & GV_CONV_POOL_ACT2) {
-        return GV_E_BADARG;
+// Step 3: BatchNorm sums in the epilogue: 16-bit storage, one plain destination (the sums are those of the stored values).
+int set_stats(const ConvCall& c, bool lp, ConvArgs& a) {
+    const gv_conv_desc* d = c.d;
+    const gv_bn_stats* stats = c.stats;
+    if (stats->mode != GV_BN_STATS_FWD && stats->mode != GV_BN_STATS_BWD) return GV_E_BADARG;
+    if (stats->groups <= 0 || stats->nseg <= 0 || stats->nseg > GV_BN_STATS_MAX_SEG) return GV_E_BADARG;
+    if (!lp || a.split || c.y2 || (d->flags & (GV_CONV_RELU | GV_CONV_RELU2))) return GV_E_UNSUPPORTED;
+    // whole 16-byte chunks of 8 channels everywhere (the lean epilogue of the instantiations that fold the sums)
+    if (d->cout % 8 != 0 || d->y_ld % 8 != 0 || !gv_aligned16(c.y) ||
+        (c.residual && (d->res_ld % 8 != 0 || !gv_aligned16(c.residual))))
+        return GV_E_UNSUPPORTED;
+    a.st.mode = stats->mode == GV_BN_STATS_FWD ? gvconv::STAT_FWD : gvconv::STAT_BWD;
+    a.st.hw = d->oh * d->ow;
+    a.st.G = stats->groups;
+    a.st.nseg = stats->nseg;
+    a.st.hw_magic = a.st.hw > 1 ? (unsigned)((0x100000000ull + (unsigned)a.st.hw - 1) / (unsigned)a.st.hw) : 0u;
+    a.st.lds_off = a.st.slots = a.st.fold = a.st.pad_ = 0;
+    a.st.dbg = g_debug;
+    for (int i = 0; i < stats->nseg; ++i) {
+        const gv_bn_stats_seg& g = stats->seg[i];
+        if (g.c0 < 0 || g.c1 <= g.c0 || g.c1 > d->cout) return GV_E_BADARG;
+        if (stats->mode == GV_BN_STATS_BWD && g.acc && (!g.z || g.z_ld < g.c1 - g.c0 || (g.scale == nullptr) != (g.shift == nullptr)))
+            return GV_E_BADARG;
+        if (stats->mode == GV_BN_STATS_BWD && g.acc && (g.z_ld % 8 != 0 || !gv_aligned16(g.z))) return GV_E_ALIGN;
+        a.st.seg[i].c0 = g.c0; a.st.seg[i].c1 = g.c1; a.st.seg[i].z_ld = g.z_ld; a.st.seg[i].pad_ = 0;
+        a.st.seg[i].z = (const unsigned short*)g.z; a.st.seg[i].scale = g.scale; a.st.seg[i].shift = g.shift;
+        a.st.seg[i].acc = g.acc;
     }
-    if (lp) {
-        // vector loader: 8-channel (16-byte) chunks inside one filter tap, 16-byte aligned pixels
-        const bool xf32 = (d->flags & GV_CONV_X_F32) != 0;
-        const bool generic = xf32 || (d->cin % 8 != 0) || (d->x_ld % 8 != 0) || !gv_aligned16(x);
-        if (a.pool && !((a.pool == 1 && gvconv::lp_halo_pool_ok(a, generic)) || gvconv::lp_stem_pool_ok(a, xf32)))
-            return GV_E_UNSUPPORTED;
-        if (a.dil_shift && generic) return GV_E_UNSUPPORTED;
-        // the vector loader keeps 32-bit element offsets
-        if (!generic && (int64_t)d->nb * d->ih * d->iw * d->x_ld > 0xffffffffll) return GV_E_UNSUPPORTED;
-        if (xscale) {
-            // pre-activation on load: the register-staged loader of the 1x1 / unpadded class (a padding tap would have
-            // to read relu(xshift), not 0), (scale, shift) table of the input channels in LDS
-            const int want = g_tile_override >= 0 && g_tile_override < ncfg ? g_tile_override : d->tile_cfg - 1;
-            // the special tile index: the streaming TAIL form of the bottleneck launch (csrc/conv_chain.hip), where it serves
-            if (want == gvconv::lp_special_cfg() && !generic)
-                return gvconv::chain_tail_launch(d->dtype, a, (hipStream_t)stream);
-            if (generic || d->kh != 1 || d->kw != 1 || d->pad_t != 0 || d->pad_l != 0 || a.dil_shift ||
-                d->cin > 2048 || (want >= 0 && !gvconv::lp_xpre_cfg_ok(want)))
-                return GV_E_UNSUPPORTED;
-            const int cfg = want >= 0 ? want : gvconv::lp_xpre_pick(a.M, a.cout);
-            return gvconv::lp_launch(d->dtype, cfg, a, false, false, (hipStream_t)stream);
-        }
-        const int cfg = g_tile_override >= 0 && g_tile_override < ncfg ? g_tile_override
-                        : (d->tile_cfg > 0 ? d->tile_cfg - 1
-                           : ((gvconv::lp_halo_ok(a, generic) || gvconv::lp_stem_ok(a, xf32)) && (a.M >= 100000 || a.pool)
-                                  ? gvconv::lp_special_cfg()
-                                                                              : gvconv::lp_pick_tile(a.M, a.cout, a.K)));
-        return gvconv::lp_launch(d->dtype, cfg, a, generic, xf32, (hipStream_t)stream);
+    return GV_OK;
+}
+
+// Step 4: conv -> max_pool2d 3x3 / 2 in one launch: y is the pooled tensor.  Which layer classes are served is the strip /
+// halo families' business (lp_special_launch, bf16s_special_launch); fp32 storage: three-plane math and the VALID pool only.
+int set_pool(const ConvCall& c, const ConvKind& k, ConvArgs& a) {
+    const gv_conv_desc* d = c.d;
+    if (!(d->flags & (GV_CONV_MAXPOOL3S2 | GV_CONV_MAXPOOL3S2_SAME))) return (d->flags & GV_CONV_POOL_ACT2) ? GV_E_BADARG : GV_OK;
+    const bool same = (d->flags & GV_CONV_MAXPOOL3S2_SAME) != 0;
+    if (same && (d->flags & GV_CONV_MAXPOOL3S2)) return GV_E_BADARG;
+    if ((!k.lp && (k.np != 3 || same || k.form == FORM_X3IN || a.y_p3)) || a.split || c.y2 || c.residual || c.stats || c.xscale ||
+        d->y_step != 0 || a.dil_shift || d->oh < 3 || d->ow < 3)
+        return GV_E_UNSUPPORTED;
+    if (same && ((d->oh | d->ow) & 1)) return GV_E_UNSUPPORTED;          // TF's SAME pads (0, 1) on an even map only
+    a.pool = same ? 2 : 1;
+    a.ph = same ? d->oh / 2 : (d->oh - 3) / 2 + 1;
+    a.pw = same ? d->ow / 2 : (d->ow - 3) / 2 + 1;
+    // GV_CONV_POOL_ACT2: the pooled tensor leaves as act2(pool * scale2 + shift2) (16-bit storage, the stem strip kernel)
+    if (d->flags & GV_CONV_POOL_ACT2) {
+        if (!c.scale2 || !c.shift2) return GV_E_BADARG;
+        if (!k.lp) return GV_E_UNSUPPORTED;
+    } else {
+        a.scale2 = a.shift2 = nullptr;
     }
-    if (xscale) return GV_E_UNSUPPORTED;                 // pre-activation on load: 16-bit storage only
-    if (xp3) {                                           // three-plane input: the LDS-DMA kernel
-        if (!gvconv::dma_x3_ok(a) || !gv_aligned16(x) || (y2 && !split)) return GV_E_UNSUPPORTED;
-        if (split && (d->split_col % 8 != 0 || d->cout % 8 != 0 || (!yp3 && (d->y_ld % 4 != 0 || !gv_aligned16(y))) ||
-                      (!y2p3 && (d->y2_ld % 4 != 0 || !gv_aligned16(y2)))))
+    return GV_OK;
+}
+
+// Step 6 (used by every family selection of step 5): the tile a launch asks for: the override (a tuning hook) where it names
+// an index of the table, else the descriptor's; -1: neither names one, the caller's default pick applies.
+int wanted_tile(const gv_conv_desc* d, Form form) {
+    return g_tile_override >= 0 && g_tile_override < table_size(form) ? g_tile_override : d->tile_cfg - 1;
+}
+
+// Step 5, 16-bit storage.
+int run_lp(const ConvCall& c, const ConvArgs& a) {
+    using namespace gvconv;
+    const gv_conv_desc* d = c.d;
+    // vector loader: 8-channel (16-byte) chunks inside one filter tap, 16-byte aligned pixels
+    const bool xf32 = (d->flags & GV_CONV_X_F32) != 0;
+    const bool generic = xf32 || (d->cin % 8 != 0) || (d->x_ld % 8 != 0) || !gv_aligned16(c.x);
+    if (a.dil_shift && generic) return GV_E_UNSUPPORTED;
+    // the vector loader keeps 32-bit element offsets
+    if (!generic && (int64_t)d->nb * d->ih * d->iw * d->x_ld > 0xffffffffll) return GV_E_UNSUPPORTED;
+    const int want = wanted_tile(d, FORM_LP);
+    if (c.xscale) {
+        // pre-activation on load: the register-staged loader of the 1x1 / unpadded class (a padding tap would have
+        // to read relu(xshift), not 0), (scale, shift) table of the input channels in LDS
+        // the special tile index: the streaming TAIL form of the bottleneck launch (csrc/conv_chain.hip), where it serves
+        if (want == family_first(FORM_LP, LP_SPECIAL) && !generic) return chain_tail_launch(d->dtype, a, c.st);
+        if (generic || d->kh != 1 || d->kw != 1 || d->pad_t != 0 || d->pad_l != 0 || a.dil_shift ||
+            d->cin > 2048 || (want >= 0 && !lp_xpre_cfg_ok(want)))
             return GV_E_UNSUPPORTED;
-        const int cfg = g_tile_override >= 0 && g_tile_override < ncfg ? g_tile_override
-                        : (d->tile_cfg > 0 ? d->tile_cfg - 1 : 0);
-        return gvconv::dma_x3_launch(cfg, a, (hipStream_t)stream);
+        return launch_lp_tile(d->dtype, want >= 0 ? want : lp_xpre_pick(a.M, a.cout), a, false, false, c.st);
+    }
+    // default: the strip / halo kernels for their classes on large maps (and for a fused pool, which only they serve)
+    const bool special = (lp_halo_ok(a, generic) || lp_stem_ok(a, xf32)) && (a.M >= 100000 || a.pool);
+    const int cfg = want >= 0 ? want : (special ? family_first(FORM_LP, LP_SPECIAL) : staged_pick_tile(a.M, a.cout));
+    return launch_lp_tile(d->dtype, cfg, a, generic, xf32, c.st);
+}
+
+// Step 5, fp32 storage: three-plane input, math on bf16 planes, exact fp32.
+int run_f32(const ConvCall& c, const ConvKind& k, const ConvArgs& a) {
+    using namespace gvconv;
+    const gv_conv_desc* d = c.d;
+    if (c.xscale) return GV_E_UNSUPPORTED;               // pre-activation on load: 16-bit storage only
+    const int want = wanted_tile(d, k.form);
+    if (k.form == FORM_X3IN) {                           // three-plane input: the LDS-DMA kernel
+        const bool split = a.split > 0;
+        if (!dma_x3_ok(a) || !gv_aligned16(c.x) || (c.y2 && !split)) return GV_E_UNSUPPORTED;
+        if (split && (d->split_col % 8 != 0 || d->cout % 8 != 0 || (!a.y_p3 && (d->y_ld % 4 != 0 || !gv_aligned16(c.y))) ||
+                      (!a.y2_p3 && (d->y2_ld % 4 != 0 || !gv_aligned16(c.y2)))))
+            return GV_E_UNSUPPORTED;
+        return launch_x3in_tile(want >= 0 ? want : 0, a, c.st);
     }
     // vector loader needs 16-channel chunks inside one filter tap and 16-byte aligned pixels
-    const bool generic = (d->cin % CH != 0) || (d->x_ld % 4 != 0) || !gv_aligned16(x);
-    if (a.pool) {                                        // conv -> max pool on fp32 storage: one kernel serves it
-        if (!gvconv::bf16s_halo_pool_ok(np, a, generic)) return GV_E_UNSUPPORTED;
-        return gvconv::bf16s_launch(np, gvconv::bf16s_special_cfg(), a, generic, (hipStream_t)stream);
-    }
-    if (np > 0) {
-        // the vector loader keeps 32-bit element offsets
-        if (!generic && (int64_t)d->nb * d->ih * d->iw * d->x_ld > 0xffffffffll) return GV_E_UNSUPPORTED;
-        const int cfg = g_tile_override >= 0 && g_tile_override < ncfg ? g_tile_override
-                        : (d->tile_cfg > 0 ? d->tile_cfg - 1
-                           : ((gvconv::bf16s_halo_ok(np, a, generic) || gvconv::bf16s_stem_ok(np, a)) &&
-                                      a.M >= 100000
-                                  ? gvconv::bf16s_special_cfg()
-                                                                                     : gvconv::bf16s_pick_tile(np, a.M, a.cout, a.K)));
-        return gvconv::bf16s_launch(np, cfg, a, generic, (hipStream_t)stream);
-    }
-    const int cfg = g_tile_override >= 0 && g_tile_override < kNumTiles ? g_tile_override
-                    : (d->tile_cfg > 0 ? d->tile_cfg - 1 : pick_tile(a.M, a.cout, a.K));
-    return launch_tile(cfg, a, generic, (hipStream_t)stream);
+    const bool generic = (d->cin % CH != 0) || (d->x_ld % 4 != 0) || !gv_aligned16(c.x);
+    // conv -> max pool on fp32 storage: one kernel serves it
+    if (a.pool) return launch_planes_tile(k.np, family_first(FORM_PLANES, PLANES_SPECIAL), a, generic, c.st);
+    if (k.form == FORM_F32) return launch_f32_tile(want >= 0 ? want : pick_tile(a.M, a.cout, a.K), a, generic, c.st);
+    // the vector loader keeps 32-bit element offsets
+    if (!generic && (int64_t)d->nb * d->ih * d->iw * d->x_ld > 0xffffffffll) return GV_E_UNSUPPORTED;
+    const bool special = (bf16s_halo_ok(k.np, a, generic) || bf16s_stem_ok(k.np, a)) && a.M >= 100000;
+    const int cfg = want >= 0 ? want : (special ? family_first(FORM_PLANES, PLANES_SPECIAL) : staged_pick_tile(a.M, a.cout));
+    return launch_planes_tile(k.np, cfg, a, generic, c.st);
+}
+
+int conv2d_fwd_impl(const ConvCall& c) {
+    ConvKind kind;
+    int rc = check_desc(c, &kind);
+    if (rc != GV_OK) return rc;
+    ConvArgs a = make_args(c);
+    if (c.stats && (rc = set_stats(c, kind.lp, a)) != GV_OK) return rc;
+    if ((rc = set_pool(c, kind, a)) != GV_OK) return rc;
+    return kind.lp ? run_lp(c, a) : run_f32(c, kind, a);
+}
+
+}  // namespace
+
+extern "C" int gv_conv2d_fwd(const gv_conv_desc* d, const void* x, const void* w_packed,
+                             const float* scale, const float* shift, const void* residual,
+                             void* y, void* y2, const float* scale2, const float* shift2,
+                             void* stream) {
+    return conv2d_fwd_impl({d, x, nullptr, nullptr, w_packed, scale, shift, residual, y, y2, scale2, shift2, nullptr, (hipStream_t)stream});
+}
+
+extern "C" int gv_conv2d_fwd_xpre(const gv_conv_desc* d, const void* x, const float* xscale, const float* xshift,
+                                  const void* w_packed, const float* scale, const float* shift,
+                                  const void* residual, void* y, void* y2, const float* scale2,
+                                  const float* shift2, void* stream) {
+    if (!xscale || !xshift) return GV_E_BADARG;
+    return conv2d_fwd_impl({d, x, xscale, xshift, w_packed, scale, shift, residual, y, y2, scale2, shift2, nullptr, (hipStream_t)stream});
+}
+
+extern "C" int gv_conv2d_fwd_bnstats(const gv_conv_desc* d, const void* x, const void* w_packed, const float* scale,
+                                     const float* shift, const void* residual, void* y, const gv_bn_stats* stats,
+                                     void* stream) {
+    if (!stats) return GV_E_BADARG;
+    return conv2d_fwd_impl({d, x, nullptr, nullptr, w_packed, scale, shift, residual, y, nullptr, nullptr, nullptr, stats, (hipStream_t)stream});
 }
 
 extern "C" int gv_conv2d_time(const gv_conv_desc* d, const void* x, const void* w_packed,

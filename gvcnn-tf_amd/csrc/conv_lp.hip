@@ -1008,23 +1008,21 @@ __global__ __launch_bounds__(256) void pack_filters_batched_lp(const gv_pack_job
     reinterpret_cast<unsigned short*>(j.out)[dst] = to_bits<T>(v);
 }
 
-struct TileCfg { int bm, bn; };
-constexpr TileCfg kTiles[] = {{128, 128}, {128, 64}, {64, 64}, {128, 96}, {64, 128}, {128, 32},
-                              {256, 128}, {128, 256}, {256, 64},    // these three: 8 waves
-                              {128, 192}, {64, 192},                // one n-tile for the many 192-channel layers
-                              {256, 192}};                          // 8 waves: least operand traffic per flop (Conv2d_4a)
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// The register-staged tiles, index by index: X(index, WM, WN, TM, TN) — BM = WM * TM * 32 rows x BN = WN * TN * 32 columns.
+//   0 .. 5: 128 x 128, 128 x 64, 64 x 64, 128 x 96, 64 x 128, 128 x 32;   6 .. 8: 256 x 128, 128 x 256, 256 x 64 (8 waves);
+//   9, 10: 128 x 192, 64 x 192 (one n-tile for the many 192-channel layers);
+//   11: 256 x 192 (8 waves: least operand traffic per flop, Conv2d_4a)
+#define GV_LP_STAGED_TILES(X)                                                                                          \
+    X(0, 2, 2, 2, 2) X(1, 2, 2, 2, 1) X(2, 2, 2, 1, 1) X(3, 4, 1, 1, 3) X(4, 2, 2, 1, 2) X(5, 4, 1, 1, 1) X(6, 4, 2, 2, 2)     \
+    X(7, 2, 4, 2, 2) X(8, 4, 2, 2, 1) X(9, 2, 2, 2, 3) X(10, 2, 2, 1, 3) X(11, 4, 2, 2, 3)
+#define GV_X(i, wm, wn, tm, tn) +1
+constexpr int kNumTiles = 0 GV_LP_STAGED_TILES(GV_X);
+#undef GV_X
 
 template <typename T, int WM, int WN, int TM, int TN, bool GENERIC, bool XF32, bool XPRE = false, int STATS = 0>
 int launch_one(const ConvArgs& a, int64_t nwg, size_t lds, hipStream_t st) {
     if (lds > 160 * 1024) return GV_E_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        const bool ok = GV_BIG_LDS_OK((&conv_igemm_lp<T, WM, WN, TM, TN, GENERIC, XF32, XPRE, STATS>), 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL((conv_igemm_lp<T, WM, WN, TM, TN, GENERIC, XF32, XPRE, STATS>), dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_igemm_lp<T, WM, WN, TM, TN, GENERIC, XF32, XPRE, STATS>>(dim3((unsigned)nwg), dim3(WM * WN * 64), lds, st, a);
 }
 
 // the tiles the pre-activation-on-load loader is instantiated for: 128 / 256 rows x 64 / 128 / 256 columns (the conv1 of a
@@ -1038,27 +1036,17 @@ template <typename T, int WM, int WN, int TM, int TN>
 int launch_cfg(const ConvArgs& a0, bool generic, bool xf32, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     ConvArgs a = a0;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int tiles_m = gv_ceil_div(a.M, BM);
-    const int64_t nwg = (int64_t)tiles_m * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     const size_t lds_main = (size_t)(2 * BM + 2 * BN) * RB + ((generic || xf32) ? (size_t)a.Kpad * 8 : 0) +
                             (a.xscale ? (size_t)a.cin * 8 : 0);
     const size_t lds_epi = (size_t)(WM * WN) * EpiGeom<TN>::BYTES;
-    size_t lds = ((lds_main > lds_epi ? lds_main : lds_epi) + 15) / 16 * 16 + 16 * BN;   // + the epilogue's constants
+    const size_t ss_off = ((lds_main > lds_epi ? lds_main : lds_epi) + 15) / 16 * 16;
+    size_t lds = ss_off + 16 * BN;                    // + the epilogue's constants
     if (a.st.mode != gvconv::STAT_OFF) {              // BatchNorm sums in the epilogue: vector loader, plain epilogue
         if (a.xscale || xf32 || generic || !gvconv::stat_tile_ok(a.st, BM, a.cout, TM * 32)) return GV_E_UNSUPPORTED;
-        a.st.slots = gvconv::stat_rows(BM, a.st.hw, a.st.G);
-        a.st.fold = gvconv::stat_slots(BM, a.st.hw) > a.st.G ? 1 : 0;
-        // the tables live in the main-loop buffers the epilogue has freed, behind the waves' staging blocks, where they
-        // fit in front of the epilogue's constants; else behind everything (more LDS per workgroup)
-        const size_t tab = gvconv::stat_lds_bytes(a.st.mode, a.st.slots, BN), ss_off = ((lds_main > lds_epi ? lds_main : lds_epi) + 15) / 16 * 16;
-        if (lds_epi + tab <= ss_off) {
-            a.st.lds_off = (int)lds_epi;
-        } else {
-            a.st.lds_off = (int)lds;
-            lds += tab;
-        }
+        // the tables live in the main-loop buffers the epilogue has freed (conv_stats.h: stat_place)
+        lds = gvconv::stat_place(a.st, BM, BN, lds_epi, ss_off, lds);
         if (a.st.mode == gvconv::STAT_FWD) return launch_one<T, WM, WN, TM, TN, false, false, false, gvconv::STAT_FWD>(a, nwg, lds, st);
         return launch_one<T, WM, WN, TM, TN, false, false, false, gvconv::STAT_BWD>(a, nwg, lds, st);
     }
@@ -1079,18 +1067,9 @@ int launch_cfg(const ConvArgs& a0, bool generic, bool xf32, hipStream_t st) {
 template <typename T>
 int launch_t(int cfg, const ConvArgs& a, bool generic, bool xf32, hipStream_t st) {
     switch (cfg) {
-        case 0: return launch_cfg<T, 2, 2, 2, 2>(a, generic, xf32, st);
-        case 1: return launch_cfg<T, 2, 2, 2, 1>(a, generic, xf32, st);
-        case 2: return launch_cfg<T, 2, 2, 1, 1>(a, generic, xf32, st);
-        case 3: return launch_cfg<T, 4, 1, 1, 3>(a, generic, xf32, st);
-        case 4: return launch_cfg<T, 2, 2, 1, 2>(a, generic, xf32, st);
-        case 5: return launch_cfg<T, 4, 1, 1, 1>(a, generic, xf32, st);
-        case 6: return launch_cfg<T, 4, 2, 2, 2>(a, generic, xf32, st);
-        case 7: return launch_cfg<T, 2, 4, 2, 2>(a, generic, xf32, st);
-        case 8: return launch_cfg<T, 4, 2, 2, 1>(a, generic, xf32, st);
-        case 9: return launch_cfg<T, 2, 2, 2, 3>(a, generic, xf32, st);
-        case 10: return launch_cfg<T, 2, 2, 1, 3>(a, generic, xf32, st);
-        case 11: return launch_cfg<T, 4, 2, 2, 3>(a, generic, xf32, st);
+#define GV_X(i, wm, wn, tm, tn) case i: return launch_cfg<T, wm, wn, tm, tn>(a, generic, xf32, st);
+        GV_LP_STAGED_TILES(GV_X)
+#undef GV_X
     }
     return GV_E_UNSUPPORTED;
 }
@@ -1101,17 +1080,9 @@ int launch_halo_r(const ConvArgs& a, hipStream_t st) {
     const int tiles_x = (a.ow + 31) / 32;
     const dim3 grid((unsigned)(a.nb * tiles_x));
     const size_t halo = (size_t)(4 * RPW + 2) * 34 * 80;
-    if (a.cout <= 32) {
-        const size_t lds = halo + 4 * 32 * (32 + 4) * 4;
-        hipLaunchKernelGGL((conv3x3_halo_lp<T, 1, RPW, 32, STATS>), grid, dim3(256), lds, st, a);
-    } else {
-        const size_t lds = halo + (RPW == 2 ? 0 : 4 * 32 * (32 + 4) * 4) + 64 * (288 * 2 + 16);   // (RPW = 2: staging aliases the halo)
-        const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_lp<T, 2, RPW, 32, STATS>), 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-        hipLaunchKernelGGL((conv3x3_halo_lp<T, 2, RPW, 32, STATS>), grid, dim3(256), lds, st, a);
-    }
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    if (a.cout <= 32) return gv_launch<conv3x3_halo_lp<T, 1, RPW, 32, STATS>>(grid, dim3(256), halo + 4 * 32 * (32 + 4) * 4, st, a);
+    const size_t lds = halo + (RPW == 2 ? 0 : 4 * 32 * (32 + 4) * 4) + 64 * (288 * 2 + 16);   // (RPW = 2: staging aliases the halo)
+    return gv_launch<conv3x3_halo_lp<T, 2, RPW, 32, STATS>>(grid, dim3(256), lds, st, a);
 }
 
 // GV_CONV_MAXPOOL3S2: 27 KB halo (staging aliased) + 38 KB filter + 15 KB of reduced rows = 80 448 B: two per CU
@@ -1119,22 +1090,14 @@ template <typename T>
 int launch_halo_pool(const ConvArgs& a, hipStream_t st) {
     const int tiles_x = (a.pw + 14) / 15;
     const size_t lds = (size_t)10 * 34 * 80 + 64 * (288 * 2 + 16) + 8 * (2 * 15 * 32 * 2);
-    const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_lp<T, 2, 2, 32, 0, true>), 160 * 1024);
-    if (!ok) return GV_E_UNSUPPORTED;
-    hipLaunchKernelGGL((conv3x3_halo_lp<T, 2, 2, 32, 0, true>), dim3((unsigned)(a.nb * tiles_x)), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv3x3_halo_lp<T, 2, 2, 32, 0, true>>(dim3((unsigned)(a.nb * tiles_x)), dim3(256), lds, st, a);
 }
 
 template <typename T, int STATS>
 int launch_halo64(const ConvArgs& a, hipStream_t st) {                       // 64 input channels, <= 32 output channels
     const int tiles_x = (a.ow + 31) / 32;
     const size_t lds = (size_t)6 * 34 * (64 * 2 + 16) + 32 * (9 * 64 * 2 + 16);      // (staging aliases the halo)
-    const bool ok = GV_BIG_LDS_OK((&conv3x3_halo_lp<T, 1, 1, 64, STATS>), 160 * 1024);
-    if (!ok) return GV_E_UNSUPPORTED;
-    hipLaunchKernelGGL((conv3x3_halo_lp<T, 1, 1, 64, STATS>), dim3((unsigned)(a.nb * tiles_x)), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv3x3_halo_lp<T, 1, 1, 64, STATS>>(dim3((unsigned)(a.nb * tiles_x)), dim3(256), lds, st, a);
 }
 
 template <typename T, int STATS>
@@ -1163,9 +1126,7 @@ int launch_stem_one(const ConvArgs& a, hipStream_t st) {
     constexpr int KR = KW == 3 ? 16 : 24, NG = (KW * KR / 8 + 1) / 2 * 2, PR = 3 * 2 + KW + 1, PC = 31 * 2 + KW;
     constexpr int PITCH = (PC * 3 * 2 + 16 + 3) / 4 * 4;
     const size_t lds = (size_t)PR * PITCH + 4 * 32 * 36 * 4 + (size_t)32 * TN * (NG * 16 + 16);
-    hipLaunchKernelGGL((conv_stem_patch_lp<T, TN, KW, STATS>), dim3((unsigned)(a.nb * ((a.ow + 31) / 32))), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_stem_patch_lp<T, TN, KW, STATS>>(dim3((unsigned)(a.nb * ((a.ow + 31) / 32))), dim3(256), lds, st, a);
 }
 
 template <typename T, int KW>
@@ -1173,9 +1134,7 @@ int launch_stem_pool(const ConvArgs& a, hipStream_t st) {
     constexpr int KR = KW == 3 ? 16 : 24, NG = (KW * KR / 8 + 1) / 2 * 2, PR = 3 * 2 + KW + 1, PC = 31 * 2 + KW;
     constexpr int PITCH = (PC * 3 * 2 + 16 + 3) / 4 * 4;
     const size_t lds = (size_t)PR * PITCH + 4 * 32 * 96 + (size_t)32 * 2 * (NG * 16 + 16) + 4 * (2 * 15 * 32 * 2);   // (16-bit staging rows)
-    hipLaunchKernelGGL((conv_stem_patch_lp<T, 2, KW, 0, true>), dim3((unsigned)(a.nb * ((a.pw + 14) / 15))), dim3(256), lds, st, a);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_stem_patch_lp<T, 2, KW, 0, true>>(dim3((unsigned)(a.nb * ((a.pw + 14) / 15))), dim3(256), lds, st, a);
 }
 
 template <typename T>
@@ -1194,10 +1153,7 @@ int launch_stem(const ConvArgs& a, hipStream_t st) {
 
 namespace gvconv {
 
-// configurations: [0, kNumTiles) register-staged tiles, kNumTiles = the strip / halo kernels of the stem layers,
-// then the LDS-DMA tiles of conv_dma.hip
-int lp_num_cfgs() { return kNumTiles + 1 + dma_lp_num_cfgs(); }
-int lp_special_cfg() { return kNumTiles; }
+int lp_staged_num_cfgs() { return kNumTiles; }
 
 // the 3-channel stems read from the fp32 images: square 3x3 or 7x7 window, stride 2, <= 64 output channels
 bool lp_stem_ok(const ConvArgs& a, bool xf32) {
@@ -1215,68 +1171,43 @@ bool lp_halo_ok(const ConvArgs& a, bool generic) {
            a.ow == a.iw + 2 * a.pad_l - 2;
 }
 
-bool lp_xpre_cfg_ok(int cfg) { return cfg == 0 || cfg == 1 || cfg == 6 || cfg == 7 || cfg == 8; }
+bool lp_xpre_cfg_ok(int cfg) {
+    switch (cfg) {
+#define GV_X(i, wm, wn, tm, tn) case i: return xpre_cfg(wm, wn, tm, tn);
+        GV_LP_STAGED_TILES(GV_X)
+#undef GV_X
+    }
+    return false;
+}
 int lp_xpre_pick(int /*M*/, int N) { return N <= 64 ? 1 : 0; }
 
-int lp_pick_tile(int M, int N, int /*K*/) {
-    int best = 0;
-    double best_cost = 1e30;
-    const int order[] = {0, 3, 1, 5};                 // 128 x {128, 96, 64, 32}
-    const double pen[] = {1.00, 1.02, 1.05, 1.20};
-    for (int t = 0; t < 4; ++t) {
-        const int bn = kTiles[order[t]].bn;
-        const double cost = (double)gv_ceil_div(N, bn) * bn * pen[t];
-        if (cost < best_cost) { best_cost = cost; best = order[t]; }
-    }
-    const int64_t blocks = (int64_t)gv_ceil_div(M, 128) * gv_ceil_div(N, kTiles[best].bn);
-    if (blocks < 1024) {
-        if (kTiles[best].bn == 128) best = 4;
-        else if (kTiles[best].bn == 64) best = 2;
-    }
-    return best;
-}
-
 // GV_CONV_MAXPOOL3S2: the halo kernel's 32 -> 64 channel form with a plain ReLU epilogue into aligned 16-byte chunks
-bool lp_halo_pool_ok(const ConvArgs& a, bool generic) {
+static bool lp_halo_pool_ok(const ConvArgs& a, bool generic) {
     return lp_halo_ok(a, generic) && a.cin == 32 && a.cout == 64 && a.relu && a.relu_limit >= a.cout && a.res == nullptr &&
            a.st.mode == STAT_OFF && a.y_step == 0 && a.xscale == nullptr && a.oh >= 3 && a.ow >= 3 && a.y_ld % 8 == 0 &&
            (((uintptr_t)a.y) & 15) == 0;
 }
 
 // ... and the strip kernel of the 3-channel stems at 64 output channels (either pool geometry)
-bool lp_stem_pool_ok(const ConvArgs& a, bool xf32) {
+static bool lp_stem_pool_ok(const ConvArgs& a, bool xf32) {
     return lp_stem_ok(a, xf32) && a.cout == 64 && a.st.mode == STAT_OFF && a.y_step == 0 && a.xscale == nullptr &&
            a.oh >= 3 && a.ow >= 3 && a.y_ld % 8 == 0 && (((uintptr_t)a.y) & 15) == 0;
 }
 
-int lp_launch(int dtype, int cfg, const ConvArgs& a0, bool generic, bool xf32, hipStream_t st) {
-    ConvArgs a = a0;
-    a.Kpad = (a.K + KT - 1) / KT * KT;
-    a.ktiles = a.Kpad / KT;
-    if (a.pool && (cfg != kNumTiles || !((a.pool == 1 && lp_halo_pool_ok(a, generic)) || lp_stem_pool_ok(a, xf32))))
-        return GV_E_UNSUPPORTED;
+int lp_staged_launch(int dtype, int cfg, const ConvArgs& a, bool generic, bool xf32, hipStream_t st) {
+    GV_LP_DISPATCH(dtype, return launch_t<T>(cfg, a, generic, xf32, st));
+}
+
+// the strip kernel of the 3-channel stems, else the halo kernel; a fused max pool (a.pool) for the classes above only
+int lp_special_launch(int dtype, const ConvArgs& a, bool generic, bool xf32, hipStream_t st) {
+    if (a.pool && !((a.pool == 1 && lp_halo_pool_ok(a, generic)) || lp_stem_pool_ok(a, xf32))) return GV_E_UNSUPPORTED;
     if (a.pool && a.scale2 != nullptr && !lp_stem_pool_ok(a, xf32)) return GV_E_UNSUPPORTED;   // GV_CONV_POOL_ACT2: the stem strip kernel only
-    if (cfg == kNumTiles) {
-        if (a.y_step != 0) return GV_E_UNSUPPORTED;              // (the strip / halo kernels have no two-level output stride)
-        // BatchNorm sums: one segment over every output column (these kernels own whole images: no slot table)
-        if (a.st.mode != STAT_OFF && !stat_strip_ok_host(a.st, a.cout)) return GV_E_UNSUPPORTED;
-        if (lp_stem_ok(a, xf32)) {
-            if (dtype == GV_BF16) return launch_stem<__bf16>(a, st);
-            if (dtype == GV_F16) return launch_stem<_Float16>(a, st);
-            return GV_E_UNSUPPORTED;
-        }
-        if (!lp_halo_ok(a, generic)) return GV_E_UNSUPPORTED;
-        if (dtype == GV_BF16) return launch_halo<__bf16>(a, st);
-        if (dtype == GV_F16) return launch_halo<_Float16>(a, st);
-        return GV_E_UNSUPPORTED;
-    }
-    if (cfg > kNumTiles) {
-        if (!dma_lp_ok(a, generic, xf32)) return GV_E_UNSUPPORTED;
-        return dma_lp_launch(dtype, cfg - kNumTiles - 1, a, st);
-    }
-    if (dtype == GV_BF16) return launch_t<__bf16>(cfg, a, generic, xf32, st);
-    if (dtype == GV_F16) return launch_t<_Float16>(cfg, a, generic, xf32, st);
-    return GV_E_UNSUPPORTED;
+    if (a.y_step != 0) return GV_E_UNSUPPORTED;              // (the strip / halo kernels have no two-level output stride)
+    // BatchNorm sums: one segment over every output column (these kernels own whole images: no slot table)
+    if (a.st.mode != STAT_OFF && !stat_strip_ok_host(a.st, a.cout)) return GV_E_UNSUPPORTED;
+    if (lp_stem_ok(a, xf32)) GV_LP_DISPATCH(dtype, return launch_stem<T>(a, st));
+    if (!lp_halo_ok(a, generic)) return GV_E_UNSUPPORTED;
+    GV_LP_DISPATCH(dtype, return launch_halo<T>(a, st));
 }
 
 int64_t lp_packed_bytes(int kh, int kw, int cin, int cout) {
@@ -1288,26 +1219,12 @@ int lp_pack_filter(const float* w_hwio, int kh, int kw, int cin, int cout, int d
     const int K = kh * kw * cin;
     const int Kpad = (K + KT - 1) / KT * KT;
     const dim3 grid((unsigned)gv_ceil_div((int64_t)cout * Kpad, 256));
-    if (dtype == GV_BF16)
-        hipLaunchKernelGGL(pack_filter_lp<__bf16>, grid, dim3(256), 0, st, w_hwio, K, Kpad, cout, (unsigned short*)out);
-    else if (dtype == GV_F16)
-        hipLaunchKernelGGL(pack_filter_lp<_Float16>, grid, dim3(256), 0, st, w_hwio, K, Kpad, cout, (unsigned short*)out);
-    else
-        return GV_E_UNSUPPORTED;
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    GV_LP_DISPATCH(dtype, return gv_launch<pack_filter_lp<T>>(grid, dim3(256), 0, st, w_hwio, K, Kpad, cout, (unsigned short*)out));
 }
 
 int lp_pack_filters_batched(const gv_pack_job* jobs_dev, const int* block_job_dev, int nblocks, int dtype,
                             hipStream_t st) {
-    if (dtype == GV_BF16)
-        hipLaunchKernelGGL(pack_filters_batched_lp<__bf16>, dim3((unsigned)nblocks), dim3(256), 0, st, jobs_dev, block_job_dev);
-    else if (dtype == GV_F16)
-        hipLaunchKernelGGL(pack_filters_batched_lp<_Float16>, dim3((unsigned)nblocks), dim3(256), 0, st, jobs_dev, block_job_dev);
-    else
-        return GV_E_UNSUPPORTED;
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    GV_LP_DISPATCH(dtype, return gv_launch<pack_filters_batched_lp<T>>(dim3((unsigned)nblocks), dim3(256), 0, st, jobs_dev, block_job_dev));
 }
 
 }  // namespace gvconv

@@ -67,6 +67,21 @@ static inline size_t stat_lds_bytes(int mode, int slots, int bn) {
 }
 // table rows for row tiles of `bm` pixels: one per image the tile can span, folded onto the G groups
 static inline int stat_rows(int bm, int hw, int G) { const int n = stat_slots(bm, hw); return n < G ? n : G; }
+// Where a bm x bn tile kernel keeps its tables, and the launch's dynamic LDS with them (`lds` without): in the main-loop
+// buffers the epilogue has freed, behind what the epilogue still uses there (`epi_bytes`: the waves' staging blocks and a
+// constants table loaded late), where they fit in front of the epilogue's constants at `ss_off`; else behind everything (more
+// LDS per workgroup).  Fills slots, fold and lds_off.
+static inline size_t stat_place(ConvStats& s, int bm, int bn, size_t epi_bytes, size_t ss_off, size_t lds) {
+    s.slots = stat_rows(bm, s.hw, s.G);
+    s.fold = stat_slots(bm, s.hw) > s.G ? 1 : 0;
+    const size_t tab = stat_lds_bytes(s.mode, s.slots, bn);
+    if (epi_bytes + tab <= ss_off) {
+        s.lds_off = (int)epi_bytes;
+        return lds;
+    }
+    s.lds_off = (int)((lds + 15) / 16 * 16);
+    return (size_t)s.lds_off + tab;
+}
 // Can a kernel with row tiles of `bm` pixels fold the sums?  (whole 8-channel chunks per segment, the slot division
 // exact, a bounded number of images per tile)
 static inline bool stat_tile_ok(const ConvStats& s, int bm, int cout, int wave_rows) {

@@ -588,9 +588,8 @@ int launch_ws(const ConvArgs& a0, hipStream_t st) {
         diet = false;
     w.strip_off = diet ? 128 : 0;
     w.strip_bytes = w.strip_off + w.strip_blocks * 1024;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int64_t nwg = (int64_t)gv_ceil_div(a.M, BM) * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     size_t ring = (size_t)WS_ZERO + (size_t)NB * BN * WS_RB + (size_t)w.na * w.strip_bytes;
     w.tab_off = (int)ring;
     if (diet) ring += ((size_t)w.taps * BM * 2 + 127) / 128 * 128;   // (16-bit entries: offsets / 16 — any strip fits)
@@ -598,25 +597,11 @@ int launch_ws(const ConvArgs& a0, hipStream_t st) {
     const size_t lds = ring > epi ? ring : epi;
     if (lds > (NL == 2 ? 80 : 160) * 1024) return GV_E_UNSUPPORTED;   // (two of the small workgroups per CU)
     auto go = [&](auto mode, auto gm) -> int {
+        constexpr int MODE = decltype(mode)::value;
         constexpr bool GM = decltype(gm)::value;
-        if (!GM && diet) {
-            auto kern = &conv_ws<T, WM, WN, TM, TN, NB, decltype(mode)::value, false, KT, NL, true>;
-            if (lds > 64 * 1024) {
-                const bool ok = GV_BIG_LDS_OK(kern, 160 * 1024);
-                if (!ok) return GV_E_UNSUPPORTED;
-            }
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((NC + NL) * 64), lds, st, a, w);
-            GV_LAUNCH_CHECK();
-            return GV_OK;
-        }
-        auto kern = &conv_ws<T, WM, WN, TM, TN, NB, decltype(mode)::value, decltype(gm)::value, KT, NL>;
-        if (lds > 64 * 1024) {
-            const bool ok = GV_BIG_LDS_OK(kern, 160 * 1024);
-            if (!ok) return GV_E_UNSUPPORTED;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((NC + NL) * 64), lds, st, a, w);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
+        const dim3 grid((unsigned)nwg), block((NC + NL) * 64);
+        if (!GM && diet) return gv_launch<conv_ws<T, WM, WN, TM, TN, NB, MODE, false, KT, NL, true>>(grid, block, lds, st, a, w);
+        return gv_launch<conv_ws<T, WM, WN, TM, TN, NB, MODE, GM, KT, NL>>(grid, block, lds, st, a, w);
     };
     const bool lean = gvconv::lp_epilogue_lean_ok(a);
     using L = std::integral_constant<int, gvconv::STAT_LEAN>;
@@ -666,11 +651,8 @@ namespace gvconv {
 int ws_lp_num_cfgs() { return 11; }
 
 int ws_lp_launch(int dtype, int cfg, const ConvArgs& a, hipStream_t st) {
-    static const bool off = getenv("GV_NO_WS") != nullptr;       // (A/B of whole plans: the autotuner then never sees these tiles)
-    if (off) return GV_E_UNSUPPORTED;
-    if (dtype == GV_BF16) return launch_ws_cfg<__bf16>(cfg, a, st);
-    if (dtype == GV_F16) return launch_ws_cfg<_Float16>(cfg, a, st);
-    return GV_E_UNSUPPORTED;
+    if (ws_disabled()) return GV_E_UNSUPPORTED;
+    GV_LP_DISPATCH(dtype, return launch_ws_cfg<T>(cfg, a, st));
 }
 
 }  // namespace gvconv

@@ -513,21 +513,13 @@ int launch_ws_x3(const ConvArgs& a0, hipStream_t st) {
     w.strip_blocks = gv_ceil_div(w.halo_lo + BM + halo_hi, 32);
     if (w.strip_blocks > SBMAX) return GV_E_UNSUPPORTED;
     w.pad_[0] = w.pad_[1] = w.pad_[2] = 0;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int64_t nwg = (int64_t)gv_ceil_div(a.M, BM) * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     constexpr size_t ring = (size_t)NB * 96 * BN + 6 * (size_t)(X3W_HEAD + SBMAX * 1024);
     constexpr size_t epi = (size_t)NC * X3EpiGeom<TN>::BYTES + 2 * BN * sizeof(float);
     constexpr size_t lds = ring > epi ? ring : epi;
     static_assert(lds <= 160 * 1024, "one workgroup per CU");
-    auto kern = &conv_ws_x3<WM, WN, TM, TN, NB, SBMAX, 0>;
-    if (lds > 64 * 1024) {
-        const bool ok = GV_BIG_LDS_OK(kern, 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((NC + X3W_NL) * 64), lds, st, a, w);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_ws_x3<WM, WN, TM, TN, NB, SBMAX, 0>>(dim3((unsigned)nwg), dim3((NC + X3W_NL) * 64), lds, st, a, w);
 }
 
 // GEMM mode: 1x1 / stride 1 on plain fp32 input, whole 16-channel groups, 16-byte aligned pixels
@@ -549,21 +541,13 @@ int launch_wsg_x3(const ConvArgs& a0, hipStream_t st) {
     w.halo_lo = 0;
     w.strip_blocks = 0;
     w.pad_[0] = w.pad_[1] = w.pad_[2] = 0;
-    a.tiles_n = gv_ceil_div(a.cout, BN);
-    const int64_t nwg = (int64_t)gv_ceil_div(a.M, BM) * a.tiles_n;
-    if (nwg > 0x7fffffff) return GV_E_UNSUPPORTED;
+    const int64_t nwg = gvconv::conv_grid(a, BM, BN);
+    if (nwg < 0) return GV_E_UNSUPPORTED;
     constexpr size_t ring = (size_t)NB * 96 * BN + 9 * (size_t)BM * 32;
     constexpr size_t epi = (size_t)NC * X3EpiGeom<TN>::BYTES + 2 * BN * sizeof(float);
     constexpr size_t lds = ring > epi ? ring : epi;
     static_assert(lds <= 160 * 1024, "one workgroup per CU");
-    auto kern = &conv_ws_x3<WM, WN, TM, TN, NB, 0, MODE>;
-    if (lds > 64 * 1024) {
-        const bool ok = GV_BIG_LDS_OK(kern, 160 * 1024);
-        if (!ok) return GV_E_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((NC + X3W_NL) * 64), lds, st, a, w);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gv_launch<conv_ws_x3<WM, WN, TM, TN, NB, 0, MODE>>(dim3((unsigned)nwg), dim3((NC + X3W_NL) * 64), lds, st, a, w);
 }
 #endif
 
@@ -575,8 +559,7 @@ namespace gvconv {
 int ws_x3_num_cfgs() { return 5; }
 
 int ws_x3_launch(int cfg, const ConvArgs& a, hipStream_t st) {
-    static const bool off = getenv("GV_NO_WS") != nullptr;       // (A/B of whole plans: the autotuner then never sees these tiles)
-    if (off) return GV_E_UNSUPPORTED;
+    if (ws_disabled()) return GV_E_UNSUPPORTED;
     switch (cfg) {
         case 0: return launch_ws_x3<4, 2, 2, 3, 4, 13>(a, st);     // 256 x 192: 8 consumers of 64 x 96 (154 KB)
         case 1: return launch_ws_x3<4, 2, 2, 2, 4, 13>(a, st);     // 256 x 128
@@ -591,8 +574,7 @@ int ws_x3_launch(int cfg, const ConvArgs& a, hipStream_t st) {
 int wsg_x3_num_cfgs() { return 2; }
 
 int wsg_x3_launch(int cfg, const ConvArgs& a, hipStream_t st) {
-    static const bool off = getenv("GV_NO_WS") != nullptr;
-    if (off) return GV_E_UNSUPPORTED;
+    if (ws_disabled()) return GV_E_UNSUPPORTED;
     switch (cfg) {
         case 0: return launch_wsg_x3<4, 2, 2, 3, 1>(a, st);        // 256 x 192 (144 KB)
         case 1: return launch_wsg_x3<4, 2, 2, 2, 1>(a, st);        // 256 x 128

@@ -45,6 +45,29 @@ struct GvPerDeviceOnce {
         });                                                                                                       \
     }())
 
+#if defined(__HIPCC__)
+// Launch Kernel with `lds` bytes of dynamic LDS.  Above 64 KB the kernel's limit is raised first (to the CU's 160 KB; the
+// outcome is remembered per kernel and device).  GV_OK, GV_E_UNSUPPORTED where the device refuses the limit, else the
+// launch's HIP error.
+template <auto Kernel, typename... Args>
+int gv_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > 64 * 1024) {
+        if (!GV_BIG_LDS_OK(Kernel, 160 * 1024)) return GV_E_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+#endif
+
+// the 16-bit storage types: T the type a stored element stands for
+#define GV_LP_DISPATCH(dtype, CALL)                       \
+    do {                                                  \
+        if ((dtype) == GV_BF16) { using T = __bf16; CALL; }   \
+        if ((dtype) == GV_F16) { using T = _Float16; CALL; }  \
+        return GV_E_UNSUPPORTED;                          \
+    } while (0)
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -81,7 +104,7 @@ static inline int gv_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) /
 static inline bool gv_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 // rows of p (stride ld elements) can be walked in 16-byte accesses of n elements; nullptr: an operand that is not used
 static inline bool gv_vec_ok(const void* p, int ld, int n) { return p == nullptr || (gv_aligned16(p) && ld % n == 0); }
-// workgroups of 256 threads for a grid-stride loop over `total` items
+// workgroups of 256 threads for a grid-stride loop over `total` items: at most 16 per CU, the loop strides the rest
 static inline unsigned gv_grid_for(int64_t total) {
     const int64_t b = (total + 255) / 256, cap = 256 * 16;
     return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);

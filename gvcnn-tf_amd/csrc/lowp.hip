@@ -424,12 +424,6 @@ __global__ __launch_bounds__(256) void view_pool_fuse_lp(const unsigned short* _
 
 int g_pool_rows = 1;      // multi-row form of the 3x3 / stride-2 max pool (gv_pool2d_set_rows: 0 = one output per thread; A/B)
 
-inline unsigned grid_for(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    const int64_t cap = 256 * 16;
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
 template <typename T>
 int pool2d_t(const gv_pool_desc* d, const unsigned short* x, unsigned short* y, hipStream_t st) {
     const bool vec = (d->c % 8 == 0) && (d->x_ld % 8 == 0) && (d->y_ld % 8 == 0) && gv_aligned16(x) && gv_aligned16(y);
@@ -441,21 +435,21 @@ int pool2d_t(const gv_pool_desc* d, const unsigned short* x, unsigned short* y, 
             hipLaunchKernelGGL(avgpool3x3s1_row4x2_lp<T>, dim3((unsigned)blk2), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw, d->c,
                                d->x_ld, d->y_ld, d->mode == GV_POOL_AVG_RELU ? 1 : 0);
         else
-            hipLaunchKernelGGL(avgpool3x3s1_row4_lp<T>, dim3(grid_for(tot4)), dim3(256), 0, st, x, y, d->nb, d->ih,
+            hipLaunchKernelGGL(avgpool3x3s1_row4_lp<T>, dim3(gv_grid_for(tot4)), dim3(256), 0, st, x, y, d->nb, d->ih,
                                d->iw, d->c, d->x_ld, d->y_ld, d->mode == GV_POOL_AVG_RELU ? 1 : 0);
     } else if (vec && g_pool_rows && d->mode == GV_POOL_MAX && d->kh == 3 && d->kw == 3 && d->stride == 2 && d->pad_t == 0 &&
                d->pad_l == 0 && d->oh == (d->ih - 3) / 2 + 1 && d->ow == (d->iw - 3) / 2 + 1) {
         constexpr int RH = 4;
         const int64_t tot = (int64_t)d->nb * ((d->oh + RH - 1) / RH) * d->ow * (d->c / 8);
-        hipLaunchKernelGGL((maxpool3x3s2_rows_lp<T, RH>), dim3(grid_for(tot)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
+        hipLaunchKernelGGL((maxpool3x3s2_rows_lp<T, RH>), dim3(gv_grid_for(tot)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
                            d->c, d->x_ld, d->oh, d->ow, d->y_ld);
     } else if (vec) {
         const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / 8);
-        hipLaunchKernelGGL((pool2d_lp<T, 8>), dim3(grid_for(total)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
+        hipLaunchKernelGGL((pool2d_lp<T, 8>), dim3(gv_grid_for(total)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
                            d->c, d->x_ld, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
     } else {
         const int64_t total = (int64_t)d->nb * d->oh * d->ow * d->c;
-        hipLaunchKernelGGL((pool2d_lp<T, 1>), dim3(grid_for(total)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
+        hipLaunchKernelGGL((pool2d_lp<T, 1>), dim3(gv_grid_for(total)), dim3(256), 0, st, x, y, d->nb, d->ih, d->iw,
                            d->c, d->x_ld, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
     }
     GV_LAUNCH_CHECK();
@@ -467,10 +461,10 @@ int ssa_t(const unsigned short* x, int64_t npix, int c, int x_ld, const float* s
           unsigned short* y, int y_ld, hipStream_t st) {
     const bool vec = (c % 8 == 0) && (x_ld % 8 == 0) && (y_ld % 8 == 0) && gv_aligned16(x) && gv_aligned16(y);
     if (vec)
-        hipLaunchKernelGGL((scale_shift_act_lp<T, 8>), dim3(grid_for(npix * (c / 8))), dim3(256), 0, st, x, npix, c,
+        hipLaunchKernelGGL((scale_shift_act_lp<T, 8>), dim3(gv_grid_for(npix * (c / 8))), dim3(256), 0, st, x, npix, c,
                            x_ld, scale, shift, relu, y, y_ld);
     else
-        hipLaunchKernelGGL((scale_shift_act_lp<T, 1>), dim3(grid_for(npix * c)), dim3(256), 0, st, x, npix, c, x_ld,
+        hipLaunchKernelGGL((scale_shift_act_lp<T, 1>), dim3(gv_grid_for(npix * c)), dim3(256), 0, st, x, npix, c, x_ld,
                            scale, shift, relu, y, y_ld);
     GV_LAUNCH_CHECK();
     return GV_OK;

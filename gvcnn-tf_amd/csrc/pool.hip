@@ -320,12 +320,6 @@ __global__ __launch_bounds__(256) void avgpool3x3s1_p3x8(const char* __restrict_
     }
 }
 
-inline unsigned grid_for(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    const int64_t cap = 256 * 16;            // 16 blocks per CU, grid-stride the rest
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
 }  // namespace
 
 // train_data.py:63,81-84,101: legacy bilinear resize + flips + brightness + x/255 - 0.5; thread per output pixel
@@ -368,7 +362,7 @@ extern "C" int gv_preprocess_views(const uint8_t* src, int32_t nimg, int32_t h0,
                                    void* stream) {
     if (!src || !dst || nimg <= 0 || h0 <= 0 || w0 <= 0 || height <= 0 || width <= 0) return GV_E_BADARG;
     const int64_t total = (int64_t)nimg * height * width;
-    hipLaunchKernelGGL(preprocess_views_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, nimg, h0,
+    hipLaunchKernelGGL(preprocess_views_kernel, dim3(gv_grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, nimg, h0,
                        w0, height, width, flip, delta, dst);
     GV_LAUNCH_CHECK();
     return GV_OK;
@@ -404,13 +398,13 @@ extern "C" int gv_pool2d_fwd(const gv_pool_desc* d, const void* x, void* y, void
                 GV_LAUNCH_CHECK();
                 return GV_OK;
             }
-#define GV_AVG4(XP, YP) hipLaunchKernelGGL((avgpool3x3s1_row4_f32<XP, YP>), dim3(grid_for(tot4)), dim3(256), 0, st, xf, yf, \
+#define GV_AVG4(XP, YP) hipLaunchKernelGGL((avgpool3x3s1_row4_f32<XP, YP>), dim3(gv_grid_for(tot4)), dim3(256), 0, st, xf, yf, \
                                            d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, relu)
             if (xp3 && yp3) GV_AVG4(true, true); else if (xp3) GV_AVG4(true, false); else GV_AVG4(false, true);
 #undef GV_AVG4
         } else {
             const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / 4);
-#define GV_POOL4(XP, YP) hipLaunchKernelGGL((pool2d_f32<4, XP, YP>), dim3(grid_for(total)), dim3(256), 0, st, xf, yf, d->nb, \
+#define GV_POOL4(XP, YP) hipLaunchKernelGGL((pool2d_f32<4, XP, YP>), dim3(gv_grid_for(total)), dim3(256), 0, st, xf, yf, d->nb, \
                                             d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, \
                                             d->ow, d->y_ld, mode)
             if (xp3 && yp3) GV_POOL4(true, true); else if (xp3) GV_POOL4(true, false); else GV_POOL4(false, true);
@@ -427,7 +421,7 @@ extern "C" int gv_pool2d_fwd(const gv_pool_desc* d, const void* x, void* y, void
     if (vec && d->mode != GV_POOL_MAX && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 &&
         d->pad_l == 1 && d->oh == d->ih && d->ow == d->iw) {
         const int64_t tot4 = (int64_t)d->nb * d->ih * ((d->iw + 3) / 4) * (d->c / 4);
-        hipLaunchKernelGGL((avgpool3x3s1_row4_f32<false, false>), dim3(grid_for(tot4)), dim3(256), 0, st, (const float*)x,
+        hipLaunchKernelGGL((avgpool3x3s1_row4_f32<false, false>), dim3(gv_grid_for(tot4)), dim3(256), 0, st, (const float*)x,
                            (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, d->mode == GV_POOL_AVG_RELU ? 1 : 0);
         GV_LAUNCH_CHECK();
         return GV_OK;
@@ -436,17 +430,17 @@ extern "C" int gv_pool2d_fwd(const gv_pool_desc* d, const void* x, void* y, void
         d->pad_l == 0 && d->oh == (d->ih - 3) / 2 + 1 && d->ow == (d->iw - 3) / 2 + 1) {
         constexpr int RH = 4;
         const int64_t tot = (int64_t)d->nb * ((d->oh + RH - 1) / RH) * d->ow * (d->c / 4);
-        hipLaunchKernelGGL(maxpool3x3s2_rows_f32<RH>, dim3(grid_for(tot)), dim3(256), 0, st, (const float*)x, (float*)y,
+        hipLaunchKernelGGL(maxpool3x3s2_rows_f32<RH>, dim3(gv_grid_for(tot)), dim3(256), 0, st, (const float*)x, (float*)y,
                            d->nb, d->ih, d->iw, d->c, d->x_ld, d->oh, d->ow, d->y_ld);
         GV_LAUNCH_CHECK();
         return GV_OK;
     }
     if (vec)
-        hipLaunchKernelGGL(pool2d_f32<4>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)x,
+        hipLaunchKernelGGL(pool2d_f32<4>, dim3(gv_grid_for(total)), dim3(256), 0, st, (const float*)x,
                            (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride,
                            d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
     else
-        hipLaunchKernelGGL(pool2d_f32<1>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)x,
+        hipLaunchKernelGGL(pool2d_f32<1>, dim3(gv_grid_for(total)), dim3(256), 0, st, (const float*)x,
                            (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride,
                            d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
     GV_LAUNCH_CHECK();
@@ -464,10 +458,10 @@ extern "C" int gv_scale_shift_act(const void* x, int64_t npix, int32_t c, int32_
     const int64_t total = npix * (vec ? c / 4 : c);
     hipStream_t st = (hipStream_t)stream;
     if (vec)
-        hipLaunchKernelGGL(scale_shift_act_f32<4>, dim3(grid_for(total)), dim3(256), 0, st,
+        hipLaunchKernelGGL(scale_shift_act_f32<4>, dim3(gv_grid_for(total)), dim3(256), 0, st,
                            (const float*)x, npix, c, x_ld, scale, shift, relu, (float*)y, y_ld);
     else
-        hipLaunchKernelGGL(scale_shift_act_f32<1>, dim3(grid_for(total)), dim3(256), 0, st,
+        hipLaunchKernelGGL(scale_shift_act_f32<1>, dim3(gv_grid_for(total)), dim3(256), 0, st,
                            (const float*)x, npix, c, x_ld, scale, shift, relu, (float*)y, y_ld);
     GV_LAUNCH_CHECK();
     return GV_OK;

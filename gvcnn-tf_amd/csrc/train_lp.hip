@@ -1832,13 +1832,6 @@ extern "C" void gv_conv2d_wgrad_set_strip_taps(int n) { g_strip_ntw = n; }
 
 namespace gvlp {
 
-#define GV_LP_DISPATCH(dtype, CALL)                       \
-    do {                                                  \
-        if ((dtype) == GV_BF16) { using T = __bf16; CALL; }   \
-        if ((dtype) == GV_F16) { using T = _Float16; CALL; }  \
-        return GV_E_UNSUPPORTED;                          \
-    } while (0)
-
 // every storage type: E the element type in HBM, T the type it stands for
 #define GV_ST_DISPATCH(dtype, CALL)                                                   \
     do {                                                                              \

@@ -705,7 +705,7 @@ int gv_sgd_momentum(float* w, const float* g, float* m, int64_t n, float lr, flo
 
 /* ---- the training step on 16-bit storage (configs[2]: bf16 forward + backward) --------------------------
  * Storage-typed forms of the functions above: activations and activation gradients (z, y, dy, dz, F, dF, src, dst)
- * are `dtype` elements (GV_BF16 / GV_F16; GV_F32 forwards to the fp32 function), arithmetic is fp32 with one
+ * are `dtype` elements (GV_BF16 / GV_F16; with GV_F32 the function above, which forwards here), arithmetic is fp32 with one
  * rounding per stored element, batch statistics accumulate in fp64, parameter gradients (dbeta, dgamma, dbias, dW),
  * dS and the optimizer state stay fp32.  gv_conv2d_fwd (forward and data gradient), gv_conv2d_wgrad,
  * gv_pool2d_fwd/_bwd, gv_global_avg_pool, gv_view_score_partial and gv_view_pool_fuse_fwd take the storage type

@@ -41,8 +41,9 @@ def pack_filter(w_hwio, math=0):
 
 
 def run_conv(x, w, stride, pads, out_hw, scale, shift, relu, residual=None, y_ld=None, y_off=0,
-             x_ld=None, x_off=0, second=None, tile=None, math=0):
-    """x [nb,ih,iw,cin] cpu tensor.  Returns y [nb,oh,ow,cout] (and y2) as numpy."""
+             x_ld=None, x_off=0, second=None, tile=None, math=0, expect=None):
+    """x [nb,ih,iw,cin] cpu tensor.  Returns y [nb,oh,ow,cout] (and y2) as numpy.
+    expect: the launch must return this code and write nothing."""
     nb, ih, iw, cin = x.shape
     kh, kw, _, cout = w.shape
     oh, ow = out_hw
@@ -71,6 +72,11 @@ def run_conv(x, w, stride, pads, out_hw, scale, shift, relu, residual=None, y_ld
                                  sh2.data_ptr() if second else None, st())
     finally:
         lib().gv_conv2d_set_tile_override(-1)
+    if expect is not None:
+        assert rc == expect, rc
+        torch.cuda.synchronize()
+        assert bool((yd == -77.0).all())               # nothing was written
+        return None
     _lib.check(rc, "gv_conv2d_fwd")
     torch.cuda.synchronize()
     y = yd.cpu().numpy()
@@ -590,3 +596,36 @@ def test_halo_stem_kernel_random_geometries(seed):
     y = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, relu, tile=11, math=1)
     y0 = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, relu, tile=0, math=1)
     np.testing.assert_allclose(y, y0, rtol=1e-5, atol=1e-5)
+
+
+# Which index of the fp32-storage tile tables serves which layer class.  Three bf16 planes (math 1): register-staged tiles
+# 0-10, the halo / stem slot 11, the wave-specialised kernel's GEMM mode 12-13; exact fp32 (math 0): its own tiles 0-11.  The
+# accepted sets are literals (a tile that starts to decline is invisible to the parity tests above: the autotuner silently
+# takes another one).
+#                         math k    cin cout  hw       tolerance  accepted indices
+TILE_CLASS_CASES = {
+    "planes_gemm_1x1":   (1, (1, 1), 64, 192, (12, 12), 2e-5, set(range(0, 11)) | {12, 13}),
+    "planes_halo_3x3":   (1, (3, 3), 32, 64, (16, 16), 2e-5, set(range(0, 12))),
+    "exact_ragged_3x3":  (0, (3, 3), 40, 48, (13, 11), 2e-4, set(range(0, 12))),
+}
+
+
+@pytest.mark.parametrize("case", sorted(TILE_CLASS_CASES))
+def test_fp32_tile_index_serves_its_layer_class(case):
+    """Every index of the table on one small stride-1 SAME layer per class (nb 2): exactly the recorded indices run, each to the
+    oracle at this file's tolerance for the math mode; every other index returns GV_E_UNSUPPORTED and writes nothing."""
+    math, k, cin, cout, hw, tol, accepted = TILE_CLASS_CASES[case]
+    g = torch.Generator().manual_seed(cin * 1000 + cout + k[0])
+    x = torch.randn(2, hw[0], hw[1], cin, generator=g)
+    w = torch.randn(k[0], k[1], cin, cout, generator=g) * (1.0 / (k[0] * k[1] * cin) ** 0.5)
+    scale, shift = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
+    ref = oracle_conv(x, w, 1, "SAME", scale, shift, True)
+    pads = (tf_pads(hw[0], k[0], 1, "SAME"), tf_pads(hw[1], k[1], 1, "SAME"))
+    n = lib().gv_conv2d_num_tile_cfgs(math)
+    assert n == (14 if math else 12)
+    for tile in range(n):
+        if tile in accepted:
+            y = run_conv(x, w, 1, pads, hw, scale, shift, True, tile=tile, math=math)
+            np.testing.assert_allclose(y, ref.numpy(), rtol=tol, atol=tol)
+        else:
+            run_conv(x, w, 1, pads, hw, scale, shift, True, tile=tile, math=math, expect=_lib.GV_E_UNSUPPORTED)

@@ -952,3 +952,46 @@ def test_lp_baseline_configs_at_full_size(backbone, V, size, G, ty):
                               Hd["dense_%d/bias" % V].numpy())
     close(S.float().cpu().numpy(), oS, ulp)
     assert rel_l2(logits.cpu().numpy(), oL) < 2 * ulp
+
+
+# Which index of the 16-bit tile table serves which layer class: register-staged tiles 0-11, the strip / halo slot 12, the
+# LDS-DMA tiles 13-37 (64-deep k-tiles: 29-34 and 37), the wave-specialised tiles 38-48 (64-deep: 43-46).  The accepted sets
+# are literals (what the launchers took before the dispatch was reshaped into one table): a tile that starts to decline is
+# invisible to the parity tests above, because the autotuner silently takes another one.
+#                       k       stride padding cin cout  hw        x_f32  pooled  accepted indices
+TILE_CLASS_CASES = {
+    "ragged_3x3":      ((3, 3), 1, "SAME", 40, 48, (13, 11), False, None, set(range(0, 12)) | set(range(13, 29)) | {35, 36}),
+    "strip_1x7":       ((1, 7), 1, "SAME", 128, 128, (12, 12), False, None, set(range(0, 12)) | set(range(13, 49))),
+    "gemm_1x1":        ((1, 1), 1, "SAME", 256, 64, (12, 12), False, None, set(range(0, 12)) | set(range(13, 43)) | {44, 45}),
+    "halo_3x3":        ((3, 3), 1, "SAME", 32, 64, (16, 16), False, None, set(range(0, 29)) | {35, 36} | set(range(38, 43)) | {47, 48}),
+    "halo_3x3_pooled": ((3, 3), 1, "SAME", 32, 64, (16, 16), False, (7, 7), {12}),
+    "stem_3x3s2":      ((3, 3), 2, "VALID", 3, 32, (23, 23), True, None, set(range(0, 13))),
+}
+
+
+@pytest.mark.parametrize("ty", ["bf16", "f16"])
+@pytest.mark.parametrize("case", sorted(TILE_CLASS_CASES))
+def test_lp_tile_index_serves_its_layer_class(case, ty):
+    """Every index of the table on one small layer per class (nb 2): exactly the recorded indices run, each to the oracle at
+    this file's tolerance; every other index returns GV_E_UNSUPPORTED and writes nothing."""
+    k, stride, padding, cin, cout, hw, x_f32, pooled, accepted = TILE_CLASS_CASES[case]
+    code, td, ulp = TYPES[ty]
+    g = torch.Generator().manual_seed(cin * 1000 + cout)
+    x = torch.randn(2, hw[0], hw[1], cin, generator=g)
+    x = x if x_f32 else rnd(x, td)
+    w = rnd(torch.randn(k[0], k[1], cin, cout, generator=g) * (1.0 / (k[0] * k[1] * cin) ** 0.5), td)
+    scale, shift = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
+    ref = oracle_conv(rnd(x, td), w, stride, padding, scale, shift, True)
+    out_hw = tuple(ref.shape[1:3])
+    if pooled:
+        ref = OB.max_pool2d(ref, 3, 2, "VALID")
+    pads = (tf_pads(hw[0], k[0], stride, padding), tf_pads(hw[1], k[1], stride, padding))
+    n = lib().gv_conv2d_num_tile_cfgs(-1)
+    assert n == 49 and special_tile() == 12
+    for tile in range(n):
+        kw = dict(tile=tile, x_f32=x_f32, pooled=pooled)
+        if tile in accepted:
+            y = run_conv(x, w, stride, pads, out_hw, scale, shift, True, ty, **kw)
+            close(y, ref.numpy(), 2 * ulp if x_f32 and tile == special_tile() else ulp)   # (the strip kernel's, as above)
+        else:
+            run_conv(x, w, stride, pads, out_hw, scale, shift, True, ty, expect=_lib.GV_E_UNSUPPORTED, **kw)

@@ -39,8 +39,9 @@ def pack_filter(w):
 
 
 def conv(x, w, stride, pads, out_hw, scale, shift, relu, x_p3=False, y_p3=False, split=0, y2_p3=False, relu_cols=0,
-         residual=None, tile=None, x_ld=None, x_off=0, y_ld=None, y_off=0):
-    """x [nb,ih,iw,cin] fp32 cpu.  Returns y (and y2 with split) as fp32 cpu tensors, whatever the storage format."""
+         residual=None, tile=None, x_ld=None, x_off=0, y_ld=None, y_off=0, expect=None):
+    """x [nb,ih,iw,cin] fp32 cpu.  Returns y (and y2 with split) as fp32 cpu tensors, whatever the storage format.
+    expect: the launch must return this code and write nothing."""
     nb, ih, iw, cin = x.shape
     kh, kw, _, cout = w.shape
     oh, ow = out_hw
@@ -72,6 +73,11 @@ def conv(x, w, stride, pads, out_hw, scale, shift, relu, x_p3=False, y_p3=False,
                                  yd.data_ptr() + (6 if y_p3 else 4) * y_off, y2d.data_ptr() if split else None, None, None, st())
     finally:
         lib().gv_conv2d_set_tile_override(-1)
+    if expect is not None:
+        assert rc == expect, rc
+        torch.cuda.synchronize()
+        assert bool(((p3.from_p3(yd) if y_p3 else yd) == -77.0).all())      # nothing was written
+        return None
     _lib.check(rc, "gv_conv2d_fwd")
     torch.cuda.synchronize()
     y = (p3.from_p3(yd) if y_p3 else yd).cpu()
@@ -493,3 +499,33 @@ def test_plan_rebuilds_when_the_library_declines_a_fused_max_pool(monkeypatch):
         torch.cuda.synchronize()
         outs.append(p.view(p.end_points["Mixed_7c"]).clone())
     assert torch.equal(outs[0], outs[1]) and float(outs[0].abs().max()) > 1e-3
+
+
+# Which index of the three-plane-input table serves which layer class: the LDS-DMA tiles 0-18, the wave-specialised strip
+# tiles 19-23.  The accepted sets are literals (a tile that starts to decline is invisible to the parity tests above: the
+# autotuner silently takes another one).
+#                   k       cin cout hw        accepted indices
+TILE_CLASS_CASES = {
+    "strip_3x3": ((3, 3), 64, 96, (12, 12), set(range(0, 24))),
+    "gemm_1x1":  ((1, 1), 64, 96, (12, 12), set(range(0, 19))),
+}
+
+
+@pytest.mark.parametrize("case", sorted(TILE_CLASS_CASES))
+def test_p3_tile_index_serves_its_layer_class(case):
+    """Every index of the table on one small stride-1 SAME layer per class (nb 2): exactly the recorded indices run, each to the
+    oracle at this file's tolerance; every other index returns GV_E_UNSUPPORTED and writes nothing."""
+    k, cin, cout, hw, accepted = TILE_CLASS_CASES[case]
+    g = torch.Generator().manual_seed(cin * 1000 + cout + k[0])
+    x = torch.randn(2, hw[0], hw[1], cin, generator=g)
+    w = torch.randn(k[0], k[1], cin, cout, generator=g) * (1.0 / (k[0] * k[1] * cin) ** 0.5)
+    scale, shift = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
+    ref = oracle_conv(x, w, 1, "SAME", scale, shift, True)
+    pads = (OB.same_pads(hw[0], k[0], 1)[0], OB.same_pads(hw[1], k[1], 1)[0])
+    n = lib().gv_conv2d_num_tile_cfgs(-3)
+    assert n == 24
+    for tile in range(n):
+        if tile in accepted:
+            close(conv(x, w, 1, pads, hw, scale, shift, True, x_p3=True, tile=tile), ref)
+        else:
+            conv(x, w, 1, pads, hw, scale, shift, True, x_p3=True, tile=tile, expect=_lib.GV_E_UNSUPPORTED)
