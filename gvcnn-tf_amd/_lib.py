@@ -165,6 +165,9 @@ SIGNATURES = {
     "gv_pool2d_bwd_argmax_bn": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "gv_view_pool_fuse_bwd": (C.c_int, [_P, _P, _I, _I, _L, _L, _L, _P, _I, _P, _I, _P, _P]),
     "gv_view_pool_fuse_bwd_per_shape": (C.c_int, [_P, _P, _I, _I, _L, _L, _L, _P, _I, _P, _I, _P, _P]),
+    "gv_group_weight_bwd_workspace_bytes": (_L, [_I, _L, _I]),
+    "gv_group_weight_bwd_per_shape": (C.c_int, [_P, _P, _I, _I, _L, _L, _L, _P, _I, _P, _I, _P, _P, _L, _I, _P]),
+    "gv_view_score_bwd": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "gv_global_avg_pool_bwd": (C.c_int, [_P, _I, _I, _I, _P, _I, _P]),
     "gv_softmax_ce": (C.c_int, [_P, _P, _I, _I, _P, _P, _P]),
     "gv_dense_bwd": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

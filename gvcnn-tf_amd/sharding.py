@@ -418,6 +418,9 @@ class ShardedTrainGVCNN:
                   shape group."""
 
     def __init__(self, engine, group=None, bucket_bytes=64 << 20, mode="views", overlap_grads=True):
+        if getattr(engine, "train_scorer", False):
+            # (the scorer's gradients are sums over the shapes and would need an all-reduce of their own)
+            raise ValueError("train_scorer is a single-rank option: a sharded engine does not reduce the scorer gradients")
         if mode not in ("views", "shapes", "hybrid"):
             raise ValueError(mode)
         self.eng = engine

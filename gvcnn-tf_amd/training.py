@@ -149,11 +149,25 @@ class TrainGVCNN:
                  num_classes=40, num_group=10, backbone_params=None, head_params=None, device=None,
                  raw_tap=None, final_tap=None, num_bins=10, pool="max", empty_fill=1.0, math="bf16x3", seed=2,
                  head_views=None, view_offset=0, per_shape=False, weight_mode="count", storage="f32",
-                 fuse_siblings=True, frozen_bn=False, deterministic=True, dw_workspace_mb=256):
+                 fuse_siblings=True, frozen_bn=False, deterministic=True, dw_workspace_mb=256, train_scorer=False):
         """head_views / view_offset: view-sharded data parallelism (sharding.ShardedTrainGVCNN) — this engine
         runs the backbone for views [view_offset, view_offset + num_views) of the head_views views of every shape
         (so each view's BatchNorm statistics stay on one rank, exactly the reference's per-view statistics),
-        while the grouping head works on all head_views views."""
+        while the grouping head works on all head_views views.
+        train_scorer: the V scorer layers are trained (the reference's are not: nets/model.py takes the scores out of
+        the graph).  With per-shape grouping and mean_score weights the group weight is a function of the scores, so the
+        loss has a gradient with respect to them; backward_head sends it to the scorer and into the raw tap (the binning
+        stays a constant of the backward pass).  Single rank, the engine's own views only."""
+        self.train_scorer = bool(train_scorer)
+        if self.train_scorer:
+            if not per_shape:
+                raise ValueError("train_scorer needs per_shape=True: the batch-mean head's weights are counts")
+            if weight_mode != "mean_score":
+                raise ValueError("train_scorer needs weight_mode='mean_score': count weights do not depend on the scores")
+            if head_views not in (None, num_views):
+                raise ValueError("train_scorer needs head_views == num_views: a view-sharded engine is not supported")
+            if view_offset != 0:
+                raise ValueError("train_scorer needs view_offset == 0: a view-sharded engine is not supported")
         self.lib = _lib.load()
         # deterministic: every filter gradient through gv_conv2d_wgrad_ws — pixel slices store their partial images of dW
         # into one workspace shared by all layers and are added in slice order, so two runs of a step give the same bits
@@ -232,6 +246,14 @@ class TrainGVCNN:
                 bs.append(torch.as_tensor(head_params[bn], dtype=f32).reshape(-1)[:1])
             self.score_kernel = torch.stack(ks).to(dev).contiguous()
             self.score_bias = torch.cat(bs).to(dev).contiguous()
+            if self.train_scorer:
+                # the scorer in one flat fp32 buffer [V*cr kernels | V biases] with its gradient and Momentum buffers
+                # beside it; score_kernel / score_bias are views of it (same shapes, same values)
+                nk = self.score_kernel.numel()
+                self._flat_sp = torch.cat([self.score_kernel.reshape(-1), self.score_bias]).contiguous()
+                self._flat_sg, self._flat_sm = torch.zeros_like(self._flat_sp), torch.zeros_like(self._flat_sp)
+                self.score_kernel = self._flat_sp[:nk].view(num_views, -1)
+                self.score_bias = self._flat_sp[nk:]
             kn, bn = _params.classifier_names(self.Vh)
             self.cls_names = (kn, bn)
             # Trainable variables, their gradients and the Momentum slots live in three FLAT fp32 buffers (the dicts
@@ -293,6 +315,13 @@ class TrainGVCNN:
                 self.params[k].copy_(init[k])
             for k in moving:
                 self.params[k] = init[k].to(dev).contiguous().clone()
+            if self.train_scorer:
+                cr, nk = self.score_kernel.shape[1], self.score_kernel.numel()
+                for v in range(num_views):
+                    skn, sbn = _params.scorer_names(v)
+                    for d, buf in ((self.grads, self._flat_sg), (self.momentum, self._flat_sm)):
+                        d[skn] = buf[v * cr:(v + 1) * cr].view(cr, 1)
+                        d[sbn] = buf[nk + v:nk + v + 1]
             # per-op device state
             cmax = max(op["x"].c for op in p.ops if op["kind"] == "bn") if any(o["kind"] == "bn" for o in p.ops) else 4
             cmax = max(cmax, max(max(op["y"].c, op["x"].c) for op in p.ops if op["kind"] == "conv"))
@@ -357,6 +386,13 @@ class TrainGVCNN:
                 self.gidx_ps = torch.empty((num_shapes, self.Vh), dtype=torch.int32, device=dev)
                 self.scheme_ps = torch.empty((num_shapes, num_group, self.Vh), dtype=torch.int32, device=dev)
                 self.weight_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
+            if self.train_scorer:
+                self.dw_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
+                nws = self.lib.gv_group_weight_bwd_workspace_bytes(num_shapes, self.final.h * self.final.w * self.final.c,
+                                                                   num_group)
+                if nws < 0:
+                    _lib.check(int(nws), "gv_group_weight_bwd_workspace_bytes")
+                self._gw_ws = torch.empty(int(nws), dtype=torch.uint8, device=dev)
             f = self.final
             self.S = torch.empty((num_shapes, f.h, f.w, f.c), dtype=self.tdt, device=dev)
             self.dS = torch.empty((num_shapes, f.h, f.w, f.c), dtype=f32, device=dev)
@@ -1116,7 +1152,8 @@ class TrainGVCNN:
 
     def score_partial(self):
         """Scorer responses r_img [N*V] of this engine's views (model.py:144-145); no gradient flows through the
-        scorer: the scores leave the graph in partial_run #1."""
+        scorer: the scores leave the graph in partial_run #1.  (train_scorer=True: backward_head computes the gradient
+        the per-shape mean_score weights carry, see _backward_scorer.)"""
         r = self.raw
         _lib.check(self.lib.gv_view_score_partial(self._ptr(r), r.nb, r.h * r.w, r.c, r.ld,
                                                   self.score_kernel.data_ptr(), self.score_bias.data_ptr(), self.V,
@@ -1220,6 +1257,35 @@ class TrainGVCNN:
         _lib.check(lib.gv_view_pool_fuse_bwd_t(F_ptr, self.dS.data_ptr(), V, self.N, E, E, V * E, scheme.data_ptr(),
                                                self.G, weight.data_ptr(), self.pool_mode, dF_ptr, int(self.per_shape),
                                                self.dt, _st()), "pool_fuse_bwd")
+        if self.train_scorer:
+            self._backward_scorer(F_ptr, E)
+
+    def _backward_scorer(self, F_ptr, E):
+        """The gradient that reaches the scores through the mean_score group weights: dL/dw_g from the descriptors and
+        dS (the schemes are constants: the binning has no gradient), then through w_g = mean of the member scores and
+        s = sigmoid(log|r|) into the scorer layers and the raw tap.
+        The raw tap's gradient is CLAIMED here and the scorer term stored into it, so everything the trunk sends back
+        later adds (the lazy-accumulate rule of _claim; in the plain form the term adds into the zero-filled buffer).
+        A claimed tensor is never the `first` contributor of a residual fan-in, so _can_alias_grad cannot hand its
+        buffer to another tensor while it holds the term; this call runs on the caller's stream before
+        backward_backbone's _phase_begin, whose fork event orders every branch lane after it."""
+        lib, V, r = self.lib, self.V, self.raw
+        # ASSUMPTION: the raw tap is not the residual operand of a later op (true of both backbones: it feeds a
+        # pre-activation / the next block's branches).  As a residual it would reach the fan-in code of _backward_op
+        # already claimed, and a buffer aliased by an earlier pass would be dropped there together with the stored term.
+        assert not any(op.get("res") is not None and op["res"].vbuf == r.vbuf for op in self.plan.ops), \
+            "train_scorer: the raw tap is a residual operand"
+        _lib.check(lib.gv_group_weight_bwd_per_shape(F_ptr, self.dS.data_ptr(), V, self.N, E, E, V * E,
+                                                     self.scheme_ps.data_ptr(), self.G, self.weight_ps.data_ptr(),
+                                                     self.pool_mode, self.dw_ps.data_ptr(), self._gw_ws.data_ptr(),
+                                                     self._gw_ws.numel(), self.dt, _st()), "group_weight_bwd")
+        nk = self.score_kernel.numel()
+        draw = self._ptr(r, grad=True)
+        accumulate = 0 if self._claim(r) else 1
+        _lib.check(lib.gv_view_score_bwd(self._ptr(r), r.nb, r.h * r.w, r.c, r.ld, self.score_kernel.data_ptr(),
+                                         self.r_img.data_ptr(), self.gidx_ps.data_ptr(), self.dw_ps.data_ptr(), self.G, V,
+                                         self._flat_sg.data_ptr(), self._flat_sg.data_ptr() + 4 * nk, draw, r.ld,
+                                         accumulate, self.dt, _st()), "view_score_bwd")
 
     def final_grad(self):
         """[N, V, h, w, C] view of the gradient buffer of the final tap (allocated on first use)."""
@@ -1429,6 +1495,10 @@ class TrainGVCNN:
                 _lib.check(self.lib.gv_sgd_momentum(self._flat_p.data_ptr() + 4 * lo, self._flat_g.data_ptr() + 4 * lo,
                                                     self._flat_m.data_ptr() + 4 * lo, hi - lo, float(lr), float(mu),
                                                     float(wd), _st()), "sgd")
+        if self.train_scorer:                             # (the reference's Dense(1) layers carry no regulariser)
+            _lib.check(self.lib.gv_sgd_momentum(self._flat_sp.data_ptr(), self._flat_sg.data_ptr(),
+                                                self._flat_sm.data_ptr(), self._flat_sp.numel(), float(lr), float(mu),
+                                                0.0, _st()), "sgd (scorer)")
         self._packed_dirty = True
 
     def update_moving_averages(self, decay=None):

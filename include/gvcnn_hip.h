@@ -687,10 +687,39 @@ int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t num_views, in
                           int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
                           int32_t num_groups, const float* weight, int32_t mode, float* dF, void* stream);
 /* The same with one scheme [G,V] / weight [G] per shape (gv_view_pool_fuse_fwd_per_shape); the scores that produced
- * scheme and weight receive no gradient (they are constants of the backward pass, as in the batch form). */
+ * scheme and weight receive no gradient FROM THIS CALL (scheme and weight are its constants, as in the batch form).
+ * With mean_score weights the weight is a function of the scores: gv_group_weight_bwd_per_shape + gv_view_score_bwd
+ * below compute that gradient, down to the scorer and the raw tap. */
 int gv_view_pool_fuse_bwd_per_shape(const float* F, const float* dS, int32_t num_views, int32_t num_shapes,
                                     int64_t E, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
                                     int32_t num_groups, const float* weight, int32_t mode, float* dF, void* stream);
+/* ---- the scorer's gradient (per-shape grouping, GV_WEIGHT_MEAN_SCORE) ----------------------------------------------
+ * S = sum_g w_g D_g / W with w_g = mean of the member scores is differentiable in the scores; the binning that decides
+ * the members is piecewise constant and stays a constant of the backward pass (no straight-through term).
+ *   dw[n,g] = (1/W) sum_e dS[n,e] (D_g[n,e] - S[n,e])     0 for an empty group and for W = 0
+ * D_g and S are recomputed from F, scheme and weight with the forward kernel's arithmetic (no stored S is read); an
+ * empty group counts with weight 0, which is what GV_WEIGHT_MEAN_SCORE gives it.  F in `dtype`, dS fp32 [N,E], dw fp32
+ * [N,G].  Workgroups store their partial sums into ws ([N][chunks][G] fp32, at least
+ * gv_group_weight_bwd_workspace_bytes, 4-byte aligned), a second launch adds them in chunk order: no atomics, the same
+ * bits every run.  V, G <= 64, N <= 65535.  Argument errors (before any HIP call): GV_E_UNSUPPORTED for an unknown
+ * dtype or a size above its cap, GV_E_BADARG for a NULL pointer, a size <= 0, an unknown mode, a short workspace. */
+int64_t gv_group_weight_bwd_workspace_bytes(int32_t num_shapes, int64_t E, int32_t num_groups);
+int gv_group_weight_bwd_per_shape(const void* F, const float* dS, int32_t num_views, int32_t num_shapes, int64_t E,
+                                  int64_t view_stride, int64_t shape_stride, const int32_t* scheme, int32_t num_groups,
+                                  const float* weight, int32_t mode, float* dw, void* ws, int64_t ws_bytes,
+                                  int32_t dtype, void* stream);
+/* From dw to the scorer (image b = n*num_views + v, shape-major; gidx [N,V] as gv_group_assign_per_shape wrote it):
+ *   dr_b       = dw[n, gidx_b] / #{u: gidx[n,u] = gidx_b} * sign(r_b) / (1 + |r_b|)^2     (= dL/ds * sign(r) (1 - s)^2;
+ *                0 for r_b = 0 and for a view in no group, gidx_b outside [0, G))
+ *   dbias[v]   = sum_n dr_{n,v}                                    (n ascending; stored)
+ *   dkernel[v] = sum_n dr_{n,v} * mean_p raw[n,v,p,:]              (fp32 [V,cr]; stored)
+ *   draw[b,p,c] = (accumulate ? draw[b,p,c] : 0) + dr_b * kernel[v,c] / hw     (nullable; one rounding into `dtype`)
+ * raw and draw are `dtype` tensors [nb, hw, cr] with pixel strides raw_ld / draw_ld >= cr (a channel slice of a wider
+ * tensor; the columns past cr are not touched).  Three launches, fixed reduction order.  nb <= 65535, V, G <= 64. */
+int gv_view_score_bwd(const void* raw, int32_t nb, int32_t hw, int32_t cr, int32_t raw_ld, const float* kernel,
+                      const float* r_img, const int32_t* gidx, const float* dw, int32_t num_groups, int32_t num_views,
+                      float* dkernel, float* dbias, void* draw, int32_t draw_ld, int32_t accumulate, int32_t dtype,
+                      void* stream);
 int gv_global_avg_pool_bwd(const float* dgap, int32_t nb, int32_t hw, int32_t c, float* dx, int32_t dx_ld,
                            void* stream);
 /* Mean sparse-softmax cross-entropy (train.py:145): loss (device scalar) and dlogits = (softmax-onehot)/n. */
