@@ -32,6 +32,7 @@ GV_KNN_MAX_K = 256
 GV_RETR_AP_MAX_NDB = 16384
 GV_METRIC_MAX_RANK, GV_METRIC_MAX_BATCH = 256, 16384
 GV_RENDER_PERSPECTIVE, GV_RENDER_TWO_SIDED = 1, 2
+GV_RENDER_LAMBERT = 1
 GV_RENDER_OUT_F32_QUANTIZED, GV_RENDER_OUT_F32, GV_RENDER_OUT_U8 = 0, 1, 2
 GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RENDER_TOO_LARGE, GV_RENDER_BAD_OFFSETS = \
     0, 1, 2, 3, 4, 5
@@ -89,6 +90,10 @@ class RenderDesc(C.Structure):
                 ("background", C.c_float * 3)]
 
 
+class RenderShading(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("shininess", C.c_int32), ("specular", C.c_float), ("reserved", C.c_int32)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nb", "ih", "iw", "c", "x_ld", "kh", "kw", "stride", "pad_t", "pad_l",
@@ -142,6 +147,11 @@ SIGNATURES = {
                                        _P]),
     "gv_render_draw_ss": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L, _I,
                                     _P, _P, _P, _I, _P]),
+    "gv_render_normals_bytes": (_L, [_I, _I, _L]),
+    "gv_render_vertex_normals": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _P,
+                                           _L, _P, _L, _P]),
+    "gv_render_draw_smooth": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L,
+                                        _I, _P, _P, _P, _I, C.POINTER(RenderShading), _P, _P, _P, _L, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

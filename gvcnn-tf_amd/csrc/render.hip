@@ -23,6 +23,13 @@
 // triangle's box is taken over the sample grid, so binning depends on S; a raster thread still owns one pixel and keeps
 // its S * S keys in registers, and resolves them to the pixel in the same launch.
 //
+// Smooth shading (gv_render_vertex_normals, then gv_render_draw_smooth in place of the draw call):
+//   vertex_normals_kernel  one thread per (normal table, vertex): gathers the face vectors of the vertex's corners over a
+//                          host-built CSR in ascending triangle order and normalises the sum.
+//   raster_kernel<.., SM = true>  the same raster loop; the resolve recomputes the winning triangle's setup and edge
+//                          functions per covered sample, interpolates the three vertex normals and shades the sample
+//                          (smooth_colour).  SM = false is the flat code, instantiated from the same source as before.
+//
 // No thread walks more than one tile's pixels: a triangle that covers the whole screen sits in every tile list it
 // touches and each tile's threads test it against their own pixel.  The triangle setup is a pure function of (mesh,
 // view, triangle), recomputed where needed (count, scatter, raster), so the bins hold 4-byte ids only.
@@ -78,6 +85,7 @@ struct Tri {
     unsigned z0, z1, z2;
     int px0, px1, py0, py1;
     long long area;
+    int flip;                                                    // vertices 1 and 2 were swapped (smooth shading)
 };
 
 __device__ __forceinline__ float dot3(const float* r, float a, float b, float c) {
@@ -156,6 +164,7 @@ __device__ bool tri_setup(const Args& a, int m, int v, int t, Tri& T) {
     project(a, C, w, T.x2, T.y2, T.z2);
     long long area = (long long)(T.x1 - T.x0) * (T.y2 - T.y0) - (long long)(T.y1 - T.y0) * (T.x2 - T.x0);
     if (area == 0) return false;
+    T.flip = area < 0;
     if (area < 0) {                                              // orient to positive area
         int s = T.x1; T.x1 = T.x2; T.x2 = s;
         s = T.y1; T.y1 = T.y2; T.y2 = s;
@@ -193,6 +202,75 @@ __device__ float shade_factor(const MeshXf& x, const float* M, const float* p0, 
     const float s = nn > 0.0f ? __fdiv_rn(nl, __builtin_sqrtf(nn)) : 0.0f;
     const float h = two_sided ? fabsf(s) : mul_rn(add_rn(s, 1.0f), 0.5f);
     return add_rn(ambient, mul_rn(add_rn(1.0f, -ambient), h));
+}
+
+// ---- smooth shading: vertex normals --------------------------------------------------------------------------------
+// face vector n = (w1 - w0) x (w2 - w0) of a triangle, unnormalised (the steps of shade_factor)
+__device__ __forceinline__ void face_vector(const MeshXf& x, const float* M, const float* p0, const float* p1,
+                                            const float* p2, float n[3]) {
+    float w0[3], w1[3], w2[3];
+    world(x, M, p0, w0);
+    world(x, M, p1, w1);
+    world(x, M, p2, w2);
+    const float a0 = add_rn(w1[0], -w0[0]), a1 = add_rn(w1[1], -w0[1]), a2 = add_rn(w1[2], -w0[2]);
+    const float b0 = add_rn(w2[0], -w0[0]), b1 = add_rn(w2[1], -w0[1]), b2 = add_rn(w2[2], -w0[2]);
+    n[0] = add_rn(mul_rn(a1, b2), -mul_rn(a2, b1));
+    n[1] = add_rn(mul_rn(a2, b0), -mul_rn(a0, b2));
+    n[2] = add_rn(mul_rn(a0, b1), -mul_rn(a1, b0));
+}
+
+// One thread per (table, vertex of the group): the face vectors of the vertex's corners (CSR: corner_off per vertex of
+// the packed arrays, re-based by corner_off[0] as the mesh offsets are; corner_tri the local triangle ids, ascending)
+// added in list order, then normalised.  Table v of a two-sided render turns every face vector towards view v's eye
+// first; a one-sided render has one table.  No atomics: the result is a pure function of the inputs.
+__global__ __launch_bounds__(RT) void vertex_normals_kernel(Args a, int n, long long total_verts,
+                                                            const long long* __restrict__ corner_off,
+                                                            const int* __restrict__ corner_tri, long long total_corners,
+                                                            int two_sided, float* __restrict__ normals) {
+    const long long gv = (long long)blockIdx.x * RT + threadIdx.x;
+    const int tab = blockIdx.y;
+    if (gv >= total_verts) return;
+    int lo = 0, hi = n;                                          // the last mesh that starts at or before the vertex
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.voff[mid] - a.voff[0] <= gv) lo = mid;
+        else hi = mid;
+    }
+    const int m = lo;
+    float g[3] = {0.0f, 0.0f, 0.0f};
+    const long long c0 = corner_off[gv] - corner_off[0], c1 = corner_off[gv + 1] - corner_off[0];
+    // a mesh with status OK has its vertex and triangle ranges inside the arrays (normalise_kernel)
+    if (a.xf[m].status == GV_RENDER_OK && gv >= a.voff[m] - a.voff[0] && gv < a.voff[m + 1] - a.voff[0] && c0 >= 0 &&
+        c1 >= c0 && c1 <= total_corners) {
+        const MeshXf x = a.xf[m];
+        const float* M = a.rots ? a.rots + (size_t)m * 9 : nullptr;
+        const float* fwd = a.cams + (size_t)tab * 9 + 6;
+        bool first = true;
+        for (long long c = c0; c < c1; ++c) {
+            const float *p0, *p1, *p2;
+            if (!load_tri(a, m, corner_tri[c], p0, p1, p2)) continue;
+            float f[3];
+            face_vector(x, M, p0, p1, p2, f);
+            if (two_sided && dot3(fwd, f[0], f[1], f[2]) > 0.0f) {
+                f[0] = -f[0];
+                f[1] = -f[1];
+                f[2] = -f[2];
+            }
+            for (int k = 0; k < 3; ++k) g[k] = first ? f[k] : add_rn(g[k], f[k]);
+            first = false;
+        }
+        const float nn = add_rn(add_rn(mul_rn(g[0], g[0]), mul_rn(g[1], g[1])), mul_rn(g[2], g[2]));
+        if (nn > 0.0f && nn < INFINITY) {
+            const float r = __builtin_sqrtf(nn);
+            for (int k = 0; k < 3; ++k) g[k] = __fdiv_rn(g[k], r);
+        } else {
+            g[0] = g[1] = g[2] = 0.0f;
+        }
+    }
+    float* o = normals + ((long long)tab * total_verts + gv) * 3;
+    o[0] = g[0];
+    o[1] = g[1];
+    o[2] = g[2];
 }
 
 // ---- normalisation -------------------------------------------------------------------------------------------------
@@ -393,17 +471,91 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
     return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
 }
 
+// ---- smooth shading: per covered sample ------------------------------------------------------------------------------
+struct Smooth {                                                  // the extra kernel argument of a smooth raster_kernel
+    const float* normals;                                        // [tables, total_verts, 3], vertex_normals_kernel
+    const float* lights;                                         // [V, 3] unit light of every view
+    const float* halfs;                                          // [V, 3] unit half-vector of every view
+    long long table_stride;                                      // vertices between two views' tables (0: one table)
+    float specular, ambient;
+    int squarings, lambert, two_sided;                           // squarings = log2(shininess)
+};
+struct SmoothTri {                                               // the recomputed setup of the last shaded triangle id
+    int id, ok;
+    Tri q;
+    float area;
+    float g[3][3];                                               // unit normals of vertices 0, 1, 2 after the swap
+};
+
+struct NoSmooth {};                                              // ... and of a flat one (its resolve keeps no state either)
+template <bool SM> struct SmoothParam { typedef NoSmooth type; typedef NoSmooth state; };
+template <> struct SmoothParam<true> { typedef Smooth type; typedef SmoothTri state; };
+
+// colour cs of a covered sample at (SX, SY) whose winning triangle is id: the setup is recomputed (a pure function of
+// the id) and kept while consecutive samples hold the same id; the three edge functions are the integers the raster
+// loop had.  A sample whose interpolated normal has no finite positive length takes the triangle's flat factor.
+template <int LS>
+__device__ __forceinline__ void smooth_colour(const Args& a, const Smooth& sm, const float* __restrict__ shade, int m,
+                                              int v, int id, int SX, int SY, float3 color, SmoothTri& st, float cs[3]) {
+    const long long tb = a.toff[m] - a.toff[0];
+    if (id != st.id) {
+        st.id = id;
+        st.ok = tri_setup<LS>(a, m, v, id, st.q) ? 1 : 0;
+        if (st.ok) {                                             // (load_tri has checked the three indices)
+            const int* ix = a.tris + (tb + id) * 3;
+            const int i[3] = {ix[0], st.q.flip ? ix[2] : ix[1], st.q.flip ? ix[1] : ix[2]};
+            const float* N = sm.normals + ((long long)v * sm.table_stride + (a.voff[m] - a.voff[0])) * 3;
+            for (int k = 0; k < 3; ++k)
+                for (int c = 0; c < 3; ++c) st.g[k][c] = N[(long long)i[k] * 3 + c];
+            st.area = (float)st.q.area;
+        }
+    }
+    if (st.ok) {
+        const Tri& q = st.q;
+        const float b0 = __fdiv_rn((float)edge(q.x1, q.y1, q.x2, q.y2, SX, SY), st.area);
+        const float b1 = __fdiv_rn((float)edge(q.x2, q.y2, q.x0, q.y0, SX, SY), st.area);
+        const float b2 = __fdiv_rn((float)edge(q.x0, q.y0, q.x1, q.y1, SX, SY), st.area);
+        float n[3];
+        for (int c = 0; c < 3; ++c)
+            n[c] = add_rn(add_rn(mul_rn(b0, st.g[0][c]), mul_rn(b1, st.g[1][c])), mul_rn(b2, st.g[2][c]));
+        const float nn = add_rn(add_rn(mul_rn(n[0], n[0]), mul_rn(n[1], n[1])), mul_rn(n[2], n[2]));
+        if (nn > 0.0f && nn < INFINITY) {
+            const float len = __builtin_sqrtf(nn);
+            const float s = __fdiv_rn(dot3(sm.lights + v * 3, n[0], n[1], n[2]), len);
+            const float h = sm.two_sided ? fabsf(s) : sm.lambert ? fmaxf(s, 0.0f) : mul_rn(add_rn(s, 1.0f), 0.5f);
+            const float f = add_rn(sm.ambient, mul_rn(add_rn(1.0f, -sm.ambient), h));
+            float sp = 0.0f;
+            if (sm.specular > 0.0f) {                            // (uniform; specular = 0 adds exactly nothing)
+                const float t = __fdiv_rn(dot3(sm.halfs + v * 3, n[0], n[1], n[2]), len);
+                float p = sm.two_sided ? fabsf(t) : fmaxf(t, 0.0f);
+                for (int k = 0; k < sm.squarings; ++k) p = mul_rn(p, p);
+                sp = mul_rn(sm.specular, p);
+            }
+            cs[0] = fminf(add_rn(mul_rn(color.x, f), sp), 1.0f);
+            cs[1] = fminf(add_rn(mul_rn(color.y, f), sp), 1.0f);
+            cs[2] = fminf(add_rn(mul_rn(color.z, f), sp), 1.0f);
+            return;
+        }
+    }
+    const float f = shade[tb + id];
+    cs[0] = mul_rn(color.x, f);
+    cs[1] = mul_rn(color.y, f);
+    cs[2] = mul_rn(color.z, f);
+}
+
 // S = 1 << LS samples per pixel and axis.  The thread of pixel (px, py) holds the S * S keys of its samples (b rows,
 // a columns, key b * S + a) in registers: every index into best[] below is a compile-time constant of a fully unrolled
 // loop.  The edge functions are affine, so they are evaluated once per triangle at sample (0, 0) and stepped by the
 // exact 64-bit increments d/dx = -(by - ay) * step, d/dy = (bx - ax) * step.
-template <int OUT, int LS>
+// SM: smooth shading; the resolve then shades every covered sample at its own position (smooth_colour) where the flat
+// one reads its triangle's factor.
+template <int OUT, int LS, bool SM>
 __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restrict__ shade,
                                                     const int* __restrict__ tile_count,
                                                     const long long* __restrict__ tile_start,
                                                     const int* __restrict__ bins, long long cap, float3 color,
                                                     float3 background, void* __restrict__ out, int* __restrict__ face_id,
-                                                    unsigned* __restrict__ depth) {
+                                                    unsigned* __restrict__ depth, typename SmoothParam<SM>::type sm) {
     constexpr int S = 1 << LS, NS = S * S, STEP = 256 >> LS;
     __shared__ LTri s_tri[RT];
     const int T = a.tiles_x * a.tiles_y;
@@ -501,15 +653,21 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
     // resolve: u8 per sample and channel, summed exactly; fp32 colours added in row-major sample order
     float acc[3] = {0.0f, 0.0f, 0.0f};
     unsigned sum[3] = {0u, 0u, 0u};
+    [[maybe_unused]] typename SmoothParam<SM>::state st;
+    if constexpr (SM) st.id = -1;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         float cs[3] = {background.x, background.y, background.z};
         if (best[s] != BG_KEY) {
             const int id = (int)(best[s] & 0xffffffffu);
-            const float f = shade[a.toff[m] - a.toff[0] + id];
-            cs[0] = mul_rn(color.x, f);
-            cs[1] = mul_rn(color.y, f);
-            cs[2] = mul_rn(color.z, f);
+            if constexpr (SM) {
+                smooth_colour<LS>(a, sm, shade, m, v, id, PX + (s % S) * STEP, PY + (s / S) * STEP, color, st, cs);
+            } else {
+                const float f = shade[a.toff[m] - a.toff[0] + id];
+                cs[0] = mul_rn(color.x, f);
+                cs[1] = mul_rn(color.y, f);
+                cs[2] = mul_rn(color.z, f);
+            }
         }
         if (face_id || depth) {
             const size_t q = ((size_t)img * (a.H << LS) + (py << LS) + s / S) * (a.W << LS) + (px << LS) + s % S;
@@ -634,10 +792,10 @@ void launch_count(dim3 grid, hipStream_t st, const Args& a, int* tile_count, lon
                        (d->flags & GV_RENDER_TWO_SIDED) ? 1 : 0, nullptr, nullptr, nullptr, 0ll);
 }
 
-template <int LS>
+template <int LS, bool SM>
 int launch_draw(dim3 bgrid, dim3 grid, hipStream_t st, const Args& a, const float* shade, const int* tc,
                 const long long* ts, int* tile_fill, int* bins, long long cap, const gv_render_desc* d, int32_t output,
-                void* out, int32_t* face_id, uint32_t* depth) {
+                void* out, int32_t* face_id, uint32_t* depth, typename SmoothParam<SM>::type sm) {
     hipLaunchKernelGGL((bin_kernel<true, LS>), bgrid, dim3(RT), 0, st, a, nullptr, nullptr, nullptr,
                        make_float3(0.f, 0.f, 0.f), 0.f, 0, ts, tile_fill, bins, cap);
     GV_LAUNCH_CHECK();
@@ -645,14 +803,14 @@ int launch_draw(dim3 bgrid, dim3 grid, hipStream_t st, const Args& a, const floa
     const float3 bg = make_float3(d->background[0], d->background[1], d->background[2]);
     const int* b = bins;
     if (output == GV_RENDER_OUT_F32_QUANTIZED)
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32_QUANTIZED, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b,
-                           cap, color, bg, out, face_id, depth);
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32_QUANTIZED, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts,
+                           b, cap, color, bg, out, face_id, depth, sm);
     else if (output == GV_RENDER_OUT_F32)
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color,
-                           bg, out, face_id, depth);
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap,
+                           color, bg, out, face_id, depth, sm);
     else
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_U8, LS>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap, color,
-                           bg, out, face_id, depth);
+        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_U8, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap,
+                           color, bg, out, face_id, depth, sm);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
@@ -699,20 +857,51 @@ int render_prepare(const float* verts, const int64_t* vert_offsets, const int32_
     return GV_OK;
 }
 
+int64_t normal_tables(const gv_render_desc* d) { return (d->flags & GV_RENDER_TWO_SIDED) ? d->num_views : 1; }
+
+int64_t normals_bytes(int64_t tables, int64_t total_verts) {
+    return round_up((total_verts > 0 ? tables * total_verts : 1) * 12, 256);
+}
+
+// shininess -> the number of squarings; -1 for a power of two above 128 (GV_E_UNSUPPORTED once the shared checks have
+// passed); false for anything else (GV_E_BADARG)
+bool shininess_shift(int32_t shininess, int* k) {
+    if (shininess <= 0 || (shininess & (shininess - 1))) return false;
+    *k = -1;
+    for (int i = 0; i <= 7; ++i)
+        if (shininess == 1 << i) *k = i;
+    return true;
+}
+
+struct SmoothCall {                                              // what gv_render_draw_smooth adds to a draw call
+    const gv_render_shading* shading;
+    const float *lights, *halfs, *normals;
+    int64_t normals_size;
+};
+
 int render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
                 int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
                 const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
                 int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth, int ls,
-                void* stream) {
+                void* stream, const SmoothCall* sc = nullptr) {
     if (!bins || !out || total < 0) return GV_E_BADARG;
     if (output != GV_RENDER_OUT_F32_QUANTIZED && output != GV_RENDER_OUT_F32 && output != GV_RENDER_OUT_U8)
         return GV_E_BADARG;
+    int squarings = 0;
+    if (sc) {
+        if (!sc->shading || !sc->lights || !sc->halfs || !sc->normals) return GV_E_BADARG;
+        if ((sc->shading->flags & ~GV_RENDER_LAMBERT) || !(sc->shading->specular >= 0.0f && sc->shading->specular <= 1.0f))
+            return GV_E_BADARG;
+        if (!shininess_shift(sc->shading->shininess, &squarings)) return GV_E_BADARG;
+    }
     const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
                                 cameras, workspace, workspace_bytes);
     if (rc != GV_OK) return rc;
-    if (ls < 0) return GV_E_UNSUPPORTED;
+    if (ls < 0 || squarings < 0) return GV_E_UNSUPPORTED;
     if (bins_bytes < gv_render_bins_bytes(total)) return GV_E_BADARG;
+    if (sc && sc->normals_size < normals_bytes(normal_tables(desc), total_verts)) return GV_E_BADARG;
     if (!gv_aligned16(bins) || (output != GV_RENDER_OUT_U8 && ((uintptr_t)out & 3u))) return GV_E_ALIGN;
+    if (sc && !gv_aligned16(sc->normals)) return GV_E_ALIGN;
     if (((uintptr_t)face_id & 3u) || ((uintptr_t)depth & 3u)) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
     const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
@@ -730,9 +919,49 @@ int render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* 
     const long long* ts = reinterpret_cast<const long long*>(ws + L.tile_start);
     int* tf = reinterpret_cast<int*>(ws + L.tile_fill);
     int* b = static_cast<int*>(bins);
-    if (ls == 0) return launch_draw<0>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
-    if (ls == 1) return launch_draw<1>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
-    return launch_draw<2>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth);
+    if (sc) {
+        const bool two = (desc->flags & GV_RENDER_TWO_SIDED) != 0;
+        const Smooth sm = {sc->normals, sc->lights, sc->halfs, two ? (long long)total_verts : 0ll, sc->shading->specular,
+                           desc->ambient, squarings, (sc->shading->flags & GV_RENDER_LAMBERT) ? 1 : 0, two ? 1 : 0};
+        if (ls == 0)
+            return launch_draw<0, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth,
+                                        sm);
+        if (ls == 1)
+            return launch_draw<1, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth,
+                                        sm);
+        return launch_draw<2, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, sm);
+    }
+    const NoSmooth no;
+    if (ls == 0)
+        return launch_draw<0, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
+    if (ls == 1)
+        return launch_draw<1, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
+    return launch_draw<2, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
+}
+
+int render_vertex_normals(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                          const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                          int32_t max_tris, const gv_render_desc* desc, const float* cameras, const float* rotations,
+                          void* workspace, int64_t workspace_bytes, const int64_t* corner_offsets,
+                          const int32_t* corner_tris, int64_t total_corners, float* normals, int64_t normals_size,
+                          void* stream) {
+    if (!corner_offsets || !corner_tris || !normals || total_corners < 0) return GV_E_BADARG;
+    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
+                                cameras, workspace, workspace_bytes);
+    if (rc != GV_OK) return rc;
+    if (normals_size < normals_bytes(normal_tables(desc), total_verts)) return GV_E_BADARG;
+    if (!gv_aligned16(normals)) return GV_E_ALIGN;
+    if (total_verts == 0) return GV_OK;
+    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    const MeshXf* xf = reinterpret_cast<const MeshXf*>(static_cast<char*>(workspace) + L.xf);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
+    const int64_t blocks = (total_verts + RT - 1) / RT;
+    if (blocks > 0x7fffffffll) return GV_E_UNSUPPORTED;
+    hipLaunchKernelGGL(vertex_normals_kernel, dim3((unsigned)blocks, (unsigned)normal_tables(desc)), dim3(RT), 0,
+                       (hipStream_t)stream, a, n, (long long)total_verts, (const long long*)corner_offsets, corner_tris,
+                       (long long)total_corners, (desc->flags & GV_RENDER_TWO_SIDED) ? 1 : 0, normals);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
 }
 
 }  // namespace
@@ -791,4 +1020,38 @@ extern "C" int gv_render_draw_ss(const float* verts, const int64_t* vert_offsets
     return render_draw(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
                        rotations, workspace, workspace_bytes, bins, bins_bytes, total, output, out, face_id, depth, ls,
                        stream);
+}
+
+// ---- smooth shading (contract: include/gvcnn_hip.h, "smooth shading") -------------------------------------------------
+extern "C" int64_t gv_render_normals_bytes(int32_t num_views, int32_t flags, int64_t total_verts) {
+    if (num_views <= 0 || total_verts < 0 || (flags & ~(GV_RENDER_PERSPECTIVE | GV_RENDER_TWO_SIDED))) return GV_E_BADARG;
+    if (num_views > 64) return GV_E_UNSUPPORTED;
+    return normals_bytes((flags & GV_RENDER_TWO_SIDED) ? num_views : 1, total_verts);
+}
+
+extern "C" int gv_render_vertex_normals(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                                        const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                                        int32_t max_tris, const gv_render_desc* desc, const float* cameras,
+                                        const float* rotations, void* workspace, int64_t workspace_bytes,
+                                        const int64_t* corner_offsets, const int32_t* corner_tris, int64_t total_corners,
+                                        float* normals, int64_t normals_bytes, void* stream) {
+    return render_vertex_normals(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
+                                 cameras, rotations, workspace, workspace_bytes, corner_offsets, corner_tris,
+                                 total_corners, normals, normals_bytes, stream);
+}
+
+extern "C" int gv_render_draw_smooth(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                                     const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                                     int32_t max_tris, const gv_render_desc* desc, const float* cameras,
+                                     const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
+                                     int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id,
+                                     uint32_t* depth, int32_t samples, const gv_render_shading* shading,
+                                     const float* lights, const float* halfs, const float* normals,
+                                     int64_t normals_size, void* stream) {
+    int ls = 0;
+    if (!sample_shift(samples, &ls)) return GV_E_BADARG;
+    const SmoothCall sc = {shading, lights, halfs, normals, normals_size};
+    return render_draw(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                       rotations, workspace, workspace_bytes, bins, bins_bytes, total, output, out, face_id, depth, ls,
+                       stream, &sc);
 }

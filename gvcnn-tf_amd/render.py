@@ -25,10 +25,26 @@ reproducible bit for bit:
   - samples=S (1, 2 or 4): S x S coverage and depth samples per pixel on a regular grid ((256 / S) * a + 128 / S in
     1/256 pixel), each treated as a pixel centre above and resolved in the same launch: the uint8 pixel is the rounded
     mean of the samples' uint8 values, the unquantised one the mean of their colours added in row-major order, - 0.5.
+  - shading="smooth" (Phong reflection on interpolated normals; every step fp32, rounded on its own, still bit-exact
+    against tests/render_smooth_oracle.py): the face vectors n_t = (w1-w0) x (w2-w0), unnormalised (area weights), are
+    added per vertex over its corners in ascending triangle order, starting from the first (MeshBatch.adjacency: a CSR
+    built on the host with a stable sort, uploaded once; one thread per vertex gathers, no atomics) and normalised,
+    (0, 0, 0) when the sum has no finite positive length.  two_sided=True first turns every face vector towards the
+    viewer (negated when forward_v . n_t > 0), so there is one normal table per view.  Per covered sample the resolve
+    recomputes the winning triangle's setup and its three integer edge functions e_k at the sample; b_k = float(e_k) /
+    float(area), n = (b0*ga + b1*gb) + b2*gc with the normals following the setup's swap of vertices 1 and 2: affine in
+    screen space like the depth, NOT perspective-correct.  s = (n.l_v) / |n|; h = (s+1)/2 (diffuse="wrap"), max(s, 0)
+    ("lambert") or |s| (two_sided); f = ambient + (1-ambient) * h; t = max((n.m_v) / |n|, 0) (|.| when two_sided),
+    p = t squared log2(shininess) times; channel = min(color * f + specular * p, 1).  l_v is the world light or, with
+    light="camera", the unit vector from the origin to view v's eye; m_v = normalize(l_v + eye_v), float64 on the host,
+    rounded to fp32.  A sample whose interpolated normal has no finite positive length takes its triangle's flat
+    factor (the table of the flat mode: wrap or |s|, the world light; DEFAULT_LIGHT with light="camera").  With
+    samples > 1 every sample is shaded at its own position.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -230,6 +246,21 @@ def pack_meshes(meshes):
             "vert_offsets": vo, "tri_offsets": to}
 
 
+def vertex_adjacency(tris, nv):
+    """Vertex-to-corner adjacency of one mesh as a CSR: (offsets int64 [nv + 1], triangle ids int32 [corners]); vertex
+    i is named by the corners of triangles ids[offsets[i]:offsets[i + 1]], ascending (a triangle that names it twice
+    appears twice).  A stable sort of the flattened index array; corners of a triangle with any index outside [0, nv)
+    are left out (the rasteriser drops those triangles)."""
+    t = np.asarray(tris, np.int64).reshape(-1, 3)
+    ok = ((t >= 0) & (t < nv)).all(axis=1)
+    tid = np.repeat(np.arange(len(t), dtype=np.int64)[ok], 3)
+    key = t[ok].reshape(-1)
+    order = np.argsort(key, kind="stable")
+    off = np.zeros(nv + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(key, minlength=nv)[:nv]) if nv else 0
+    return off, tid[order].astype(np.int32)
+
+
 class MeshBatch:
     """Meshes packed and uploaded once (a dataset held on the device can be re-rendered every epoch)."""
 
@@ -246,6 +277,30 @@ class MeshBatch:
         self.tris = torch.from_numpy(np.ascontiguousarray(t)).to(self.device)
         self.vert_offsets = torch.from_numpy(p["vert_offsets"]).to(self.device)
         self.tri_offsets = torch.from_numpy(p["tri_offsets"]).to(self.device)
+        self._adjacency_host = self._adjacency = None
+
+    def adjacency_host(self):
+        """(corner_offsets int64 [sum nv + 1], corner_tris int32 [corners]): vertex_adjacency of every mesh, the offsets
+        running on through the packed vertices.  Built once, on first use, from the triangles the device holds."""
+        if self._adjacency_host is None:
+            vo, to = self.vert_offsets_host, self.tri_offsets_host
+            tris = self.tris.cpu().numpy()
+            offs, ids, base = [np.zeros(1, np.int64)], [], 0
+            for m in range(self.n):
+                off, tid = vertex_adjacency(tris[to[m]:to[m + 1]], int(vo[m + 1] - vo[m]))
+                offs.append(off[1:] + base)
+                ids.append(tid)
+                base += len(tid)
+            self._adjacency_host = (np.concatenate(offs), np.concatenate(ids) if ids else np.zeros(0, np.int32))
+        return self._adjacency_host
+
+    def adjacency(self):
+        """The adjacency on the device (uploaded once, on the first smooth render)."""
+        if self._adjacency is None:
+            off, tid = self.adjacency_host()
+            tid = tid if len(tid) else np.zeros(1, np.int32)             # an address to hand over
+            self._adjacency = (torch.from_numpy(off).to(self.device), torch.from_numpy(tid).to(self.device))
+        return self._adjacency
 
     def __len__(self):
         return self.n
@@ -256,6 +311,14 @@ class MeshBatch:
         return (self.verts.data_ptr() + int(vo[a]) * 12, self.vert_offsets.data_ptr() + a * 8,
                 self.tris.data_ptr() + int(to[a]) * 12, self.tri_offsets.data_ptr() + a * 8, b - a,
                 int(vo[b] - vo[a]), int(to[b] - to[a]), int(self.num_tris[a:b].max()))
+
+    def group_adjacency(self, a, b):
+        """The adjacency arguments of meshes [a, b): (corner_offsets pointer, corner_tris pointer, corners).  The
+        library re-bases the offsets by their first entry, as it does the mesh offsets."""
+        off, tid = self.adjacency()
+        vo, co = self.vert_offsets_host, self.adjacency_host()[0]
+        c0, c1 = int(co[vo[a]]), int(co[vo[b]])
+        return off.data_ptr() + int(vo[a]) * 8, tid.data_ptr() + c0 * 4, c1 - c0
 
 
 def random_rotations(n, mode="z", seed=0):
@@ -313,6 +376,10 @@ def default_azimuths(num_views):
 
 def camera_matrices(elevation, azimuths):
     """[V, 3, 3] float32: rows right, up, forward (eye -> origin) of matplotlib's view_init(elev, azim), +z up."""
+    return _camera_matrices64(elevation, azimuths).astype(np.float32)
+
+
+def _camera_matrices64(elevation, azimuths):
     azimuths = list(azimuths)
     el = np.broadcast_to(np.asarray(elevation, np.float64), (len(azimuths),))
     C = np.zeros((len(azimuths), 3, 3))
@@ -323,7 +390,25 @@ def camera_matrices(elevation, azimuths):
         r = np.array([-math.sin(a), math.cos(a), 0.0])
         u = np.cross(r, f)
         C[i] = np.stack([r, u, f])
-    return C.astype(np.float32)
+    return C
+
+
+def shading_vectors(elevation, azimuths, light):
+    """(lights, halfs) float32 [V, 3] of smooth shading, built in float64 and rounded once.  light: a direction
+    (normalised here) or "camera", the headlight: the unit vector from the origin towards every view's eye (the negated
+    forward row of its camera).  halfs: m_v = normalize(l_v + eye_v), the Blinn half-vector of a directional viewer
+    (zero where the light looks straight back at the eye)."""
+    eye = -_camera_matrices64(elevation, azimuths)[:, 2, :]
+    if isinstance(light, str):
+        lights = eye.copy()
+    else:
+        lt = np.asarray(light, np.float64)
+        lights = np.broadcast_to(lt / np.linalg.norm(lt), eye.shape)
+    m = lights + eye
+    nm = np.linalg.norm(m, axis=1, keepdims=True)
+    halfs = np.where(nm > 0, m / np.where(nm > 0, nm, 1.0), 0.0)
+    # (C order spelled out: astype keeps a broadcast array's stride order, and the kernels read [V, 3] rows)
+    return np.ascontiguousarray(lights, dtype=np.float32), np.ascontiguousarray(halfs, dtype=np.float32)
 
 
 def projection(height, width, fov):
@@ -342,11 +427,15 @@ class ViewRenderer:
     in degrees, (0, 120]; fit: the normalised radius in (0, 1]; color / background: RGB in [0, 1]; light: a direction
     (normalised here); max_workspace_bytes: a batch whose workspace or tile lists would pass it is rendered in groups of
     meshes, with identical results; samples: 1, 2 or 4 coverage samples per pixel and axis (anti-aliasing; 1 is one sample
-    at the pixel centre)."""
+    at the pixel centre); shading: "flat" (one factor per triangle) or "smooth" (Phong reflection on interpolated vertex
+    normals, per sample).  Smooth only: light="camera" (a headlight that travels with the view), diffuse="lambert"
+    (max(s, 0); "wrap" is matplotlib's (s + 1) / 2; two_sided makes both |s|), specular in [0, 1] with shininess 1, 2,
+    4, ..., 128 (the exponent of the highlight)."""
 
     def __init__(self, num_views, height, width, elevation=30.0, azimuths=None, fov=0.0, fit=0.9,
                  color=DEFAULT_COLOR, background=DEFAULT_BACKGROUND, light=DEFAULT_LIGHT, ambient=0.3,
-                 two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE, samples=1):
+                 two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE, samples=1, shading="flat",
+                 diffuse="wrap", specular=0.0, shininess=16):
         if not 1 <= int(num_views) <= MAX_VIEWS:
             raise ValueError("num_views must be in [1, %d]" % MAX_VIEWS)
         if not (1 <= int(height) <= MAX_SIDE and 1 <= int(width) <= MAX_SIDE):
@@ -359,8 +448,29 @@ class ViewRenderer:
             raise ValueError("fov must be 0 (orthographic) or in (0, 120] degrees")
         if samples not in (1, 2, 4):
             raise ValueError("samples must be 1, 2 or 4")
+        if shading not in ("flat", "smooth"):
+            raise ValueError("shading must be 'flat' or 'smooth'")
+        if diffuse not in ("wrap", "lambert"):
+            raise ValueError("diffuse must be 'wrap' or 'lambert'")
+        if isinstance(light, str) and light != "camera":
+            raise ValueError("light must be a nonzero 3-vector or 'camera'")
+        if isinstance(specular, bool) or not isinstance(specular, numbers.Real) or not 0.0 <= specular <= 1.0:
+            raise ValueError("specular must be in [0, 1]")
+        if (isinstance(shininess, bool) or not isinstance(shininess, numbers.Integral)
+                or shininess not in (1, 2, 4, 8, 16, 32, 64, 128)):
+            raise ValueError("shininess must be one of 1, 2, 4, ..., 128")
+        if shading == "flat":
+            # the flat table is per triangle and view-independent, and stays so
+            for bad, what in ((isinstance(light, str), "light='camera'"), (diffuse != "wrap", "diffuse='lambert'"),
+                              (specular != 0, "a specular term"), (shininess != 16, "a shininess")):
+                if bad:
+                    raise ValueError("%s needs shading='smooth'" % what)
         self.samples = int(samples)
         self._ss = self.samples > 1                      # through gv_render_*_ss (samples = 1: the original pair)
+        self.shading, self.diffuse, self.specular, self.shininess = shading, diffuse, float(specular), int(shininess)
+        self.light_mode = "camera" if isinstance(light, str) else "world"
+        if self.light_mode == "camera":
+            light = DEFAULT_LIGHT                        # the flat table (a smooth sample's fallback) keeps a world light
         self.lib = _lib.load()
         self.V, self.H, self.W = int(num_views), int(height), int(width)
         self.azimuths = default_azimuths(self.V) if azimuths is None else [float(a) for a in azimuths]
@@ -388,6 +498,15 @@ class ViewRenderer:
         self.max_workspace_bytes = int(max_workspace_bytes)
         self.cameras = torch.from_numpy(self.cameras_host).to(self.device)
         self.status = None
+        self.lights_host, self.halfs_host = shading_vectors(elevation, self.azimuths,
+                                                            "camera" if self.light_mode == "camera" else lt)
+        if shading == "smooth":
+            sh = _lib.RenderShading()
+            sh.flags = _lib.GV_RENDER_LAMBERT if diffuse == "lambert" else 0
+            sh.shininess, sh.specular = shininess, self.specular
+            self.shade_desc = sh
+            self.lights = torch.from_numpy(self.lights_host).to(self.device)
+            self.halfs = torch.from_numpy(self.halfs_host).to(self.device)
 
     def descriptor(self):
         """The descriptor's fields as Python values (fp32-rounded), for an oracle."""
@@ -395,7 +514,10 @@ class ViewRenderer:
         return {"height": d.height, "width": d.width, "num_views": d.num_views, "flags": d.flags, "fit": d.fit,
                 "proj_scale": d.proj_scale, "persp_dist": d.persp_dist, "depth_a": d.depth_a, "depth_b": d.depth_b,
                 "ambient": d.ambient, "light": list(d.light), "color": list(d.color),
-                "background": list(d.background), "cameras": self.cameras_host.copy(), "samples": self.samples}
+                "background": list(d.background), "cameras": self.cameras_host.copy(), "samples": self.samples,
+                "shading": self.shading, "diffuse": self.diffuse, "light_mode": self.light_mode,
+                "specular": float(np.float32(self.specular)), "shininess": self.shininess,
+                "lights": self.lights_host.copy(), "halfs": self.halfs_host.copy()}
 
     def _rotations(self, rotations, n):
         if rotations is None:
@@ -417,7 +539,12 @@ class ViewRenderer:
         n, total_tris = args[4], args[6]
         ws_bytes = lib.gv_render_workspace_bytes(n, self.V, self.H, self.W, total_tris)
         _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_render_workspace_bytes")
-        if ws_bytes > self.max_workspace_bytes and n > 1:
+        smooth = self.shading == "smooth"
+        nb = 0
+        if smooth:                                                       # the normal table counts as workspace
+            nb = lib.gv_render_normals_bytes(self.V, d.flags, args[5])
+            _lib.check(nb if nb < 0 else 0, "gv_render_normals_bytes")
+        if ws_bytes + nb > self.max_workspace_bytes and n > 1:
             h = (a + b) // 2
             self._draw(batch, a, h, rot, output, out, face_id, depth, status)
             self._draw(batch, h, b, rot, output, out, face_id, depth, status)
@@ -439,7 +566,7 @@ class ViewRenderer:
         status[a:b] = host[1:].view(np.int32)[:n]
         bins_bytes = lib.gv_render_bins_bytes(total)
         _lib.check(bins_bytes if bins_bytes < 0 else 0, "gv_render_bins_bytes")
-        if ws_bytes + bins_bytes > self.max_workspace_bytes and n > 1:
+        if ws_bytes + nb + bins_bytes > self.max_workspace_bytes and n > 1:
             del ws, info
             h = (a + b) // 2
             self._draw(batch, a, h, rot, output, out, face_id, depth, status)
@@ -452,7 +579,14 @@ class ViewRenderer:
                 out.data_ptr() + a * img * 3 * esz,
                 None if face_id is None else face_id.data_ptr() + a * img * S * S * 4,        # the sample grid
                 None if depth is None else depth.data_ptr() + a * img * S * S * 4)
-        if not self._ss:
+        if smooth:
+            normals = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            rc = lib.gv_render_vertex_normals(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
+                                              *batch.group_adjacency(a, b), normals.data_ptr(), nb, _model._st())
+            _lib.check(rc, "gv_render_vertex_normals")
+            rc = lib.gv_render_draw_smooth(*args, *tail, S, self.shade_desc, self.lights.data_ptr(),
+                                           self.halfs.data_ptr(), normals.data_ptr(), nb, _model._st())
+        elif not self._ss:
             rc = lib.gv_render_draw(*args, *tail, _model._st())
         else:
             rc = lib.gv_render_draw_ss(*args, *tail, S, _model._st())

@@ -565,6 +565,65 @@ int gv_render_draw_ss(const float* verts, const int64_t* vert_offsets, const int
                       const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
                       int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth,
                       int32_t samples, void* stream);
+/* Smooth shading: per-vertex normals computed on the device for each render and interpolated per coverage sample in the
+ * raster kernel's resolve (Phong reflection: a diffuse and an optional specular term, a light per view).  Coverage,
+ * depth, face_id, binning and the resolve from the sample colours on are exactly those above; only the colour of a
+ * covered sample changes.  Every fp32 step rounds on its own (no FMA), so the pictures stay defined bit for bit.
+ *  - face vector of triangle t: n_t = (w1-w0) x (w2-w0) from world positions, the steps of the flat shading, left
+ *    unnormalised (the sum below is area-weighted; a triangle that names a vertex twice gives exactly zero).
+ *  - GV_RENDER_TWO_SIDED: before it is summed, n_t is turned to face the viewer of view v: d = (F0*n0 + F1*n1) + F2*n2
+ *    with F the forward row of C_v (orthographic and perspective alike); n_t is negated when d > 0.  The normal table
+ *    is then [V, total_verts, 3], otherwise [1, total_verts, 3].
+ *  - vertex normal: the corners of vertex i are the (triangle, corner) pairs that name it, of triangles whose three
+ *    indices are all inside [0, nv); corner_offsets int64 [total_verts + 1] (per vertex of the packed arrays; as with
+ *    the mesh offsets, corner_offsets[0] need not be 0: vertex i owns corner_tris[corner_offsets[i]-corner_offsets[0]
+ *    .. corner_offsets[i+1]-corner_offsets[0]) of the array passed) and corner_tris int32 [total_corners], the LOCAL
+ *    triangle ids in ascending order (a stable sort of the flattened index array).  g_i = the face vectors of the list
+ *    added per component in list order, starting from the first; nn = (g0*g0 + g1*g1) + g2*g2; the unit normal is
+ *    g_i / sqrt(nn) per component when nn is finite and > 0, else (0, 0, 0).  One thread per (table, vertex), no
+ *    atomics: a pure function of the inputs.  Vertices of a mesh whose status is not GV_RENDER_OK get (0, 0, 0).
+ *  - per covered sample: the winning key holds depth and id only; the triangle's setup is recomputed from the id and,
+ *    with it, the three integer edge functions e0 = E_12, e1 = E_20, e2 = E_01 at the sample.  Where the setup swapped
+ *    vertices 1 and 2 (negative screen area) the normals follow: (a, b, c) = (i0, i2, i1).  b_k = (float)e_k /
+ *    (float)area (int64 -> fp32 round to nearest even), n = ((b0*ga + b1*gb) + b2*gc) per component: affine in SCREEN
+ *    space like the depth, NOT perspective-correct.  nn = (n0*n0 + n1*n1) + n2*n2; when nn is not finite and > 0 the
+ *    sample takes colour = color * f of its triangle from the flat table of the prepare call (desc->light, h =
+ *    (s+1)*0.5 or |s|) and no specular term.
+ *  - shading: s = ((l0*n0 + l1*n1) + l2*n2) / sqrt(nn) with l = lights[v]; h = (s+1)*0.5, or max(s, 0) with
+ *    GV_RENDER_LAMBERT, or |s| with GV_RENDER_TWO_SIDED; f = ambient + (1-ambient) * h.  t = (m.n) / sqrt(nn) with m =
+ *    halfs[v], clamped max(t, 0) (|t| with GV_RENDER_TWO_SIDED); p = t squared log2(shininess) times, one rounding per
+ *    squaring; channel c = min(color_c * f + specular * p, 1).  lights / halfs [V, 3] are unit vectors built by the
+ *    host (float64, rounded to fp32): a world light repeated, or the headlight -F_v; m_v = normalize(l_v + eye_v) with
+ *    eye_v = -F_v, a directional viewer for both projections.
+ *  - samples > 1: each of the S x S samples is shaded at its own position, then resolved as above.
+ * Sequence: prepare[_ss] (binning does not depend on shading; its flat table is the fallback above), then
+ * gv_render_vertex_normals into a table of gv_render_normals_bytes(num_views, desc->flags, total_verts) bytes, then
+ * gv_render_draw_smooth with the arguments of gv_render_draw_ss, the shading descriptor, lights, halfs and the table.
+ * Rejections before any launch: those of the pair above; GV_E_BADARG for a NULL shading / lights / halfs / normals /
+ * corner array, unknown shading flags, specular outside [0, 1], a shininess that is no power of two, a normal table
+ * smaller than the size query's answer; GV_E_UNSUPPORTED for a power-of-two shininess above 128; GV_E_ALIGN for a normal
+ * table that is not 16-byte aligned. */
+#define GV_RENDER_LAMBERT 1           /* gv_render_shading.flags: h = max(s, 0) */
+typedef struct gv_render_shading {
+    int32_t flags;
+    int32_t shininess;                /* 1, 2, 4, ..., 128 */
+    float specular;                   /* [0, 1] */
+    int32_t reserved;
+} gv_render_shading;
+int64_t gv_render_normals_bytes(int32_t num_views, int32_t flags, int64_t total_verts);
+int gv_render_vertex_normals(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                             const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                             int32_t max_tris, const gv_render_desc* desc, const float* cameras, const float* rotations,
+                             void* workspace, int64_t workspace_bytes, const int64_t* corner_offsets,
+                             const int32_t* corner_tris, int64_t total_corners, float* normals, int64_t normals_bytes,
+                             void* stream);
+int gv_render_draw_smooth(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
+                          const int64_t* tri_offsets, int32_t n, int64_t total_verts, int64_t total_tris,
+                          int32_t max_tris, const gv_render_desc* desc, const float* cameras, const float* rotations,
+                          void* workspace, int64_t workspace_bytes, void* bins, int64_t bins_bytes, int64_t total,
+                          int32_t output, void* out, int32_t* face_id, uint32_t* depth, int32_t samples,
+                          const gv_render_shading* shading, const float* lights, const float* halfs,
+                          const float* normals, int64_t normals_bytes, void* stream);
 
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several

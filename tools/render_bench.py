@@ -1,6 +1,7 @@
 """Rasteriser throughput on seeded synthetic meshes; prints one JSON line.
 
     python tools/render_bench.py [--forward c4|c2] [--samples 1,2,4] [--pool-baseline] [--steps 20] [--warmup 5]
+                                 [--shading smooth [--light camera] [--diffuse lambert] [--specular 0.3]]
 
 Cases: icospheres of 80, 1 280, 20 480 and 327 680 faces and a giant/tiny mix (two screen-size triangles + 20 000
 small ones), N = 32 meshes x V = 12 views at 224^2 and 299^2, each mesh under its own random rotation.  Per case: ms per
@@ -10,7 +11,8 @@ forward time of the same views, so the render cost reads against what it feeds. 
 (S x S samples per pixel resolved in the rasteriser), one case per S, each with the device time of its prepare and draw
 calls (events around the two C-ABI calls; the rest of "ms" is the host read between them).  --pool-baseline: next to
 every S = 2 case whose doubled side the rasteriser takes (<= 512), what one sample per pixel can do: render at 2H x 2W
-and average-pool in torch.
+and average-pool in torch.  --shading smooth: the same cases with interpolated vertex normals (gv_render_vertex_normals +
+gv_render_draw_smooth); the normals kernel's own device time is reported next to prepare and draw.
 """
 import argparse
 import json
@@ -54,11 +56,12 @@ class SplitTimer:
     """Stands in for the library of a ViewRenderer: device events around every prepare and every draw call."""
 
     def __init__(self, lib):
-        self.lib, self.events = lib, {"prepare": [], "draw": []}
+        self.lib, self.events = lib, {"prepare": [], "draw": [], "normals": []}
 
     def __getattr__(self, name):
         fn = getattr(self.lib, name)
-        kind = "prepare" if name.startswith("gv_render_prepare") else "draw" if name.startswith("gv_render_draw") else None
+        kind = ("prepare" if name.startswith("gv_render_prepare") else "draw" if name.startswith("gv_render_draw") else
+                "normals" if name == "gv_render_vertex_normals" else None)
         if kind is None:
             return fn
 
@@ -77,8 +80,8 @@ class SplitTimer:
 
 
 def timed_split(r, fn, steps, warmup):
-    """(ms, prepare ms, draw ms) per render: the whole render as `timed` measures it, then the two calls' own times in
-    a second pass (the extra events stay out of the first)."""
+    """(ms, prepare ms, draw ms, normals ms) per render: the whole render as `timed` measures it, then the calls' own
+    times in a second pass (the extra events stay out of the first).  normals ms is 0 for a flat renderer."""
     ms = timed(fn, steps, warmup)
     lib = r.lib
     r.lib = t = SplitTimer(lib)
@@ -88,7 +91,7 @@ def timed_split(r, fn, steps, warmup):
         torch.cuda.synchronize()
     finally:
         r.lib = lib
-    return ms, t.ms("prepare", steps), t.ms("draw", steps)
+    return ms, t.ms("prepare", steps), t.ms("draw", steps), t.ms("normals", steps)
 
 
 def main(argv=None):
@@ -102,6 +105,12 @@ def main(argv=None):
     ap.add_argument("--samples", default="1", help="samples per pixel and axis, comma separated (1, 2, 4)")
     ap.add_argument("--pool-baseline", action="store_true",
                     help="next to S = 2: one sample per pixel at twice the side, then avg_pool2d")
+    ap.add_argument("--shading", default="flat", choices=("flat", "smooth"))
+    ap.add_argument("--light", default="world", choices=("world", "camera"), help="camera: a headlight (smooth only)")
+    ap.add_argument("--diffuse", default="wrap", choices=("wrap", "lambert"))
+    ap.add_argument("--specular", type=float, default=0.0)
+    ap.add_argument("--shininess", type=int, default=16, help="exponent of the highlight: 1, 2, 4, ..., 128")
+    ap.add_argument("--two-sided", action="store_true", help="shade both faces alike (one normal table per view)")
     ap.add_argument("--meshes", default="", help="comma separated subset of the mesh names (default: all)")
     ap.add_argument("--table", action="store_true", help="a plain-text table of the cases in front of the JSON line")
     a = ap.parse_args(argv)
@@ -120,12 +129,16 @@ def main(argv=None):
     for size in [int(s) for s in a.sizes.split(",")]:
         out = torch.empty((N, V, size, size, 3), dtype=torch.float32, device=dev)
         for S in samples:
-            r = R.ViewRenderer(V, size, size, device=dev, samples=S)
+            r = R.ViewRenderer(V, size, size, device=dev, samples=S, shading=a.shading, diffuse=a.diffuse,
+                               specular=a.specular, shininess=a.shininess, two_sided=a.two_sided,
+                               **({"light": "camera"} if a.light == "camera" else {}))
             for name, m in meshes.items():
                 batch = R.MeshBatch([m] * N, dev)
-                ms, prep, draw = timed_split(r, lambda: r.render(batch, rotations=rots, out=out), a.steps, a.warmup)
+                ms, prep, draw, nrm = timed_split(r, lambda: r.render(batch, rotations=rots, out=out), a.steps,
+                                                  a.warmup)
                 case = {"mesh": name, "faces": int(len(m[1])), "size": size, "samples": S, "N": N, "V": V,
-                        "ms": round(ms, 4), "prepare_ms": round(prep, 4), "draw_ms": round(draw, 4),
+                        "shading": a.shading, "ms": round(ms, 4), "prepare_ms": round(prep, 4),
+                        "draw_ms": round(draw, 4), "normals_ms": round(nrm, 4),
                         "meshes_per_s": round(N / ms * 1e3, 1), "views_per_s": round(N * V / ms * 1e3, 1),
                         "tri_views_per_s": float("%.4g" % (N * V * len(m[1]) / ms * 1e3))}
                 cases.append(case)
@@ -154,13 +167,15 @@ def main(argv=None):
             del eng
             torch.cuda.empty_cache()
     if a.table:
-        print("%-11s %7s %5s %2s  %9s %10s %9s  %s" % ("mesh", "faces", "size", "S", "ms/batch", "prepare ms", "draw ms", ""))
+        print("%-11s %7s %5s %2s  %9s %10s %9s %10s  %s" % ("mesh", "faces", "size", "S", "ms/batch", "prepare ms", "draw ms",
+                                                            "normals ms", ""))
         for c in cases:
             if "mesh" in c:
-                print("%-11s %7d %5d %2d  %9.3f %10s %9s  %s" % (
+                print("%-11s %7d %5d %2d  %9.3f %10s %9s %10s  %s" % (
                     c["mesh"], c["faces"], c["size"], c["samples"], c["ms"],
                     "%.3f" % c["prepare_ms"] if "prepare_ms" in c else "-",
-                    "%.3f" % c["draw_ms"] if "draw_ms" in c else "-", c.get("baseline", "")))
+                    "%.3f" % c["draw_ms"] if "draw_ms" in c else "-",
+                    "%.3f" % c["normals_ms"] if c.get("shading") == "smooth" else "-", c.get("baseline", "")))
     print(json.dumps({"metric": "render_ms_per_batch", "unit": "ms", "cases": cases}))
 
 

@@ -1,7 +1,7 @@
 """ModelNet meshes -> GZIP TFRecords of rendered views, on the device (replaces the reference's off2obj.py ->
 obj2png.py -> create_modelnet_tf_record.py chain).
 
-    python tools/render_modelnet.py --src ModelNet40 --split train --out modelnet40_train.tfrecord --views 12 --size 224 [--samples 4]
+    python tools/render_modelnet.py --src ModelNet40 --split train --out modelnet40_train.tfrecord --views 12 --size 224 [--samples 4] [--shading smooth --light camera --diffuse lambert --specular 0.3]
 
 Walks SRC/<class>/<split>/*.off in sorted order; the label of a shape is the index of its class directory among the
 sorted class directories (create_modelnet_tf_record.py's convention).  Meshes are rendered `--batch` at a time with
@@ -38,6 +38,14 @@ def main(argv=None):
     ap.add_argument("--fov", type=float, default=0.0)
     ap.add_argument("--samples", type=int, default=1, choices=(1, 2, 4),
                     help="coverage samples per pixel and axis (anti-aliasing inside the rasteriser)")
+    ap.add_argument("--shading", default="flat", choices=("flat", "smooth"),
+                    help="smooth: Phong reflection on interpolated vertex normals (the look of the published 12-view sets)")
+    ap.add_argument("--light", default="world", choices=("world", "camera"),
+                    help="camera: a headlight that travels with the view (smooth only)")
+    ap.add_argument("--diffuse", default="wrap", choices=("wrap", "lambert"), help="lambert: max(s, 0) (smooth only)")
+    ap.add_argument("--specular", type=float, default=0.0, help="weight of the highlight in [0, 1] (smooth only)")
+    ap.add_argument("--shininess", type=int, default=16, help="exponent of the highlight: 1, 2, 4, ..., 128")
+    ap.add_argument("--two-sided", action="store_true", help="shade both faces alike (inconsistently wound meshes)")
     ap.add_argument("--batch", type=int, default=32, help="meshes per device render")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -50,7 +58,9 @@ def main(argv=None):
         raise SystemExit("no %s/*.off files under %s" % (a.split, a.src))
     dev = torch.device(a.device)
     r = render.ViewRenderer(a.views, a.size, a.size, elevation=a.elevation, fov=a.fov, device=dev,
-                            samples=a.samples)
+                            samples=a.samples, shading=a.shading, diffuse=a.diffuse, specular=a.specular,
+                            shininess=a.shininess, two_sided=a.two_sided,
+                            **({"light": "camera"} if a.light == "camera" else {}))
 
     def examples():
         for b0 in range(0, len(shapes), a.batch):
