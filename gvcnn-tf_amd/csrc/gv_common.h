@@ -133,6 +133,26 @@ static inline int64_t gv_dw_clamp(const GvDw& o, size_t elems, int64_t splits) {
     const int64_t cap = (int64_t)(o.cap_bytes / (((elems + 3) / 4 * 4) * sizeof(float)));
     return cap < 2 ? 1 : (splits < cap ? splits : cap);
 }
+// The slice plan of a launch: `units` of work along the split axis (pixels, or strip stages) go to `splits` slices of
+// `per` units each, the last one ragged.  Enough slices that `tiles` workgroups per slice fill `target_wgs`, but at least
+// `min_units` a slice, at most `max_splits` slices (0: no such cap) and what the sink holds; `per` is then rounded up to
+// `granule` and the slices counted again.  `per` is only ever rounded UP after gv_dw_clamp, so the slices never
+// outnumber what the clamp allowed: splits <= gv_dw_clamp(o, elems, ...) — the workspace holds every slice's image.
+struct GvSlices {
+    int64_t splits, per;
+};
+static inline GvSlices gv_dw_plan(const GvDw& o, size_t elems, int64_t units, int64_t tiles, int64_t target_wgs,
+                                  int64_t min_units, int64_t granule, int64_t max_splits) {
+    int64_t splits = (target_wgs + tiles - 1) / tiles;
+    const int64_t most = (units + min_units - 1) / min_units;
+    if (splits > most) splits = most;
+    if (splits < 1) splits = 1;
+    if (max_splits && splits > max_splits) splits = max_splits;
+    splits = gv_dw_clamp(o, elems, splits);
+    int64_t per = (units + splits - 1) / splits;
+    per = (per + granule - 1) / granule * granule;
+    return GvSlices{(units + per - 1) / per, per};
+}
 // The sink the KERNEL gets for `splits` slices (the plain one for a single slice) ...
 static inline GvDw gv_dw_sink(const GvDw& o, size_t elems, int64_t splits) {
     if (!o.part || splits <= 1) return GvDw{o.dw, nullptr, 0, 0};
@@ -144,6 +164,14 @@ int gv_dw_finish(const GvDw& o, size_t elems, int64_t splits, hipStream_t st);  
 __device__ __forceinline__ void gv_dw_put(const GvDw& o, int64_t slice, size_t idx, float v) {
     if (o.part) o.part[(size_t)slice * o.stride + idx] = v;      // (wave-uniform branch)
     else atomicAdd(&o.dw[idx], v);
+}
+// The tap-per-workgroup kernels (conv_wgrad_f32, conv_wgrad2_f32, conv_wgrad_lp) take one argument list: the layer, `per`
+// pixels a slice, the sink.
+template <auto Kernel, typename E>
+int gv_wgrad_launch(dim3 grid, const gv_conv_desc* d, const E* x, const E* dz, int dz_ld, int64_t per, const GvDw& sink,
+                    hipStream_t st) {
+    return gv_launch<Kernel>(grid, dim3(256), 0, st, x, d->x_ld, dz, dz_ld, d->nb, d->ih, d->iw, d->cin, d->kh, d->kw,
+                             d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, (int64_t)d->nb * d->oh * d->ow, per, sink);
 }
 #endif
 

@@ -45,8 +45,45 @@ int view_pool_fuse_bwd(int dtype, const void* F, const float* dS, int V, int N, 
 bool wgrad_mfma_ok(const gv_conv_desc* d, const void* x, const void* dz, int dz_ld);
 int conv_wgrad(const gv_conv_desc* d, const void* x, const void* dz, int dz_ld, const GvDw& dw, hipStream_t st);
 int conv_wgrad_stem(const gv_conv_desc* d, const void* x, const void* dz, int dz_ld, const GvDw& dw, hipStream_t st);
-// wgrad_dma.hip: the same filter gradient with LDS-DMA operand staging (tile_cfg 31 .. 30 + wgrad_dma_num_cfgs())
-int wgrad_dma_num_cfgs();
+
+// ---- the configurations of the 16-bit filter gradient -------------------------------------------------------------------
+// gv_conv_desc::tile_cfg (1-based; 0: the heuristic) names one launch configuration.  The table is the kernel families IN
+// ORDER, each with as many indices as it has configurations: the one place that says which index is whose.  The autotuner,
+// tools, documents and tests hold indices as numbers: append to the last family or add a family, never reorder.
+enum WgradFamily {
+    WGRAD_TILES,       // tap-per-workgroup tiles (conv_wgrad_lp): sides (TI, TO) in {1,2,3}^2 x 1024 / 2048 / 4096 workgroups
+    WGRAD_STRIPS,      // 32-pixel strips (conv_wgrad_strip_lp): 1024 / 2048 / 4096 workgroups
+    WGRAD_DMA,         // LDS-DMA staging (wgrad_dma.hip: its table of tiles, ring depths and targets)
+    WGRAD_DEEP,        // 8 x 32 pixel strips: 512 / 768 / 1024 / 2048 / 4096 workgroups
+    WGRAD_NONE
+};
+struct WgradRange { WgradFamily fam; int count; };
+struct WgradRef { WgradFamily fam; int local; };             // configuration `local` of family `fam`
+constexpr WgradRange kWgradTable[] = {{WGRAD_TILES, 27}, {WGRAD_STRIPS, 3}, {WGRAD_DMA, 61}, {WGRAD_DEEP, 5}};
+
+constexpr int wgrad_family_count(WgradFamily fam) {
+    for (const WgradRange& r : kWgradTable)
+        if (r.fam == fam) return r.count;
+    return 0;
+}
+constexpr int wgrad_num_cfgs() {
+    int n = 0;
+    for (const WgradRange& r : kWgradTable) n += r.count;
+    return n;
+}
+// tile_cfg -> (family, local index); WGRAD_NONE for 0 and outside the table
+inline WgradRef wgrad_lookup(int tile_cfg) {
+    int k = tile_cfg - 1;
+    for (const WgradRange& r : kWgradTable) {
+        if (k < 0) break;
+        if (k < r.count) return {r.fam, k};
+        k -= r.count;
+    }
+    return {WGRAD_NONE, 0};
+}
+int wgrad_strip_taps();                                       // train.hip: gv_conv2d_wgrad_set_strip_taps
+// wgrad_dma.hip: configuration k of the LDS-DMA family; the first one with these properties, -1 if there is none
 int conv_wgrad_dma_launch(const gv_conv_desc* d, const void* x, const void* dz, int dz_ld, const GvDw& dw, int k, hipStream_t st);
+int wgrad_dma_find(int ti, int to, int stages, int stage_pixels, int target_wgs);
 
 }  // namespace gvlp

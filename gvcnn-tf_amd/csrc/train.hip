@@ -1187,14 +1187,27 @@ extern "C" int gv_bn_update_moving(const float* mean, const float* var, const in
     return GV_OK;
 }
 
-static int g_wgrad_v1 = 0;
+// The filter gradient's tuning hooks (tests and tools compare forms with them; nothing else sets them):
+static int g_wgrad_v1 = 0;             // fp32 storage on the first-generation kernel (conv_wgrad_f32), not the fp32 MFMA
+static int g_wgrad_lp_f32 = 0;         // 16-bit storage on the fp32 MFMA (typed loads), not the 16-bit MFMA kernels
+static int g_wgrad_strip_taps = 5;     // taps per workgroup of the general strip variant: 5 keeps two waves per SIMD (9: one)
 extern "C" void gv_conv2d_wgrad_set_v1(int on) { g_wgrad_v1 = on; }
+extern "C" void gv_conv2d_wgrad_set_lp_f32(int on) { g_wgrad_lp_f32 = on; }
+extern "C" void gv_conv2d_wgrad_set_strip_taps(int n) { g_wgrad_strip_taps = n; }
+int gvlp::wgrad_strip_taps() { return g_wgrad_strip_taps; }
 
 // few-channel stem layers: all taps in one wave, operands straight from global memory
 static bool wgrad_direct_ok(const gv_conv_desc* d) {
     const int64_t M = (int64_t)d->nb * d->oh * d->ow;
     return d->kh * d->kw * d->cin <= 288 && d->cin <= 32 && M >= 200000 &&
            (int64_t)d->nb * d->ih * d->iw * d->x_ld < 0x7fffffffll;
+}
+
+template <auto Kernel, typename S>
+static int wgrad_direct_launch(dim3 grid, const gv_conv_desc* d, const S* x, const S* dz, int dz_ld, int64_t per,
+                               const GvDw& sink, hipStream_t st) {
+    return gv_launch<Kernel>(grid, dim3(256), 0, st, x, d->x_ld, dz, dz_ld, d->ih, d->iw, d->cin, d->kh, d->kw, d->stride,
+                             d->pad_t, d->pad_l, d->oh, d->ow, d->cout, (int64_t)d->nb * d->oh * d->ow, per, sink);
 }
 
 // the fp32-MFMA filter gradient for storage type S (float; 16-bit: stems and shapes the 16-bit MFMA kernel
@@ -1206,57 +1219,31 @@ static int wgrad_f32mfma(const gv_conv_desc* d, const S* x, const S* dz, int32_t
     const size_t elems = (size_t)R * d->cout;
     if (wgrad_direct_ok(d)) {
         const int nrt = (R + 31) / 32;
-        const int64_t waves = gv_dw_clamp(dw, elems, 256 * 4 * (nrt == 1 ? 6 : (nrt <= 5 ? 2 : 1)));   // (a wave is a slice)
-        int64_t per = (M + waves - 1) / waves;
-        per = (per + 1) / 2 * 2;
-        const int64_t nw = (M + per - 1) / per;
-        const GvDw sink = gv_dw_sink(dw, elems, nw);
-        const dim3 grid((unsigned)(((nw + 3) / 4) * ((d->cout + 31) / 32)));
-#define GV_WGRAD_D(NRT, U)                                                                                          \
-        hipLaunchKernelGGL((conv_wgrad_direct_f32<S, NRT, U>), grid, dim3(256), 0, st, x, d->x_ld, dz, dz_ld, d->ih,  \
-                           d->iw, d->cin, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, M, per,  \
-                           sink)
-        if (nrt == 1) GV_WGRAD_D(1, 8);
-        else if (nrt <= 5) GV_WGRAD_D(5, 4);
-        else GV_WGRAD_D(9, 8);
-#undef GV_WGRAD_D
-        GV_LAUNCH_CHECK();
-        return gv_dw_finish(dw, elems, nw, st);
+        // a wave is a slice of pixel pairs (M >= 200000: the one-pixel minimum never binds)
+        const GvSlices p = gv_dw_plan(dw, elems, M, 1, 256 * 4 * (nrt == 1 ? 6 : (nrt <= 5 ? 2 : 1)), 1, 2, 0);
+        const dim3 grid((unsigned)(((p.splits + 3) / 4) * ((d->cout + 31) / 32)));
+        const auto launch = nrt == 1   ? wgrad_direct_launch<conv_wgrad_direct_f32<S, 1, 8>, S>
+                            : nrt <= 5 ? wgrad_direct_launch<conv_wgrad_direct_f32<S, 5, 4>, S>
+                                       : wgrad_direct_launch<conv_wgrad_direct_f32<S, 9, 8>, S>;
+        const int rc = launch(grid, d, x, dz, dz_ld, p.per, gv_dw_sink(dw, elems, p.splits), st);
+        return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
     }
     // 128 channels on a side only where that wastes no more rows than 64-wide tiles would
     const int ti = (d->cin + 127) / 128 * 128 == (d->cin + 63) / 64 * 64 ? 2 : 1;
     const int to = (d->cout + 127) / 128 * 128 == (d->cout + 63) / 64 * 64 ? 2 : 1;
     const int tiles = d->kh * d->kw * ((d->cin + 64 * ti - 1) / (64 * ti)) * ((d->cout + 64 * to - 1) / (64 * to));
-    int64_t splits = (2048 + tiles - 1) / tiles;            // ~2k workgroups: 256 CUs x 2-4 resident, 2+ rounds
-    const int64_t max_splits = (M + 511) / 512;             // at least 512 pixels per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    splits = gv_dw_clamp(dw, elems, splits);
-    int64_t per = (M + splits - 1) / splits;
-    per = (per + 31) / 32 * 32;
-    splits = (M + per - 1) / per;
-    const dim3 grid((unsigned)(tiles * splits));
-    const GvDw sink = gv_dw_sink(dw, elems, splits);
-#define GV_WGRAD2(TI, TO)                                                                                          \
-    hipLaunchKernelGGL((conv_wgrad2_f32<S, TI, TO>), grid, dim3(256), 0, st, x, d->x_ld, dz, dz_ld, d->nb, d->ih,    \
-                       d->iw, d->cin, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, M, per,     \
-                       sink)
-    if (ti == 2 && to == 2) GV_WGRAD2(2, 2);
-    else if (ti == 2) GV_WGRAD2(2, 1);
-    else if (to == 2) GV_WGRAD2(1, 2);
-    else GV_WGRAD2(1, 1);
-#undef GV_WGRAD2
-    GV_LAUNCH_CHECK();
-    return gv_dw_finish(dw, elems, splits, st);
+    // ~2k workgroups (256 CUs x 2-4 resident, 2+ rounds) of at least 512 pixels, in steps of 32
+    const GvSlices p = gv_dw_plan(dw, elems, M, tiles, 2048, 512, 32, 65535);
+    const auto launch = ti == 2 && to == 2 ? gv_wgrad_launch<conv_wgrad2_f32<S, 2, 2>, S>
+                        : ti == 2          ? gv_wgrad_launch<conv_wgrad2_f32<S, 2, 1>, S>
+                        : to == 2          ? gv_wgrad_launch<conv_wgrad2_f32<S, 1, 2>, S>
+                                           : gv_wgrad_launch<conv_wgrad2_f32<S, 1, 1>, S>;
+    const int rc = launch(dim3((unsigned)(tiles * p.splits)), d, x, dz, dz_ld, p.per, gv_dw_sink(dw, elems, p.splits), st);
+    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
 }
 
 /* tuning hook: number of launch configurations gv_conv2d_wgrad accepts in gv_conv_desc.tile_cfg for `dtype` */
-extern "C" int gv_conv2d_wgrad_num_cfgs(int dtype) { return dtype == GV_BF16 || dtype == GV_F16 ? 30 + gvlp::wgrad_dma_num_cfgs() + 5 : 0; }
-
-static int g_wgrad_lp_f32 = 0;
-/* tuning hook: 16-bit storage filter gradients on the fp32 MFMA (typed loads) instead of the 16-bit MFMA kernel */
-extern "C" void gv_conv2d_wgrad_set_lp_f32(int on) { g_wgrad_lp_f32 = on; }
+extern "C" int gv_conv2d_wgrad_num_cfgs(int dtype) { return dtype == GV_BF16 || dtype == GV_F16 ? gvlp::wgrad_num_cfgs() : 0; }
 
 // ---- the slices of a filter gradient, added in slice order (the deterministic form: gv_common.h, GvDw) ----------------
 // dw[i] += part[0][i] + part[1][i] + ... : a workgroup owns 64 (float4) or 256 (scalar) consecutive elements and splits the
@@ -1317,23 +1304,13 @@ static int wgrad_dispatch(const gv_conv_desc* d, const void* x, const void* dz, 
     }
     if (d->dtype != GV_F32) return GV_E_UNSUPPORTED;
     if (!g_wgrad_v1) return wgrad_f32mfma<float>(d, (const float*)x, (const float*)dz, dz_ld, dw, st);
-    const int64_t M = (int64_t)d->nb * d->oh * d->ow;
     const int tiles = d->kh * d->kw * ((d->cin + 63) / 64) * ((d->cout + 63) / 64);
     const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    int64_t splits = (4096 + tiles - 1) / tiles;                // ~4k workgroups in flight
-    const int64_t max_splits = (M + 255) / 256;                 // at least 256 pixels per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    splits = gv_dw_clamp(dw, elems, splits);
-    int64_t per = (M + splits - 1) / splits;
-    per = (per + 31) / 32 * 32;
-    splits = (M + per - 1) / per;
-    hipLaunchKernelGGL(conv_wgrad_f32, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, st, (const float*)x,
-                       d->x_ld, (const float*)dz, dz_ld, d->nb, d->ih, d->iw, d->cin, d->kh, d->kw, d->stride, d->pad_t,
-                       d->pad_l, d->oh, d->ow, d->cout, M, per, gv_dw_sink(dw, elems, splits));
-    GV_LAUNCH_CHECK();
-    return gv_dw_finish(dw, elems, splits, st);
+    // ~4k workgroups in flight, of at least 256 pixels, in steps of 32
+    const GvSlices p = gv_dw_plan(dw, elems, (int64_t)d->nb * d->oh * d->ow, tiles, 4096, 256, 32, 65535);
+    const int rc = gv_wgrad_launch<conv_wgrad_f32>(dim3((unsigned)tiles, (unsigned)p.splits), d, (const float*)x, (const float*)dz,
+                                                   dz_ld, p.per, gv_dw_sink(dw, elems, p.splits), st);
+    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
 }
 
 extern "C" int gv_conv2d_wgrad(const gv_conv_desc* d, const void* x, const void* dz, int32_t dz_ld,

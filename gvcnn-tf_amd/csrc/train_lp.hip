@@ -1488,18 +1488,14 @@ int strip_launch(const gv_conv_desc* d, const unsigned short* x, const unsigned 
     const int taps = d->kh * d->kw, tpg = NTW * WT;              // taps per workgroup
     const int groups = (taps + tpg - 1) / tpg;
     const int tiles = ((d->cin + BI - 1) / BI) * ((d->cout + BO - 1) / BO) * groups;
-    int64_t splits = (target_wgs + tiles - 1) / tiles;
-    const int64_t max_splits = KS == 2 ? (gm.stages + 7) / 8     // at least 8 strips per workgroup (deep: 3 of 256 pixels)
-                                       : (gm.stages + 2) / 3;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
     const size_t elems = (size_t)taps * d->cin * d->cout;
-    splits = gv_dw_clamp(dw, elems, splits);
-    gm.stages_per_block = (int)((gm.stages + splits - 1) / splits);
-    splits = (gm.stages + gm.stages_per_block - 1) / gm.stages_per_block;
+    // at least 8 strips per workgroup (deep: 3 of 256 pixels)
+    const GvSlices p = gv_dw_plan(dw, elems, gm.stages, tiles, target_wgs, KS == 2 ? 8 : 3, 1, 65535);
+    const int64_t splits = p.splits;
+    gm.stages_per_block = (int)p.per;
     const size_t lds = (size_t)(16 * KS) * (BO == 32 ? 64 : 2 * BO + 64) + (size_t)gm.xrows * (BI == 32 ? 64 : 2 * BI + 64);
     auto kern = conv_wgrad_strip_lp<T, WI, WJ, WT, NTW, KS>;
+    // the deep form needs the raised LDS limit; the 32-pixel strips fit 64 KB (strip_geom) and only ask
     const bool attr = GV_BIG_LDS_OK(kern, KS == 2 ? 64 * 1024 : 96 * 1024);
     if (KS != 2 && !attr) return GV_E_UNSUPPORTED;
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * splits)), dim3(256), lds, st, x, dz, gm, tpg,
@@ -1508,16 +1504,15 @@ int strip_launch(const gv_conv_desc* d, const unsigned short* x, const unsigned 
     return gv_dw_finish(dw, elems, splits, st);
 }
 
-int g_strip_ntw = 5;     // taps per workgroup of the general strip variant: 5 keeps two waves per SIMD (9: one)
-
 template <typename T>
 int strip_t(const gv_conv_desc* d, const unsigned short* x, const unsigned short* dz, int dz_ld, const GvDw& dw,
             int target_wgs, hipStream_t st) {
     if (d->cin <= 32 && d->cout <= 32) return strip_launch<T, 1, 1, 4, 3>(d, x, dz, dz_ld, dw, target_wgs, st);
     if (d->cin <= 32) return strip_launch<T, 1, 2, 2, 5>(d, x, dz, dz_ld, dw, target_wgs, st);
     if (d->cout <= 32) return strip_launch<T, 2, 1, 2, 5>(d, x, dz, dz_ld, dw, target_wgs, st);
-    if (g_strip_ntw == 5) return strip_launch<T, 2, 2, 1, 5>(d, x, dz, dz_ld, dw, target_wgs, st);
-    if (g_strip_ntw == 4) return strip_launch<T, 2, 2, 1, 4>(d, x, dz, dz_ld, dw, target_wgs, st);
+    const int ntw = gvlp::wgrad_strip_taps();                     // (5 unless a tool asked for 4 or 9)
+    if (ntw == 5) return strip_launch<T, 2, 2, 1, 5>(d, x, dz, dz_ld, dw, target_wgs, st);
+    if (ntw == 4) return strip_launch<T, 2, 2, 1, 4>(d, x, dz, dz_ld, dw, target_wgs, st);
     return strip_launch<T, 2, 2, 1, 9>(d, x, dz, dz_ld, dw, target_wgs, st);
 }
 
@@ -1532,83 +1527,75 @@ int strip_deep_t(const gv_conv_desc* d, const unsigned short* x, const unsigned 
     return strip_launch<T, 1, 2, 2, 5, 16>(d, x, dz, dz_ld, dw, target_wgs, st);
 }
 
-int g_strip_default = 1;
+// the tap-per-workgroup tiles: sides of 64 * ti and 64 * to channels, ~target workgroups of at least 512 pixels
+template <typename T>
+int tiles_launch(const gv_conv_desc* d, const unsigned short* x, const unsigned short* dz, int dz_ld, const GvDw& dw,
+                 int ti, int to, int target, hipStream_t st) {
+    const int tiles = d->kh * d->kw * ((d->cin + 64 * ti - 1) / (64 * ti)) * ((d->cout + 64 * to - 1) / (64 * to));
+    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
+    const GvSlices p = gv_dw_plan(dw, elems, (int64_t)d->nb * d->oh * d->ow, tiles, target, 512, 32, 65535);
+    const dim3 grid((unsigned)(tiles * p.splits));
+    const GvDw sink = gv_dw_sink(dw, elems, p.splits);
+    int rc = GV_E_BADARG;
+#define GV_WGRAD_LP(TI, TO) \
+    case TI * 10 + TO: rc = gv_wgrad_launch<conv_wgrad_lp<T, TI, TO>>(grid, d, x, dz, dz_ld, p.per, sink, st); break
+    switch (ti * 10 + to) {
+        GV_WGRAD_LP(1, 1); GV_WGRAD_LP(1, 2); GV_WGRAD_LP(1, 3);
+        GV_WGRAD_LP(2, 1); GV_WGRAD_LP(2, 2); GV_WGRAD_LP(2, 3);
+        GV_WGRAD_LP(3, 1); GV_WGRAD_LP(3, 2); GV_WGRAD_LP(3, 3);
+    }
+#undef GV_WGRAD_LP
+    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
+}
+
+// workgroup targets of the families' configurations, by local index
+constexpr int kTileTargets[] = {1024, 2048, 4096};               // x 9 sides: local = 9 * (index here) + 3 * (to - 1) + (ti - 1)
+constexpr int kStripTargets[] = {1024, 2048, 4096};
+constexpr int kDeepTargets[] = {512, 768, 1024, 2048, 4096};
+static_assert(9 * sizeof(kTileTargets) / sizeof(int) == gvlp::wgrad_family_count(gvlp::WGRAD_TILES) &&
+                  sizeof(kStripTargets) / sizeof(int) == gvlp::wgrad_family_count(gvlp::WGRAD_STRIPS) &&
+                  sizeof(kDeepTargets) / sizeof(int) == gvlp::wgrad_family_count(gvlp::WGRAD_DEEP),
+              "lowp.h: the families' counts");
 
 template <typename T>
 int wgrad_t(const gv_conv_desc* d, const unsigned short* x, const unsigned short* dz, int dz_ld, const GvDw& dw,
             hipStream_t st) {
-    const int64_t M = (int64_t)d->nb * d->oh * d->ow;
-    // side width 64 / 128 / 192 channels (TI, TO = 1..3): the widest that pads no more channels than 64-wide tiles
-    // would (a 192-wide side triples the flop/byte of this L2->LDS bound kernel on the many 192-channel layers)
+    if (d->tile_cfg > gvlp::wgrad_num_cfgs()) return GV_E_BADARG;
+    const gvlp::WgradRef c = gvlp::wgrad_lookup(d->tile_cfg);
+    switch (c.fam) {
+        case gvlp::WGRAD_TILES:
+            return tiles_launch<T>(d, x, dz, dz_ld, dw, 1 + c.local % 3, 1 + c.local % 9 / 3, kTileTargets[c.local / 9], st);
+        case gvlp::WGRAD_STRIPS: return strip_t<T>(d, x, dz, dz_ld, dw, kStripTargets[c.local], st);
+        case gvlp::WGRAD_DMA: return gvlp::conv_wgrad_dma_launch(d, x, dz, dz_ld, dw, c.local, st);
+        case gvlp::WGRAD_DEEP: {                                 // layers the deep form declines: the 32-pixel strips
+            const int rc = strip_deep_t<T>(d, x, dz, dz_ld, dw, kDeepTargets[c.local], st);
+            return rc != GV_E_UNSUPPORTED ? rc : strip_t<T>(d, x, dz, dz_ld, dw, kDeepTargets[c.local], st);
+        }
+        case gvlp::WGRAD_NONE: break;
+    }
+    // tile_cfg 0 (and below): the first of these that takes the layer
+    // 1. the strip form for the few-channel stem layers (2.5-3.5x there); its general 64x64x9-tap variant runs at one wave per
+    //    SIMD and loses to the tap-per-workgroup tiles — autotune may still pick it
+    if (d->tile_cfg == 0 && d->cin <= 32) {
+        const int rc = strip_t<T>(d, x, dz, dz_ld, dw, 2048, st);
+        if (rc != GV_E_UNSUPPORTED) return rc;
+    }
+    // 2. the two-stage LDS-DMA form (fastest on 64 of Inception-v3's 67 layers), 128-channel sides where the layer has them,
+    //    ~2048 workgroups
+    if (d->tile_cfg == 0) {
+        const int k = gvlp::wgrad_dma_find(d->cin >= 128 ? 2 : 1, d->cout >= 128 ? 2 : 1, 2, 32, 2048);
+        const int rc = k < 0 ? GV_E_UNSUPPORTED : gvlp::conv_wgrad_dma_launch(d, x, dz, dz_ld, dw, k, st);   // (no such row: the tiles)
+        if (rc != GV_E_UNSUPPORTED) return rc;
+    }
+    // 3. the tiles, sides 64 / 128 / 192 channels wide: the widest that pads no more channels than 64-wide tiles would (a
+    //    192-wide side triples the flop/byte of this L2->LDS bound kernel on the many 192-channel layers)
     auto side = [](int c) {
         const int base = (c + 63) / 64 * 64;
         if ((c + 191) / 192 * 192 == base) return 3;
         if ((c + 127) / 128 * 128 == base) return 2;
         return 1;
     };
-    int ti = side(d->cin), to = side(d->cout);
-    int64_t target = 2048;
-    if (d->tile_cfg > 30 + gvlp::wgrad_dma_num_cfgs() + 5) return GV_E_BADARG;
-    if (d->tile_cfg > 30 + gvlp::wgrad_dma_num_cfgs()) {         // 92..96: the deep strip form, 512 ... 4096 workgroups
-        const int tws[5] = {512, 768, 1024, 2048, 4096};
-        const int tw = tws[d->tile_cfg - 31 - gvlp::wgrad_dma_num_cfgs()];
-        const int rc = strip_deep_t<T>(d, x, dz, dz_ld, dw, tw, st);
-        return rc != GV_E_UNSUPPORTED ? rc : strip_t<T>(d, x, dz, dz_ld, dw, tw, st);   // (other layers: the 32-pixel strips)
-    }
-    if (d->tile_cfg > 30)                                        // 31..91: LDS-DMA staging (wgrad_dma.hip)
-        return gvlp::conv_wgrad_dma_launch(d, x, dz, dz_ld, dw, d->tile_cfg - 31, st);
-    if (d->tile_cfg > 27) {                                      // 28..30: strip form, 1024 / 2048 / 4096 workgroups
-        return strip_t<T>(d, x, dz, dz_ld, dw, 1024 << (d->tile_cfg - 28), st);
-    }
-    // heuristic: the strip form for the few-channel stem layers (2.5-3.5x there); its general 64x64x9-tap variant
-    // runs at one wave per SIMD and loses to the tap-per-workgroup tiles — autotune may still pick it (cfg 13-15)
-    if (d->tile_cfg == 0 && g_strip_default && d->cin <= 32) {
-        const int rc = strip_t<T>(d, x, dz, dz_ld, dw, 2048, st);
-        if (rc != GV_E_UNSUPPORTED) return rc;
-    }
-    if (d->tile_cfg == 0) {
-        // un-tuned default: the two-stage LDS-DMA form (fastest on 64 of Inception-v3's 67 layers), 128-channel sides
-        // where the layer has them, ~2048 workgroups; the tap-per-workgroup tiles below where it does not take the layer
-        const int shape = (d->cin >= 128 ? 1 : 0) + (d->cout >= 128 ? 2 : 0);
-        const int rc = gvlp::conv_wgrad_dma_launch(d, x, dz, dz_ld, dw, 12 + 4 + shape, st);
-        if (rc != GV_E_UNSUPPORTED) return rc;
-    }
-    if (d->tile_cfg > 0) {                                       // 1..27: tile (TI, TO) in {1,2,3}^2 x workgroup target
-        const int k = d->tile_cfg - 1;
-        ti = 1 + (k % 9) % 3;
-        to = 1 + (k % 9) / 3;
-        target = 1024 << (k / 9);
-    }
-    const int tiles = d->kh * d->kw * ((d->cin + 64 * ti - 1) / (64 * ti)) * ((d->cout + 64 * to - 1) / (64 * to));
-    int64_t splits = (target + tiles - 1) / tiles;
-    const int64_t max_splits = (M + 511) / 512;                  // at least 512 pixels per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    splits = gv_dw_clamp(dw, elems, splits);
-    int64_t per = (M + splits - 1) / splits;
-    per = (per + 31) / 32 * 32;
-    splits = (M + per - 1) / per;
-    const dim3 grid((unsigned)(tiles * splits));
-    const GvDw sink = gv_dw_sink(dw, elems, splits);
-#define GV_WGRAD_LP(TI, TO)                                                                                          \
-    hipLaunchKernelGGL((conv_wgrad_lp<T, TI, TO>), grid, dim3(256), 0, st, x, d->x_ld, dz, dz_ld, d->nb, d->ih, d->iw, \
-                       d->cin, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, M, per, sink)
-    switch (ti * 10 + to) {
-        case 11: GV_WGRAD_LP(1, 1); break;
-        case 12: GV_WGRAD_LP(1, 2); break;
-        case 13: GV_WGRAD_LP(1, 3); break;
-        case 21: GV_WGRAD_LP(2, 1); break;
-        case 22: GV_WGRAD_LP(2, 2); break;
-        case 23: GV_WGRAD_LP(2, 3); break;
-        case 31: GV_WGRAD_LP(3, 1); break;
-        case 32: GV_WGRAD_LP(3, 2); break;
-        default: GV_WGRAD_LP(3, 3); break;
-    }
-#undef GV_WGRAD_LP
-    GV_LAUNCH_CHECK();
-    return gv_dw_finish(dw, elems, splits, st);
+    return tiles_launch<T>(d, x, dz, dz_ld, dw, side(d->cin), side(d->cout), 2048, st);
 }
 
 
@@ -1769,6 +1756,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem_rows_lp(const unsigned sh
     }
 }
 
+// (above 64 KB of LDS — the wide form's dZ rows — gv_launch raises the kernel's limit first)
+template <auto Kernel>
+int stem_launch(int64_t nwg, size_t lds, const gv_conv_desc* d, const unsigned short* x, const unsigned short* dz, int dz_ld,
+                int xrow_b, int zrows, int64_t per, const GvDw& sink, hipStream_t st) {
+    return gv_launch<Kernel>(dim3((unsigned)nwg), dim3(256), lds, st, x, dz, dz_ld, d->nb, d->ih, d->iw, d->cin, d->kh, d->kw,
+                             d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, xrow_b, zrows, (int)per, sink);
+}
+
 // the stems this kernel takes: 3 input channels stored densely (x_ld == cin), stride 2, <= 64 output channels, rows that
 // fit the per-lane staging registers; 0 on success, GV_E_UNSUPPORTED otherwise
 template <typename T>
@@ -1796,7 +1791,6 @@ int wgrad_stem_rows(const gv_conv_desc* d, const unsigned short* x, const unsign
     const size_t red_b = (size_t)4 * nrt * nct * 1024 * 4;
     if (red_b > lds) lds = red_b;
     if (lds > (wide ? 160 : 64) * 1024) return GV_E_UNSUPPORTED;
-    if (wide && !GV_BIG_LDS_OK((conv_wgrad_stem_rows_lp<T, 5, 2, 14>), 160 * 1024)) return GV_E_UNSUPPORTED;
     const int64_t units = (int64_t)d->nb * d->oh;
     int64_t waves = 256 * (wide ? 1 : 3) * 4;                      // three workgroups per CU (the wide form: one)
     int64_t per = (units + waves - 1) / waves;
@@ -1809,26 +1803,16 @@ int wgrad_stem_rows(const gv_conv_desc* d, const unsigned short* x, const unsign
         nwg = ((units + per - 1) / per + 3) / 4;
     }
     const GvDw sink = gv_dw_sink(dw, elems, nwg);
-#define GV_WSTEM(NRT, NCT)                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_stem_rows_lp<T, NRT, NCT>), dim3((unsigned)nwg), dim3(256), lds, st, x, dz, dz_ld,     \
-                       d->nb, d->ih, d->iw, d->cin, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout,   \
-                       xrow_b, zrows, (int)per, sink)
-    if (wide)
-        hipLaunchKernelGGL((conv_wgrad_stem_rows_lp<T, 5, 2, 14>), dim3((unsigned)nwg), dim3(256), lds, st, x, dz, dz_ld, d->nb,
-                           d->ih, d->iw, d->cin, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, d->cout, xrow_b, zrows,
-                           (int)per, sink);
-    else if (nrt == 1 && nct == 1) GV_WSTEM(1, 1);
-    else if (nrt == 1) GV_WSTEM(1, 2);
-    else if (nct == 1) GV_WSTEM(5, 1);
-    else GV_WSTEM(5, 2);
-#undef GV_WSTEM
-    GV_LAUNCH_CHECK();
-    return gv_dw_finish(dw, elems, nwg, st);
+    const auto launch = wide                   ? stem_launch<conv_wgrad_stem_rows_lp<T, 5, 2, 14>>
+                        : nrt == 1 && nct == 1 ? stem_launch<conv_wgrad_stem_rows_lp<T, 1, 1>>
+                        : nrt == 1             ? stem_launch<conv_wgrad_stem_rows_lp<T, 1, 2>>
+                        : nct == 1             ? stem_launch<conv_wgrad_stem_rows_lp<T, 5, 1>>
+                                               : stem_launch<conv_wgrad_stem_rows_lp<T, 5, 2>>;
+    const int rc = launch(nwg, lds, d, x, dz, dz_ld, xrow_b, zrows, per, sink, st);
+    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, nwg, st);
 }
 
 }  // namespace
-
-extern "C" void gv_conv2d_wgrad_set_strip_taps(int n) { g_strip_ntw = n; }
 
 namespace gvlp {
 

@@ -270,118 +270,81 @@ int launch_wgrad_dma(const gv_conv_desc* d, const void* x, const void* dz, int d
     g.magic_ow = wmagic(d->ow);
     g.magic_oh = wmagic(d->oh);
     const int tiles = d->kh * d->kw * ((d->cin + BI - 1) / BI) * ((d->cout + BO - 1) / BO);
-    int64_t splits = (target + tiles - 1) / tiles;
-    const int64_t max_splits = (M + 511) / 512;                  // at least 512 pixels per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
     const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    splits = gv_dw_clamp(dw, elems, splits);
-    int64_t per = (M + splits - 1) / splits;
-    per = (per + PT - 1) / PT * PT;
-    splits = (M + per - 1) / per;
-    if ((int64_t)tiles * splits > 0x7fffffff) return GV_E_UNSUPPORTED;
-    g.m_per_block = (int)per;
-    g.dw = gv_dw_sink(dw, elems, splits);
-    const size_t lds = (size_t)ST * PT * 2 * (BI + BO);
-    auto kern = &conv_wgrad_dma<T, TI, TO, ST, PT>;
-    if (lds > 64 * 1024) {
-        if (!GV_BIG_LDS_OK(kern, 160 * 1024)) return GV_E_UNSUPPORTED;      // (per device)
+    // at least 512 pixels per workgroup, whole stages; no cap on the slices: the grid's size is checked instead
+    const GvSlices p = gv_dw_plan(dw, elems, M, tiles, target, 512, PT, 0);
+    if ((int64_t)tiles * p.splits > 0x7fffffff) return GV_E_UNSUPPORTED;
+    g.m_per_block = (int)p.per;
+    g.dw = gv_dw_sink(dw, elems, p.splits);
+    const int rc = gv_launch<conv_wgrad_dma<T, TI, TO, ST, PT>>(dim3((unsigned)(tiles * p.splits)), dim3(256),
+                                                               (size_t)ST * PT * 2 * (BI + BO), st, g);
+    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
+}
+
+// The configurations, in index order: sides of 64 * ti x 64 * to channels, a ring of `st` stages of `pt` pixels, a target
+// of `wgs` workgroups.  Rows are appended, never reordered (lowp.h: the table of families).
+struct DmaCfg { int ti, to, st, pt, wgs; };
+constexpr DmaCfg kDmaCfgs[] = {
+    // 0..11: four stages (16 - 64 KB of LDS: two to four workgroups per CU), 64- and 128-channel sides
+    {1, 1, 4, 32, 1024}, {2, 1, 4, 32, 1024}, {1, 2, 4, 32, 1024}, {2, 2, 4, 32, 1024},
+    {1, 1, 4, 32, 2048}, {2, 1, 4, 32, 2048}, {1, 2, 4, 32, 2048}, {2, 2, 4, 32, 2048},
+    {1, 1, 4, 32, 4096}, {2, 1, 4, 32, 4096}, {1, 2, 4, 32, 4096}, {2, 2, 4, 32, 4096},
+    // 12..23: the same on two stages (8 - 32 KB: five and more per CU — as in the forward kernels a resident neighbour
+    // covers a workgroup's barriers and its atomic epilogue better than ring depth does)
+    {1, 1, 2, 32, 1024}, {2, 1, 2, 32, 1024}, {1, 2, 2, 32, 1024}, {2, 2, 2, 32, 1024},
+    {1, 1, 2, 32, 2048}, {2, 1, 2, 32, 2048}, {1, 2, 2, 32, 2048}, {2, 2, 2, 32, 2048},
+    {1, 1, 2, 32, 4096}, {2, 1, 2, 32, 4096}, {1, 2, 2, 32, 4096}, {2, 2, 2, 32, 4096},
+    // 24..33: 192-channel sides on two stages.  A 192-channel side on 128-wide tiles is one full and one half-empty tile:
+    // a 192 x 192 layer (Mixed_6e's 1x7 / 7x1 pairs, Mixed_7a) did 16/9 of its work, loads and instructions included.
+    {3, 3, 2, 32, 1024}, {3, 1, 2, 32, 1024}, {1, 3, 2, 32, 1024}, {3, 2, 2, 32, 1024}, {2, 3, 2, 32, 1024},
+    {3, 3, 2, 32, 2048}, {3, 1, 2, 32, 2048}, {1, 3, 2, 32, 2048}, {3, 2, 2, 32, 2048}, {2, 3, 2, 32, 2048},
+    // 34..42: every two-stage tile at 512 workgroups.  With the slices STORED and reduced (gv_conv2d_wgrad_ws) every
+    // workgroup writes its whole fp32 tile and the reduce reads it back: on the 12 x 12 maps (7 tiles of 192 x 192 x 4 B
+    // over ~100 slices) that traffic is 2.6x the operands'.
+    {1, 1, 2, 32, 512}, {2, 1, 2, 32, 512}, {1, 2, 2, 32, 512}, {2, 2, 2, 32, 512}, {3, 3, 2, 32, 512},
+    {3, 1, 2, 32, 512}, {1, 3, 2, 32, 512}, {3, 2, 2, 32, 512}, {2, 3, 2, 32, 512},
+    // 43..60: the same nine tiles with 64 pixels per stage (half the barriers per MFMA, twice the LDS per stage)
+    {1, 1, 2, 64, 1024}, {2, 1, 2, 64, 1024}, {1, 2, 2, 64, 1024}, {2, 2, 2, 64, 1024}, {3, 3, 2, 64, 1024},
+    {3, 1, 2, 64, 1024}, {1, 3, 2, 64, 1024}, {3, 2, 2, 64, 1024}, {2, 3, 2, 64, 1024},
+    {1, 1, 2, 64, 2048}, {2, 1, 2, 64, 2048}, {1, 2, 2, 64, 2048}, {2, 2, 2, 64, 2048}, {3, 3, 2, 64, 2048},
+    {3, 1, 2, 64, 2048}, {1, 3, 2, 64, 2048}, {3, 2, 2, 64, 2048}, {2, 3, 2, 64, 2048},
+};
+constexpr int kNumDmaCfgs = (int)(sizeof(kDmaCfgs) / sizeof(kDmaCfgs[0]));
+static_assert(kNumDmaCfgs == gvlp::wgrad_family_count(gvlp::WGRAD_DMA), "lowp.h: the LDS-DMA family's count");
+
+constexpr int dma_key(int ti, int to, int st, int pt) { return ((ti * 4 + to) * 8 + st) * 128 + pt; }
+
+// the 22 instantiations the table names
+template <typename T>
+int launch_dma_cfg(const DmaCfg& c, const gv_conv_desc* d, const void* x, const void* dz, int dz_ld, const GvDw& dw, hipStream_t st) {
+#define GV_WD(TI, TO, ST, PT) \
+    case dma_key(TI, TO, ST, PT): return launch_wgrad_dma<T, TI, TO, ST, PT>(d, x, dz, dz_ld, dw, c.wgs, st)
+    switch (dma_key(c.ti, c.to, c.st, c.pt)) {
+        GV_WD(1, 1, 4, 32); GV_WD(2, 1, 4, 32); GV_WD(1, 2, 4, 32); GV_WD(2, 2, 4, 32);
+        GV_WD(1, 1, 2, 32); GV_WD(2, 1, 2, 32); GV_WD(1, 2, 2, 32); GV_WD(2, 2, 2, 32); GV_WD(3, 3, 2, 32);
+        GV_WD(3, 1, 2, 32); GV_WD(1, 3, 2, 32); GV_WD(3, 2, 2, 32); GV_WD(2, 3, 2, 32);
+        GV_WD(1, 1, 2, 64); GV_WD(2, 1, 2, 64); GV_WD(1, 2, 2, 64); GV_WD(2, 2, 2, 64); GV_WD(3, 3, 2, 64);
+        GV_WD(3, 1, 2, 64); GV_WD(1, 3, 2, 64); GV_WD(3, 2, 2, 64); GV_WD(2, 3, 2, 64);
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * splits)), dim3(256), lds, st, g);
-    GV_LAUNCH_CHECK();
-    return gv_dw_finish(dw, elems, splits, st);
+#undef GV_WD
+    return GV_E_UNSUPPORTED;
 }
 
 }  // namespace
 
 namespace gvlp {
 
-// k = 0..11: (TI, TO) in {1,2}^2 x workgroup target 1024 / 2048 / 4096 on a four-stage ring (16 - 64 KB: two to four
-// workgroups per CU); k = 12..23: the same on TWO stages (8 - 32 KB: five and more per CU — as in the forward kernels a
-// resident neighbour covers a workgroup's barriers and its atomic epilogue better than ring depth does)
-// k = 24..33 (round 3): 192-channel sides on two stages — (TI, TO) = (3,3), (3,1), (1,3), (3,2), (2,3) at 1024 then 2048
-// workgroups.  A 192-channel side on 128-wide tiles is one full and one half-empty tile: a 192 x 192 layer (Mixed_6e's
-// 1x7 / 7x1 pairs, Mixed_7a) did 16/9 of its work, loads and instructions included.
-// k = 34..42 (round 4): the two-stage tiles (TI, TO) in {1,2}^2 and the 192-channel tiles at a target of 512 workgroups.  With
-// the slices STORED and reduced (gv_conv2d_wgrad_ws) every workgroup writes its whole fp32 tile and the reduce reads it
-// back: on the 12 x 12 maps (7 tiles of 192 x 192 x 4 B over ~100 slices) that traffic is 2.6x the operands'.
-// k = 43..60 (round 4): 64 pixels per stage, two stages — (TI, TO) as q above — at 1024 then 2048 workgroups.
-int wgrad_dma_num_cfgs() { return 61; }
-
 int conv_wgrad_dma_launch(const gv_conv_desc* d, const void* x, const void* dz, int dz_ld, const GvDw& dw, int k, hipStream_t st) {
-    if (k < 0 || k >= 61) return GV_E_BADARG;
-    if (k >= 43) {
-        const int q = (k - 43) % 9;
-        const int64_t t6 = k - 43 < 9 ? 1024 : 2048;
-#define GV_WD6(T)                                                                                       \
-    switch (q) {                                                                                        \
-        case 0: return launch_wgrad_dma<T, 1, 1, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 1: return launch_wgrad_dma<T, 2, 1, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 2: return launch_wgrad_dma<T, 1, 2, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 3: return launch_wgrad_dma<T, 2, 2, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 4: return launch_wgrad_dma<T, 3, 3, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 5: return launch_wgrad_dma<T, 3, 1, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 6: return launch_wgrad_dma<T, 1, 3, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        case 7: return launch_wgrad_dma<T, 3, 2, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                   \
-        default: return launch_wgrad_dma<T, 2, 3, 2, 64>(d, x, dz, dz_ld, dw, t6, st);                  \
+    if (k < 0 || k >= kNumDmaCfgs) return GV_E_BADARG;
+    GV_LP_DISPATCH(d->dtype, return launch_dma_cfg<T>(kDmaCfgs[k], d, x, dz, dz_ld, dw, st));
+}
+
+int wgrad_dma_find(int ti, int to, int stages, int stage_pixels, int target_wgs) {
+    for (int k = 0; k < kNumDmaCfgs; ++k) {
+        const DmaCfg& c = kDmaCfgs[k];
+        if (c.ti == ti && c.to == to && c.st == stages && c.pt == stage_pixels && c.wgs == target_wgs) return k;
     }
-        if (d->dtype == GV_BF16) { GV_WD6(__bf16) }
-        if (d->dtype == GV_F16) { GV_WD6(_Float16) }
-#undef GV_WD6
-        return GV_E_UNSUPPORTED;
-    }
-    if (k >= 34) {
-        const int q = k - 34;
-#define GV_WD5(T)                                                                                       \
-    switch (q) {                                                                                        \
-        case 0: return launch_wgrad_dma<T, 1, 1, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 1: return launch_wgrad_dma<T, 2, 1, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 2: return launch_wgrad_dma<T, 1, 2, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 3: return launch_wgrad_dma<T, 2, 2, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 4: return launch_wgrad_dma<T, 3, 3, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 5: return launch_wgrad_dma<T, 3, 1, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 6: return launch_wgrad_dma<T, 1, 3, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        case 7: return launch_wgrad_dma<T, 3, 2, 2>(d, x, dz, dz_ld, dw, 512, st);                      \
-        default: return launch_wgrad_dma<T, 2, 3, 2>(d, x, dz, dz_ld, dw, 512, st);                     \
-    }
-        if (d->dtype == GV_BF16) { GV_WD5(__bf16) }
-        if (d->dtype == GV_F16) { GV_WD5(_Float16) }
-#undef GV_WD5
-        return GV_E_UNSUPPORTED;
-    }
-    if (k >= 24) {
-        const int q = (k - 24) % 5;
-        const int64_t t3 = k - 24 < 5 ? 1024 : 2048;
-#define GV_WD3(T)                                                                                       \
-    switch (q) {                                                                                        \
-        case 0: return launch_wgrad_dma<T, 3, 3, 2>(d, x, dz, dz_ld, dw, t3, st);                       \
-        case 1: return launch_wgrad_dma<T, 3, 1, 2>(d, x, dz, dz_ld, dw, t3, st);                       \
-        case 2: return launch_wgrad_dma<T, 1, 3, 2>(d, x, dz, dz_ld, dw, t3, st);                       \
-        case 3: return launch_wgrad_dma<T, 3, 2, 2>(d, x, dz, dz_ld, dw, t3, st);                       \
-        default: return launch_wgrad_dma<T, 2, 3, 2>(d, x, dz, dz_ld, dw, t3, st);                      \
-    }
-        if (d->dtype == GV_BF16) { GV_WD3(__bf16) }
-        if (d->dtype == GV_F16) { GV_WD3(_Float16) }
-#undef GV_WD3
-        return GV_E_UNSUPPORTED;
-    }
-    const int shape = k % 4 + (k >= 12 ? 4 : 0);
-    const int64_t target = 1024ll << ((k % 12) / 4);
-#define GV_WD(T)                                                                                        \
-    switch (shape) {                                                                                    \
-        case 0: return launch_wgrad_dma<T, 1, 1, 4>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 1: return launch_wgrad_dma<T, 2, 1, 4>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 2: return launch_wgrad_dma<T, 1, 2, 4>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 3: return launch_wgrad_dma<T, 2, 2, 4>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 4: return launch_wgrad_dma<T, 1, 1, 2>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 5: return launch_wgrad_dma<T, 2, 1, 2>(d, x, dz, dz_ld, dw, target, st);                   \
-        case 6: return launch_wgrad_dma<T, 1, 2, 2>(d, x, dz, dz_ld, dw, target, st);                   \
-        default: return launch_wgrad_dma<T, 2, 2, 2>(d, x, dz, dz_ld, dw, target, st);                  \
-    }
-    if (d->dtype == GV_BF16) { GV_WD(__bf16) }
-    if (d->dtype == GV_F16) { GV_WD(_Float16) }
-#undef GV_WD
-    return GV_E_UNSUPPORTED;
+    return -1;
 }
 
 }  // namespace gvlp

@@ -119,6 +119,46 @@ def test_ws_form_matches_autograd_and_is_bitwise_reproducible(dt, k, stride, pad
         assert torch.equal(a, b)
 
 
+# (kernel, stride, padding, cin, cout, nb, ih, iw, tile_cfgs, most configurations the layer may decline): bf16
+SMALL_WS = [
+    # 780 pixels (a ragged last slice) through every configuration.  The tiles and the LDS-DMA family want 512 pixels a
+    # slice: they plan two slices here and the three-image clamp does not bind for them; it does for the strips.
+    ((3, 3), 1, "SAME", 96, 160, 5, 13, 12, list(range(97)), 6),
+    ((3, 3), 1, "VALID", 32, 32, 3, 37, 43, [0, 28, 29, 30, 92, 93, 94, 95, 96], None),   # strips and deep strips
+    # the first layer at 2100 pixels: ceil(2100 / 512) = 5 slices wanted by every tile and LDS-DMA configuration (54 tiles
+    # or fewer against targets of 512 and more), three allowed
+    ((3, 3), 1, "SAME", 96, 160, 5, 21, 20, list(range(97)), 6),
+]
+# (the parent library declines none of these configurations on any of the shapes)
+
+
+@pytest.mark.parametrize("k,stride,padding,cin,cout,nb,ih,iw,cfgs,max_declined", SMALL_WS)
+def test_every_configuration_keeps_to_a_three_image_workspace(k, stride, padding, cin, cout, nb, ih, iw, cfgs, max_declined):
+    """A workspace with room for exactly three images of dW, in front of a fourth image's worth of guard bytes: every
+    configuration still gives the gradient, the same bits twice, and leaves the guard alone.  Where a configuration wants
+    more than three slices (the strips on every shape, every family on the third) this is the planner's clamp at work;
+    where it wants fewer, the test still pins the configuration's result and its bounds."""
+    dt = _lib.GV_BF16
+    xd, dzd, ref, geo = case(dt, k, stride, padding, cin, cout, nb, ih, iw, seed=cin + cout)
+    image = k[0] * k[1] * cin * cout * 4                    # (a whole number of 16-byte groups here)
+    buf = torch.full((4 * image,), 0xC3, dtype=torch.uint8, device=DEV)
+    ws, behind = buf[:3 * image], buf[3 * image:]
+    ref = ref.cpu()
+    declined = []
+    for cfg in cfgs:
+        rc, a = run_ws(dt, k, stride, cin, cout, nb, ih, iw, geo, xd, dzd, cfg, ws)
+        if rc == _lib.GV_E_UNSUPPORTED and cfg:
+            declined.append(cfg)                            # (a tile configuration this geometry does not take)
+            continue
+        _lib.check(rc, "wgrad_ws cfg %d, three-image workspace" % cfg)
+        close(a.cpu() - 0.5, ref, 3e-5)
+        rc, b = run_ws(dt, k, stride, cin, cout, nb, ih, iw, geo, xd, dzd, cfg, ws)
+        assert rc == 0 and torch.equal(a, b), "cfg %d: not bitwise reproducible" % cfg
+        assert bool((behind == 0xC3).all()), "cfg %d wrote behind its workspace" % cfg
+    print("declined:", declined)
+    assert max_declined is None or len(declined) <= max_declined, declined
+
+
 def test_ws_form_rejects_bad_workspaces():
     xd, dzd, ref, geo = case(_lib.GV_BF16, (1, 1), 1, "SAME", 32, 32, 2, 8, 8)
     oh, ow, pt, pl = geo
