@@ -36,6 +36,10 @@ GV_RENDER_LAMBERT = 1
 GV_RENDER_OUT_F32_QUANTIZED, GV_RENDER_OUT_F32, GV_RENDER_OUT_U8 = 0, 1, 2
 GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RENDER_TOO_LARGE, GV_RENDER_BAD_OFFSETS = \
     0, 1, 2, 3, 4, 5
+GV_PNG_STATUS = ("OK", "TRUNCATED", "BAD_HEADER", "BAD_BLOCK", "BAD_CODES", "BAD_DISTANCE", "TOO_LONG", "TOO_SHORT",
+                 "BAD_CHECKSUM", "BAD_FILTER", "BAD_PALETTE_INDEX")      # GV_PNG_* of the header, by value
+(GV_PNG_OK, GV_PNG_TRUNCATED, GV_PNG_BAD_HEADER, GV_PNG_BAD_BLOCK, GV_PNG_BAD_CODES, GV_PNG_BAD_DISTANCE, GV_PNG_TOO_LONG,
+ GV_PNG_TOO_SHORT, GV_PNG_BAD_CHECKSUM, GV_PNG_BAD_FILTER, GV_PNG_BAD_PALETTE_INDEX) = range(11)
 GV_ABI_VERSION = 1
 
 
@@ -94,6 +98,11 @@ class RenderShading(C.Structure):
     _fields_ = [("flags", C.c_int32), ("shininess", C.c_int32), ("specular", C.c_float), ("reserved", C.c_int32)]
 
 
+class PngImage(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("length", C.c_int32), ("color_type", C.c_int32), ("palette_offset", C.c_int32),
+                ("palette_len", C.c_int32)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "nb", "ih", "iw", "c", "x_ld", "kh", "kw", "stride", "pad_t", "pad_l",
@@ -127,6 +136,9 @@ SIGNATURES = {
     "gv_view_pool_fuse_fwd_per_shape": (C.c_int, [_P, _I, _I, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _I, _P]),
     "gv_preprocess_views": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gv_png_unfilter": (C.c_int, [_P, _I, _I, _I, _P]),
+    "gv_png_decode_workspace_bytes": (_L, [_I, _L]),
+    "gv_png_decode_batch": (C.c_int, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    "gv_png_decode_host": (C.c_int, [_P, _L, _P, _I, _I, _I, _P, _P, _P]),
     "gv_eval_metrics": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "gv_retr_prepare": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "gv_knn_workspace_bytes": (_L, [_I, _I, _I]),

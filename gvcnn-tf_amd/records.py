@@ -216,6 +216,83 @@ def decode_png(data):
     return np.ascontiguousarray(img[..., :3])
 
 
+def parse_png(data):
+    """The chunk walk of decode_png without the inflate: (w, h, colour type, palette uint8 [k, 3] or None, the zlib stream
+    of the IDAT chunks).  What gv_png_decode_batch / gv_png_decode_host take (pack_png_batch)."""
+    if data[:8] != _PNG_SIG:
+        raise ValueError("not a PNG")
+    pos, idat, plte = 8, [], None
+    w = h = ctype = None
+    while pos < len(data):
+        ln, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + ln]
+        pos += 12 + ln
+        if kind == b"IHDR":
+            w, h, depth, ctype, _, _, interlace = struct.unpack(">IIBBBBB", body)
+            if depth != 8 or interlace:
+                raise ValueError("only 8-bit non-interlaced PNGs are supported")
+        elif kind == b"PLTE":
+            plte = np.frombuffer(body, np.uint8).reshape(-1, 3)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+    if ctype not in (0, 2, 3, 4, 6):
+        raise ValueError("PNG colour type %r" % (ctype,))
+    if ctype == 3 and (plte is None or not len(plte)):
+        raise ValueError("palette PNG without a PLTE chunk")
+    return w, h, ctype, (plte if ctype == 3 else None), b"".join(idat)
+
+
+def png_batch_bytes(pngs):
+    """Size of the byte buffer pack_png_batch fills for these parse_png results."""
+    return sum((len(p[4]) + 15) // 16 * 16 + (0 if p[3] is None else (p[3].size + 15) // 16 * 16) for p in pngs) + 16
+
+
+def pack_png_batch(pngs, buf=None, images=None):
+    """parse_png results of one size -> (buf uint8, images (_lib.PngImage * n), (h0, w0)): every zlib stream at a
+    16-byte boundary of `buf`, a palette behind its image's stream (so `buf` serves as `streams` AND `palettes` of the
+    C entry points), 16 bytes of padding at the end.  buf: a uint8 array of at least png_batch_bytes(pngs) to fill;
+    images: a (_lib.PngImage * n) to fill (the batcher keeps both in page-locked memory)."""
+    from . import _lib
+    w0, h0 = pngs[0][0], pngs[0][1]
+    need = png_batch_bytes(pngs)
+    if buf is None:
+        buf = np.empty(need, np.uint8)
+    if images is None:
+        images = (_lib.PngImage * len(pngs))()
+    pos = 0
+    for i, (w, h, ctype, plte, z) in enumerate(pngs):
+        if (h, w) != (h0, w0):
+            raise ValueError("views of %dx%d and %dx%d (all views of a file share one size)" % (h0, w0, h, w))
+        buf[pos:pos + len(z)] = np.frombuffer(z, np.uint8)
+        images[i].offset, images[i].length, images[i].color_type = pos, len(z), ctype
+        pos += (len(z) + 15) // 16 * 16
+        if plte is not None:
+            images[i].palette_offset, images[i].palette_len = pos, len(plte)
+            buf[pos:pos + plte.size] = plte.reshape(-1)
+            pos += (plte.size + 15) // 16 * 16
+    buf[pos:pos + 16] = 0
+    return buf, images, (h0, w0)
+
+
+def png_status_name(code):
+    from . import _lib
+    return "GV_PNG_" + _lib.GV_PNG_STATUS[code] if 0 <= code < len(_lib.GV_PNG_STATUS) else "status %d" % code
+
+
+def decode_png_batch_host(pngs):
+    """parse_png results of one size -> (uint8 [n, h0, w0, 3], status int32 [n]) through gv_png_decode_host: the
+    serial, host-memory twin of the device decoder (same DEFLATE core)."""
+    from . import _lib
+    buf, images, (h0, w0) = pack_png_batch(pngs)
+    out = np.empty((len(pngs), h0, w0, 3), np.uint8)
+    status = np.empty(len(pngs), np.int32)
+    _lib.check(_lib.load().gv_png_decode_host(buf.ctypes.data, buf.size, images, len(pngs), h0, w0, buf.ctypes.data,
+                                              out.ctypes.data, status.ctypes.data), "gv_png_decode_host")
+    return out, status
+
+
 def encode_png(img):
     """uint8 [h, w, 3] -> PNG bytes (filter 0 on every line)."""
     img = np.ascontiguousarray(img, np.uint8)
@@ -235,6 +312,18 @@ def _decode_record(rec, num_views):
     if len(enc) != num_views:
         raise ValueError("record holds %d views, expected %d" % (len(enc), num_views))
     return np.stack([decode_png(e) for e in enc]), int(ex["image/label"][0])
+
+
+def _parse_record(rec, num_views):
+    """One tf.Example -> ([parse_png(view)] * V, label): the unit of ViewBatcher(decode="device") — chunk walk only."""
+    ex = parse_example(rec)
+    enc = ex["image/encoded"]
+    if len(enc) != num_views:
+        raise ValueError("record holds %d views, expected %d" % (len(enc), num_views))
+    pngs = [parse_png(e) for e in enc]
+    if any(p[:2] != pngs[0][:2] for p in pngs):
+        raise ValueError("all input arrays must have the same shape")
+    return pngs, int(ex["image/label"][0])
 
 
 _SHM_CACHE = {}
@@ -277,12 +366,26 @@ class ViewBatcher:
     The outer GZIP stream is read by this process (it is one serial stream), records are dealt to the pool with a bounded
     window in flight and come back IN ORDER, so batches are identical to the workers = 0 ones.  The pool is a `spawn`
     pool: its processes never inherit an initialised GPU runtime (create the batcher — or at least start iterating —
-    wherever convenient; nothing is forked)."""
+    wherever convenient; nothing is forked).
+
+    decode: "host" (default) is everything above.  "device": the PNGs are decoded by the GPU (gv_png_decode_batch:
+    inflate, un-filter, expand).  The consumer thread only parses each record (parse_example + parse_png, no inflate), no
+    decoder processes are started — `workers` then only switches the GZIP reader threads on — and the shuffle buffer
+    holds the parsed (still compressed) records.  A batch is packed into one of two alternating page-locked byte buffers,
+    uploaded with one asynchronous copy, decoded, and handed to the same gv_preprocess_views launch; the random draws
+    are made in the host path's order, so a seed gives identical batches in both modes.  The per-view decode status comes
+    back through an asynchronous copy and is looked at when the NEXT batch is assembled and at the end of the iteration:
+    a corrupt PNG raises ValueError (naming the record, the view and the GV_PNG_* status) at most one batch late.  On a
+    CPU `device` (tests) the same packing goes through gv_png_decode_host and raises at once."""
 
     def __init__(self, path, num_views, height, width, batch_size, device, augment=False, seed=0, shuffle_buffer=0,
-                 remainder="warn", workers=0):
+                 remainder="warn", workers=0, decode="host"):
         if remainder not in ("warn", "pad", "error"):
             raise ValueError("remainder must be 'warn', 'pad' or 'error'")
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device'")
+        self.decode = decode
+        self._pending = None
         self.path, self.V, self.H, self.W, self.N = path, num_views, height, width, batch_size
         self.device, self.augment = device, augment
         self.rng = np.random.RandomState(seed)
@@ -428,10 +531,25 @@ class ViewBatcher:
                 except Exception:
                     pass
 
+    def _parsed(self):
+        """decode="device": ((parsed views, record index), label) per record in _records() order."""
+        for k, rec in enumerate(self._records()):
+            pngs, label = _parse_record(rec, self.V)
+            yield (pngs, k), label
+
     def _shapes(self, zero_copy=False):
         """(views uint8 [V, h0, w0, 3], label) per record, through the shuffle buffer."""
+        if self.decode == "device":                                # (record by record: what tests and tools look at)
+            for item, label in self._shuffled(self._parsed()):
+                src = self._decode_items([item])
+                self._check_pending()
+                yield src.cpu().numpy(), label
+            return
+        yield from self._shuffled(self._decoded(zero_copy))
+
+    def _shuffled(self, items):
         buf = []
-        for item in self._decoded(zero_copy):
+        for item in items:
             if self.shuffle_buffer <= 0:
                 yield item
             elif len(buf) < self.shuffle_buffer:
@@ -480,6 +598,86 @@ class ViewBatcher:
             self._pin_k ^= 1
         else:
             src = torch.from_numpy(np.stack(imgs)).to(self.device)       # [N, V, h0, w0, 3] uint8
+        return self._preprocess(src, h0, w0, labels)
+
+    def _check_pending(self):
+        """Raises for the views of the last decoded batch whose status is not GV_PNG_OK (waits for that batch's copy)."""
+        pending, self._pending = self._pending, None
+        if pending is None:
+            return
+        ev, status, names = pending
+        if ev is not None:
+            ev.synchronize()
+        status = np.asarray(status if isinstance(status, np.ndarray) else status.numpy())
+        bad = np.flatnonzero(status[:len(names)])
+        if len(bad):
+            raise ValueError("corrupt PNG: " + "; ".join("record %d view %d: %s" % (names[i] + (png_status_name(int(status[i])),))
+                                                         for i in bad[:8]))
+
+    def _decode_items(self, items):
+        """[(parsed views, record index)] -> uint8 [len(items) * V, h0, w0, 3] on the device; leaves the status in
+        self._pending (_check_pending)."""
+        import torch
+        from . import _lib
+        pngs = [p for views, _ in items for p in views]
+        names = [(k, v) for views, k in items for v in range(len(views))]
+        n, (w0, h0) = len(pngs), pngs[0][:2]
+        for views, _ in items:
+            if views[0][:2] != (w0, h0):
+                raise ValueError("views of %d bytes, the batcher's slots hold %d (all shapes of a file share one size)"
+                                 % (len(views) * views[0][0] * views[0][1] * 3, len(views) * h0 * w0 * 3))
+        self._check_pending()                                      # the previous batch's verdict, at most one batch late
+        if not str(self.device).startswith("cuda"):
+            out, status = decode_png_batch_host(pngs)
+            self._pending = (None, status, names)
+            self._check_pending()
+            return torch.from_numpy(out)
+        lib = _lib.load()
+        table = (n * _lib.C.sizeof(_lib.PngImage) + 15) // 16 * 16
+        need = table + png_batch_bytes(pngs)
+        if getattr(self, "_zpin", None) is None or self._zpin[0].numel() < need or self._zstat[0].numel() < n:
+            cap = need + need // 4
+            for ev in getattr(self, "_zpin_ev", []):
+                if ev is not None:
+                    ev.synchronize()
+            self._zpin = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self._zstat = [torch.empty(n, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._zdev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            self._zpin_ev, self._zpin_k = [None, None], 0
+        k = self._zpin_k
+        # the host may only write into a staging buffer (streams, image table, status) once the work that last used it is done
+        if self._zpin_ev[k] is not None:
+            self._zpin_ev[k].synchronize()
+        stage = self._zpin[k].numpy()
+        images = (_lib.PngImage * n).from_buffer(stage)
+        pack_png_batch(pngs, stage[table:], images)
+        self._zdev[:need].copy_(self._zpin[k][:need], non_blocking=True)
+        ws_bytes = lib.gv_png_decode_workspace_bytes(n, h0 * (1 + 4 * w0))
+        if getattr(self, "_zws", None) is None or self._zws.numel() < ws_bytes:
+            self._zws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        from .model import _st
+        base = self._zdev.data_ptr() + table
+        _lib.check(lib.gv_png_decode_batch(base, need - table, _lib.C.addressof(images), n, h0, w0, base, out.data_ptr(),
+                                           status.data_ptr(), self._zws.data_ptr(), ws_bytes, _st()), "gv_png_decode_batch")
+        self._zstat[k][:n].copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._zpin_ev[k] = ev
+        self._pending = (ev, self._zstat[k], names)
+        self._zpin_k ^= 1
+        return out
+
+    def _batch_device(self, items, labels):
+        src = self._decode_items(items)
+        return self._preprocess(src, src.shape[1], src.shape[2], labels)
+
+    def _preprocess(self, src, h0, w0, labels):
+        import torch
+        from . import _lib
+        from .model import _st
+        nimg = self.N * self.V
         dst = torch.empty((self.N, self.V, self.H, self.W, 3), dtype=torch.float32, device=self.device)
         flip = delta = None
         if self.augment:
@@ -495,11 +693,20 @@ class ViewBatcher:
         import warnings
         imgs, labels = [], []
         self.dropped, self.last_valid = 0, self.N
-        for img, label in self._shapes(zero_copy=True):
+        device = self.decode == "device"                           # imgs then holds parsed records, not pixels
+        source = self._shuffled(self._parsed()) if device else self._shapes(zero_copy=True)
+        make = self._batch_device if device else self._batch
+        yield from self._batches(source, make, imgs, labels)
+        if device:
+            self._check_pending()
+
+    def _batches(self, source, make, imgs, labels):
+        import warnings
+        for img, label in source:
             imgs.append(img)
             labels.append(label)
             if len(imgs) == self.N:
-                yield self._batch(imgs, labels)
+                yield make(imgs, labels)
                 imgs, labels = [], []
         if imgs:
             if self.remainder == "error":
@@ -509,7 +716,7 @@ class ViewBatcher:
                 while len(imgs) < self.N:
                     imgs.append(imgs[self.last_valid - 1])
                     labels.append(-1)
-                yield self._batch(imgs, labels)
+                yield make(imgs, labels)
             else:
                 self.dropped = len(imgs)
                 warnings.warn("ViewBatcher: the last %d shapes of %s do not fill a batch of %d and were dropped"

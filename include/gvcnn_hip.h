@@ -372,6 +372,51 @@ int gv_preprocess_views(const uint8_t* src, int32_t nimg, int32_t h0, int32_t w0
  * specification, bpp bytes per pixel.  Both pointers are host memory; no stream. */
 int gv_png_unfilter(const uint8_t* raw, int32_t h, int32_t rowbytes, int32_t bpp, uint8_t* out);
 
+/* ---- PNG decode of a whole batch (the other half of tf.image.decode_png(channels=3): zlib inflate, un-filter, expand) --
+ * Input: the zlib stream of every image (its IDAT bodies concatenated by the caller, who walks the chunks) in ONE byte
+ * buffer, plus one gv_png_image per image.  8-bit, non-interlaced images that all share one size h0 x w0.
+ * Output: out [n, h0, w0, 3] uint8 (gray replicated to three channels, alpha dropped, palette indices looked up) and
+ * status [n] int32, one GV_PNG_* value per image.  An image whose status is not GV_PNG_OK leaves its own slot of `out`
+ * unspecified and touches nothing else; the other images of the batch are decoded.  Every byte is exact (there is no
+ * tolerance): the stream is checked like zlib checks it (block types, stored lengths, over-subscribed and incomplete
+ * code sets, distances, the Adler-32 trailer; FDICT is rejected, any window size CINFO <= 7 accepted).
+ *
+ * Layout rules (GV_E_BADARG otherwise, checked before any launch): every stream starts at a multiple of 16 bytes,
+ * ends at or before stream_bytes - 16 (the buffer closes with 16 bytes of padding so that wide loads stay inside it);
+ * colour type 0, 2, 3, 4 or 6; a palette image has 1..256 entries; n > 0, h0, w0 > 0, no NULL pointer (palettes may
+ * be NULL when no image has colour type 3).  GV_E_UNSUPPORTED: h0 * (1 + 4 * w0) does not fit 31 bits.
+ *
+ * gv_png_decode_batch: streams, palettes, out, status and ws are DEVICE memory; `images` is HOST memory, checked
+ * during the call and copied into the workspace by an asynchronous copy on `stream` (keep it unchanged until the stream
+ * has passed the call).  ws: gv_png_decode_workspace_bytes(n, h0 * (1 + 4 * w0)) bytes, 16-byte aligned — the
+ * inflated rows of every image, whose already written part is also the DEFLATE window.
+ * gv_png_decode_host: the same decoder run serially on the host, every pointer host memory, no workspace. */
+#define GV_PNG_OK 0
+#define GV_PNG_TRUNCATED 1          /* the stream ends inside a block or inside the trailer */
+#define GV_PNG_BAD_HEADER 2         /* zlib header: method, window size, check bits, or a preset dictionary (FDICT) */
+#define GV_PNG_BAD_BLOCK 3          /* block type 3, or a stored block whose LEN and NLEN do not match */
+#define GV_PNG_BAD_CODES 4          /* over-subscribed / incomplete code set, bad repeat, unused or reserved symbol */
+#define GV_PNG_BAD_DISTANCE 5       /* a match reaches back past the first byte of the output */
+#define GV_PNG_TOO_LONG 6           /* the stream holds more than h0 * (1 + w0 * channels) bytes */
+#define GV_PNG_TOO_SHORT 7          /* ... fewer */
+#define GV_PNG_BAD_CHECKSUM 8       /* Adler-32 trailer */
+#define GV_PNG_BAD_FILTER 9         /* a row's filter byte is above 4 */
+#define GV_PNG_BAD_PALETTE_INDEX 10 /* a pixel's index is past the end of the image's palette */
+typedef struct gv_png_image {
+    int64_t offset;          /* of the zlib stream in `streams`, bytes, a multiple of 16 */
+    int32_t length;          /* of the zlib stream, bytes */
+    int32_t color_type;      /* IHDR colour type: 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA */
+    int32_t palette_offset;  /* colour type 3: of the image's PLTE body (RGB triples) in `palettes`, bytes */
+    int32_t palette_len;     /* colour type 3: entries of that palette, 1..256 */
+} gv_png_image;
+/* negative: an error code (n <= 0, max_raw_bytes <= 0: GV_E_BADARG) */
+int64_t gv_png_decode_workspace_bytes(int32_t n, int64_t max_raw_bytes);
+int gv_png_decode_batch(const uint8_t* streams, int64_t stream_bytes, const gv_png_image* images, int32_t n,
+                        int32_t h0, int32_t w0, const uint8_t* palettes, uint8_t* out, int32_t* status, void* ws,
+                        int64_t ws_bytes, void* stream);
+int gv_png_decode_host(const uint8_t* streams, int64_t stream_bytes, const gv_png_image* images, int32_t n,
+                       int32_t h0, int32_t w0, const uint8_t* palettes, uint8_t* out, int32_t* status);
+
 /* ---- evaluation metrics (eval.py:94-99) ---------------------------------------------------------
  * prediction[n] = argmax_c logits[n,c] (first maximum, like tf.argmax); confusion[label, prediction] += 1
  * (tf.math.confusion_matrix, int32 [C,C], ACCUMULATED so a whole evaluation run needs one buffer);

@@ -2,7 +2,9 @@
 """Can the input pipeline (GZIP TFRecord -> tf.Example -> PNG decode -> resize / normalise) feed the
 kernels?  Synthetic ModelNet-like renders (gray shaded blobs on white, 256x256 PNG with adaptive filters), V views per
 shape; views/s of ViewBatcher end to end (host decode + H2D + gv_preprocess_views on the device) per worker count.
-    python tools/pipeline_bench.py [--shapes 1536] [--files 1 4] [--views 12] [--sizes 224 299] [--workers 0 4 8 16 32 64]"""
+--decode device: the PNGs are decoded by the GPU (gv_png_decode_batch), `workers` > 0 only starts the GZIP reader threads.
+    python tools/pipeline_bench.py [--shapes 1536] [--files 1 4] [--views 12] [--sizes 224 299] [--workers 0 4 8 16 32 64]
+                                   [--decode host device | host:16 device:0] [--repeat 1]"""
 import argparse
 import io
 import os
@@ -34,7 +36,19 @@ def main():
     ap.add_argument("--workers", type=int, nargs="+", default=[0, 4, 8, 16, 32, 64])
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--files", type=int, nargs="+", default=[1, 4], help="split the set into this many record files")
+    ap.add_argument("--decode", nargs="+", default=["host"], metavar="{host,device}[:WORKERS]",
+                    help="where the PNGs are decoded; several: their runs alternate.  host:16 device:0 pins a mode to ONE "
+                         "worker count instead of crossing it with --workers")
+    ap.add_argument("--repeat", type=int, default=1, help="run every configuration this many times (the spread)")
     a = ap.parse_args()
+    runs = []
+    for d in a.decode:
+        mode, _, w = d.partition(":")
+        if mode not in ("host", "device"):
+            ap.error("--decode %s" % d)
+        runs.append([(int(w), mode)] if w else [(k, mode) for k in a.workers])
+    # worker counts outermost, the modes of one count next to each other
+    runs = [r for k in range(max(map(len, runs))) for rr in runs for r in rr[k:k + 1]] * a.repeat
     import torch
     import gvcnn_tf_amd                              # noqa: F401  (same import order as every other entry point)
     from gvcnn_tf_amd import records as R           # (the decoder pools are spawn pools: nothing inherits a GPU context)
@@ -67,8 +81,9 @@ def main():
     dev = "cuda:0" if torch.cuda.is_available() else "cpu"
     for size in a.sizes:
         for nf in a.files:
-            for w in a.workers:
-                vb = R.ViewBatcher(sets[nf] if nf > 1 else sets[nf][0], a.views, size, size, a.batch, dev, augment=True, workers=w)
+            for w, decode in runs:
+                vb = R.ViewBatcher(sets[nf] if nf > 1 else sets[nf][0], a.views, size, size, a.batch, dev, augment=True, workers=w,
+                                   decode=decode)
                 try:
                     n = 0
                     it = iter(vb)
@@ -82,8 +97,8 @@ def main():
                     dt = time.time() - t0
                 finally:
                     vb.close()
-                print("  %dx%d  %d file(s)  workers %2d: %8.0f views/s  (%d views in %.2f s after the second batch)"
-                      % (size, size, nf, w, n / dt, n, dt))
+                print("  %dx%d  %d file(s)  workers %2d  decode %-6s: %8.0f views/s  (%d views in %.2f s after the second batch)"
+                      % (size, size, nf, w, decode, n / dt, n, dt))
 
 
 if __name__ == "__main__":
