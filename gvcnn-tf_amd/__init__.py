@@ -12,14 +12,14 @@ _lib.load()
 
 from . import backbones, params  # noqa: E402
 from . import model  # noqa: E402
-from .model import (AUTO_REUSE, GVCNN, basic, configure, group_fusion, group_scheme, group_weight,  # noqa: E402,F401
-                    grouping_module, gvcnn, gvcnn_fused, view_pooling)
+from .model import (AUTO_REUSE, GVCNN, Explanation, basic, configure, explain_views, group_fusion,  # noqa: E402,F401
+                    group_scheme, group_weight, grouping_module, gvcnn, gvcnn_fused, view_pooling)
 from . import retrieval  # noqa: E402
 from .retrieval import MetricLearner, ShapeIndex  # noqa: E402,F401
 from . import render  # noqa: E402
 from .render import MeshBatch, ViewRenderer, load_obj, load_off, pack_meshes, random_rotations  # noqa: E402,F401
 
 __all__ = ["GVCNN", "gvcnn", "basic", "group_scheme", "group_weight", "view_pooling", "group_fusion",
-           "grouping_module", "gvcnn_fused", "configure", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
+           "grouping_module", "gvcnn_fused", "configure", "explain_views", "Explanation", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
            "ShapeIndex", "MetricLearner", "render", "MeshBatch", "ViewRenderer", "load_off", "load_obj", "pack_meshes",
            "random_rotations"]

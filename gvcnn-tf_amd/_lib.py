@@ -27,6 +27,7 @@ GV_OK, GV_E_BADARG, GV_E_UNSUPPORTED, GV_E_ALIGN, GV_E_PLAN = 0, -1, -2, -3, -4
 GV_VIEWPOOL_MAX, GV_VIEWPOOL_MEAN = 0, 1
 GV_ORDER_SHAPE_MAJOR, GV_ORDER_VIEW_MAJOR = 0, 1
 GV_WEIGHT_COUNT, GV_WEIGHT_MEAN_SCORE = 0, 1
+GV_EXPLAIN_EXACT, GV_EXPLAIN_GRADCAM = 0, 1
 GV_METRIC_L2, GV_METRIC_COSINE = 0, 1
 GV_KNN_MAX_K = 256
 GV_RETR_AP_MAX_NDB = 16384
@@ -134,6 +135,9 @@ SIGNATURES = {
     "gv_view_score_per_shape": (C.c_int, [_P, _I, _P, _P]),
     "gv_group_assign_per_shape": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "gv_view_pool_fuse_fwd_per_shape": (C.c_int, [_P, _I, _I, _L, _L, _L, _P, _I, _P, _I, _F, _P, _P, _I, _P]),
+    "gv_explain_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "gv_explain_views": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _I, _I, _F, _P, _P, _I, _P, _P, _I, _P, _P, _P,
+                                   _P, _P, _P, _I, _P]),
     "gv_preprocess_views": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gv_png_unfilter": (C.c_int, [_P, _I, _I, _I, _P]),
     "gv_png_decode_workspace_bytes": (_L, [_I, _L]),

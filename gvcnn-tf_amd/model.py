@@ -19,6 +19,8 @@ plus the fused, device-resident forms BASELINE.json:north_star asks for:
 Every array that crosses this API is a torch tensor on the HIP device (PyTorch is plumbing:
 device memory + streams).  All arithmetic happens in libgvcnn_hip.so; there is no CPU path.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -181,6 +183,110 @@ def group_fusion(group_descriptors, group_weight):
     eye = torch.eye(G, dtype=torch.int32, device=dev)
     _, S = _pool_fuse(stacked, G, N, E, N * E, E, eye, w, "max", 1.0, False, True)
     return S.reshape(stacked.shape[1:])
+
+
+# ------------------------------------------------------------------------------------------------
+# explain a prediction: which views, and which pixels of them, carry a logit (csrc/explain.hip)
+# ------------------------------------------------------------------------------------------------
+_EXPLAIN_KINDS = {"exact": _lib.GV_EXPLAIN_EXACT, "gradcam": _lib.GV_EXPLAIN_GRADCAM}
+_STORAGE_OF = {torch.float32: _lib.GV_F32, torch.bfloat16: _lib.GV_BF16, torch.float16: _lib.GV_F16}
+
+
+class Explanation(collections.namedtuple(
+        "Explanation", "logits target baseline view_contrib maps scores gidx weight")):
+    """Device tensors: logits [N, num_classes] (None when the caller gave none), target int64 [N] (the class explained),
+    baseline [N], view_contrib [N, V], maps [N, V, h, w], and copies of the forward's scores / gidx / weight ([V], [V],
+    [G]; per shape [N, V], [N, V], [N, G]).  kind='exact': logit[n, target] = baseline[n] + maps[n].sum()."""
+    __slots__ = ()
+
+    def resized(self, height, width):
+        """maps, bilinearly resized to [N, V, height, width] (the input resolution, for an overlay)."""
+        return torch.nn.functional.interpolate(self.maps, size=(int(height), int(width)), mode="bilinear",
+                                               align_corners=False)
+
+
+def _as_targets(target, N, dev):
+    if target is None:
+        return None
+    if torch.is_tensor(target):
+        t = target.to(device=dev, dtype=torch.int64).reshape(-1)
+    else:
+        t = torch.as_tensor(np.asarray(target, dtype=np.int64).reshape(-1)).to(dev)
+    if t.numel() == 1 and N != 1:
+        t = t.expand(N)
+    if t.numel() != N:
+        raise ValueError("target holds %d classes for %d shapes" % (t.numel(), N))
+    return t.contiguous()
+
+
+def _explain_launch(F_ptr, dtype, N, V, h, w, C, view_stride, shape_stride, scheme, weight, per_shape, pool, empty_fill,
+                    cls_kernel, cls_bias, logits, targets, kind, check, dev):
+    """gv_explain_views on raw geometry.  Returns (target, baseline, view_contrib, maps, workspace); the workspace (None
+    for 'exact') starts with alpha [N, V, C]."""
+    lib = _lib.load()
+    if kind not in _EXPLAIN_KINDS:
+        raise ValueError("kind must be 'exact' or 'gradcam', not %r" % (kind,))
+    if logits is None and targets is None:
+        raise ValueError("without logits a target is mandatory")
+    num_classes = cls_kernel.shape[1]
+    f32 = torch.float32
+    maps = torch.empty((N, V, h, w), dtype=f32, device=dev)
+    contrib = torch.empty((N, V), dtype=f32, device=dev)
+    baseline = torch.empty(N, dtype=f32, device=dev)
+    target_out = torch.empty(N, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.gv_explain_workspace_bytes(V, N, C, _EXPLAIN_KINDS[kind])
+    if nbytes < 0:
+        raise _lib.GvError(nbytes, "gv_explain_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=f32, device=dev) if nbytes else None
+    G = scheme.shape[-2]
+    _lib.check(lib.gv_explain_views(F_ptr, V, N, h * w, C, view_stride, shape_stride, scheme.data_ptr(), G,
+                                    weight.data_ptr(), 1 if per_shape else 0, _POOL_MODES[pool], float(empty_fill),
+                                    cls_kernel.data_ptr(), cls_bias.data_ptr(), num_classes,
+                                    logits.data_ptr() if logits is not None else None,
+                                    targets.data_ptr() if targets is not None else None, _EXPLAIN_KINDS[kind],
+                                    maps.data_ptr(), contrib.data_ptr(), baseline.data_ptr(), target_out.data_ptr(),
+                                    status.data_ptr(), ws.data_ptr() if ws is not None else None, dtype, _st()),
+               "gv_explain_views")
+    if check and int(status.item()):
+        bad = [int(t) for t in targets.tolist() if t < 0 or t >= num_classes]
+        raise IndexError("target %d is out of bounds for %d classes" % (bad[0], num_classes))
+    return target_out, baseline, contrib, maps, ws
+
+
+def explain_views(F, scheme, weight, cls_kernel, cls_bias, logits=None, target=None, pool="max", empty_fill=1.0,
+                  kind="exact", check=True):
+    """Attribution of one logit per shape to (view, pixel) for callers who hold the final view descriptors only.
+    F [N, V, h, w, C] on the device, fp32 / bf16 / f16 (read as stored); scheme [G, V] or, per shape, [N, G, V] with
+    weight [G] / [N, G]; cls_kernel [C, num_classes], cls_bias [num_classes].  target: a class, or one per shape; None
+    takes the first maximum of `logits` [N, num_classes].  Returns an Explanation (scores and gidx are None)."""
+    if not (torch.is_tensor(F) and F.is_cuda and F.dim() == 5):
+        raise TypeError("F must be a device tensor [N, V, h, w, C]")
+    if F.dtype not in _STORAGE_OF:
+        raise TypeError("F must be float32, bfloat16 or float16, not %s" % F.dtype)
+    F = F.contiguous()
+    dev = F.device
+    N, V, h, w, C = F.shape
+    sch = _as_dev_scheme(scheme, dev)
+    wt = _as_dev_weight(weight, dev)
+    per_shape = sch.dim() == 3
+    G = sch.shape[-2]
+    if tuple(sch.shape) != ((N, G, V) if per_shape else (G, V)) or tuple(wt.shape) != ((N, G) if per_shape else (G,)):
+        raise ValueError("scheme %s / weight %s do not fit F %s" % (tuple(sch.shape), tuple(wt.shape), tuple(F.shape)))
+    K = torch.as_tensor(cls_kernel).to(device=dev, dtype=torch.float32).contiguous()
+    b = torch.as_tensor(cls_bias).to(device=dev, dtype=torch.float32).contiguous()
+    if K.dim() != 2 or K.shape[0] != C or tuple(b.shape) != (K.shape[1],):
+        raise ValueError("cls_kernel %s / cls_bias %s do not fit C = %d" % (tuple(K.shape), tuple(b.shape), C))
+    if logits is not None:
+        logits = logits.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(logits.shape) != (N, K.shape[1]):
+            raise ValueError("logits must be [%d, %d]" % (N, K.shape[1]))
+    E = h * w * C
+    with torch.cuda.device(dev):
+        tgt, base, contrib, maps, _ = _explain_launch(F.data_ptr(), _STORAGE_OF[F.dtype], N, V, h, w, C, E, V * E, sch,
+                                                      wt, per_shape, pool, empty_fill, K, b, logits,
+                                                      _as_targets(target, N, dev), kind, check, dev)
+    return Explanation(logits, tgt, base, contrib, maps, None, None, wt)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -497,6 +603,30 @@ class GVCNN:
     def embed_meshes(self, batch, renderer=None, rotations=None, check=True, basic=False):
         """embed() on the rendered views of N meshes (see forward_meshes)."""
         return self.embed(self._render_meshes(batch, renderer, rotations), check=check, basic=basic)
+
+    # -- why this class: attribution of a logit to views and pixels (csrc/explain.hip) ------------------------------
+    def explain(self, views, target=None, kind="exact", check=True):
+        """forward(views), then the share of every (view, pixel) of the final tap in one logit per shape: the predicted
+        class (target=None), or `target` (a class, or one per shape).  Acts on this engine's own tap, scheme, weights,
+        classifier and logits and leaves them as forward left them; the only host read is the status word
+        (check=True).  kind: 'exact' (gradient x input; logit = baseline + maps.sum()) or 'gradcam'."""
+        f = self.final
+        assert f.ld == f.c
+        self.forward(views, check=check)
+        if self.per_shape:
+            scheme, weight, scores, gidx = self.scheme_ps, self.weight_ps, self.scores_ps, self.gidx_ps
+        else:
+            scheme, weight, scores, gidx = self.scheme, self.weight, self.scores, self.gidx
+        E = f.h * f.w * f.c
+        tgt, base, contrib, maps, _ = _explain_launch(
+            self.plan.view(f).data_ptr(), self.dtype, self.N, self.V, f.h, f.w, f.c, E, self.V * E, scheme, weight,
+            self.per_shape, self.pool, self.empty_fill, self.cls_kernel, self.cls_bias, self.logits,
+            _as_targets(target, self.N, self.device), kind, check, self.device)
+        return Explanation(self.logits.clone(), tgt, base, contrib, maps, scores.clone(), gidx.clone(), weight.clone())
+
+    def explain_meshes(self, batch, renderer=None, rotations=None, **kw):
+        """explain() on the rendered views of N meshes (see forward_meshes)."""
+        return self.explain(self._render_meshes(batch, renderer, rotations), **kw)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -357,6 +357,34 @@ int gv_view_pool_fuse_fwd_per_shape(const void* F, int32_t num_views, int32_t nu
 int gv_dense_fwd(const float* x, int32_t n, int32_t f, const float* kernel, const float* bias,
                  int32_t c, float* y, void* stream);
 
+/* ---- explain a prediction: per-view, per-pixel attribution of one logit ------------------------------------------
+ * The head above the final tap (view pooling, group fusion, global average pool, Dense) is piecewise linear in the view
+ * descriptors F.  With the grouping held constant (as in gv_view_pool_fuse_bwd) the logit of class k = target[n] is
+ *   logit[n,k] = baseline[n] + sum_{v,p} maps[n,v,p]                                         (kind GV_EXPLAIN_EXACT)
+ *   dlogit/dF[n,v,p,c] = K[c,k]/hw * sum_{g contains v} w_g/W * share_g(v,p,c)
+ *   share_g = [F[v] attains the maximum of g] / #members attaining it (max pooling), 1/|g| (mean pooling)
+ *   maps[n,v,p]     = sum_c F * dlogit/dF            view_contrib[n,v] = sum_p maps[n,v,p]
+ *   baseline[n]     = b[k] + sum_{g empty} w_g/W * empty_fill * sum_c K[c,k]
+ * GV_EXPLAIN_GRADCAM: alpha[n,v,c] = 1/hw sum_p dlogit/dF, maps[n,v,p] = max(0, sum_c alpha * F); view_contrib and
+ * baseline as above.  A shape whose weights sum to 0 has maps = view_contrib = 0 and baseline = b[k].
+ * F element (n, v, p, c) at F + n*shape_stride + v*view_stride + p*C + c, in `dtype`; everything else is fp32.
+ * scheme [G,V] / weight [G], or [N,G,V] / [N,G] with per_shape != 0.  cls_kernel [C, num_classes] row-major, cls_bias
+ * [num_classes].  targets int64 [N], or NULL: the first maximum of logits [N, num_classes] (one of the two must be given).
+ * Outputs: maps [N,V,hw], view_contrib [N,V], baseline [N], target_out int64 [N] (the class used; -1 for a target
+ * outside [0, num_classes): bit 0 of *status is set and that shape's outputs are 0).  No atomics: two calls give the same
+ * bits.  exact reads F once, gradcam twice.  V, G <= 64, N <= 65535 (else GV_E_UNSUPPORTED).
+ * workspace (GV_EXPLAIN_GRADCAM only, gv_explain_workspace_bytes): alpha [N,V,C] fp32 first, then the per-chunk shares
+ * of view_contrib that the first sweep leaves for its fixed-order finish. */
+#define GV_EXPLAIN_EXACT 0
+#define GV_EXPLAIN_GRADCAM 1
+int64_t gv_explain_workspace_bytes(int32_t num_views, int32_t num_shapes, int32_t C, int32_t kind);
+int gv_explain_views(const void* F, int32_t num_views, int32_t num_shapes, int32_t hw, int32_t C, int64_t view_stride,
+                     int64_t shape_stride, const int32_t* scheme, int32_t num_groups, const float* weight,
+                     int32_t per_shape, int32_t pool_mode, float empty_fill, const float* cls_kernel,
+                     const float* cls_bias, int32_t num_classes, const float* logits, const int64_t* targets,
+                     int32_t kind, float* maps, float* view_contrib, float* baseline, int64_t* target_out,
+                     int32_t* status, void* workspace, int32_t dtype, void* stream);
+
 /* ---- input preprocessing (train_data.py:63,81-84,101; eval_data.py:72,109) -----------------------
  * One launch turns a batch of decoded 8-bit RGB views [nimg, h0, w0, 3] into the network input [nimg, H, W, 3] fp32:
  *   tf.image.resize (TF1 resize_images: bilinear, align_corners=False, src = dst * in/out — no half-pixel shift),
