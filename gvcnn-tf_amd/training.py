@@ -25,6 +25,14 @@ from . import backbones
 from . import params as _params
 from .backbones import _out_size
 from .model import _st, _dev, _raise_for_status, pin_device
+from ._train_layout import flat_layout, pick_tile, s2_parity_classes
+
+_BN_STAT_KEYS = ("mean", "var", "inv", "scale", "shift")
+
+
+def _bn_ptrs(st, *keys):
+    """Device pointers of a BatchNorm's per-view statistics, in the order of `keys` (default: all five)."""
+    return [st[k].data_ptr() for k in keys or _BN_STAT_KEYS]
 
 
 class TrainPlan(backbones.BackbonePlan):
@@ -160,14 +168,7 @@ class TrainGVCNN:
         stays a constant of the backward pass).  Single rank, the engine's own views only."""
         self.train_scorer = bool(train_scorer)
         if self.train_scorer:
-            if not per_shape:
-                raise ValueError("train_scorer needs per_shape=True: the batch-mean head's weights are counts")
-            if weight_mode != "mean_score":
-                raise ValueError("train_scorer needs weight_mode='mean_score': count weights do not depend on the scores")
-            if head_views not in (None, num_views):
-                raise ValueError("train_scorer needs head_views == num_views: a view-sharded engine is not supported")
-            if view_offset != 0:
-                raise ValueError("train_scorer needs view_offset == 0: a view-sharded engine is not supported")
+            self._check_train_scorer(per_shape, weight_mode, head_views, num_views, view_offset)
         self.lib = _lib.load()
         # deterministic: every filter gradient through gv_conv2d_wgrad_ws — pixel slices store their partial images of dW
         # into one workspace shared by all layers and are added in slice order, so two runs of a step give the same bits
@@ -211,7 +212,7 @@ class TrainGVCNN:
         self.Vh = head_views if head_views is not None else num_views
         self.view_offset = view_offset
         assert 0 <= view_offset and view_offset + num_views <= self.Vh
-        self.device = dev = _dev(device)
+        self.device = _dev(device)
         self.backbone = backbone
         self.N, self.V, self.H, self.W = num_shapes, num_views, height, width
         self.num_classes, self.G, self.num_bins = num_classes, num_group, num_bins
@@ -220,191 +221,13 @@ class TrainGVCNN:
         self.math_mode = backbones.MATH_MODES[math]
         if self.math_mode == _lib.GV_MATH_F32:
             raise ValueError("training uses the bf16-plane convolution kernels (math='bf16x3')")
-        nb = num_shapes * num_views
-        p = TrainPlan(nb, height, width, self.math_mode, self.dt)
-        raw_tap = raw_tap or backbones.TAPS[backbone][0]
-        final_tap = final_tap or backbones.TAPS[backbone][1]
-        if backbone == "inception_v3":
-            backbones.build_inception_v3(p, keep=(raw_tap, final_tap), fuse_siblings=fuse_siblings)
-        else:
-            backbones.build_resnet_v2_50(p, keep=(raw_tap, final_tap))
-        self.plan = p
-        self.raw, self.final = p.end_points[raw_tap], p.end_points[final_tap]
-        f32 = torch.float32
-        with torch.cuda.device(dev):
-            self.act = [torch.empty((n + 7) // 8 * 8, dtype=self.tdt, device=dev) for n, *_ in p.vbufs]
-            self.grad = [None] * len(p.vbufs)
-            shapes = p.param_shapes()
-            if backbone_params is None:
-                backbone_params = _params.init_backbone_params(shapes, seed=seed)
-            if head_params is None:
-                head_params = _params.init_head_params(self.Vh, self.raw.c, self.final.c, num_classes, seed=seed + 1)
-            ks, bs = [], []
-            for v in range(view_offset, view_offset + num_views):
-                kn, bn = _params.scorer_names(v)
-                ks.append(torch.as_tensor(head_params[kn], dtype=f32).reshape(-1))
-                bs.append(torch.as_tensor(head_params[bn], dtype=f32).reshape(-1)[:1])
-            self.score_kernel = torch.stack(ks).to(dev).contiguous()
-            self.score_bias = torch.cat(bs).to(dev).contiguous()
-            if self.train_scorer:
-                # the scorer in one flat fp32 buffer [V*cr kernels | V biases] with its gradient and Momentum buffers
-                # beside it; score_kernel / score_bias are views of it (same shapes, same values)
-                nk = self.score_kernel.numel()
-                self._flat_sp = torch.cat([self.score_kernel.reshape(-1), self.score_bias]).contiguous()
-                self._flat_sg, self._flat_sm = torch.zeros_like(self._flat_sp), torch.zeros_like(self._flat_sp)
-                self.score_kernel = self._flat_sp[:nk].view(num_views, -1)
-                self.score_bias = self._flat_sp[nk:]
-            kn, bn = _params.classifier_names(self.Vh)
-            self.cls_names = (kn, bn)
-            # Trainable variables, their gradients and the Momentum slots live in three FLAT fp32 buffers (the dicts
-            # hold views): zeroing the gradients is one fill and the optimizer two launches (slim's L2 term applies to
-            # the conv filters, which come first) instead of one per variable.
-            init = {k: torch.as_tensor(backbone_params[k], dtype=f32) for k in shapes}
-            init[kn] = torch.as_tensor(head_params[kn], dtype=f32)
-            init[bn] = torch.as_tensor(head_params[bn], dtype=f32)
-            moving = [k for k in init if k.endswith(("moving_mean", "moving_variance"))]
-            train = [k for k in init if k not in moving]
-            train = [k for k in train if k.endswith("/weights")] + [k for k in train if not k.endswith("/weights")]
-            # The members of a fused sibling GEMM are COLUMN SLICES of one [1,1,cin,sum of couts] block (same place in
-            # all three buffers): the fused filter gradient lands directly in the members' gradients, the forward and
-            # data-gradient images are packed from the block (row stride = its width).  Their dict entries are strided
-            # views with the reference's shapes.
-            fused_of = {}
-            for op in p.ops:
-                if op["kind"] == "conv" and op.get("members"):
-                    for wname, col, c in op["members"]:
-                        fused_of[wname] = (op, col, c)
-            offs, total = {}, 0
-            for k in train:
-                if total and not k.endswith("/weights") and "n_wd" not in offs:
-                    offs["n_wd"] = total
-                if k in fused_of:
-                    op = fused_of[k][0]
-                    if "flat_off" not in op:
-                        op["flat_off"] = total
-                        total += (op["x"].c * op["y"].c + 15) // 16 * 16
-                    continue
-                offs[k] = total
-                total += (init[k].numel() + 15) // 16 * 16
-            self._n_wd = offs.pop("n_wd", total)
-            # where each conv's filter gradient starts in the flat buffer: the filters come first, in layer order, so a
-            # backward pass finalises that region from its end towards offset 0 (backward_backbone(progress=...))
-            lows = []
-            for op in p.ops:
-                if op["kind"] == "conv":
-                    op["g_lo"] = op["flat_off"] if op.get("members") else offs.get(op["name"] + "/weights")
-                    if op["g_lo"] is not None:
-                        lows.append(op["g_lo"])
-            self._g_monotone = all(a < b for a, b in zip(lows, lows[1:]))
-            self._flat_p, self._flat_g, self._flat_m = (torch.zeros(total, dtype=f32, device=dev) for _ in range(3))
-            self.params, self.grads, self.momentum = {}, {}, {}
-            for k in train:
-                if k in fused_of:
-                    op, col, c = fused_of[k]
-                    o, cin, tot_c = op["flat_off"], op["x"].c, op["y"].c
-                    blk = lambda buf: buf[o:o + cin * tot_c].view(1, 1, cin, tot_c)
-                    self.params[k] = blk(self._flat_p)[..., col:col + c]
-                    self.grads[k] = blk(self._flat_g)[..., col:col + c]
-                    self.momentum[k] = blk(self._flat_m)[..., col:col + c]
-                    op["w_fused"], op["dw_fused"] = blk(self._flat_p), blk(self._flat_g)
-                else:
-                    o, n, shp = offs[k], init[k].numel(), tuple(init[k].shape)
-                    self.params[k] = self._flat_p[o:o + n].view(shp)
-                    self.grads[k] = self._flat_g[o:o + n].view(shp)
-                    self.momentum[k] = self._flat_m[o:o + n].view(shp)
-                self.params[k].copy_(init[k])
-            for k in moving:
-                self.params[k] = init[k].to(dev).contiguous().clone()
-            if self.train_scorer:
-                cr, nk = self.score_kernel.shape[1], self.score_kernel.numel()
-                for v in range(num_views):
-                    skn, sbn = _params.scorer_names(v)
-                    for d, buf in ((self.grads, self._flat_sg), (self.momentum, self._flat_sm)):
-                        d[skn] = buf[v * cr:(v + 1) * cr].view(cr, 1)
-                        d[sbn] = buf[nk + v:nk + v + 1]
-            # per-op device state
-            cmax = max(op["x"].c for op in p.ops if op["kind"] == "bn") if any(o["kind"] == "bn" for o in p.ops) else 4
-            cmax = max(cmax, max(max(op["y"].c, op["x"].c) for op in p.ops if op["kind"] == "conv"))
-            self.accum = torch.zeros(2 * num_views * cmax, dtype=torch.float64, device=dev)
-            # 16-bit step: one fp64 accumulator per BatchNorm layer and pass (forward sums, backward sums), all zeroed
-            # by ONE fill per step instead of one memset per call
-            bns = [op for op in p.ops if op["kind"] == "bn"]
-            tot = max(sum(2 * num_views * op["x"].c for op in bns), 4)
-            self._accum_f = torch.zeros(tot, dtype=torch.float64, device=dev)
-            self._accum_b = torch.zeros(tot, dtype=torch.float64, device=dev)
-            o = 0
-            for op in bns:
-                n = 2 * num_views * op["x"].c
-                op["acc_f"], op["acc_b"] = self._accum_f[o:o + n], self._accum_b[o:o + n]
-                o += n
-            self.ones = torch.ones(cmax, dtype=f32, device=dev)
-            self.zeros = torch.zeros(cmax, dtype=f32, device=dev)
-            self._counts = {}
-            for op in p.ops:
-                if op["kind"] == "bn":
-                    c = op["x"].c
-                    op["stat"] = {k: torch.empty((num_views, c), dtype=f32, device=dev)
-                                  for k in ("mean", "var", "inv", "scale", "shift")}
-                elif op["kind"] == "conv":
-                    kh, kw, cin, cout = op["kh"], op["kw"], op["x"].c, op["y"].c
-                    nf = self.lib.gv_packed_filter_bytes(kh, kw, cin, cout, self.dt, self.math_mode)
-                    nd = self.lib.gv_packed_filter_bytes(kh, kw, cout, cin, self.dt, self.math_mode)
-                    op["w_fwd"] = torch.zeros(nf, dtype=torch.uint8, device=dev)
-                    op["w_dgrad"] = torch.zeros(nd, dtype=torch.uint8, device=dev) if op["x"].vbuf >= 0 else None
-                    # stride-2 layer on 16-bit storage: its data gradient as FOUR parity classes (gv_conv_desc.y_step):
-                    # dX at rows of parity py / columns of parity px only receives the taps r = (py + pad) mod 2, +2, ...
-                    # — a small stride-1 convolution over the un-dilated dZ per class, 1/4 of the multiply-adds of the
-                    # zero-dilated form.  (th, tw): taps per class; pad: zero rows in front of dZ; (A, B): class outputs
-                    if op["stride"] == 2 and self.es == 2 and op["x"].vbuf >= 0 and not op.get("members"):
-                        cls = []
-                        for py in (0, 1):
-                            for px in (0, 1):
-                                r0, s0 = (py + op["pad_t"]) % 2, (px + op["pad_l"]) % 2
-                                th, tw = len(range(r0, kh, 2)), len(range(s0, kw, 2))
-                                pt = (th - 1) - (py + op["pad_t"] - r0) // 2
-                                pl = (tw - 1) - (px + op["pad_l"] - s0) // 2
-                                A, B = len(range(py, op["x"].h, 2)), len(range(px, op["x"].w, 2))
-                                if th < 1 or tw < 1 or pt < 0 or pl < 0 or A < 1 or B < 1:
-                                    cls = None
-                                    break
-                                nb_ = self.lib.gv_packed_filter_bytes(th, tw, cout, cin, self.dt, self.math_mode)
-                                cls.append(dict(py=py, px=px, r0=r0, s0=s0, th=th, tw=tw, pad_t=pt, pad_l=pl, A=A, B=B, tile=0,
-                                                w=torch.zeros(nb_, dtype=torch.uint8, device=dev)))
-                            if cls is None:
-                                break
-                        if cls:
-                            op["s2"] = cls
-            nbv = nb
-            self.r_img = torch.empty(nbv, dtype=f32, device=dev)
-            self.scores = torch.empty(self.Vh, dtype=f32, device=dev)
-            self.gidx = torch.empty(self.Vh, dtype=torch.int32, device=dev)
-            self.scheme = torch.empty((num_group, self.Vh), dtype=torch.int32, device=dev)
-            self.weight = torch.empty(num_group, dtype=f32, device=dev)
-            self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-            if self.per_shape:
-                self.scores_ps = torch.empty((num_shapes, self.Vh), dtype=f32, device=dev)
-                self.gidx_ps = torch.empty((num_shapes, self.Vh), dtype=torch.int32, device=dev)
-                self.scheme_ps = torch.empty((num_shapes, num_group, self.Vh), dtype=torch.int32, device=dev)
-                self.weight_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
-            if self.train_scorer:
-                self.dw_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
-                nws = self.lib.gv_group_weight_bwd_workspace_bytes(num_shapes, self.final.h * self.final.w * self.final.c,
-                                                                   num_group)
-                if nws < 0:
-                    _lib.check(int(nws), "gv_group_weight_bwd_workspace_bytes")
-                self._gw_ws = torch.empty(int(nws), dtype=torch.uint8, device=dev)
-            f = self.final
-            self.S = torch.empty((num_shapes, f.h, f.w, f.c), dtype=self.tdt, device=dev)
-            self.dS = torch.empty((num_shapes, f.h, f.w, f.c), dtype=f32, device=dev)
-            self.gap = torch.empty((num_shapes, f.c), dtype=f32, device=dev)
-            self.dgap = torch.empty_like(self.gap)
-            self.logits = torch.empty((num_shapes, num_classes), dtype=f32, device=dev)
-            self.dlogits = torch.empty_like(self.logits)
-            self.loss = torch.zeros(1, dtype=f32, device=dev)
-        self._packed_dirty = True
-        self._pack_jobs = None
-        self._moving_jobs = None
-        # Train-mode BatchNorm sums folded into the launch that produces the tensor (gv_conv2d_fwd_bnstats): the forward
+        self._build_plan(raw_tap, final_tap, fuse_siblings)
+        with torch.cuda.device(self.device):
+            self._layout_params(backbone_params, head_params, seed)
+            self._alloc_op_state()
+            self._alloc_head()
+        self._packed_dirty, self._pack_jobs, self._moving_jobs = True, None, None
+        # Train-mode BatchNorm sums folded into the launch that produces the tensor (_conv_or_stats): the forward
         # sums of z in the convolution's epilogue, the backward sums of dy in the epilogue of the data-gradient launch
         # that writes the FINAL dy (16-bit storage; False: the separate sums passes, kept for A/B and tests)
         self.fuse_bn_stats = self.es == 2
@@ -414,13 +237,182 @@ class TrainGVCNN:
         # Bias gradients that need no pass over dy (ResNet-v2; `_bias_sources`): a bias in front of a train-mode BatchNorm has
         # a zero gradient, one behind a residual add has the gradient of the bias of that add.  False: every bias summed
         self.bias_grad_identities = True
-        self._bias_src = None
-        self._bias_src_key = None
+        self._bias_src = self._bias_src_key = None
         self.s2_classes = True                            # stride-2 data gradients by parity classes (False: zero-dilated dZ; A/B)
         self.s2_concurrent = False                        # ... their four launches side by side on extra streams: measured
                                                           # 15.66 k against 15.89 k views/s in sequence (fork / join cost more
                                                           # than the overlap returns); kept as an A/B switch
         self._plan_bn_fusion()
+
+    @staticmethod
+    def _check_train_scorer(per_shape, weight_mode, head_views, num_views, view_offset):
+        if not per_shape:
+            raise ValueError("train_scorer needs per_shape=True: the batch-mean head's weights are counts")
+        if weight_mode != "mean_score":
+            raise ValueError("train_scorer needs weight_mode='mean_score': count weights do not depend on the scores")
+        if head_views not in (None, num_views):
+            raise ValueError("train_scorer needs head_views == num_views: a view-sharded engine is not supported")
+        if view_offset != 0:
+            raise ValueError("train_scorer needs view_offset == 0: a view-sharded engine is not supported")
+
+    def _build_plan(self, raw_tap, final_tap, fuse_siblings):
+        p = TrainPlan(self.N * self.V, self.H, self.W, self.math_mode, self.dt)
+        raw_tap = raw_tap or backbones.TAPS[self.backbone][0]
+        final_tap = final_tap or backbones.TAPS[self.backbone][1]
+        if self.backbone == "inception_v3":
+            backbones.build_inception_v3(p, keep=(raw_tap, final_tap), fuse_siblings=fuse_siblings)
+        else:
+            backbones.build_resnet_v2_50(p, keep=(raw_tap, final_tap))
+        self.plan = p
+        self.raw, self.final = p.end_points[raw_tap], p.end_points[final_tap]
+
+    def _layout_params(self, backbone_params, head_params, seed):
+        """Activation buffers, the scorer, and every trainable variable with its gradient and Momentum slot."""
+        p, dev, f32, num_views = self.plan, self.device, torch.float32, self.V
+        self.act = [torch.empty((n + 7) // 8 * 8, dtype=self.tdt, device=dev) for n, *_ in p.vbufs]
+        self.grad = [None] * len(p.vbufs)
+        shapes = p.param_shapes()
+        if backbone_params is None:
+            backbone_params = _params.init_backbone_params(shapes, seed=seed)
+        if head_params is None:
+            head_params = _params.init_head_params(self.Vh, self.raw.c, self.final.c, self.num_classes, seed=seed + 1)
+        ks, bs = [], []
+        for v in range(self.view_offset, self.view_offset + num_views):
+            kn, bn = _params.scorer_names(v)
+            ks.append(torch.as_tensor(head_params[kn], dtype=f32).reshape(-1))
+            bs.append(torch.as_tensor(head_params[bn], dtype=f32).reshape(-1)[:1])
+        self.score_kernel = torch.stack(ks).to(dev).contiguous()
+        self.score_bias = torch.cat(bs).to(dev).contiguous()
+        if self.train_scorer:
+            # the scorer in one flat fp32 buffer [V*cr kernels | V biases] with its gradient and Momentum buffers
+            # beside it; score_kernel / score_bias are views of it (same shapes, same values)
+            nk = self.score_kernel.numel()
+            self._flat_sp = torch.cat([self.score_kernel.reshape(-1), self.score_bias]).contiguous()
+            self._flat_sg, self._flat_sm = torch.zeros_like(self._flat_sp), torch.zeros_like(self._flat_sp)
+            self.score_kernel = self._flat_sp[:nk].view(num_views, -1)
+            self.score_bias = self._flat_sp[nk:]
+        kn, bn = self.cls_names = tuple(_params.classifier_names(self.Vh))
+        # Trainable variables, their gradients and the Momentum slots live in three FLAT fp32 buffers (the dicts
+        # hold views): zeroing the gradients is one fill and the optimizer two launches (slim's L2 term applies to
+        # the conv filters, which come first) instead of one per variable.
+        init = {k: torch.as_tensor(backbone_params[k], dtype=f32) for k in shapes}
+        init[kn] = torch.as_tensor(head_params[kn], dtype=f32)
+        init[bn] = torch.as_tensor(head_params[bn], dtype=f32)
+        moving = [k for k in init if k.endswith(("moving_mean", "moving_variance"))]
+        train = [k for k in init if k not in moving]
+        train = [k for k in train if k.endswith("/weights")] + [k for k in train if not k.endswith("/weights")]
+        # The members of a fused sibling GEMM are COLUMN SLICES of one [1,1,cin,sum of couts] block (same place in
+        # all three buffers): the fused filter gradient lands directly in the members' gradients, the forward and
+        # data-gradient images are packed from the block (row stride = its width).  Their dict entries are strided
+        # views with the reference's shapes.
+        fused_of = {wname: (op, col, c) for op in p.ops if op["kind"] == "conv"
+                    for wname, col, c in op.get("members") or ()}
+        offs, block_off, self._n_wd, total = flat_layout(
+            train, {k: init[k].numel() for k in train},
+            {k: (op["name"], op["x"].c * op["y"].c) for k, (op, _, _) in fused_of.items()})
+        # where each conv's filter gradient starts in the flat buffer: the filters come first, in layer order, so a
+        # backward pass finalises that region from its end towards offset 0 (backward_backbone(progress=...))
+        lows = []
+        for op in p.ops:
+            if op["kind"] == "conv":
+                if op["name"] in block_off:
+                    op["flat_off"] = block_off[op["name"]]
+                op["g_lo"] = op["flat_off"] if op.get("members") else offs.get(op["name"] + "/weights")
+                if op["g_lo"] is not None:
+                    lows.append(op["g_lo"])
+        self._g_monotone = all(a < b for a, b in zip(lows, lows[1:]))
+        self._flat_p, self._flat_g, self._flat_m = (torch.zeros(total, dtype=f32, device=dev) for _ in range(3))
+        self.params, self.grads, self.momentum = {}, {}, {}
+        for k in train:
+            if k in fused_of:
+                op, col, c = fused_of[k]
+                o, cin, tot_c = op["flat_off"], op["x"].c, op["y"].c
+                blk = lambda buf: buf[o:o + cin * tot_c].view(1, 1, cin, tot_c)
+                self.params[k] = blk(self._flat_p)[..., col:col + c]
+                self.grads[k] = blk(self._flat_g)[..., col:col + c]
+                self.momentum[k] = blk(self._flat_m)[..., col:col + c]
+                op["w_fused"], op["dw_fused"] = blk(self._flat_p), blk(self._flat_g)
+            else:
+                o, n, shp = offs[k], init[k].numel(), tuple(init[k].shape)
+                self.params[k] = self._flat_p[o:o + n].view(shp)
+                self.grads[k] = self._flat_g[o:o + n].view(shp)
+                self.momentum[k] = self._flat_m[o:o + n].view(shp)
+            self.params[k].copy_(init[k])
+        for k in moving:
+            self.params[k] = init[k].to(dev).contiguous().clone()
+        if self.train_scorer:
+            cr, nk = self.score_kernel.shape[1], self.score_kernel.numel()
+            for v in range(num_views):
+                skn, sbn = _params.scorer_names(v)
+                for d, buf in ((self.grads, self._flat_sg), (self.momentum, self._flat_sm)):
+                    d[skn] = buf[v * cr:(v + 1) * cr].view(cr, 1)
+                    d[sbn] = buf[nk + v:nk + v + 1]
+
+    def _alloc_op_state(self):
+        """Per-op device state: BatchNorm accumulators and statistics, packed filters, parity classes."""
+        p, dev, f32, num_views = self.plan, self.device, torch.float32, self.V
+        cmax = max(op["x"].c for op in p.ops if op["kind"] == "bn") if any(o["kind"] == "bn" for o in p.ops) else 4
+        cmax = max(cmax, max(max(op["y"].c, op["x"].c) for op in p.ops if op["kind"] == "conv"))
+        self.accum = torch.zeros(2 * num_views * cmax, dtype=torch.float64, device=dev)
+        # 16-bit step: one fp64 accumulator per BatchNorm layer and pass (forward sums, backward sums), all zeroed
+        # by ONE fill per step instead of one memset per call
+        bns = [op for op in p.ops if op["kind"] == "bn"]
+        tot = max(sum(2 * num_views * op["x"].c for op in bns), 4)
+        self._accum_f = torch.zeros(tot, dtype=torch.float64, device=dev)
+        self._accum_b = torch.zeros(tot, dtype=torch.float64, device=dev)
+        o = 0
+        for op in bns:
+            n = 2 * num_views * op["x"].c
+            op["acc_f"], op["acc_b"] = self._accum_f[o:o + n], self._accum_b[o:o + n]
+            o += n
+        self.ones = torch.ones(cmax, dtype=f32, device=dev)
+        self.zeros = torch.zeros(cmax, dtype=f32, device=dev)
+        self._counts = {}
+        packed = lambda kh, kw, cin, cout: torch.zeros(
+            self.lib.gv_packed_filter_bytes(kh, kw, cin, cout, self.dt, self.math_mode), dtype=torch.uint8, device=dev)
+        for op in p.ops:
+            if op["kind"] == "bn":
+                op["stat"] = {k: torch.empty((num_views, op["x"].c), dtype=f32, device=dev) for k in _BN_STAT_KEYS}
+            elif op["kind"] == "conv":
+                kh, kw, cin, cout = op["kh"], op["kw"], op["x"].c, op["y"].c
+                op["w_fwd"] = packed(kh, kw, cin, cout)
+                op["w_dgrad"] = packed(kh, kw, cout, cin) if op["x"].vbuf >= 0 else None
+                # stride-2 layer on 16-bit storage: its data gradient as FOUR parity classes (s2_parity_classes), each
+                # with its own tile choice and packed taps
+                if op["stride"] == 2 and self.es == 2 and op["x"].vbuf >= 0 and not op.get("members"):
+                    cls = s2_parity_classes(kh, kw, op["pad_t"], op["pad_l"], op["x"].h, op["x"].w)
+                    if cls:
+                        op["s2"] = [dict(c_, tile=0, w=packed(c_["th"], c_["tw"], cout, cin)) for c_ in cls]
+
+    def _alloc_head(self):
+        """Buffers of the grouping head, the classifier and the loss."""
+        dev, f32, num_shapes, num_group = self.device, torch.float32, self.N, self.G
+        self.r_img = torch.empty(self.N * self.V, dtype=f32, device=dev)
+        self.scores = torch.empty(self.Vh, dtype=f32, device=dev)
+        self.gidx = torch.empty(self.Vh, dtype=torch.int32, device=dev)
+        self.scheme = torch.empty((num_group, self.Vh), dtype=torch.int32, device=dev)
+        self.weight = torch.empty(num_group, dtype=f32, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.per_shape:
+            self.scores_ps = torch.empty((num_shapes, self.Vh), dtype=f32, device=dev)
+            self.gidx_ps = torch.empty((num_shapes, self.Vh), dtype=torch.int32, device=dev)
+            self.scheme_ps = torch.empty((num_shapes, num_group, self.Vh), dtype=torch.int32, device=dev)
+            self.weight_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
+        if self.train_scorer:
+            self.dw_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
+            nws = self.lib.gv_group_weight_bwd_workspace_bytes(num_shapes, self.final.h * self.final.w * self.final.c,
+                                                               num_group)
+            if nws < 0:
+                _lib.check(int(nws), "gv_group_weight_bwd_workspace_bytes")
+            self._gw_ws = torch.empty(int(nws), dtype=torch.uint8, device=dev)
+        f = self.final
+        self.S = torch.empty((num_shapes, f.h, f.w, f.c), dtype=self.tdt, device=dev)
+        self.dS = torch.empty((num_shapes, f.h, f.w, f.c), dtype=f32, device=dev)
+        self.gap = torch.empty((num_shapes, f.c), dtype=f32, device=dev)
+        self.dgap = torch.empty_like(self.gap)
+        self.logits = torch.empty((num_shapes, self.num_classes), dtype=f32, device=dev)
+        self.dlogits = torch.empty_like(self.logits)
+        self.loss = torch.zeros(1, dtype=f32, device=dev)
 
     # -- BatchNorm sums folded into the producing launch --------------------------------------------------
     def _plan_bn_fusion(self):
@@ -764,21 +756,65 @@ class TrainGVCNN:
             self._s2_events = [torch.cuda.Event() for _ in range(4)]
         return self._s2_side
 
+    # -- one helper per launch family: every call site of an entry point goes through it ---------------------------------
+    def _conv_launch(self, desc, src, w, shift, res, dst, stats):
+        """One implicit-GEMM launch (raw pointers, scale = ones): plain, or with the sums of `stats` in its epilogue."""
+        if stats is not None:
+            return self.lib.gv_conv2d_fwd_bnstats(C.byref(desc), src, w, self.ones.data_ptr(), shift, res, dst,
+                                                  C.byref(stats), _st())
+        return self.lib.gv_conv2d_fwd(C.byref(desc), src, w, self.ones.data_ptr(), shift, res, dst, None, None, None, _st())
+
+    def _conv_or_stats(self, desc, src, w, shift, res, dst, stats, what):
+        """The launch with the sums of `stats` folded in where the tile / geometry can (stats None: nobody asked), the
+        plain launch otherwise (GV_E_UNSUPPORTED; the separate sums pass then runs).  -> (rc, folded)"""
+        rc = self._conv_launch(desc, src, w, shift, res, dst, stats) if stats is not None else _lib.GV_E_UNSUPPORTED
+        folded = rc != _lib.GV_E_UNSUPPORTED
+        if not folded:
+            rc = self._conv_launch(desc, src, w, shift, res, dst, None)
+        _lib.check(rc, what + " (+ BN sums)" if folded else what)
+        return rc, folded
+
+    def _bn_fwd_sums(self, op, acc, flags):
+        x = op["x"]
+        return self.lib.gv_bn_sums_grouped_t(self._ptr(x), x.nb, x.h * x.w, x.c, x.ld, self.V, acc.data_ptr(),
+                                             self.dt | flags, _st())
+
+    def _bn_finalize_apply(self, b, acc, src_ptr, nb, hw, ld, y, what):
+        """Statistics of BatchNorm `b` from `acc`, then normalise src_ptr (b.x, or the pooled z of a fused pair) into y."""
+        bx = b["x"]
+        gamma = self.params[b["name"] + "/gamma"].data_ptr() if b["has_gamma"] else None
+        _lib.check(self.lib.gv_bn_finalize_apply_grouped_t(
+            acc.data_ptr(), self._count(bx.h * bx.w).data_ptr(), gamma, self.params[b["name"] + "/beta"].data_ptr(),
+            float(b["eps"]), src_ptr, nb, hw, bx.c, ld, self.V, int(b["relu"]), self._ptr(y), y.ld, *_bn_ptrs(b["stat"]),
+            self.dt, _st()), what)
+
+    def _bn_bwd_sums(self, dy, dy_ld, yptr, z_ptr, z_ld, st, nb, hw, c, acc, sc, sh, flags):
+        """(sum g, sum g*zhat) of the masked gradient g: mask from y (yptr), or from z*scale + shift > 0 (sc, sh)."""
+        return self.lib.gv_bn_relu_bwd_sums_grouped_t(
+            dy, dy_ld, yptr, dy_ld, z_ptr, z_ld, *_bn_ptrs(st, "mean", "inv"), nb, hw, c, self.V, acc.data_ptr(), sc, sh,
+            self.dt | flags, _st())
+
+    def _pool_desc(self, op, x=None, y_ld=None):
+        """Descriptor of pool `op`; x / y_ld: the fused BatchNorm -> pool pair pools the BatchNorm's INPUT, into op["pz"]."""
+        x, y = op["x"] if x is None else x, op["y"]
+        return _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, op["k"], op["k"], op["stride"], op["pad_t"], op["pad_l"],
+                             y.h, y.w, y.ld if y_ld is None else y_ld, op["mode"], self.dt)
+
+    def _pool_fwd_argmax(self, desc, src, dst, op, what):
+        """Max pool that records the winning tap of every window (one byte per output element)."""
+        y = op["y"]
+        if "argmax" not in op:
+            op["argmax"] = torch.empty(y.nb * y.h * y.w * y.c, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.gv_pool2d_fwd_argmax(C.byref(desc), src, dst, op["argmax"].data_ptr(), _st()), what)
+
     def _s2_class(self, op, ci, c_, dz, dx, store, fuse):
         """One parity-class launch of a stride-2 layer's data gradient (with or without the folded BatchNorm sums)."""
-        lib = self.lib
         dc = self._conv_desc_s2(op, c_, not store)
-        rc = _lib.GV_E_UNSUPPORTED
-        if fuse and op.get("_s2_stats_ok", True):
-            rc = lib.gv_conv2d_fwd_bnstats(C.byref(dc), dz, c_["w"].data_ptr(), self.ones.data_ptr(),
-                                           self.zeros.data_ptr(), None if store else dx, dx,
-                                           C.byref(self._bn_stats(op, "st_b")), _st())
-            if rc == _lib.GV_E_UNSUPPORTED:       # this class' tile cannot fold the sums: nobody does (from the next step on)
-                op["_s2_stats_ok"] = False
-        if rc == _lib.GV_E_UNSUPPORTED:
-            rc = lib.gv_conv2d_fwd(C.byref(dc), dz, c_["w"].data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr(),
-                                   None if store else dx, dx, None, None, None, _st())
-        _lib.check(rc, "dgrad (parity class %d) %s" % (ci, op["name"]))
+        stats = self._bn_stats(op, "st_b") if fuse and op.get("_s2_stats_ok", True) else None
+        _, folded = self._conv_or_stats(dc, dz, c_["w"].data_ptr(), self.zeros.data_ptr(), None if store else dx, dx, stats,
+                                        "dgrad (parity class %d) %s" % (ci, op["name"]))
+        if stats is not None and not folded:      # this class' tile cannot fold the sums: nobody does (from the next step on)
+            op["_s2_stats_ok"] = False
 
     def _conv_desc_s2(self, op, c_, accumulate):
         """Descriptor of ONE parity class of a stride-2 layer's data gradient: a stride-1 convolution over dZ whose
@@ -787,6 +823,44 @@ class TrainGVCNN:
         return _lib.ConvDesc(y.nb, y.h, y.w, y.c, y.ld, c_["th"], c_["tw"], 1, c_["pad_t"], c_["pad_l"], c_["A"], c_["B"],
                              x.c, x.ld, x.ld if accumulate else 0, 0, 0, self.dt, 0, c_["tile"], self.math_mode, 0, 0,
                              2, c_["py"], c_["px"], x.h, x.w)
+
+    @staticmethod
+    def _time_ms(fn, iters):
+        """ms per call of fn(): one untimed launch, then `iters` between two events; None where the first one fails."""
+        if fn() != 0:
+            return None
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    def _time_plain_ms(self, d, src, w, dst, iters):
+        """ms per plain launch of descriptor d, timed inside the library; None where it declines the tile."""
+        ms = C.c_float(0)
+        rc = self.lib.gv_conv2d_time(C.byref(d), src, w.data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr(), dst, iters,
+                                     C.byref(ms), _st())
+        return ms.value if rc == 0 else None
+
+    def _time_separate_sums(self, iters):
+        """What the SEPARATE sums passes of every fusable BatchNorm cost, per producing convolution (op["_sums_ms_*"])."""
+        for op in self.plan.ops:
+            op.pop("_sums_ms_f", None), op.pop("_sums_ms_b", None), op.pop("_nofuse_f", None), op.pop("_nofuse_b", None)
+        for b in self.plan.ops:
+            if b["kind"] != "bn":
+                continue
+            x, y, st = b["x"], b["y"], b["stat"]
+            sc, sh = _bn_ptrs(st, "scale", "shift") if b["relu"] else (None, None)
+            probes = {"f": lambda: self._bn_fwd_sums(b, self.accum, 0),
+                      "b": lambda: self._bn_bwd_sums(self._ptr(y, True), y.ld, None, self._ptr(x), x.ld, st, x.nb,
+                                                     x.h * x.w, x.c, self.accum, sc, sh, 0)}
+            for d, fn in probes.items():
+                conv = b.get("fused_" + d)
+                t_ms = self._time_ms(fn, iters) if conv is not None else None
+                if t_ms is not None:
+                    conv["_sums_ms_" + d] = conv.get("_sums_ms_" + d, 0.0) + t_ms
 
     def autotune(self, iters=2):
         """Measure, per convolution, the fastest tile configuration of the forward launch and of the data-gradient
@@ -799,36 +873,10 @@ class TrainGVCNN:
         if self._packed_dirty:
             self.repack()
         ncfg = lib.gv_conv2d_num_tile_cfgs(self.math_mode if self.dt == _lib.GV_F32 else -1)
-        ms = C.c_float(0)
-        if self._fusing():
-            # what the SEPARATE sums passes of every fusable BatchNorm cost: a tile that cannot fold the sums competes as
-            # plain launch + these
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            for op in self.plan.ops:
-                op.pop("_sums_ms_f", None), op.pop("_sums_ms_b", None), op.pop("_nofuse_f", None), op.pop("_nofuse_b", None)
-            for b in self.plan.ops:
-                if b["kind"] != "bn":
-                    continue
-                x, y, st, hw = b["x"], b["y"], b["stat"], b["x"].h * b["x"].w
-                calls = []
-                if b.get("fused_f") is not None:
-                    calls.append(("_sums_ms_f", b["fused_f"], lambda: lib.gv_bn_sums_grouped_t(
-                        self._ptr(x), x.nb, hw, x.c, x.ld, self.V, self.accum.data_ptr(), self.dt, _st())))
-                if b.get("fused_b") is not None:
-                    sc = st["scale"].data_ptr() if b["relu"] else None
-                    sh = st["shift"].data_ptr() if b["relu"] else None
-                    calls.append(("_sums_ms_b", b["fused_b"], lambda: lib.gv_bn_relu_bwd_sums_grouped_t(
-                        self._ptr(y, True), y.ld, None, y.ld, self._ptr(x), x.ld, st["mean"].data_ptr(), st["inv"].data_ptr(),
-                        x.nb, hw, x.c, self.V, self.accum.data_ptr(), sc, sh, self.dt, _st())))
-                for key, conv, fn in calls:
-                    if fn() != 0:
-                        continue
-                    ev0.record()
-                    for _ in range(iters):
-                        fn()
-                    ev1.record()
-                    ev1.synchronize()
-                    conv[key] = conv.get(key, 0.0) + ev0.elapsed_time(ev1) / iters
+        fusing = self._fusing()
+        zeros = self.zeros.data_ptr()
+        if fusing:
+            self._time_separate_sums(iters)
         for op in self.plan.ops:
             if op["kind"] != "conv":
                 continue
@@ -838,93 +886,53 @@ class TrainGVCNN:
             if x.vbuf >= 0:
                 jobs.append(("tile_d", True, self._ptr(y, True), op["w_dgrad"], self._ptr(x, True)))
             for key, dgrad, src, w, dst in jobs:
-                op[key] = 0
-                best, best_ms = 0, float("inf")
-                # a launch that also produces BatchNorm sums is timed AS that launch (its epilogue differs; a tile that
-                # cannot fold them is timed plain plus nothing: the separate sums pass then costs what it costs)
+                # a launch that also produces BatchNorm sums is timed AS that launch (its epilogue differs), and the plain
+                # launch of the same tile plus what the layer's separate sums passes cost (measured once) competes with
+                # it: a folding epilogue can cost more than the pass it saves (Conv2d_1a's strip kernel: 0.27 ms folded
+                # against 0.12 + 0.08), so the layer then keeps the separate pass (op["_nofuse_*"]).
                 skey = "st_b" if dgrad else "st_f"
-                fused = bool(op.get(skey)) and self._fusing()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                best_fused = False
-                for t in range(ncfg):
-                    op[key] = t + 1
+                stats = self._bn_stats(op, skey) if op.get(skey) and fusing else None
+                extra = op.get("_sums_ms_b" if dgrad else "_sums_ms_f", 0.0) if stats is not None else 0.0
+                rows = []
+                for t in range(1, ncfg + 1):
+                    op[key] = t
                     d = self._conv_desc(op, dgrad=dgrad)
                     d.res_ld = 0
-                    rc = -1
-                    if fused:
-                        args = (C.byref(d), src, w.data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr(), None, dst,
-                                C.byref(self._bn_stats(op, skey)), _st())
-                        rc = lib.gv_conv2d_fwd_bnstats(*args)
-                        if rc == 0:
-                            e0.record()
-                            for _ in range(iters):
-                                lib.gv_conv2d_fwd_bnstats(*args)
-                            e1.record()
-                            e1.synchronize()
-                            t_ms = e0.elapsed_time(e1) / iters
-                            if t_ms < best_ms:
-                                best, best_ms, best_fused = t + 1, t_ms, True
-                    # the plain launch of the same tile — of a fusable layer too: plus what its separate sums pass costs
-                    # (measured once).  A folding epilogue can cost more than the pass it saves (Conv2d_1a's strip kernel:
-                    # 0.27 ms folded against 0.12 + 0.08), so the layer then keeps the separate pass (op["_nofuse_*"]).
-                    rc = lib.gv_conv2d_time(C.byref(d), src, w.data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr(),
-                                            dst, iters, C.byref(ms), _st())
-                    extra = op.get("_sums_ms_b" if dgrad else "_sums_ms_f", 0.0) if fused else 0.0
-                    if rc == 0 and ms.value + extra < best_ms:
-                        best, best_ms, best_fused = t + 1, ms.value + extra, False
-                op[key] = best
-                op["_" + key + "_ms"] = best_ms
-                if fused:
+                    if stats is not None:
+                        rows.append((t, self._time_ms(
+                            lambda: self._conv_launch(d, src, w.data_ptr(), zeros, None, dst, stats), iters), True))
+                    t_ms = self._time_plain_ms(d, src, w, dst, iters)
+                    rows.append((t, None if t_ms is None else t_ms + extra, False))
+                op[key], op["_" + key + "_ms"], best_fused = pick_tile(rows)
+                if stats is not None:
                     op["_nofuse_b" if dgrad else "_nofuse_f"] = not best_fused
             # the parity classes of a stride-2 layer's data gradient: one tile choice each
             for c_ in op.get("s2", ()) if self.s2_classes else ():
-                fused = bool(op.get("st_b")) and self._fusing()
-                best, best_ms = 0, float("inf")
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                for t in range(ncfg):
-                    c_["tile"] = t + 1
+                stats = self._bn_stats(op, "st_b") if op.get("st_b") and fusing else None
+                src, dst = self._ptr(y, True), self._ptr(x, True)
+                rows = []
+                for t in range(1, ncfg + 1):
+                    c_["tile"] = t
                     dc = self._conv_desc_s2(op, c_, False)
-                    src, dst = self._ptr(y, True), self._ptr(x, True)
-                    if fused:
-                        args = (C.byref(dc), src, c_["w"].data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr(), None, dst,
-                                C.byref(self._bn_stats(op, "st_b")), _st())
-                        if lib.gv_conv2d_fwd_bnstats(*args) == 0:
-                            e0.record()
-                            for _ in range(iters):
-                                lib.gv_conv2d_fwd_bnstats(*args)
-                            e1.record()
-                            e1.synchronize()
-                            if e0.elapsed_time(e1) / iters < best_ms:
-                                best, best_ms = t + 1, e0.elapsed_time(e1) / iters
-                        continue                              # (classes must all fold, or none: only folding tiles compete)
-                    rc = lib.gv_conv2d_time(C.byref(dc), src, c_["w"].data_ptr(), self.ones.data_ptr(),
-                                            self.zeros.data_ptr(), dst, iters, C.byref(ms), _st())
-                    if rc == 0 and ms.value < best_ms:
-                        best, best_ms = t + 1, ms.value
-                c_["tile"] = best
-                c_["ms"] = best_ms
+                    if stats is not None:                     # (classes must all fold, or none: only folding tiles compete)
+                        rows.append((t, self._time_ms(
+                            lambda: self._conv_launch(dc, src, c_["w"].data_ptr(), zeros, None, dst, stats), iters), True))
+                    else:
+                        rows.append((t, self._time_plain_ms(dc, src, c_["w"], dst, iters), False))
+                c_["tile"], c_["ms"], _ = pick_tile(rows, folding_only=stats is not None)
             if op.get("s2") and self.s2_classes:              # four class launches or the one zero-dilated launch?
                 op["_s2_use"] = sum(c_["ms"] for c_ in op["s2"]) < op.get("_tile_d_ms", float("inf"))
             # filter gradient (16-bit storage): tile and pixel-split choice, timed with events on the launch stream
             nw = lib.gv_conv2d_wgrad_num_cfgs(self.dt)
             if nw:
                 dw = torch.empty_like(self._dw(op))
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                best, best_ms = 0, float("inf")
+                rows = []
                 for t in range(nw + 1):
                     op["tile_w"] = t
                     d = self._conv_desc(op, wgrad=True)
-                    args = (d, self._ptr(x), self._ptr(y, True), y.ld, dw.data_ptr())
-                    if self._wgrad(*args) != 0:
-                        continue
-                    e0.record()
-                    for _ in range(iters):
-                        self._wgrad(*args)
-                    e1.record()
-                    e1.synchronize()
-                    if e0.elapsed_time(e1) < best_ms:
-                        best, best_ms = t, e0.elapsed_time(e1)
-                op["tile_w"] = best
+                    rows.append((t, self._time_ms(
+                        lambda: self._wgrad(d, self._ptr(x), self._ptr(y, True), y.ld, dw.data_ptr()), iters), False))
+                op["tile_w"] = pick_tile(rows)[0]
 
     def repack(self, sync=True):
         """Refresh the packed filters from the trainable HWIO variables (after an optimizer step)."""
@@ -1070,85 +1078,64 @@ class TrainGVCNN:
         once); otherwise the sums call clears it itself, so calling an op on its own is always safe.
         part (BatchNorm only): "sums" = the statistics pass alone, "apply" = finalize + apply alone — the pass loops use
         the two halves to all-reduce the sums of several layers in ONE collective (shape-sharded training)."""
-        lib, V = self.lib, self.V
-        x, y = op["x"], op["y"]
         if op["kind"] == "conv":
-            d = self._conv_desc(op)
-            shift = self.params[op["bias"]] if op["bias"] else self.zeros
-            res = op["res"]
-            op["_st_f_done"] = False
-            xin = self._x32.data_ptr() + 4 * x.off if (x.vbuf < 0 and self.es == 2) else self._ptr(x)
-            if op.get("st_f") and zeroed and self._fusing() and not op.get("_nofuse_f"):   # the BatchNorm sums of z in this launch's epilogue
-                # (a ResNet unit's conv3: the sums are those of shortcut + residual, the tensor the next pre-activation reads)
-                rc = lib.gv_conv2d_fwd_bnstats(C.byref(d), xin, op["w_fwd"].data_ptr(), self.ones.data_ptr(),
-                                               shift.data_ptr(), self._ptr(res) if res is not None else None, self._ptr(y),
-                                               C.byref(self._bn_stats(op, "st_f")), _st())
-                if rc != _lib.GV_E_UNSUPPORTED:               # (unsupported tile / geometry: the plain launch below)
-                    _lib.check(rc, "conv + BN sums " + op["name"])
-                    op["_st_f_done"] = True
-                    return
-            _lib.check(lib.gv_conv2d_fwd(C.byref(d), xin, op["w_fwd"].data_ptr(), self.ones.data_ptr(),
-                                         shift.data_ptr(), self._ptr(res) if res is not None else None,
-                                         self._ptr(y), None, None, None, _st()), "conv " + op["name"])
-        elif op["kind"] == "bn":
-            st = op["stat"]
-            gamma = self.params[op["name"] + "/gamma"] if op["has_gamma"] else None
-            beta = self.params[op["name"] + "/beta"]
-            hw = x.h * x.w
-            acc = op["acc_f"] if self._zacc else self.accum
-            zf = _lib.GV_ACCUM_ZEROED if zeroed else 0
-            if part == "apply":
-                pass
-            elif self.frozen_bn:                          # sums that finalize to (moving_mean, moving_variance)
-                mm = self.params[op["name"] + "/moving_mean"].double()
-                mv = self.params[op["name"] + "/moving_variance"].double()
-                cnt = self._count(hw).double().view(V, 1)
-                a = acc[:2 * V * x.c].view(V, x.c, 2)
-                a[..., 0] = cnt * mm
-                a[..., 1] = cnt * (mv + mm * mm)
-            elif not (zeroed and op.get("fused_f") is not None and op["fused_f"].get("_st_f_done")):
-                _lib.check(lib.gv_bn_sums_grouped_t(self._ptr(x), x.nb, hw, x.c, x.ld, V, acc.data_ptr(), self.dt | zf,
-                                                    _st()), "bn sums " + op["name"])
-            if part == "sums":
-                return
-            if part == "all" and self.bn_sync is not None and not self.frozen_bn:   # shape-sharded: reduce the sums first
-                self._bn_sync_call(acc[:2 * V * x.c])
-            if self._pool_fused(op):                      # normalised after the max pool that follows (see the pool op)
-                return
-            _lib.check(lib.gv_bn_finalize_apply_grouped_t(
-                acc.data_ptr(), self._count(hw).data_ptr(), gamma.data_ptr() if gamma is not None else None,
-                beta.data_ptr(), float(op["eps"]), self._ptr(x), x.nb, hw, x.c, x.ld, V, int(op["relu"]), self._ptr(y),
-                y.ld, st["mean"].data_ptr(), st["var"].data_ptr(), st["inv"].data_ptr(), st["scale"].data_ptr(),
-                st["shift"].data_ptr(), self.dt, _st()), "bn finalize + apply " + op["name"])
+            return self._fwd_conv(op, zeroed)
+        if op["kind"] == "bn":
+            return self._fwd_bn(op, zeroed, part)
+        return self._fwd_pool(op)
+
+    def _fwd_conv(self, op, zeroed):
+        x, y, res = op["x"], op["y"], op["res"]
+        d = self._conv_desc(op)
+        shift = self.params[op["bias"]] if op["bias"] else self.zeros
+        op["_st_f_done"] = False
+        xin = self._x32.data_ptr() + 4 * x.off if (x.vbuf < 0 and self.es == 2) else self._ptr(x)
+        # the BatchNorm sums of z in this launch's epilogue (a ResNet unit's conv3: the sums are those of shortcut +
+        # residual, the tensor the next pre-activation reads); an unsupported tile / geometry launches plain
+        fold = op.get("st_f") and zeroed and self._fusing() and not op.get("_nofuse_f")
+        _, op["_st_f_done"] = self._conv_or_stats(
+            d, xin, op["w_fwd"].data_ptr(), shift.data_ptr(), self._ptr(res) if res is not None else None, self._ptr(y),
+            self._bn_stats(op, "st_f") if fold else None, "conv " + op["name"])
+
+    def _fwd_bn(self, op, zeroed, part):
+        V, x = self.V, op["x"]
+        acc = op["acc_f"] if self._zacc else self.accum
+        if part == "apply":
+            pass
+        elif self.frozen_bn:                              # sums that finalize to (moving_mean, moving_variance)
+            mm = self.params[op["name"] + "/moving_mean"].double()
+            mv = self.params[op["name"] + "/moving_variance"].double()
+            cnt = self._count(x.h * x.w).double().view(V, 1)
+            a = acc[:2 * V * x.c].view(V, x.c, 2)
+            a[..., 0] = cnt * mm
+            a[..., 1] = cnt * (mv + mm * mm)
+        elif not (zeroed and op.get("fused_f") is not None and op["fused_f"].get("_st_f_done")):
+            _lib.check(self._bn_fwd_sums(op, acc, _lib.GV_ACCUM_ZEROED if zeroed else 0), "bn sums " + op["name"])
+        if part == "sums":
+            return
+        if part == "all" and self.bn_sync is not None and not self.frozen_bn:   # shape-sharded: reduce the sums first
+            self._bn_sync_call(acc[:2 * V * x.c])
+        if self._pool_fused(op):                          # normalised after the max pool that follows (see the pool op)
+            return
+        self._bn_finalize_apply(op, acc, self._ptr(x), x.nb, x.h * x.w, x.ld, op["y"], "bn finalize + apply " + op["name"])
+
+    def _fwd_pool(self, op):
+        x, y = op["x"], op["y"]
+        if self._pool_fused(op):
+            # pool z (BN + ReLU with a positive scale are monotone: same winner, same value after normalising), then
+            # BatchNorm + ReLU on the POOLED tensor with the statistics of the whole z
+            b = op["bn_before"]
+            bx = b["x"]
+            self._pool_fwd_argmax(self._pool_desc(op, x=bx, y_ld=bx.c), self._ptr(bx), op["pz"].data_ptr(), op,
+                                  "pool z + argmax " + op["name"])
+            self._bn_finalize_apply(b, b["acc_f"] if self._zacc else self.accum, op["pz"].data_ptr(), y.nb, y.h * y.w, bx.c,
+                                    y, "bn finalize + apply (pooled) " + b["name"])
+        elif op["mode"] == _lib.GV_POOL_MAX and self.pool_argmax:
+            # the winning tap of every window is recorded: the backward pass routes dy by it and never re-reads x
+            self._pool_fwd_argmax(self._pool_desc(op), self._ptr(x), self._ptr(y), op, "pool+argmax " + op["name"])
         else:
-            d = _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, op["k"], op["k"], op["stride"], op["pad_t"],
-                              op["pad_l"], y.h, y.w, y.ld, op["mode"], self.dt)
-            if self._pool_fused(op):
-                # pool z (BN + ReLU with a positive scale are monotone: same winner, same value after normalising), then
-                # BatchNorm + ReLU on the POOLED tensor with the statistics of the whole z
-                b = op["bn_before"]
-                bx, st = b["x"], b["stat"]
-                dz_ = _lib.PoolDesc(bx.nb, bx.h, bx.w, bx.c, bx.ld, 3, 3, 2, 0, 0, y.h, y.w, bx.c, _lib.GV_POOL_MAX, self.dt)
-                if "argmax" not in op:
-                    op["argmax"] = torch.empty(y.nb * y.h * y.w * y.c, dtype=torch.uint8, device=self.device)
-                _lib.check(lib.gv_pool2d_fwd_argmax(C.byref(dz_), self._ptr(bx), op["pz"].data_ptr(), op["argmax"].data_ptr(),
-                                                    _st()), "pool z + argmax " + op["name"])
-                accf = b["acc_f"] if self._zacc else self.accum
-                _lib.check(lib.gv_bn_finalize_apply_grouped_t(
-                    accf.data_ptr(), self._count(bx.h * bx.w).data_ptr(), None, self.params[b["name"] + "/beta"].data_ptr(),
-                    float(b["eps"]), op["pz"].data_ptr(), y.nb, y.h * y.w, bx.c, bx.c, V, 1, self._ptr(y), y.ld,
-                    st["mean"].data_ptr(), st["var"].data_ptr(), st["inv"].data_ptr(), st["scale"].data_ptr(),
-                    st["shift"].data_ptr(), self.dt, _st()), "bn finalize + apply (pooled) " + b["name"])
-                return
-            if op["mode"] == _lib.GV_POOL_MAX and self.pool_argmax:
-                # the winning tap of every window is recorded (one byte per output element): the backward pass routes dy
-                # by it and never re-reads x
-                if "argmax" not in op:
-                    op["argmax"] = torch.empty(y.nb * y.h * y.w * y.c, dtype=torch.uint8, device=self.device)
-                _lib.check(lib.gv_pool2d_fwd_argmax(C.byref(d), self._ptr(x), self._ptr(y), op["argmax"].data_ptr(), _st()),
-                           "pool+argmax " + op["name"])
-            else:
-                _lib.check(lib.gv_pool2d_fwd(C.byref(d), self._ptr(x), self._ptr(y), _st()), "pool " + op["name"])
+            _lib.check(self.lib.gv_pool2d_fwd(C.byref(self._pool_desc(op)), self._ptr(x), self._ptr(y), _st()),
+                       "pool " + op["name"])
 
     def score_partial(self):
         """Scorer responses r_img [N*V] of this engine's views (model.py:144-145); no gradient flows through the
@@ -1313,180 +1300,192 @@ class TrainGVCNN:
     def _backward_op(self, op, zeroed=False, part="all"):
         """Backward of one op: reads the gradient of its output, ACCUMULATES into the gradient of its input(s) and
         of its variables.  part (BatchNorm only): "sums" / "apply", see _forward_op."""
-        lib, V = self.lib, self.V
-        x, y = op["x"], op["y"]
         if op["kind"] == "bn":
-            st = op["stat"]
-            hw = x.h * x.w
-            gamma = self.params[op["name"] + "/gamma"] if op["has_gamma"] else None
-            dbeta = self.grads[op["name"] + "/beta"].data_ptr()
-            dgamma = self.grads[op["name"] + "/gamma"].data_ptr() if gamma is not None else None
-            yptr = self._ptr(y) if op["relu"] and not self._lazy else None
-            sc = st["scale"].data_ptr() if op["relu"] and self._lazy else None      # mask from z*scale + shift > 0
-            sh = st["shift"].data_ptr() if op["relu"] and self._lazy else None
-            accb = op["acc_b"] if self._zacc else self.accum
-            zf = _lib.GV_ACCUM_ZEROED if zeroed else 0
-            if self._pool_fused(op):
-                # BatchNorm -> max pool pair: only a window's winner carries a gradient, so the sums run over the POOLED
-                # tensors (the pool's output gradient, the pooled z); the pool's backward kernel then gathers every input
-                # pixel's gradient, masks it and finishes dz = A*g + B*z + C
-                p_ = op["pool_after"]
-                py = p_["y"]
-                if part != "apply":
-                    _lib.check(lib.gv_bn_relu_bwd_sums_grouped_t(
-                        self._ptr(py, True), py.ld, None, py.ld, p_["pz"].data_ptr(), x.c, st["mean"].data_ptr(),
-                        st["inv"].data_ptr(), py.nb, py.h * py.w, x.c, V, accb.data_ptr(), st["scale"].data_ptr(),
-                        st["shift"].data_ptr(), self.dt | zf, _st()), "bn_bwd sums (pooled) " + op["name"])
-                if part == "sums":
-                    return
-                if part == "all" and self.bn_sync is not None:
-                    self._bn_sync_call(accb[:2 * V * x.c])
-                assert self._claim(x), "the BatchNorm input of a fused pair has one reader"
-                ca, cb, cc = op["coef"]
-                _lib.check(lib.gv_bn_bwd_coeffs_t(accb.data_ptr(), self._count(hw).data_ptr(), st["mean"].data_ptr(),
-                                                  st["inv"].data_ptr(), None, x.c, V, 0, ca.data_ptr(), cb.data_ptr(),
-                                                  cc.data_ptr(), dbeta, None, _st()), "bn_bwd coefficients " + op["name"])
-                dp = _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, 3, 3, 2, 0, 0, py.h, py.w, py.ld, _lib.GV_POOL_MAX, self.dt)
-                _lib.check(lib.gv_pool2d_bwd_argmax_bn(C.byref(dp), p_["argmax"].data_ptr(), self._ptr(py, True), py.ld,
-                                                       self._ptr(x), x.ld, V, ca.data_ptr(), cb.data_ptr(), cc.data_ptr(),
-                                                       st["scale"].data_ptr(), st["shift"].data_ptr(), self._ptr(x, True),
-                                                       x.ld, _st()), "pool_bwd + bn_bwd apply " + op["name"])
-                return
-            # (sum g, sum g*z) already added by the data-gradient launch that wrote the final dy?
-            raw = zeroed and op.get("fused_b") is not None and op["fused_b"].get("_st_b_done", False)
-            if not raw and part != "apply":
-                _lib.check(lib.gv_bn_relu_bwd_sums_grouped_t(
-                    self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, st["mean"].data_ptr(),
-                    st["inv"].data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), sc, sh, self.dt | zf, _st()),
-                    "bn_bwd sums " + op["name"])
-            if part == "sums":
-                return
-            acc = 0 if self._claim(x) else 1
-            if part == "all" and self.bn_sync is not None:
-                self._bn_sync_call(accb[:2 * V * x.c])
-            if self.frozen_bn:                            # beta / gamma take their gradients, the statistics terms vanish
-                ab = accb[:2 * V * x.c].view(V, x.c, 2)
-                self.grads[op["name"] + "/beta"] += ab[..., 0].sum(0).float()
-                if gamma is not None:
-                    self.grads[op["name"] + "/gamma"] += ab[..., 1].sum(0).float()
-                ab.zero_()
-                dbeta = dgamma = None
-            def apply(flag):
-                return lib.gv_bn_relu_bwd_apply_grouped_t(
-                    self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, st["mean"].data_ptr(),
-                    st["inv"].data_ptr(), gamma.data_ptr() if gamma is not None else None,
-                    self._count(hw).data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), self._ptr(x, True), x.ld,
-                    dbeta, dgamma, sc, sh, acc if self._lazy else 1, self.dt | flag, _st())
-            rc = apply(_lib.GV_ACCUM_RAW_Z if raw else 0)
-            if raw and rc == _lib.GV_E_UNSUPPORTED and self.bn_sync is None:
-                # the apply kernel cannot convert (sum g, sum g*z) for this geometry (its non-vector path): nothing was
-                # written — take the sums from the separate pass after all, and remember it for the next steps
-                accb[:2 * V * x.c].zero_()
-                _lib.check(lib.gv_bn_relu_bwd_sums_grouped_t(
-                    self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, st["mean"].data_ptr(),
-                    st["inv"].data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), sc, sh, self.dt | _lib.GV_ACCUM_ZEROED, _st()),
-                    "bn_bwd sums " + op["name"])
-                op["fused_b"]["_nofuse_b"] = True
-                rc = apply(0)
-            _lib.check(rc, "bn_bwd apply " + op["name"])
-        elif op["kind"] == "conv":
-            dz = self._ptr(y, True)
-            if op["bias"]:
-                src = self._bias_sources()[op["bias"]]
-                if src is not None:                           # known without a pass over dy: zero, or other biases' gradients
-                    for other in src:                         # (theirs are final: their ops ran earlier in this pass)
-                        self.grads[op["bias"]].add_(self.grads[other])
-                else:
-                    _lib.check(lib.gv_bias_grad_t(dz, y.ld, y.npix, y.c, self.accum.data_ptr(),
-                                                  self.grads[op["bias"]].data_ptr(), self.dt, _st()), "bias_grad")
-            if op["res"] is not None:
-                # y = conv(x) + r: the gradient of r receives dy.  Where this op is the FIRST contributor to it (always, in
-                # ResNet-v2: a unit's conv3 is the last reader of its shortcut), the gradient of r simply IS dy's buffer
-                # from here on — nothing reads dy after this op, and the later contributions (the unit's pre-activation,
-                # the subsampling pool, the shortcut convolution's own backward) add to / read it in place.  Otherwise
-                # (or with the A/B switch off) dy is added into r's own buffer: 16 copy passes of 100 - 800 MB per step.
-                r = op["res"]
-                first = self._claim(r)
-                if first and self._can_alias_grad(r, y):
-                    self._ptr(y, True)
-                    self.grad[r.vbuf] = self.grad[y.vbuf]
-                else:
-                    if self.grad[r.vbuf] is not None and self.grad[r.vbuf] is self.grad[y.vbuf]:
-                        self.grad[r.vbuf] = None                  # (aliased by an earlier pass: its own buffer again)
-                    if first:
-                        self._zero_grad_of(r)
-                    _lib.check(lib.gv_accumulate_t(dz, y.ld, self._ptr(r, True), r.ld, y.npix, y.c, self.dt, _st()),
-                               "res grad")
-            d = self._conv_desc(op, wgrad=True)
-            _lib.check(self._wgrad(d, self._ptr(x), dz, y.ld, self._dw(op).data_ptr()), "wgrad " + op["name"])
-            # (a fused sibling GEMM: its gradient block IS the members' gradients, column by column)
-            if x.vbuf >= 0:
-                dd = self._conv_desc(op, dgrad=True)
-                dx = self._ptr(x, True)
-                store = self._claim(x)                        # first contribution: no residual read, plain store
-                if store:
-                    dd.res_ld = 0
-                op["_st_b_done"] = False
-                if op.get("s2") and self.s2_classes and op.get("_s2_use", x.npix >= 100000):
-                    # four parity classes instead of one launch over the zero-dilated dZ (where that is faster: four
-                    # launches of a quarter of the pixels each fill the chip only on the larger maps — autotune() measures
-                    # both forms, the default goes by size); the BatchNorm sums of the
-                    # layers that produced x ride on all four (each adds the pixels it writes) or on none
-                    fuse = bool(op.get("st_b")) and zeroed and self._fusing() and op.get("_s2_stats_ok", True)
-                    # The four launches are independent (disjoint pixels of dX, commutative exact sums) and each covers a
-                    # quarter of the pixels — under one wave of workgroups on the 12x12 maps — so they run side by side on
-                    # three extra streams, forked from and joined back into the launch stream (eager steps only: the
-                    # multi-stream capture problem of enable_lanes() applies).
-                    side = self._s2_streams() if (self.s2_concurrent and self._lane_streams is None and
-                                                  not torch.cuda.is_current_stream_capturing()) else None
-                    main = torch.cuda.current_stream(self.device)
-                    if side is not None:
-                        ev0 = self._s2_events[0]
-                        ev0.record(main)
-                    for ci, c_ in enumerate(op["s2"]):
-                        stream = main if side is None or ci == 0 else side[ci - 1]
-                        if stream is not main:
-                            stream.wait_event(ev0)
-                        with torch.cuda.stream(stream):
-                            self._s2_class(op, ci, c_, dz, dx, store, fuse)
-                        if stream is not main:
-                            self._s2_events[ci].record(stream)
-                    if side is not None:
-                        for ci in range(1, len(op["s2"])):
-                            main.wait_event(self._s2_events[ci])
-                    ok = fuse and op.get("_s2_stats_ok", True)
-                    if fuse and not ok:                       # a class declined the sums after others had added theirs
-                        for b in op["st_b"]:
-                            b["acc_b"].zero_()
-                    op["_st_b_done"] = ok
-                    return
-                if op.get("st_b") and zeroed and self._fusing() and not op.get("_nofuse_b"):
-                    # this launch writes the FINAL gradient of x: the backward sums of the BatchNorm layers that
-                    # produced x leave its epilogue
-                    rc = lib.gv_conv2d_fwd_bnstats(C.byref(dd), dz, op["w_dgrad"].data_ptr(), self.ones.data_ptr(),
-                                                   self.zeros.data_ptr(), None if store else dx, dx,
-                                                   C.byref(self._bn_stats(op, "st_b")), _st())
-                    if rc != _lib.GV_E_UNSUPPORTED:
-                        _lib.check(rc, "dgrad + BN sums " + op["name"])
-                        op["_st_b_done"] = True
-                        return
-                _lib.check(lib.gv_conv2d_fwd(C.byref(dd), dz, op["w_dgrad"].data_ptr(), self.ones.data_ptr(),
-                                             self.zeros.data_ptr(), None if store else dx, dx, None, None, None,
-                                             _st()), "dgrad " + op["name"])
+            return self._bwd_bn(op, zeroed, part)
+        if op["kind"] == "conv":
+            return self._bwd_conv(op, zeroed)
+        return self._bwd_pool(op)
+
+    def _bwd_bn(self, op, zeroed, part):
+        accb = op["acc_b"] if self._zacc else self.accum
+        bwd = self._bwd_bn_pooled if self._pool_fused(op) else self._bwd_bn_plain
+        return bwd(op, accb, _lib.GV_ACCUM_ZEROED if zeroed else 0, part)
+
+    def _bwd_bn_pooled(self, op, accb, zf, part):
+        """BatchNorm -> max pool pair: only a window's winner carries a gradient, so the sums run over the POOLED tensors
+        (the pool's output gradient, the pooled z); the pool's backward kernel then gathers every input pixel's gradient,
+        masks it and finishes dz = A*g + B*z + C."""
+        lib, V, x, st = self.lib, self.V, op["x"], op["stat"]
+        p_ = op["pool_after"]
+        py = p_["y"]
+        scale, shift = _bn_ptrs(st, "scale", "shift")
+        if part != "apply":
+            _lib.check(self._bn_bwd_sums(self._ptr(py, True), py.ld, None, p_["pz"].data_ptr(), x.c, st, py.nb, py.h * py.w,
+                                         x.c, accb, scale, shift, zf), "bn_bwd sums (pooled) " + op["name"])
+        if part == "sums":
+            return
+        if part == "all" and self.bn_sync is not None:
+            self._bn_sync_call(accb[:2 * V * x.c])
+        assert self._claim(x), "the BatchNorm input of a fused pair has one reader"
+        ca, cb, cc = (t.data_ptr() for t in op["coef"])
+        _lib.check(lib.gv_bn_bwd_coeffs_t(accb.data_ptr(), self._count(x.h * x.w).data_ptr(), *_bn_ptrs(st, "mean", "inv"),
+                                          None, x.c, V, 0, ca, cb, cc, self.grads[op["name"] + "/beta"].data_ptr(), None,
+                                          _st()), "bn_bwd coefficients " + op["name"])
+        _lib.check(lib.gv_pool2d_bwd_argmax_bn(C.byref(self._pool_desc(p_, x=x)), p_["argmax"].data_ptr(),
+                                               self._ptr(py, True), py.ld, self._ptr(x), x.ld, V, ca, cb, cc, scale, shift,
+                                               self._ptr(x, True), x.ld, _st()), "pool_bwd + bn_bwd apply " + op["name"])
+
+    def _bwd_bn_plain(self, op, accb, zf, part):
+        lib, V, x, y, st = self.lib, self.V, op["x"], op["y"], op["stat"]
+        hw = x.h * x.w
+        gamma =self.params[op["name"] + "/gamma"] if op["has_gamma"] else None
+        dbeta = self.grads[op["name"] + "/beta"].data_ptr()
+        dgamma = self.grads[op["name"] + "/gamma"].data_ptr() if gamma is not None else None
+        yptr = self._ptr(y) if op["relu"] and not self._lazy else None
+        # (the lazy form takes the ReLU mask from z*scale + shift > 0)
+        sc, sh = _bn_ptrs(st, "scale", "shift") if op["relu"] and self._lazy else (None, None)
+        sums = lambda flags: _lib.check(self._bn_bwd_sums(self._ptr(y, True), y.ld, yptr, self._ptr(x), x.ld, st, x.nb, hw,
+                                                          x.c, accb, sc, sh, flags), "bn_bwd sums " + op["name"])
+        # (sum g, sum g*z) already added by the data-gradient launch that wrote the final dy?
+        raw = bool(zf) and op.get("fused_b") is not None and op["fused_b"].get("_st_b_done", False)
+        if not raw and part != "apply":
+            sums(zf)
+        if part == "sums":
+            return
+        acc = 0 if self._claim(x) else 1
+        if part == "all" and self.bn_sync is not None:
+            self._bn_sync_call(accb[:2 * V * x.c])
+        if self.frozen_bn:                                # beta / gamma take their gradients, the statistics terms vanish
+            ab = accb[:2 * V * x.c].view(V, x.c, 2)
+            self.grads[op["name"] + "/beta"] += ab[..., 0].sum(0).float()
+            if gamma is not None:
+                self.grads[op["name"] + "/gamma"] += ab[..., 1].sum(0).float()
+            ab.zero_()
+            dbeta = dgamma = None
+        def apply(flag):
+            return lib.gv_bn_relu_bwd_apply_grouped_t(
+                self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, *_bn_ptrs(st, "mean", "inv"),
+                gamma.data_ptr() if gamma is not None else None,
+                self._count(hw).data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), self._ptr(x, True), x.ld,
+                dbeta, dgamma, sc, sh, acc if self._lazy else 1, self.dt | flag, _st())
+        rc = apply(_lib.GV_ACCUM_RAW_Z if raw else 0)
+        if raw and rc == _lib.GV_E_UNSUPPORTED and self.bn_sync is None:
+            # the apply kernel cannot convert (sum g, sum g*z) for this geometry (its non-vector path): nothing was
+            # written — take the sums from the separate pass after all, and remember it for the next steps
+            accb[:2 * V * x.c].zero_()
+            sums(_lib.GV_ACCUM_ZEROED)
+            op["fused_b"]["_nofuse_b"] = True
+            rc = apply(0)
+        _lib.check(rc, "bn_bwd apply " + op["name"])
+
+    def _bwd_conv(self, op, zeroed):
+        dz = self._ptr(op["y"], True)
+        if op["bias"]:
+            self._bwd_bias(op, dz)
+        if op["res"] is not None:
+            self._bwd_residual(op, dz)
+        self._bwd_filter(op, dz)
+        if op["x"].vbuf >= 0:
+            self._dgrad(op, dz, zeroed)
+
+    def _bwd_bias(self, op, dz):
+        y = op["y"]
+        src = self._bias_sources()[op["bias"]]
+        if src is not None:                               # known without a pass over dy: zero, or other biases' gradients
+            for other in src:                             # (theirs are final: their ops ran earlier in this pass)
+                self.grads[op["bias"]].add_(self.grads[other])
         else:
-            if self._pool_fused(op):                          # its backward is part of the BatchNorm's (see there): the gradient
-                self._claim(x)                                # of x is never materialised, only marked as produced
-                return
-            d = _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, op["k"], op["k"], op["stride"], op["pad_t"],
-                              op["pad_l"], y.h, y.w, y.ld, op["mode"], self.dt)
-            if self._claim(x):                                # first contribution: the gather kernels store
-                d.mode |= _lib.GV_POOL_BWD_STORE
-            if self.pool_argmax and "argmax" in op:          # (a record left by an earlier pool_argmax = True pass is stale)
-                _lib.check(lib.gv_pool2d_bwd_argmax(C.byref(d), op["argmax"].data_ptr(), self._ptr(y, True), y.ld,
-                                                    self._ptr(x, True), x.ld, _st()), "pool_bwd (argmax) " + op["name"])
-            else:
-                _lib.check(lib.gv_pool2d_bwd(C.byref(d), self._ptr(x), self._ptr(y, True), y.ld, self._ptr(x, True),
-                                             x.ld, _st()), "pool_bwd " + op["name"])
+            _lib.check(self.lib.gv_bias_grad_t(dz, y.ld, y.npix, y.c, self.accum.data_ptr(),
+                                               self.grads[op["bias"]].data_ptr(), self.dt, _st()), "bias_grad")
+
+    def _bwd_residual(self, op, dz):
+        # y = conv(x) + r: the gradient of r receives dy.  Where this op is the FIRST contributor to it (always, in
+        # ResNet-v2: a unit's conv3 is the last reader of its shortcut), the gradient of r simply IS dy's buffer
+        # from here on — nothing reads dy after this op, and the later contributions (the unit's pre-activation,
+        # the subsampling pool, the shortcut convolution's own backward) add to / read it in place.  Otherwise
+        # (or with the A/B switch off) dy is added into r's own buffer: 16 copy passes of 100 - 800 MB per step.
+        y, r = op["y"], op["res"]
+        first = self._claim(r)
+        if first and self._can_alias_grad(r, y):
+            self._ptr(y, True)
+            self.grad[r.vbuf] = self.grad[y.vbuf]
+        else:
+            if self.grad[r.vbuf] is not None and self.grad[r.vbuf] is self.grad[y.vbuf]:
+                self.grad[r.vbuf] = None                  # (aliased by an earlier pass: its own buffer again)
+            if first:
+                self._zero_grad_of(r)
+            _lib.check(self.lib.gv_accumulate_t(dz, y.ld, self._ptr(r, True), r.ld, y.npix, y.c, self.dt, _st()),
+                       "res grad")
+
+    def _bwd_filter(self, op, dz):                        # (a fused sibling GEMM: its block IS the members' gradients)
+        d =self._conv_desc(op, wgrad=True)
+        _lib.check(self._wgrad(d, self._ptr(op["x"]), dz, op["y"].ld, self._dw(op).data_ptr()), "wgrad " + op["name"])
+
+    def _dgrad(self, op, dz, zeroed):
+        """Data gradient of a convolution: the forward kernel on dZ with the flipped / transposed filter."""
+        x = op["x"]
+        dd = self._conv_desc(op, dgrad=True)
+        dx = self._ptr(x, True)
+        store = self._claim(x)                            # first contribution: no residual read, plain store
+        if store:
+            dd.res_ld = 0
+        op["_st_b_done"] = False
+        if op.get("s2") and self.s2_classes and op.get("_s2_use", x.npix >= 100000):
+            return self._dgrad_s2(op, dz, dx, store, zeroed)
+        # this launch writes the FINAL gradient of x: the backward sums of the BatchNorm layers that produced x leave
+        # its epilogue
+        fold = op.get("st_b") and zeroed and self._fusing() and not op.get("_nofuse_b")
+        _, op["_st_b_done"] = self._conv_or_stats(
+            dd, dz, op["w_dgrad"].data_ptr(), self.zeros.data_ptr(), None if store else dx, dx,
+            self._bn_stats(op, "st_b") if fold else None, "dgrad " + op["name"])
+
+    def _dgrad_s2(self, op, dz, dx, store, zeroed):
+        """Four parity classes instead of one launch over the zero-dilated dZ (where that is faster: four launches of a
+        quarter of the pixels each fill the chip only on the larger maps — autotune() measures both forms, the default
+        goes by size); the BatchNorm sums of the layers that produced x ride on all four (each adds the pixels it
+        writes) or on none."""
+        fuse = bool(op.get("st_b")) and zeroed and self._fusing() and op.get("_s2_stats_ok", True)
+        # The four launches are independent (disjoint pixels of dX, commutative exact sums) and each covers a
+        # quarter of the pixels — under one wave of workgroups on the 12x12 maps — so they run side by side on
+        # three extra streams, forked from and joined back into the launch stream (eager steps only: the
+        # multi-stream capture problem of enable_lanes() applies).
+        side = self._s2_streams() if (self.s2_concurrent and self._lane_streams is None and
+                                      not torch.cuda.is_current_stream_capturing()) else None
+        main = torch.cuda.current_stream(self.device)
+        if side is not None:
+            ev0 = self._s2_events[0]
+            ev0.record(main)
+        for ci, c_ in enumerate(op["s2"]):
+            stream = main if side is None or ci == 0 else side[ci - 1]
+            if stream is not main:
+                stream.wait_event(ev0)
+            with torch.cuda.stream(stream):
+                self._s2_class(op, ci, c_, dz, dx, store, fuse)
+            if stream is not main:
+                self._s2_events[ci].record(stream)
+        if side is not None:
+            for ci in range(1, len(op["s2"])):
+                main.wait_event(self._s2_events[ci])
+        ok = fuse and op.get("_s2_stats_ok", True)
+        if fuse and not ok:                               # a class declined the sums after others had added theirs
+            for b in op["st_b"]:
+                b["acc_b"].zero_()
+        op["_st_b_done"] = ok
+
+    def _bwd_pool(self, op):
+        x, y = op["x"], op["y"]
+        if self._pool_fused(op):                          # its backward is part of the BatchNorm's (see there): the gradient
+            self._claim(x)                                # of x is never materialised, only marked as produced
+            return
+        d = self._pool_desc(op)
+        if self._claim(x):                                # first contribution: the gather kernels store
+            d.mode |= _lib.GV_POOL_BWD_STORE
+        if self.pool_argmax and "argmax" in op:          # (a record left by an earlier pool_argmax = True pass is stale)
+            _lib.check(self.lib.gv_pool2d_bwd_argmax(C.byref(d), op["argmax"].data_ptr(), self._ptr(y, True), y.ld,
+                                                     self._ptr(x, True), x.ld, _st()), "pool_bwd (argmax) " + op["name"])
+        else:
+            _lib.check(self.lib.gv_pool2d_bwd(C.byref(d), self._ptr(x), self._ptr(y, True), y.ld, self._ptr(x, True),
+                                              x.ld, _st()), "pool_bwd " + op["name"])
 
     def apply_momentum(self, lr, mu=0.9, weight_decay=0.0):
         """tf.train.MomentumOptimizer(lr, 0.9); the slim L2 term (wd * w) applies to conv weights only."""
