@@ -223,6 +223,65 @@ def test_loss_dense_gap_and_momentum():
     close(wd_.cpu(), w0 - 0.01 * m1, 1e-6)
 
 
+@pytest.mark.parametrize("n,c", [(300, 40), (1, 3)])
+def test_softmax_ce_past_one_pass_of_the_block(n, c):
+    """gv_softmax_ce with more rows than the block has threads (each thread takes rows i, i + 256, ...) and with one row: a
+    logit of 80 makes the max-subtraction matter (exp(80) overflows fp32).  Against torch's cross_entropy in float64."""
+    g = torch.Generator().manual_seed(40 + n)
+    logits = torch.randn(n, c, generator=g) * 3
+    logits[n // 2, 1] = 80.0
+    labels = torch.randint(0, c, (n,), generator=g)
+    labels[n // 2] = 2                                   # (not the large logit: the row's loss is ~80)
+    l64 = logits.double().requires_grad_(True)
+    loss = torch.nn.functional.cross_entropy(l64, labels)
+    loss.backward()
+    lossd, dl = torch.full((1,), float("nan"), device=DEV), torch.full((n, c), float("nan"), device=DEV)
+    ld, lab = logits.to(DEV), labels.to(DEV)
+    _lib.check(lib().gv_softmax_ce(ld.data_ptr(), lab.data_ptr(), n, c, lossd.data_ptr(), dl.data_ptr(), st()), "ce")
+    close(lossd.cpu(), [float(loss)], 1e-5)
+    close(dl.cpu(), l64.grad, 1e-5)
+
+
+@pytest.mark.parametrize("n,f,c", [(40, 24, 5), (3, 2048, 40)])
+def test_dense_backward_accumulates_and_stores(n, f, c):
+    """gv_dense_bwd with n*f > f*c and with f*c > n*f (one flat grid covers the three index ranges), more than one block:
+    dW and db start non-zero (the contract is +=), dx starts as NaN (it is stored).  Against float64."""
+    g = torch.Generator().manual_seed(n + f)
+    x, dy = torch.randn(n, f, generator=g), torch.randn(n, c, generator=g)
+    Wk = torch.randn(f, c, generator=g) * 0.1
+    dW0, db0 = torch.randn(f, c, generator=g), torch.randn(c, generator=g)
+    dx, dW, db = torch.full((n, f), float("nan"), device=DEV), dW0.to(DEV), db0.to(DEV)
+    xd, dyd, Wd = x.to(DEV), dy.to(DEV), Wk.to(DEV)
+    _lib.check(lib().gv_dense_bwd(xd.data_ptr(), dyd.data_ptr(), Wd.data_ptr(), n, f, c, dx.data_ptr(), dW.data_ptr(),
+                                  db.data_ptr(), st()), "dense_bwd")
+    close(dx.cpu(), dy.double() @ Wk.double().T, 1e-5)
+    close(dW.cpu().double() - dW0.double(), x.double().T @ dy.double(), 1e-5)
+    close(db.cpu().double() - db0.double(), dy.double().sum(0), 1e-5)
+
+
+def test_global_avg_pool_backward_into_a_slice_and_ragged_momentum():
+    """gv_global_avg_pool_bwd adds dgap / hw into a channel slice of a wider gradient buffer that already holds values (the
+    other channels keep their sentinel); gv_sgd_momentum at n = 1000 (a ragged last block).  Against float64."""
+    g = torch.Generator().manual_seed(6)
+    n, hw, c, ld = 5, 9, 70, 96
+    dgap = torch.randn(n, c, generator=g)
+    dx0 = torch.randn(n, hw, c, generator=g)
+    dx = torch.full((n, hw, ld), -7.0, device=DEV)
+    dx[..., :c] = dx0.to(DEV)
+    dgd = dgap.to(DEV)
+    _lib.check(lib().gv_global_avg_pool_bwd(dgd.data_ptr(), n, hw, c, dx.data_ptr(), ld, st()), "gap_bwd")
+    close(dx[..., :c].cpu().double() - dx0.double(), (dgap.double() / hw)[:, None, :].expand(n, hw, c), 1e-5)
+    assert bool((dx[..., c:] == -7.0).all())
+    nw = 1000
+    w0, g0, m0 = torch.randn(nw, generator=g), torch.randn(nw, generator=g), torch.randn(nw, generator=g)
+    wd_, gd_, md_ = w0.to(DEV), g0.to(DEV), m0.to(DEV)
+    _lib.check(lib().gv_sgd_momentum(wd_.data_ptr(), gd_.data_ptr(), md_.data_ptr(), nw, 0.01, 0.9, 1e-4, st()), "sgd")
+    m1 = 0.9 * m0.double() + (g0.double() + 1e-4 * w0.double())
+    close(md_.cpu(), m1, 1e-6)
+    close(wd_.cpu(), w0.double() - 0.01 * m1, 1e-6)
+    assert torch.equal(gd_.cpu(), g0)
+
+
 @pytest.mark.parametrize("backbone,size,N,V", [("inception_v3", 171, 4, 2), ("resnet_v2_50", 97, 3, 2)])
 def test_training_step_vs_oracle(backbone, size, N, V):
     """Whole step against torch autograd through the oracle (CPU).  Train-mode BN over a handful of

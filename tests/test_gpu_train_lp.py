@@ -16,6 +16,7 @@ import gvcnn_tf_amd as gv                          # noqa: E402
 from gvcnn_tf_amd import _lib                       # noqa: E402
 from gvcnn_tf_amd.training import TrainGVCNN        # noqa: E402
 from oracle import backbone as OB                   # noqa: E402
+import bn_ref                                       # noqa: E402   (tests/bn_ref.py)
 
 DEV = "cuda:0"
 TYPES = [(_lib.GV_BF16, torch.bfloat16, 2.0 ** -8), (_lib.GV_F16, torch.float16, 2.0 ** -11)]
@@ -132,6 +133,250 @@ def test_bn_train_forward_and_backward_typed(dt, tdt, eps, c, ld):
         close(dz2[..., :c].float().cpu(), zz.grad, 2 * eps)
 
 
+# ---- the per-view BatchNorm kernels over their launch geometries, every storage type, against fp64 (tests/bn_ref.py) ----
+# name: (storage code, torch type, tolerance of y, tolerance of dz), of the tensor's scale
+BN_TYPES = {"f32": (_lib.GV_F32, torch.float32, 1e-5, 1e-4), "bf16": (_lib.GV_BF16, torch.bfloat16, 2.0 ** -8, 2.0 ** -7),
+            "f16": (_lib.GV_F16, torch.float16, 2.0 ** -11, 2.0 ** -10)}
+# name: (N, V, h, w, c, ld).  Pixel splits (grid y) of the sums launches / of the apply launches, as the library chooses them:
+BN_CASES = {
+    "A": (3, 4, 7, 7, 80, 96),         # 2 / 2: 74 pixels per block, the second starts at pixel 25 of image 1; channel blocks 64 + 16
+    "B": (4, 3, 10, 9, 200, 200),      # 3 / 3: 120 pixels per block; four channel blocks, the last with 8 channels
+    "C": (24, 4, 1, 1, 64, 64),        # 1 / 1: hw = 1, a lane step hops 16 images on fp32 (16-bit: 24 pixels < 32 lanes, no step)
+    "H": (80, 4, 1, 1, 64, 64),        # 1 / 1: hw = 1 with 80 pixels per view: several lane steps of 16 / 32 images on every type
+    "D": (40, 2, 2, 2, 72, 80),        # 2 / 2: hw = 4, 80 pixels per block
+    "E": (6, 5, 3, 3, 136, 136),       # 1 / 1: hw = 9, five views, ragged third channel block
+    "F": (3, 4, 7, 7, 6, 7),           # 2 / -: no 16-byte walk: the scalar kernels of every type (their apply has a flat grid)
+    "G": (2, 12, 25, 32, 2048, 2048),  # 3 / 3: 534 pixels per block (ragged last), block 1 crosses into the next image at
+}                                      #        pixel 800; 16-bit: 17 steps per lane = 4 unrolled trips + 1, the fold at step 12
+# (case, operands start 16 bytes into their buffers, storage); G has 39 M elements: bf16 and fp32 only
+BN_SWEEP = [(case, off, t) for case, off in [("A", 0), ("A", 1), ("B", 0), ("B", 1), ("C", 0), ("H", 0), ("D", 0), ("E", 0),
+                                             ("F", 0), ("G", 0)] for t in BN_TYPES if (case, t) != ("G", "f16")]
+NAN, SENTINEL = float("nan"), -7.0
+
+
+class _Slab:
+    """An [npix, c] operand of pixel stride ld that starts `off` elements into a flat buffer filled with `fill` (NaN for an
+    input: the neighbours must not leak in; a sentinel for an output: they must stay as they are)."""
+
+    def __init__(self, npix, c, ld, off, tdt, fill, values=None):
+        self.buf = torch.full((npix * ld + off,), fill, dtype=tdt, device=DEV)
+        self.v = self.buf.as_strided((npix, c), (ld, 1), off)
+        self.fill = fill
+        if values is not None:
+            self.v.copy_(values.reshape(npix, c))
+        self.ptr = self.v.data_ptr()
+
+    def outside_intact(self):
+        if self.v.numel() == self.buf.numel():
+            return True
+        m = torch.ones(self.buf.shape, dtype=torch.bool, device=DEV)
+        m.as_strided(self.v.shape, self.v.stride(), self.v.storage_offset()).fill_(False)
+        out = self.buf[m]
+        return bool(torch.isnan(out).all()) if self.fill != self.fill else bool((out == self.fill).all())
+
+
+def _hold(tag, what, got, want, tol, floor=0.0):
+    """max |got - want| <= tol * max |want| + floor, in float64 on the device; the figure is printed first."""
+    got, want = got.double(), want.double()
+    scale = max(float(want.abs().max()), 1e-30)
+    err = float((got.reshape(want.shape) - want).abs().max())
+    print("%s %-12s rel %.3e (bound %.1e)" % (tag, what, err / scale, tol))
+    assert err <= tol * scale + floor, "%s %s: max|diff| %.3e vs scale %.3e (%.2e rel)" % (tag, what, err, scale, err / scale)
+
+
+def _hold_totals(tag, what, acc, want0, want1):
+    """The fp64 accumulator [V, c, 2] against the reference totals: 1e-6 of the largest total + 1e-9 each."""
+    _hold(tag, what + "[0]", acc[..., 0], want0, 1e-6, 1e-9)
+    _hold(tag, what + "[1]", acc[..., 1], want1, 1e-6, 1e-9)
+
+
+def _bn_operands(case, off, tdt):
+    """(z, dy) as NaN-padded slabs of values representable in the storage type, beta, gamma, counts, element offset."""
+    N, V, h, w, c, ld = BN_CASES[case]
+    npix = N * V * h * w
+    o = off * (16 // torch.empty(0, dtype=tdt).element_size())
+    g = torch.Generator(device=DEV).manual_seed(ord(case) * 2 + off)
+    z = _Slab(npix, c, ld, o, tdt, NAN, (torch.randn(npix, c, generator=g, device=DEV) * 2 + 0.5).to(tdt))
+    dy = _Slab(npix, c, ld, o, tdt, NAN, torch.randn(npix, c, generator=g, device=DEV).to(tdt))
+    beta = torch.randn(c, generator=g, device=DEV)
+    gamma = torch.rand(c, generator=g, device=DEV) + 0.5
+    counts = torch.full((V,), N * h * w, dtype=torch.int32, device=DEV)
+    return z, dy, beta, gamma, counts, o, g
+
+
+def _bn_stats(V, c, fill=NAN):
+    return {k: torch.full((V, c), fill, device=DEV) for k in ("mean", "var", "inv", "scale", "shift")}
+
+
+@pytest.mark.parametrize("case,off,tname", BN_SWEEP)
+def test_bn_kernels_over_their_launch_geometries_against_fp64(case, off, tname):
+    """gv_bn_sums_grouped_t / gv_bn_finalize_grouped / gv_scale_shift_act_grouped_t / gv_bn_finalize_apply_grouped_t and
+    gv_bn_relu_bwd_{sums,apply}_grouped_t on fp32, bf16 and fp16 storage at the geometries of BN_CASES — several pixel splits,
+    blocks that start inside an image, several and ragged channel blocks, maps smaller than the pixel-lane count, the unrolled
+    loop with its tail and fp32 fold, operands that are channel slices of wider buffers and start 16 bytes into them, the
+    scalar kernels — against the fp64 restatement of tests/bn_ref.py evaluated on the stored values, with and without gamma.
+    The ReLU mask of the backward reference is taken as the kernel defines it (the stored y > 0, or float32(z*scale + shift)
+    > 0 with the device's scale / shift).  Accumulators start as garbage (the sums clear them), dz / dbeta / dgamma start
+    non-zero where the contract is +=, dz starts as NaN where it is stored, and nothing outside a slice may change.
+
+    Measured worst case over all geometries (relative to the tensor's scale; bound):
+                     fp32      bf16      fp16
+      mean           4.3e-8    4.4e-8    4.2e-8     (1e-5)
+      var            5.2e-8    7.4e-8    8.8e-8     (1e-5)
+      y              1.0e-7    3.5e-3    4.2e-4     (1e-5 / 2^-8 = 3.9e-3 / 2^-11 = 4.9e-4: half an ulp at the foot of a binade)
+      dz             1.4e-7    3.8e-3    4.6e-4     (1e-4 / 2^-7 = 7.8e-3 / 2^-10 = 9.8e-4)
+      dbeta          8.4e-8    8.3e-8    9.1e-8     (1e-5)
+      dgamma         8.2e-8    1.0e-7    9.6e-8     (1e-4)
+      totals         8.0e-8    9.1e-8    9.2e-8     (1e-6; the backward ones carry the fp32 rounding of zhat)"""
+    dt, tdt, tol_y, tol_dz = BN_TYPES[tname]
+    N, V, h, w, c, ld = BN_CASES[case]
+    nb, hw, npix = N * V, h * w, N * V * h * w
+    L = lib()
+    z, dy, beta, gamma, counts, o, g = _bn_operands(case, off, tdt)
+    shape = (nb, hw, c)
+    zs, dys = z.v.reshape(shape), dy.v.reshape(shape)            # the stored values
+    pre = ((torch.rand(npix, c, generator=g, device=DEV) - 0.5) / 2).to(tdt)
+    db0, dg0 = torch.randn(c, generator=g, device=DEV), torch.randn(c, generator=g, device=DEV)
+    no_f32_apply = dt == _lib.GV_F32 and c % 4 != 0              # fp32 storage has no forward apply for such a shape
+
+    def slab(fill, values=None):
+        return _Slab(npix, c, ld, o, tdt, fill, values)
+
+    def garbage():
+        return torch.full((V, c, 2), 1e30, dtype=torch.float64, device=DEV)
+
+    for gm in (None, gamma):
+        tag = "bn %s%s %s %s" % (case, "+16B" if off else "", tname, "gamma" if gm is not None else "-")
+        gp = gm.data_ptr() if gm is not None else None
+        # ---- forward: sums -> finalize -> apply, and the same as finalize + apply in one call
+        ref = bn_ref.forward(zs, V, beta, gm, 1e-3)
+        accum, stt, y = garbage(), _bn_stats(V, c), slab(SENTINEL)
+        _lib.check(L.gv_bn_sums_grouped_t(z.ptr, nb, hw, c, ld, V, accum.data_ptr(), dt, st()), "sums")
+        _lib.check(L.gv_bn_finalize_grouped(accum.data_ptr(), c, V, counts.data_ptr(), gp, beta.data_ptr(), 1e-3,
+                                            stt["mean"].data_ptr(), stt["var"].data_ptr(), stt["inv"].data_ptr(),
+                                            stt["scale"].data_ptr(), stt["shift"].data_ptr(), st()), "finalize")
+        rc = L.gv_scale_shift_act_grouped_t(z.ptr, nb, hw, c, ld, stt["scale"].data_ptr(), stt["shift"].data_ptr(), V, 1,
+                                            y.ptr, ld, dt, st())
+        _hold_totals(tag, "sum z,z^2", accum, ref["sum_z"], ref["sum_z2"])
+        _hold(tag, "mean", stt["mean"], ref["mean"], 1e-5)
+        _hold(tag, "var", stt["var"], ref["var"], 1e-5)
+        st2, y2 = _bn_stats(V, c, 7.0), slab(SENTINEL)
+        rc2 = L.gv_bn_finalize_apply_grouped_t(accum.data_ptr(), counts.data_ptr(), gp, beta.data_ptr(), 1e-3, z.ptr, nb, hw,
+                                               c, ld, V, 1, y2.ptr, ld, st2["mean"].data_ptr(), st2["var"].data_ptr(),
+                                               st2["inv"].data_ptr(), st2["scale"].data_ptr(), st2["shift"].data_ptr(), dt,
+                                               st())
+        for k in stt:
+            assert torch.equal(st2[k], stt[k]), k
+        if no_f32_apply:
+            assert rc == _lib.GV_E_ALIGN and rc2 == _lib.GV_E_ALIGN
+            assert bool((y.buf == SENTINEL).all()) and bool((y2.buf == SENTINEL).all())
+            # the activation such a layer would keep: one rounding of z*scale + shift with the device's scale / shift
+            lin = zs.double().reshape(N, V, hw, c) * stt["scale"].double()[None, :, None, :] + \
+                stt["shift"].double()[None, :, None, :]
+            y.v.copy_(lin.float().clamp_min(0.0).reshape(npix, c))
+        else:
+            _lib.check(rc, "apply")
+            _lib.check(rc2, "finalize + apply")
+            _hold(tag, "y", y.v, ref["y"].reshape(npix, c), tol_y)
+            assert torch.equal(y2.buf, y.buf) and y.outside_intact()
+        # ---- backward from the kept activation: its mask is the stored y > 0; dz, dbeta, dgamma are accumulated into
+        ys = y.v.reshape(shape)
+        rb = bn_ref.backward(zs, dys, ys > 0, V, gm, 1e-3)
+        acc_y, dz = garbage(), slab(SENTINEL, pre)
+        dbeta, dgamma = db0.clone(), dg0.clone()
+        _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy.ptr, ld, y.ptr, ld, z.ptr, ld, stt["mean"].data_ptr(),
+                                                   stt["inv"].data_ptr(), nb, hw, c, V, acc_y.data_ptr(), None, None, dt,
+                                                   st()), "bwd sums (kept y)")
+        _lib.check(L.gv_bn_relu_bwd_apply_grouped_t(dy.ptr, ld, y.ptr, ld, z.ptr, ld, stt["mean"].data_ptr(),
+                                                    stt["inv"].data_ptr(), gp, counts.data_ptr(), nb, hw, c, V,
+                                                    acc_y.data_ptr(), dz.ptr, ld, dbeta.data_ptr(),
+                                                    dgamma.data_ptr() if gm is not None else None, None, None, 1, dt, st()),
+                   "bwd apply (kept y)")
+        _hold_totals(tag, "sum g,gzh", acc_y, rb["sum_g"], rb["sum_gzh"])
+        _hold(tag, "dz", dz.v.double() - pre.double(), rb["dz"].reshape(npix, c), tol_dz)
+        _hold(tag, "dbeta", dbeta.double() - db0.double(), rb["dbeta"], 1e-5)
+        if gm is not None:
+            _hold(tag, "dgamma", dgamma.double() - dg0.double(), rb["dgamma"], 1e-4)
+        else:
+            assert torch.equal(dgamma, dg0)
+        assert dz.outside_intact()
+        # ---- the engine's form: mask recomputed from z (y is not read), dz STORED over NaN
+        rz = bn_ref.backward(zs, dys, bn_ref.mask_from_z(zs, V, stt["scale"], stt["shift"]), V, gm, 1e-3)
+        acc_z, dz2, dz3 = garbage(), slab(SENTINEL), slab(SENTINEL)
+        dz2.v.fill_(NAN)
+        dz3.v.zero_()
+        _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy.ptr, ld, None, 0, z.ptr, ld, stt["mean"].data_ptr(),
+                                                   stt["inv"].data_ptr(), nb, hw, c, V, acc_z.data_ptr(),
+                                                   stt["scale"].data_ptr(), stt["shift"].data_ptr(), dt, st()),
+                   "bwd sums (mask from z)")
+        _hold_totals(tag, "sum g,gzh", acc_z, rz["sum_g"], rz["sum_gzh"])
+        # Both masks select the same elements (an fp16 y may underflow to 0 where z*scale + shift > 0: fp16 has the two
+        # comparisons with the reference above instead), so the two sums are the same bits — where the sums are order-
+        # independent at all, i.e. inside the exactness range of their fixed grid: 2^13 on 16-bit storage, 2 on fp32.  fp32
+        # sums of three splits beyond it differ by the rounding of three fp64 additions (<= 2^-50 of sum |g|, asserted;
+        # measured 1.2e-16 on cases B and G, 0 elsewhere), so fp32 repeats the two launches with dy * 2^-10.
+        bound = torch.stack([rb["sum_abs_g"], rb["sum_abs_gzh"]], dim=-1)
+        print("%s kept-y vs recomputed sums: max |diff| / sum|g| %.3e" % (tag, float(((acc_z - acc_y).abs() / bound.clamp_min(1e-300)).max())))
+        if tname == "bf16":
+            assert float(bound.max()) < 2.0 ** 13 and torch.equal(acc_z, acc_y)
+        elif tname == "f32":
+            assert bool(((acc_z - acc_y).abs() <= 2.0 ** -50 * bound).all())
+            assert float(bound.max()) * 2.0 ** -10 < 2.0
+            dy_s, acc_ys, acc_zs = slab(NAN, dy.v * 2.0 ** -10), garbage(), garbage()
+            for a, yp, sp, hp in ((acc_ys, y.ptr, None, None), (acc_zs, None, stt["scale"].data_ptr(), stt["shift"].data_ptr())):
+                _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy_s.ptr, ld, yp, ld if yp else 0, z.ptr, ld,
+                                                           stt["mean"].data_ptr(), stt["inv"].data_ptr(), nb, hw, c, V,
+                                                           a.data_ptr(), sp, hp, dt, st()), "bwd sums (dy * 2^-10)")
+            assert torch.equal(acc_zs, acc_ys)
+            _hold_totals(tag, "sum g,gzh", acc_zs, rz["sum_g"] * 2.0 ** -10, rz["sum_gzh"] * 2.0 ** -10)
+        for out, accumulate in ((dz2, 0), (dz3, 1)):
+            _lib.check(L.gv_bn_relu_bwd_apply_grouped_t(dy.ptr, ld, None, 0, z.ptr, ld, stt["mean"].data_ptr(),
+                                                        stt["inv"].data_ptr(), gp, counts.data_ptr(), nb, hw, c, V,
+                                                        acc_z.data_ptr(), out.ptr, ld, None, None, stt["scale"].data_ptr(),
+                                                        stt["shift"].data_ptr(), accumulate, dt, st()),
+                       "bwd apply (mask from z)")
+        _hold(tag, "dz", dz2.v, rz["dz"].reshape(npix, c), tol_dz)
+        assert torch.equal(dz2.v, dz3.v)                         # a store is an accumulation into zeros
+        assert dz2.outside_intact() and dz3.outside_intact()
+    assert z.outside_intact() and dy.outside_intact()
+
+
+@pytest.mark.parametrize("case,tname", [(case, t) for case in "ABG" for t in BN_TYPES if (case, t) != ("G", "f16")])
+def test_bn_split_sums_do_not_depend_on_the_order_of_their_blocks(case, tname):
+    """The blocks of a sums launch round their partials to a fixed grid before the fp64 atomics, so inside the documented
+    ranges (fp32 storage: sum z < 2^13, sum z^2 < 2^17, backward < 2; 16-bit: 2^23 / 2^29 / 2^13) every addition is exact and
+    two runs give the same bits whatever order the 2 or 3 pixel splits arrive in.  That the inputs ARE inside the ranges is
+    asserted from the reference's totals of absolute values, which bound every partial sum."""
+    dt, tdt, _, _ = BN_TYPES[tname]
+    N, V, h, w, c, ld = BN_CASES[case]
+    nb, hw = N * V, h * w
+    L = lib()
+    z, dy, beta, _, counts, _, _ = _bn_operands(case, 0, tdt)
+    if dt == _lib.GV_F32:
+        dy.v.mul_(2.0 ** -10)                                    # (a power of two: still exact values)
+    zs, dys = z.v.reshape(nb, hw, c), dy.v.reshape(nb, hw, c)
+    lim_z, lim_z2, lim_b = (2.0 ** 13, 2.0 ** 17, 2.0) if dt == _lib.GV_F32 else (2.0 ** 23, 2.0 ** 29, 2.0 ** 13)
+    ref = bn_ref.forward(zs, V, beta, None, 1e-3)
+    assert float(ref["sum_abs_z"].max()) < lim_z and float(ref["sum_z2"].max()) < lim_z2
+    acc = [torch.full((V, c, 2), 1e30, dtype=torch.float64, device=DEV) for _ in range(2)]
+    for a in acc:
+        _lib.check(L.gv_bn_sums_grouped_t(z.ptr, nb, hw, c, ld, V, a.data_ptr(), dt, st()), "sums")
+    assert torch.equal(acc[0], acc[1])
+    stt = _bn_stats(V, c)
+    _lib.check(L.gv_bn_finalize_grouped(acc[0].data_ptr(), c, V, counts.data_ptr(), None, beta.data_ptr(), 1e-3,
+                                        stt["mean"].data_ptr(), stt["var"].data_ptr(), stt["inv"].data_ptr(),
+                                        stt["scale"].data_ptr(), stt["shift"].data_ptr(), st()), "finalize")
+    rz = bn_ref.backward(zs, dys, bn_ref.mask_from_z(zs, V, stt["scale"], stt["shift"]), V, None, 1e-3)
+    assert float(rz["sum_abs_g"].max()) < lim_b and float(rz["sum_abs_gzh"].max()) < lim_b
+    accb = [torch.full((V, c, 2), 1e30, dtype=torch.float64, device=DEV) for _ in range(2)]
+    for a in accb:
+        _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy.ptr, ld, None, 0, z.ptr, ld, stt["mean"].data_ptr(),
+                                                   stt["inv"].data_ptr(), nb, hw, c, V, a.data_ptr(), stt["scale"].data_ptr(),
+                                                   stt["shift"].data_ptr(), dt, st()), "bwd sums")
+    assert torch.equal(accb[0], accb[1])
+    _hold_totals("order %s %s" % (case, tname), "sum g,gzh", accb[0], rz["sum_g"], rz["sum_gzh"])
+
+
 @pytest.mark.parametrize("dt,tdt,eps", TYPES)
 @pytest.mark.parametrize("k,stride,padding,mode", [(3, 2, "VALID", "max"), (3, 2, "SAME", "max"),
                                                     (3, 1, "SAME", "avg"), (1, 2, "VALID", "max"),
@@ -244,7 +489,42 @@ def test_accumulate_and_bias_grad_typed(dt, tdt, eps):
         close(db.cpu() - 0.5, src.sum(0), 1e-5)
 
 
-CONVS = [((3, 3), 1, "SAME", 32, 48, 3, 12, 11), ((3, 3), 2, "VALID", 32, 64, 3, 12, 11),
+@pytest.mark.parametrize("tname", list(BN_TYPES))
+@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7)])
+def test_bias_grad_over_several_pixel_splits(tname, c, ld):
+    """gv_bias_grad_t with more than one pixel split (fp32: 2100 pixels = 2 workgroups of 2048; 16-bit: 300 pixels = 3 of
+    128), on the streaming and on the scalar kernel, a slice of a wider buffer whose other channels hold NaN: dbias, which
+    starts non-zero, grows by the fp64 column sums (bound 1e-5 of their scale; measured 3.4e-8 / 4.0e-8 / 4.2e-8 on fp32 /
+    bf16 / fp16)."""
+    dt, tdt, _, _ = BN_TYPES[tname]
+    npix = 2100 if dt == _lib.GV_F32 else 300
+    g = torch.Generator(device=DEV).manual_seed(c)
+    dz = _Slab(npix, c, ld, 0, tdt, NAN, torch.randn(npix, c, generator=g, device=DEV).to(tdt))
+    db0 = torch.randn(c, generator=g, device=DEV)
+    db = db0.clone()
+    accum = torch.full((2 * c,), 1e30, dtype=torch.float64, device=DEV)
+    _lib.check(lib().gv_bias_grad_t(dz.ptr, ld, npix, c, accum.data_ptr(), db.data_ptr(), dt, st()), "bias")
+    _hold("bias %s c=%d" % (tname, c), "dbias", db.double() - db0.double(), dz.v.double().sum(0), 1e-5)
+    assert dz.outside_intact()
+
+
+@pytest.mark.parametrize("tname", list(BN_TYPES))
+@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7)])
+def test_accumulate_is_the_exact_sum_rounded_once(tname, c, ld):
+    """gv_accumulate_t at 300 pixels (more than one workgroup), vector and scalar kernel, slices of wider buffers: dst is the
+    sum formed in fp64 and rounded once to the storage type, bit for bit; the other channels of dst keep their sentinel."""
+    dt, tdt, _, _ = BN_TYPES[tname]
+    npix = 300
+    g = torch.Generator(device=DEV).manual_seed(c + 1)
+    src = _Slab(npix, c, ld, 0, tdt, NAN, torch.randn(npix, c, generator=g, device=DEV).to(tdt))
+    dst = _Slab(npix, c, ld, 0, tdt, SENTINEL, torch.randn(npix, c, generator=g, device=DEV).to(tdt))
+    want = (src.v.double() + dst.v.double()).to(tdt)
+    _lib.check(lib().gv_accumulate_t(src.ptr, ld, dst.ptr, ld, npix, c, dt, st()), "acc")
+    assert torch.equal(dst.v, want)
+    assert dst.outside_intact() and src.outside_intact()
+
+
+CONVS =[((3, 3), 1, "SAME", 32, 48, 3, 12, 11), ((3, 3), 2, "VALID", 32, 64, 3, 12, 11),
          ((1, 7), 1, "SAME", 48, 32, 3, 12, 11), ((5, 5), 1, "SAME", 48, 64, 3, 12, 11),
          ((3, 3), 1, "VALID", 80, 96, 3, 12, 11), ((1, 1), 1, "SAME", 96, 32, 3, 12, 11),
          ((3, 3), 2, (1, 1, 1, 1), 64, 64, 3, 12, 11), ((1, 1), 2, "VALID", 64, 128, 3, 12, 11),
