@@ -41,6 +41,7 @@ GV_PNG_STATUS = ("OK", "TRUNCATED", "BAD_HEADER", "BAD_BLOCK", "BAD_CODES", "BAD
                  "BAD_CHECKSUM", "BAD_FILTER", "BAD_PALETTE_INDEX")      # GV_PNG_* of the header, by value
 (GV_PNG_OK, GV_PNG_TRUNCATED, GV_PNG_BAD_HEADER, GV_PNG_BAD_BLOCK, GV_PNG_BAD_CODES, GV_PNG_BAD_DISTANCE, GV_PNG_TOO_LONG,
  GV_PNG_TOO_SHORT, GV_PNG_BAD_CHECKSUM, GV_PNG_BAD_FILTER, GV_PNG_BAD_PALETTE_INDEX) = range(11)
+GV_PNG_FILTER_ADAPTIVE, GV_PNG_COLOR_AUTO, GV_PNG_COLOR_RGB = 5, 0, 1
 GV_ABI_VERSION = 1
 
 
@@ -143,6 +144,11 @@ SIGNATURES = {
     "gv_png_decode_workspace_bytes": (_L, [_I, _L]),
     "gv_png_decode_batch": (C.c_int, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     "gv_png_decode_host": (C.c_int, [_P, _L, _P, _I, _I, _I, _P, _P, _P]),
+    "gv_png_encode_segment_bytes": (_L, []),
+    "gv_png_encode_bound": (_L, [_I, _I]),
+    "gv_png_encode_workspace_bytes": (_L, [_I, _I, _I]),
+    "gv_png_encode_batch": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P]),
+    "gv_png_encode_host": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "gv_eval_metrics": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "gv_retr_prepare": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "gv_knn_workspace_bytes": (_L, [_I, _I, _I]),

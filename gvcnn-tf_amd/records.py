@@ -12,6 +12,10 @@
 The writer halves (write_tfrecords / make_example / encode_png) exist for tests and for building fixtures; they
 produce files the reference's own readers accept (masked CRC32C framing).  Pure Python + zlib: decoding stays on
 host cores, the arithmetic on the pixels happens on the device.
+
+    encode_png_batch(views)       uint8 [n, h, w, 3] -> n PNG files through the batch encoder: a CUDA tensor on the
+                                  device (gv_png_encode_batch), a numpy array through its host twin; the host only
+                                  frames the chunks (png_from_stream)
 """
 import gzip
 import struct
@@ -303,6 +307,79 @@ def encode_png(img):
     raw = b"".join(b"\x00" + img[y].tobytes() for y in range(h))
     return (_PNG_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
             chunk(b"IDAT", zlib.compress(raw)) + chunk(b"IEND", b""))
+
+
+def png_from_stream(w, h, color_type, stream):
+    """A PNG file around a ready zlib stream: signature, IHDR (8 bits, the colour type, no interlace), one IDAT, IEND."""
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+    return (_PNG_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", int(w), int(h), 8, int(color_type), 0, 0, 0)) +
+            chunk(b"IDAT", bytes(stream)) + chunk(b"IEND", b""))
+
+
+_PNG_FILTERS = {"adaptive": 5, "none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4}
+_PNG_COLORS = {"auto": 0, "rgb": 1}
+
+
+def _png_encode_constants(filter, color):
+    if filter not in _PNG_FILTERS and filter not in (0, 1, 2, 3, 4):
+        raise ValueError("filter must be 'adaptive', 'none', 'sub', 'up', 'average', 'paeth' or a PNG filter type 0-4")
+    if color not in _PNG_COLORS:
+        raise ValueError("color must be 'auto' or 'rgb'")
+    return _PNG_FILTERS.get(filter, filter), _PNG_COLORS[color]
+
+
+def encode_png_streams(views, filter="adaptive", color="auto"):
+    """uint8 [n, h, w, 3] -> (streams uint8 [n, max length] on the host, length int32 [n], colour type int32 [n]): the
+    zlib stream of every view.  A CUDA tensor is encoded by the device (gv_png_encode_batch: only the used part of the
+    stream buffer and the two int arrays come back), a numpy array by the host twin (gv_png_encode_host); the bytes are
+    the same."""
+    from . import _lib
+    lib = _lib.load()
+    ft, col = _png_encode_constants(filter, color)
+    if isinstance(views, np.ndarray):
+        views = np.ascontiguousarray(views, np.uint8)
+        if views.ndim != 4 or views.shape[3] != 3 or 0 in views.shape:
+            raise ValueError("views must be uint8 [n, h, w, 3]")
+        n, h, w, _ = views.shape
+        stride = lib.gv_png_encode_bound(h, w)
+        _lib.check(stride if stride < 0 else 0, "gv_png_encode_bound")
+        out = np.empty((n, stride), np.uint8)
+        length, ctype = np.empty(n, np.int32), np.empty(n, np.int32)
+        _lib.check(lib.gv_png_encode_host(views.ctypes.data, n, h, w, ft, col, out.ctypes.data, stride, length.ctypes.data,
+                                          ctype.ctypes.data), "gv_png_encode_host")
+        return out[:, :int(length.max())], length, ctype
+    import torch
+    from .model import _st
+    if (not torch.is_tensor(views) or not views.is_cuda or views.dtype != torch.uint8 or views.dim() != 4
+            or views.shape[3] != 3 or 0 in views.shape):
+        raise ValueError("views must be a uint8 [n, h, w, 3] numpy array or CUDA tensor")
+    views = views.contiguous()
+    n, h, w, _ = views.shape
+    with torch.cuda.device(views.device):
+        stride = lib.gv_png_encode_bound(h, w)
+        _lib.check(stride if stride < 0 else 0, "gv_png_encode_bound")
+        ws_bytes = lib.gv_png_encode_workspace_bytes(n, h, w)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_png_encode_workspace_bytes")
+        out = torch.empty((n, stride), dtype=torch.uint8, device=views.device)
+        info = torch.empty((2, n), dtype=torch.int32, device=views.device)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=views.device)
+        _lib.check(lib.gv_png_encode_batch(views.data_ptr(), n, h, w, ft, col, out.data_ptr(), stride, info[0].data_ptr(),
+                                           info[1].data_ptr(), ws.data_ptr(), ws_bytes, _st()), "gv_png_encode_batch")
+        host = info.cpu().numpy()
+        length, ctype = host[0], host[1]
+        if (length <= 0).any():
+            raise RuntimeError("gv_png_encode_batch: a segment did not fit its slot")
+        return out[:, :int(length.max())].cpu().numpy(), length, ctype
+
+
+def encode_png_batch(views, filter="adaptive", color="auto"):
+    """uint8 [n, h, w, 3] (a CUDA tensor: encoded on the device; a numpy array: by the host twin) -> n PNG files
+    (bytes): colour type 0 for a view whose pixels are all gray (color="rgb": always 2), the line filter chosen per row
+    (filter: "adaptive", or one PNG filter type for every row).  The host frames the chunks (png_from_stream)."""
+    h, w = int(views.shape[1]), int(views.shape[2])
+    streams, length, ctype = encode_png_streams(views, filter, color)
+    return [png_from_stream(w, h, int(ctype[i]), streams[i, :int(length[i])].tobytes()) for i in range(len(length))]
 
 
 def _decode_record(rec, num_views):

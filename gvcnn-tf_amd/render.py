@@ -628,3 +628,13 @@ class ViewRenderer:
     def render_uint8(self, batch, rotations=None, out=None, return_buffers=False):
         """views uint8 [N, V, H, W, 3] on the device (what a PNG of the render holds)."""
         return self._render(batch, rotations, out, _lib.GV_RENDER_OUT_U8, return_buffers)
+
+    def render_png(self, batch, rotations=None, filter="adaptive", color="auto"):
+        """One list of V PNG files (bytes) per mesh: render_uint8, then the device encoder (records.encode_png_batch:
+        the pixels stay on the device, the finished zlib streams come back).  Sets `status` as render_uint8 does."""
+        from . import records
+        views = self.render_uint8(batch, rotations)
+        n = views.shape[0]
+        with torch.cuda.device(self.device):
+            pngs = records.encode_png_batch(views.view(n * self.V, self.H, self.W, 3), filter, color)
+        return [pngs[i * self.V:(i + 1) * self.V] for i in range(n)]

@@ -445,6 +445,40 @@ int gv_png_decode_batch(const uint8_t* streams, int64_t stream_bytes, const gv_p
 int gv_png_decode_host(const uint8_t* streams, int64_t stream_bytes, const gv_png_image* images, int32_t n,
                        int32_t h0, int32_t w0, const uint8_t* palettes, uint8_t* out, int32_t* status);
 
+/* ---- PNG encode of a whole batch (the mirror of the decoder: colour type, line filter, DEFLATE) ------------------------
+ * Input: src [n, h0, w0, 3] uint8.  Output: the zlib stream (what one IDAT chunk holds) of image i in
+ * out[i * out_stride, i * out_stride + length[i]), and color_type[i]: 0 (gray, one byte per pixel) or 2 (RGB).  The
+ * caller frames the chunks (signature, IHDR, IDAT, IEND, CRC-32).  Bytes of a slot past length[i] are not written.
+ *  - color: GV_PNG_COLOR_AUTO stores an image whose every pixel has R = G = B as colour type 0, GV_PNG_COLOR_RGB never.
+ *  - filter: 0-4 forces that PNG filter type on every row; GV_PNG_FILTER_ADAPTIVE takes per row the type with the smallest
+ *    sum of |signed residual| (a residual byte v counts v below 128, 256 - v otherwise), the lowest type on a tie; the
+ *    candidates are computed from the unfiltered neighbours.
+ *  - stream: 78 01, then the raw stream (h0 rows of filter byte + w0 * channels bytes) in SEGMENTS of
+ *    gv_png_encode_segment_bytes() bytes, each encoded on its own — run matches at distance 1 and at the pixel stride,
+ *    lengths 3-258; stored, fixed or dynamic Huffman block, whichever is shortest (ties: stored, fixed, dynamic) — and
+ *    every segment but the last followed by an empty non-final stored block; then the Adler-32.  The bytes are the same
+ *    on every run and the same from both entry points.
+ * gv_png_encode_bound: the most bytes the stream of an h0 x w0 image can take, a multiple of 16.  out_stride must be at
+ * least that and a multiple of 16.
+ * GV_E_BADARG: NULL pointer, n / h0 / w0 <= 0, unknown filter or colour constant, out_stride too small or not a multiple
+ * of 16, workspace too small.  GV_E_ALIGN: ws not 16-byte aligned.  GV_E_UNSUPPORTED: h0 * (1 + 3 * w0) does not fit 31
+ * bits (or the batch has more than 2^31 - 1 segments).  Arguments are checked before any HIP call.
+ * gv_png_encode_batch: src, out, length, color_type and ws are DEVICE memory; ws: gv_png_encode_workspace_bytes(n, h0,
+ * w0) bytes, 16-byte aligned (the filtered rows, the segments' outputs and their lengths / Adler sums).  No global
+ * atomics.  gv_png_encode_host: the same encoder run serially on host memory, no workspace. */
+#define GV_PNG_FILTER_ADAPTIVE 5
+#define GV_PNG_COLOR_AUTO 0
+#define GV_PNG_COLOR_RGB 1
+int64_t gv_png_encode_segment_bytes(void);
+/* negative: an error code (h0, w0 <= 0: GV_E_BADARG; 31 bits exceeded: GV_E_UNSUPPORTED) */
+int64_t gv_png_encode_bound(int32_t h0, int32_t w0);
+int64_t gv_png_encode_workspace_bytes(int32_t n, int32_t h0, int32_t w0);
+int gv_png_encode_batch(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t filter, int32_t color,
+                        uint8_t* out, int64_t out_stride, int32_t* length, int32_t* color_type, void* ws,
+                        int64_t ws_bytes, void* stream);
+int gv_png_encode_host(const uint8_t* src, int32_t n, int32_t h0, int32_t w0, int32_t filter, int32_t color,
+                       uint8_t* out, int64_t out_stride, int32_t* length, int32_t* color_type);
+
 /* ---- evaluation metrics (eval.py:94-99) ---------------------------------------------------------
  * prediction[n] = argmax_c logits[n,c] (first maximum, like tf.argmax); confusion[label, prediction] += 1
  * (tf.math.confusion_matrix, int32 [C,C], ACCUMULATED so a whole evaluation run needs one buffer);

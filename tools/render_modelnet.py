@@ -47,6 +47,9 @@ def main(argv=None):
     ap.add_argument("--shininess", type=int, default=16, help="exponent of the highlight: 1, 2, 4, ..., 128")
     ap.add_argument("--two-sided", action="store_true", help="shade both faces alike (inconsistently wound meshes)")
     ap.add_argument("--batch", type=int, default=32, help="meshes per device render")
+    ap.add_argument("--encode", default="host", choices=("host", "device"),
+                    help="host: copy the pixels back and deflate every view with zlib; device: the views leave the device as "
+                         "finished PNG streams (adaptive line filter, colour type 0 for gray views; ViewRenderer.render_png)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     import torch
@@ -65,12 +68,17 @@ def main(argv=None):
     def examples():
         for b0 in range(0, len(shapes), a.batch):
             part = shapes[b0:b0 + a.batch]
-            views = r.render_uint8([render.load_off(p) for p, _ in part]).cpu().numpy()
-            for (p, label), st, v in zip(part, r.status, views):
+            meshes = [render.load_off(p) for p, _ in part]
+            if a.encode == "device":
+                encoded = r.render_png(meshes)
+            else:
+                views = r.render_uint8(meshes).cpu().numpy()
+                encoded = ([records.encode_png(v[i]) for i in range(a.views)] for v in views)
+            for (p, label), st, pngs in zip(part, r.status, encoded):
                 if st != gv._lib.GV_RENDER_OK:
                     print("warning: %s renders as background (%s)" % (p, render.STATUS.get(int(st), st)),
                           file=sys.stderr)
-                yield records.make_example([records.encode_png(v[i]) for i in range(a.views)], label)
+                yield records.make_example(pngs, label)
     records.write_tfrecords(a.out, examples())
     print("%d shapes of %d classes -> %s" % (len(shapes), len(classes), a.out))
 
