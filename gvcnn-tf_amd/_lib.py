@@ -249,11 +249,9 @@ TUNING = {
     "gv_bottleneck_chain_set_debug": (None, [C.c_int]),
     "gv_conv2d_num_tile_cfgs": (C.c_int, [C.c_int]),
     "gv_conv2d_special_tile_cfg": (C.c_int, [C.c_int]),
-    "gv_conv2d_wgrad_set_v1": (None, [C.c_int]),
     "gv_conv2d_wgrad_set_lp_f32": (None, [C.c_int]),
     "gv_conv2d_wgrad_num_cfgs": (C.c_int, [C.c_int]),
     "gv_conv2d_wgrad_set_strip_taps": (None, [C.c_int]),
-    "gv_pool2d_bwd_set_scatter": (None, [C.c_int]),
     "gv_pool2d_set_rows": (None, [C.c_int]),
 }
 

@@ -1,6 +1,6 @@
 // Why a shape got its class: per-view, per-pixel attribution of one logit through the head above the final tap
 // (view pooling -> group fusion -> global average pool -> Dense), with the grouping held constant as in the backward
-// pass (view_pool_fuse_bwd_f32 in train.hip: the tie rule and the order of the coefficient's operations are its).
+// pass (view_pool_fuse_bwd_t in train_lp.hip: the tie rule and the order of the coefficient's operations are its).
 //
 //   dlogit_k/dF[n,v,p,c] = sum_{g contains v} ((w_g/W) * (K[c,k]/hw)) / ties_g(p,c)   where F[v] attains the maximum of g
 //                                                                     / |g|            mean pooling
@@ -110,7 +110,7 @@ __device__ __forceinline__ bool ex_groups(const ExArgs& a, int n, unsigned long 
     }
     __syncthreads();
     float ws = 0.f;
-    for (int g = 0; g < a.G; ++g) ws += cg[g];                  // the order of view_pool_fuse_bwd_f32
+    for (int g = 0; g < a.G; ++g) ws += cg[g];                  // the order of view_pool_fuse_bwd_t
     __syncthreads();
     if (ws != 0.f)
         for (int g = threadIdx.x; g < a.G; g += blockDim.x) cg[g] = cg[g] / ws;

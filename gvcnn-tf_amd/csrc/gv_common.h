@@ -165,7 +165,7 @@ __device__ __forceinline__ void gv_dw_put(const GvDw& o, int64_t slice, size_t i
     if (o.part) o.part[(size_t)slice * o.stride + idx] = v;      // (wave-uniform branch)
     else atomicAdd(&o.dw[idx], v);
 }
-// The tap-per-workgroup kernels (conv_wgrad_f32, conv_wgrad2_f32, conv_wgrad_lp) take one argument list: the layer, `per`
+// The tap-per-workgroup kernels (conv_wgrad2_f32, conv_wgrad_lp) take one argument list: the layer, `per`
 // pixels a slice, the sink.
 template <auto Kernel, typename E>
 int gv_wgrad_launch(dim3 grid, const gv_conv_desc* d, const E* x, const E* dz, int dz_ld, int64_t per, const GvDw& sink,

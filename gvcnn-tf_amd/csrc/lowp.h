@@ -17,7 +17,8 @@ int view_pool_fuse(int dtype, const void* F, int V, int N, int64_t E, int64_t vs
                    int64_t scheme_stride = 0, int64_t weight_stride = 0);
 
 
-// train_lp.hip: the training step on 16-bit storage
+// train_lp.hip: the HBM-bound ops of the training step for every storage type (dtype GV_F32 | GV_BF16 | GV_F16), and the
+// filter gradient of 16-bit storage
 int accumulate(int dtype, const void* src, int src_ld, void* dst, int dst_ld, int64_t npix, int c, hipStream_t st);
 int grouped_sums(int dtype, int mode, const void* z, int z_ld, const void* dy, int dy_ld, const void* y, int y_ld,
                  const float* mean, const float* inv, const float* scale, const float* shift, int nb, int hw, int c,

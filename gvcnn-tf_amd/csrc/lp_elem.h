@@ -1,5 +1,5 @@
-// Element helpers of the 16-bit storage kernels (lowp.hip, train_lp.hip): a 16-bit element travels as an
-// unsigned short, arithmetic is fp32, T = __bf16 or _Float16 selects the encoding.
+// Element helpers of the storage-typed kernels (lowp.hip, train_lp.hip): a 16-bit element travels as an
+// unsigned short, arithmetic is fp32, T = __bf16 or _Float16 selects the encoding; fp32 storage is E = T = float.
 #pragma once
 #include "gv_common.h"
 
@@ -10,7 +10,16 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ float up(unsigned short b) { return (float)__builtin_bit_cast(T, b); }
 template <typename T>
-__device__ __forceinline__ unsigned short down(float v) { const T h = (T)v; return __builtin_bit_cast(unsigned short, h); }
+__device__ __forceinline__ float up(float v) { return v; }      // fp32 storage (T = float): the identity
+template <typename T>
+__device__ __forceinline__ auto down(float v) {
+    if constexpr (sizeof(T) == 4) {
+        return v;
+    } else {
+        const T h = (T)v;
+        return __builtin_bit_cast(unsigned short, h);
+    }
+}
 
 template <typename T>
 __device__ __forceinline__ void unpack8(u32x4 v, float (&f)[8]) {

@@ -2,136 +2,17 @@
 // batch-statistics BatchNorm grouped by view (the reference builds one graph copy per view, so every
 // BN normalises over the N*h*w values of ONE view: nets/model.py:129-141 + slim.batch_norm with
 // is_training=True), the backward of every forward op, the loss (train.py:145) and the Momentum
-// update (train.py:171).  fp32 storage; reductions accumulate in fp64 (HBM-bound kernels, the fp64
-// adds are free) so that per-(view, channel) sums over up to 1.5e5 pixels are reproducible to fp32.
+// update (train.py:171).  This file holds the extern "C" entry points of the step, the fp32-only kernels (BatchNorm
+// finalize / parameter gradients / moving averages, loss, dense backward, optimizer) and the fp32-MFMA filter gradient.
+// The HBM-bound ops that exist for every storage type (BatchNorm sums and applies, accumulate, the pool and view-pool
+// backward) are checked here and launched by gvlp:: in train_lp.hip.  Reductions accumulate in fp64 (HBM-bound
+// kernels, the fp64 adds are free) so that per-(view, channel) sums over up to 1.5e5 pixels are reproducible to fp32.
 #include <math.h>
 
 #include "gv_common.h"
 #include "lowp.h"
 
 namespace {
-
-// dst[p][c] += src[p][c]  (gradient fan-in of the residual add, nets/resnet_v2.py:91)
-__global__ __launch_bounds__(256) void accumulate_f32(const float* __restrict__ src, int src_ld,
-                                                      float* __restrict__ dst, int dst_ld, int64_t npix, int c) {
-    const int64_t total = npix * c;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int ch = (int)(idx % c);
-        const int64_t pix = idx / c;
-        dst[pix * dst_ld + ch] += src[pix * src_ld + ch];
-    }
-}
-
-// ---- grouped per-(group, channel) sums -----------------------------------------------------------
-// acc[g][c][0] += sum u,  acc[g][c][1] += sum u*w   over the pixels of images b with b % G == g.
-//   MODE 0 (BN forward stats):  u = z,            w = z                       -> sum z, sum z^2
-//   MODE 1 (BN backward):       u = dy*[y>0],     w = (z-mean)*inv            -> sum g, sum g*zhat
-//   MODE 2 (bias gradient):     u = dz,           w = 0
-// Thread layout: VEC consecutive channels per thread (16-byte loads when VEC = 4), 64/VEC... threads span
-// 64 channels, the remaining threads of the 256 are pixel lanes; grid (channel blocks, pixel splits, G).
-template <int MODE, int VEC>
-__global__ __launch_bounds__(256) void grouped_sums_f32(const float* __restrict__ z, int z_ld,
-                                                        const float* __restrict__ dy, int dy_ld,
-                                                        const float* __restrict__ y, int y_ld,
-                                                        const float* __restrict__ mean,
-                                                        const float* __restrict__ inv, int nb, int hw, int c,
-                                                        int G, double* __restrict__ acc,
-                                                        const float* __restrict__ scale = nullptr,
-                                                        const float* __restrict__ shift = nullptr) {
-    constexpr int TPC = 64 / VEC;                          // threads across the 64-channel block
-    constexpr int PL = 256 / TPC;                          // pixel lanes
-    const int cl = threadIdx.x % TPC;
-    const int pl = threadIdx.x / TPC;
-    const int ch = blockIdx.x * 64 + cl * VEC;
-    const int g = blockIdx.z;
-    const int nimg = (nb - g + G - 1) / G;                 // images of this group
-    const int64_t npix = (int64_t)nimg * hw;
-    const int64_t per = (npix + gridDim.y - 1) / gridDim.y;
-    const int64_t p0 = (int64_t)blockIdx.y * per;
-    const int64_t p1 = p0 + per < npix ? p0 + per : npix;
-    double s0[VEC], s1[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) s0[e] = s1[e] = 0.0;
-    if (ch < c) {                                          // c % VEC == 0 (checked by the launcher)
-        float mu[VEC], iv[VEC], sc[VEC], sh[VEC];
-        const bool rmask = MODE == 1 && !y && scale;          // ReLU mask recomputed from z: [z*scale + shift > 0]
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            mu[e] = MODE == 1 ? mean[g * c + ch + e] : 0.f;
-            iv[e] = MODE == 1 ? inv[g * c + ch + e] : 0.f;
-            sc[e] = rmask ? scale[g * c + ch + e] : 0.f;
-            sh[e] = rmask ? shift[g * c + ch + e] : 0.f;
-        }
-        // division-free walk over the group's pixels (images g, g+G, ... of the batch): one division to start
-        int64_t pw = p0 + pl;
-        int kw_ = (int)(pw / hw);
-        int rw = (int)(pw - (int64_t)kw_ * hw);
-        int64_t pix = (int64_t)(kw_ * G + g) * hw + rw;
-        const int64_t step_img = (int64_t)(G - 1) * hw;
-        for (int64_t p = pw; p < p1; p += PL) {
-            float zv[VEC], gv[VEC], yv[VEC];
-            if constexpr (VEC == 4) {
-                if (MODE != 2) *reinterpret_cast<f32x4*>(zv) = *reinterpret_cast<const f32x4*>(z + pix * z_ld + ch);
-                if (MODE != 0) *reinterpret_cast<f32x4*>(gv) = *reinterpret_cast<const f32x4*>(dy + pix * dy_ld + ch);
-                if (MODE == 1 && y) *reinterpret_cast<f32x4*>(yv) = *reinterpret_cast<const f32x4*>(y + pix * y_ld + ch);
-            } else {
-                if (MODE != 2) zv[0] = z[pix * z_ld + ch];
-                if (MODE != 0) gv[0] = dy[pix * dy_ld + ch];
-                if (MODE == 1 && y) yv[0] = y[pix * y_ld + ch];
-            }
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                if (MODE == 0) {
-                    s0[e] += zv[e];
-                    s1[e] += (double)zv[e] * zv[e];
-                } else if (MODE == 1) {
-                    float gr = gv[e];
-                    if (y && !(yv[e] > 0.f)) gr = 0.f;
-                    if (rmask && !(zv[e] * sc[e] + sh[e] > 0.f)) gr = 0.f;
-                    s0[e] += gr;
-                    s1[e] += (double)gr * ((zv[e] - mu[e]) * iv[e]);
-                } else {
-                    s0[e] += gv[e];
-                }
-            }
-            pix += PL;
-            if (step_img) {                                   // (one group: the pixels are contiguous, nothing to skip)
-                rw += PL;
-                while (rw >= hw) { rw -= hw; pix += step_img; }
-            }
-        }
-    }
-    __shared__ double red[2][PL][64];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        red[0][pl][cl * VEC + e] = s0[e];
-        red[1][pl][cl * VEC + e] = s1[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < 64 && blockIdx.x * 64 + threadIdx.x < c) {
-        double a = 0.0, b = 0.0;
-        for (int q = 0; q < PL; ++q) { a += red[0][q][threadIdx.x]; b += red[1][q][threadIdx.x]; }
-        const size_t o = ((size_t)g * c + blockIdx.x * 64 + threadIdx.x) * 2;
-        // the block's partial on fixed grids (2^-40 / 2^-36 forward, 2^-52 backward: grouped_sums_v8 in train_lp.hip says
-        // why): exact fp64 additions within their range, so the totals do not depend on the order the blocks arrive in
-        const double q0 = MODE == 0 ? 1099511627776.0 : 4503599627370496.0, q1 = MODE == 0 ? 68719476736.0 : 4503599627370496.0;
-        atomicAdd(&acc[o], rint(a * q0) / q0);
-        if (MODE != 2) atomicAdd(&acc[o + 1], rint(b * q1) / q1);
-    }
-}
-
-template <int MODE>
-void launch_grouped_sums(dim3 grid, hipStream_t st, bool vec, const float* z, int z_ld, const float* dy, int dy_ld,
-                         const float* y, int y_ld, const float* mean, const float* inv, int nb, int hw, int c, int G,
-                         double* acc, const float* scale = nullptr, const float* shift = nullptr) {
-    if (vec)
-        hipLaunchKernelGGL((grouped_sums_f32<MODE, 4>), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, inv,
-                           nb, hw, c, G, acc, scale, shift);
-    else
-        hipLaunchKernelGGL((grouped_sums_f32<MODE, 1>), grid, dim3(256), 0, st, z, z_ld, dy, dy_ld, y, y_ld, mean, inv,
-                           nb, hw, c, G, acc, scale, shift);
-}
 
 // mean/var (biased) + folded scale/shift per (group, channel)
 __global__ void bn_finalize_grouped(const double* __restrict__ acc, int G, int c, const int* __restrict__ counts,
@@ -154,59 +35,6 @@ __global__ void bn_finalize_grouped(const double* __restrict__ acc, int G, int c
     shift[i] = beta[ch] - (float)mu * iv * ga;
 }
 
-// y = act(x*scale[g][c] + shift[g][c]),  g = image % G
-__global__ __launch_bounds__(256) void scale_shift_act_grouped_f32(const float* __restrict__ x, int nb, int hw,
-                                                                   int c, int x_ld,
-                                                                   const float* __restrict__ scale,
-                                                                   const float* __restrict__ shift, int G,
-                                                                   int relu, float* __restrict__ y, int y_ld) {
-    const int cg = c >> 2;
-    const int64_t total = (int64_t)nb * hw * cg;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(idx % cg);
-        const int64_t pix = idx / cg;
-        const int g = (int)((pix / hw) % G);
-        f32x4 v = *reinterpret_cast<const f32x4*>(x + pix * x_ld + 4 * q);
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + (size_t)g * c + 4 * q);
-        const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + (size_t)g * c + 4 * q);
-        v = v * sc + sh;
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        *reinterpret_cast<f32x4*>(y + pix * y_ld + 4 * q) = v;
-    }
-}
-
-// dz += gamma*inv * (g - s1/m - zhat*s2/m),  g = dy*[y>0]   (train-mode BN + ReLU backward)
-__global__ __launch_bounds__(256) void bn_bwd_apply_grouped_f32(
-    const float* __restrict__ dy, int dy_ld, const float* __restrict__ y, int y_ld, const float* __restrict__ z,
-    int z_ld, const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ gamma,
-    const double* __restrict__ acc, const int* __restrict__ counts, int nb, int hw, int c, int G,
-    float* __restrict__ dz, int dz_ld, const float* __restrict__ scale = nullptr,
-    const float* __restrict__ shift = nullptr, int accumulate = 1) {
-    const int64_t total = (int64_t)nb * hw * c;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int ch = (int)(idx % c);
-        const int64_t pix = idx / c;
-        const int g = (int)((pix / hw) % G);
-        const int gi = g * c + ch;
-        float gr = dy[pix * dy_ld + ch];
-        if (y && !(y[pix * y_ld + ch] > 0.f)) gr = 0.f;
-        const float zval = z[pix * z_ld + ch];
-        if (!y && scale && !(zval * scale[gi] + shift[gi] > 0.f)) gr = 0.f;
-        const float iv = inv[gi];
-        const float zh = (zval - mean[gi]) * iv;
-        const float m = (float)counts[g];
-        const float s1 = (float)acc[(size_t)gi * 2], s2 = (float)acc[(size_t)gi * 2 + 1];
-        const float coef = (gamma ? gamma[ch] : 1.f) * iv;
-        const float upd = coef * (gr - s1 / m - zh * s2 / m);
-        dz[pix * dz_ld + ch] = accumulate ? dz[pix * dz_ld + ch] + upd : upd;
-    }
-}
-
 // per-channel parameter gradients: dbeta[c] += sum_g acc[g][c][0], dgamma[c] += sum_g acc[g][c][1]
 __global__ void bn_param_grads(const double* __restrict__ acc, int G, int c, float* __restrict__ dbeta,
                                float* __restrict__ dgamma) {
@@ -216,116 +44,6 @@ __global__ void bn_param_grads(const double* __restrict__ acc, int G, int c, flo
     for (int g = 0; g < G; ++g) { a += acc[((size_t)g * c + ch) * 2]; b += acc[((size_t)g * c + ch) * 2 + 1]; }
     if (dbeta) dbeta[ch] += (float)a;
     if (dgamma) dgamma[ch] += (float)b;
-}
-
-// ---- pooling backward ------------------------------------------------------------------------------
-// max: the gradient of a window goes to its first maximum in scan order (tf MaxPoolGrad / torch);
-// scatter with atomics because 3x3/2 windows overlap.  avg: dy / (#valid taps) to every valid tap.
-__global__ __launch_bounds__(256) void pool2d_bwd_f32(const float* __restrict__ x, int x_ld,
-                                                      const float* __restrict__ dy, int dy_ld, int nb, int ih,
-                                                      int iw, int c, int kh, int kw, int stride, int pad_t,
-                                                      int pad_l, int oh, int ow, int mode,
-                                                      float* __restrict__ dx, int dx_ld) {
-    const int64_t total = (int64_t)nb * oh * ow * c;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int ch = (int)(idx % c);
-        const int64_t pix = idx / c;
-        const int ox = (int)(pix % ow);
-        const int64_t t = pix / ow;
-        const int oy = (int)(t % oh);
-        const int n = (int)(t / oh);
-        const float g = dy[pix * dy_ld + ch];
-        if (mode == GV_POOL_MAX) {
-            float best = -INFINITY;
-            int64_t arg = -1;
-            for (int r = 0; r < kh; ++r) {
-                const int iy = oy * stride + r - pad_t;
-                if ((unsigned)iy >= (unsigned)ih) continue;
-                for (int s = 0; s < kw; ++s) {
-                    const int ix = ox * stride + s - pad_l;
-                    if ((unsigned)ix >= (unsigned)iw) continue;
-                    const int64_t ip = ((int64_t)n * ih + iy) * iw + ix;
-                    const float v = x[ip * x_ld + ch];
-                    if (v > best || arg < 0) { best = v; arg = ip; }
-                }
-            }
-            if (arg >= 0) atomicAdd(&dx[arg * dx_ld + ch], g);
-        } else {
-            int cnt = 0;
-            for (int r = 0; r < kh; ++r) {
-                const int iy = oy * stride + r - pad_t;
-                if ((unsigned)iy >= (unsigned)ih) continue;
-                for (int s = 0; s < kw; ++s) cnt += (unsigned)(ox * stride + s - pad_l) < (unsigned)iw;
-            }
-            const float gv = g / (float)cnt;
-            for (int r = 0; r < kh; ++r) {
-                const int iy = oy * stride + r - pad_t;
-                if ((unsigned)iy >= (unsigned)ih) continue;
-                for (int s = 0; s < kw; ++s) {
-                    const int ix = ox * stride + s - pad_l;
-                    if ((unsigned)ix >= (unsigned)iw) continue;
-                    atomicAdd(&dx[(((int64_t)n * ih + iy) * iw + ix) * dx_ld + ch], gv);
-                }
-            }
-        }
-    }
-}
-
-// ---- grouping module backward (nets/model.py:44-102) ------------------------------------------------
-// dF[v] += w_g/sum(w) * dS / (#views of g tied at the maximum) for every view of g attaining the maximum
-// (tf.reduce_max splits the gradient equally among ties); mean pooling: w_g/sum(w) * dS / |g|.
-__global__ __launch_bounds__(256) void view_pool_fuse_bwd_f32(
-    const float* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
-    int64_t shape_stride, const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode,
-    float* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
-    __shared__ unsigned long long s_mask[64];
-    __shared__ float s_w[64];
-    __shared__ float s_wsum;
-    const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
-    scheme += (size_t)n * scheme_stride;
-    weight += (size_t)n * weight_stride;
-    for (int g = threadIdx.x; g < G; g += 256) {
-        unsigned long long m = 0;
-        for (int v = 0; v < V; ++v)
-            if (scheme[g * V + v] != 0) m |= 1ull << v;
-        s_mask[g] = m;
-        s_w[g] = weight[g];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ws = 0.f;
-        for (int g = 0; g < G; ++g) ws += s_w[g];
-        s_wsum = ws;
-    }
-    __syncthreads();
-    if (s_wsum == 0.f) return;                      // (per-shape, mean-score weights) S = 0 for this shape: no gradient
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-        const size_t base = (size_t)n * shape_stride + e;
-        const float ds = dS[(size_t)n * E + e];
-        for (int g = 0; g < G; ++g) {
-            const unsigned long long m0 = s_mask[g];
-            if (m0 == 0) continue;
-            const float coef = s_w[g] / s_wsum * ds;
-            if (mode == GV_VIEWPOOL_MEAN) {
-                const float each = coef / (float)__popcll(m0);
-                for (unsigned long long m = m0; m; m &= m - 1)
-                    dF[base + (size_t)(__ffsll((long long)m) - 1) * view_stride] += each;
-            } else {
-                float best = -INFINITY;
-                for (unsigned long long m = m0; m; m &= m - 1)
-                    best = fmaxf(best, F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]);
-                int ties = 0;
-                for (unsigned long long m = m0; m; m &= m - 1)
-                    ties += F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride] == best;
-                const float each = coef / (float)ties;
-                for (unsigned long long m = m0; m; m &= m - 1) {
-                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
-                    if (F[a] == best) dF[a] += each;
-                }
-            }
-        }
-    }
 }
 
 // dx[b][p][c] += dgap[b][c] / hw
@@ -408,89 +126,8 @@ __global__ void sgd_momentum_f32(float* __restrict__ w, const float* __restrict_
 }
 
 // ---- filter gradient: dW[r][s][ci][co] += sum_m X[shift_{r,s}(m)][ci] * dZ[m][co] -------------------
-// One TN GEMM per filter tap between two pixel-major matrices (the shifted input and dZ), reduction
-// over the output pixels, on the exact fp32 MFMA (32x32x2).  A workgroup owns a 64(ci) x 64(co) tile of
-// one tap and a slice of the pixels; slices are combined with fp32 atomic adds (the tile is 16 KB).
-// LDS keeps both operands pixel-major, which is exactly the k-major image the 32x32x2 operand map
-// wants (lane i reads element i of pixel row m): conflict-free ds_read_b32, no transposes.
-__global__ __launch_bounds__(256) void conv_wgrad_f32(const float* __restrict__ x, int x_ld,
-                                                      const float* __restrict__ dz, int dz_ld, int nb, int ih,
-                                                      int iw, int cin, int kh, int kw, int stride, int pad_t,
-                                                      int pad_l, int oh, int ow, int cout, int64_t M,
-                                                      int64_t m_per_block, const GvDw dw) {
-    constexpr int PT = 32;                              // pixels per LDS tile
-    __shared__ __attribute__((aligned(16))) float sX[PT][64 + 4];
-    __shared__ __attribute__((aligned(16))) float sZ[PT][64 + 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wi = wave >> 1, wj = wave & 1;            // 2x2 waves, 32x32 each
-    const int ntile_co = (cout + 63) / 64, ntile_ci = (cin + 63) / 64;
-    int b = blockIdx.x;
-    const int tco = b % ntile_co; b /= ntile_co;
-    const int tci = b % ntile_ci; b /= ntile_ci;
-    const int tap = b;                                  // r*kw + s
-    const int fr = tap / kw, fs = tap - fr * kw;
-    const int ci0 = tci * 64, co0 = tco * 64;
-    const int64_t m0 = (int64_t)blockIdx.y * m_per_block;
-    const int64_t m1 = m0 + m_per_block < M ? m0 + m_per_block : M;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int ohow = oh * ow;
-    const bool xvec = (x_ld & 3) == 0 && ((((uintptr_t)x) & 15u) == 0);      // 16-byte loads when rows are aligned
-    const bool zvec = (dz_ld & 3) == 0 && ((((uintptr_t)dz) & 15u) == 0);
-    // loader: thread -> (pixel row p = tid/16 (+16), 4 channels q = tid%16)
-    const int lp = tid >> 4, lq = (tid & 15) * 4;
-    for (int64_t mt = m0; mt < m1; mt += PT) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int p = lp + 16 * h;
-            const int64_t m = mt + p;
-            f32x4 xv = {0.f, 0.f, 0.f, 0.f}, zv = {0.f, 0.f, 0.f, 0.f};
-            if (m < m1) {
-                const int n = (int)(m / ohow);
-                const int rem = (int)(m - (int64_t)n * ohow);
-                const int oy = rem / ow, ox = rem - oy * ow;
-                const int iy = oy * stride + fr - pad_t, ix = ox * stride + fs - pad_l;
-                if ((unsigned)iy < (unsigned)ih && (unsigned)ix < (unsigned)iw) {
-                    const float* xp = x + (((size_t)n * ih + iy) * iw + ix) * x_ld + ci0 + lq;
-                    if (xvec && ci0 + lq + 3 < cin) {
-                        xv = *reinterpret_cast<const f32x4*>(xp);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (ci0 + lq + e < cin) xv[e] = xp[e];
-                    }
-                }
-                const float* zp = dz + (size_t)m * dz_ld + co0 + lq;
-                if (zvec && co0 + lq + 3 < cout) {
-                    zv = *reinterpret_cast<const f32x4*>(zp);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) if (co0 + lq + e < cout) zv[e] = zp[e];
-                }
-            }
-            *reinterpret_cast<f32x4*>(&sX[p][lq]) = xv;
-            *reinterpret_cast<f32x4*>(&sZ[p][lq]) = zv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < PT; k += 2) {
-            const float av = sX[k + (lane >> 5)][wi * 32 + (lane & 31)];
-            const float bv = sZ[k + (lane >> 5)][wj * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    const int col = co0 + wj * 32 + (lane & 31);
-    if (col < cout) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (ci < cin) gv_dw_put(dw, blockIdx.y, ((size_t)tap * cin + ci) * cout + col, acc[r]);
-        }
-    }
-}
-
-
+// One TN GEMM per filter tap between two pixel-major matrices (the shifted input and dZ), reduction over the output
+// pixels, on the exact fp32 MFMA (32x32x2).
 // Storage-typed loads of the filter-gradient kernels: S = float, __bf16 or _Float16 in HBM, fp32 in registers.
 template <typename S>
 __device__ __forceinline__ f32x4 ld4(const S* p) {
@@ -511,7 +148,7 @@ __device__ __forceinline__ bool ld4_ok(const S* p, int ld) {
     return (ld & 3) == 0 && ((((uintptr_t)p) & (4 * sizeof(S) - 1)) == 0);
 }
 
-// Filter gradient, second generation: workgroup tile (64*TI) input channels x (64*TO) output channels for one
+// The tap-per-workgroup kernel: workgroup tile (64*TI) input channels x (64*TO) output channels for one
 // filter tap, 2x2 waves of TI x TO MFMA tiles (v_mfma_f32_32x32x2_f32: exact fp32; the k axis of this GEMM is
 // the PIXEL axis, and pixel-major LDS rows are exactly the k-major operand image this instruction wants:
 // lane (i, h) reads element [pixel k + h][channel i], 32 consecutive dwords per half-wave).  16 pixels per
@@ -791,9 +428,8 @@ extern "C" int gv_bn_update_moving_batched(const gv_bn_moving_job* jobs_dev, int
 
 // ---- the HBM-bound ops of the training step: one implementation per op -----------------------------------------------
 // The storage-typed `_t` entry point (dtype GV_F32 | GV_BF16 | GV_F16, for some ops with GV_ACCUM_* bits OR-ed in) is the
-// implementation: it checks the arguments, clears the accumulator, picks the pixel splits and calls gvlp:: (the streaming
-// kernels of train_lp.hip, instantiated for every storage type).  A GV_F32 shape that gvlp:: declines runs the scalar
-// fp32 kernel of this file; a 16-bit one has its scalar kernel behind gvlp::.  The fp32 entry point passes GV_F32.
+// implementation: it checks the arguments, clears the accumulator, picks the pixel splits and calls gvlp:: (train_lp.hip),
+// which picks the streaming or the scalar kernel of the storage type.  The fp32 entry point passes GV_F32.
 static inline bool storage_type(int dtype) { return dtype == GV_F32 || dtype == GV_BF16 || dtype == GV_F16; }
 
 // pixel splits of a sums launch: 2048 pixels per workgroup on the big layers, but at least ~1024 workgroups in total
@@ -816,14 +452,8 @@ extern "C" int gv_bn_sums_grouped_t(const void* z, int32_t nb, int32_t hw, int32
     if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
         GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
     const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
-    const int rc = gvlp::grouped_sums(dtype, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb,
-                                      hw, c, num_groups, splits, accum, st);
-    if (rc == GV_OK || dtype != GV_F32) return rc;
-    const float* zf = (const float*)z;
-    launch_grouped_sums<0>(dim3((c + 63) / 64, splits, num_groups), st, (c & 3) == 0 && gv_vec_ok(zf, z_ld, 4), zf, z_ld,
-                           nullptr, 0, nullptr, 0, nullptr, nullptr, nb, hw, c, num_groups, accum);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gvlp::grouped_sums(dtype, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb, hw, c,
+                              num_groups, splits, accum, st);
 }
 
 extern "C" int gv_bn_sums_grouped(const float* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
@@ -857,17 +487,12 @@ extern "C" int gv_scale_shift_act_grouped_t(const void* x, int32_t nb, int32_t h
     if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!x || !y || !scale || !shift || nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0)
         return GV_E_BADARG;
-    // (the scalar fp32 kernel works in float4 as well; the 16-bit one takes any shape)
+    // (fp32 storage has always asked for float4 operands here; 16-bit storage takes any shape)
     if (dtype == GV_F32 && ((c & 3) || (x_ld & 3) || (y_ld & 3) || !gv_aligned16(x) || !gv_aligned16(y) ||
                             !gv_aligned16(scale) || !gv_aligned16(shift)))
         return GV_E_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = gvlp::scale_shift_act_grouped(dtype, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, st);
-    if (rc == GV_OK || dtype != GV_F32) return rc;
-    hipLaunchKernelGGL(scale_shift_act_grouped_f32, dim3(gv_grid_for((int64_t)nb * hw * (c / 4))), dim3(256), 0, st,
-                       (const float*)x, nb, hw, c, x_ld, scale, shift, num_groups, relu, (float*)y, y_ld);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gvlp::scale_shift_act_grouped(dtype, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld,
+                                         (hipStream_t)stream);
 }
 
 extern "C" int gv_scale_shift_act_grouped(const float* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
@@ -907,15 +532,8 @@ extern "C" int gv_bn_relu_bwd_sums_grouped_t(const void* dy, int32_t dy_ld, cons
     if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
         GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
     const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
-    const int rc = gvlp::grouped_sums(dtype, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c,
-                                      num_groups, splits, accum, st);
-    if (rc == GV_OK || dtype != GV_F32) return rc;
-    const float *zf = (const float*)z, *df = (const float*)dy, *yf = (const float*)y;
-    launch_grouped_sums<1>(dim3((c + 63) / 64, splits, num_groups), st,
-                           (c & 3) == 0 && gv_vec_ok(zf, z_ld, 4) && gv_vec_ok(df, dy_ld, 4) && gv_vec_ok(yf, y_ld, 4), zf,
-                           z_ld, df, dy_ld, yf, y_ld, mean, inv, nb, hw, c, num_groups, accum, scale, shift);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gvlp::grouped_sums(dtype, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c, num_groups, splits,
+                              accum, st);
 }
 
 extern "C" int gv_bn_relu_bwd_sums_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
@@ -940,15 +558,9 @@ extern "C" int gv_bn_relu_bwd_apply_grouped_t(const void* dy, int32_t dy_ld, con
     if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     bool done = false;                                           // (the streaming kernel also sums dbeta / dgamma)
-    int rc = gvlp::bn_bwd_apply_grouped(dtype, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale, shift,
-                                        accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done, st, raw_z);
-    if (rc != GV_OK && dtype == GV_F32) {
-        hipLaunchKernelGGL(bn_bwd_apply_grouped_f32, dim3(gv_grid_for((int64_t)nb * hw * c)), dim3(256), 0, st,
-                           (const float*)dy, dy_ld, (const float*)y, y_ld, (const float*)z, z_ld, mean, inv, gamma, accum,
-                           counts, nb, hw, c, num_groups, (float*)dz, dz_ld, scale, shift, accumulate);
-        rc = GV_OK;
-        done = false;                                            // (the scalar kernel leaves dbeta / dgamma to bn_param_grads)
-    }
+    const int rc = gvlp::bn_bwd_apply_grouped(dtype, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale,
+                                              shift, accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done,
+                                              st, raw_z);
     if (rc != GV_OK) return rc;
     if ((dbeta || dgamma) && !done)
         hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, num_groups, c, dbeta,
@@ -994,11 +606,7 @@ extern "C" int gv_accumulate_t(const void* src, int32_t src_ld, void* dst, int32
                                int32_t dtype, void* stream) {
     if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!src || !dst || npix <= 0 || c <= 0 || src_ld < c || dst_ld < c) return GV_E_BADARG;
-    if (dtype != GV_F32) return gvlp::accumulate(dtype, src, src_ld, dst, dst_ld, npix, c, (hipStream_t)stream);
-    hipLaunchKernelGGL(accumulate_f32, dim3(gv_grid_for(npix * c)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
-                       src_ld, (float*)dst, dst_ld, npix, c);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gvlp::accumulate(dtype, src, src_ld, dst, dst_ld, npix, c, (hipStream_t)stream);
 }
 
 extern "C" int gv_accumulate(const float* src, int32_t src_ld, float* dst, int32_t dst_ld, int64_t npix,
@@ -1012,18 +620,13 @@ extern "C" int gv_bias_grad_t(const void* dz, int32_t dz_ld, int64_t npix, int32
     if (!dz || !accum || !dbias || npix <= 0 || c <= 0 || dz_ld < c || npix > 0x7fffffff) return GV_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)c, st));
-    if (dtype == GV_F32) {
-        // the split count decides the last bits of the sums, so fp32 keeps the rule it has always had: 2048 pixels per
-        // workgroup, without the "at least ~1024 workgroups" term of sums_splits
-        const int most = gv_ceil_div(npix, 2048), splits = most < 1024 ? most : 1024;
-        const float* df = (const float*)dz;
-        launch_grouped_sums<2>(dim3((c + 63) / 64, splits, 1), st, (c & 3) == 0 && gv_vec_ok(df, dz_ld, 4), nullptr, 0, df,
-                               dz_ld, nullptr, 0, nullptr, nullptr, (int)npix, 1, c, 1, accum);
-    } else {
-        const int rc = gvlp::grouped_sums(dtype, 2, nullptr, 0, dz, dz_ld, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                          (int)npix, 1, c, 1, sums_splits(npix, 1024), accum, st);
-        if (rc != GV_OK) return rc;
-    }
+    // the split count decides the last bits of the sums, so fp32 keeps the rule it has always had: 2048 pixels per
+    // workgroup, without the "at least ~1024 workgroups" term of sums_splits
+    const int most = gv_ceil_div(npix, 2048);
+    const int splits = dtype == GV_F32 ? (most < 1024 ? most : 1024) : sums_splits(npix, 1024);
+    const int rc = gvlp::grouped_sums(dtype, 2, nullptr, 0, dz, dz_ld, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                                      (int)npix, 1, c, 1, splits, accum, st);
+    if (rc != GV_OK) return rc;
     hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, 1, c, dbias, (float*)nullptr);
     GV_LAUNCH_CHECK();
     return GV_OK;
@@ -1034,25 +637,14 @@ extern "C" int gv_bias_grad(const float* dz, int32_t dz_ld, int64_t npix, int32_
     return gv_bias_grad_t(dz, dz_ld, npix, c, accum, dbias, GV_F32, stream);
 }
 
-static int g_pool_scatter = 0;
-extern "C" void gv_pool2d_bwd_set_scatter(int on) { g_pool_scatter = on; }
-
 extern "C" int gv_pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int32_t dy_ld, void* dx,
                              int32_t dx_ld, void* stream) {
     if (!d || !dy || !dx) return GV_E_BADARG;
     const int mode = d->mode & ~GV_POOL_BWD_STORE;
     if ((mode == GV_POOL_MAX && !x) || (mode != GV_POOL_MAX && mode != GV_POOL_AVG)) return GV_E_BADARG;
-    // one deterministic gather kernel family for all storage types (train_lp.hip); the atomic-scatter fp32 kernel
-    // (pool2d_bwd_f32) is kept behind the tuning hook gv_pool2d_bwd_set_scatter for comparison
-    if (d->dtype == GV_BF16 || d->dtype == GV_F16 || (d->dtype == GV_F32 && !g_pool_scatter))
-        return gvlp::pool2d_bwd(d, x, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
-    if (d->dtype != GV_F32) return GV_E_UNSUPPORTED;
-    if (d->mode & GV_POOL_BWD_STORE) return GV_E_UNSUPPORTED;    // the scatter kernel only adds
-    hipLaunchKernelGGL(pool2d_bwd_f32, dim3(gv_grid_for((int64_t)d->nb * d->oh * d->ow * d->c)), dim3(256), 0,
-                       (hipStream_t)stream, (const float*)x, d->x_ld, (const float*)dy, dy_ld, d->nb, d->ih, d->iw, d->c,
-                       d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, d->ow, mode, (float*)dx, dx_ld);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    if (!storage_type(d->dtype)) return GV_E_UNSUPPORTED;
+    // one deterministic gather kernel family for all storage types (train_lp.hip)
+    return gvlp::pool2d_bwd(d, x, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
 }
 
 extern "C" int gv_pool2d_fwd_argmax(const gv_pool_desc* d, const void* x, void* y, uint8_t* argmax, void* stream) {
@@ -1112,16 +704,8 @@ extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t n
     if (num_views <= 0 || num_shapes <= 0 || E <= 0 || num_groups <= 0) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
     const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
-    if (dtype != GV_F32)
-        return gvlp::view_pool_fuse_bwd(dtype, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme,
-                                        num_groups, weight, mode, dF, (hipStream_t)stream, ss, ws);
-    int64_t bx = (E + 255) / 256;
-    if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(view_pool_fuse_bwd_f32, dim3((unsigned)bx, (unsigned)num_shapes), dim3(256), 0,
-                       (hipStream_t)stream, (const float*)F, dS, num_views, num_shapes, E, view_stride, shape_stride,
-                       scheme, num_groups, weight, mode, (float*)dF, ss, ws);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return gvlp::view_pool_fuse_bwd(dtype, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups,
+                                    weight, mode, dF, (hipStream_t)stream, ss, ws);
 }
 
 extern "C" int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t num_views, int32_t num_shapes,
@@ -1188,10 +772,8 @@ extern "C" int gv_bn_update_moving(const float* mean, const float* var, const in
 }
 
 // The filter gradient's tuning hooks (tests and tools compare forms with them; nothing else sets them):
-static int g_wgrad_v1 = 0;             // fp32 storage on the first-generation kernel (conv_wgrad_f32), not the fp32 MFMA
 static int g_wgrad_lp_f32 = 0;         // 16-bit storage on the fp32 MFMA (typed loads), not the 16-bit MFMA kernels
 static int g_wgrad_strip_taps = 5;     // taps per workgroup of the general strip variant: 5 keeps two waves per SIMD (9: one)
-extern "C" void gv_conv2d_wgrad_set_v1(int on) { g_wgrad_v1 = on; }
 extern "C" void gv_conv2d_wgrad_set_lp_f32(int on) { g_wgrad_lp_f32 = on; }
 extern "C" void gv_conv2d_wgrad_set_strip_taps(int n) { g_wgrad_strip_taps = n; }
 int gvlp::wgrad_strip_taps() { return g_wgrad_strip_taps; }
@@ -1303,14 +885,7 @@ static int wgrad_dispatch(const gv_conv_desc* d, const void* x, const void* dz, 
         return wgrad_f32mfma<_Float16>(d, (const _Float16*)x, (const _Float16*)dz, dz_ld, dw, st);
     }
     if (d->dtype != GV_F32) return GV_E_UNSUPPORTED;
-    if (!g_wgrad_v1) return wgrad_f32mfma<float>(d, (const float*)x, (const float*)dz, dz_ld, dw, st);
-    const int tiles = d->kh * d->kw * ((d->cin + 63) / 64) * ((d->cout + 63) / 64);
-    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    // ~4k workgroups in flight, of at least 256 pixels, in steps of 32
-    const GvSlices p = gv_dw_plan(dw, elems, (int64_t)d->nb * d->oh * d->ow, tiles, 4096, 256, 32, 65535);
-    const int rc = gv_wgrad_launch<conv_wgrad_f32>(dim3((unsigned)tiles, (unsigned)p.splits), d, (const float*)x, (const float*)dz,
-                                                   dz_ld, p.per, gv_dw_sink(dw, elems, p.splits), st);
-    return rc != GV_OK ? rc : gv_dw_finish(dw, elems, p.splits, st);
+    return wgrad_f32mfma<float>(d, (const float*)x, (const float*)dz, dz_ld, dw, st);
 }
 
 extern "C" int gv_conv2d_wgrad(const gv_conv_desc* d, const void* x, const void* dz, int32_t dz_ld,

@@ -1,8 +1,10 @@
-// train_lp.hip — the training step on 16-bit storage (configs[2]: bf16 forward + backward).
-// Activations and activation gradients live in HBM as GV_BF16 / GV_F16; batch statistics accumulate in fp64,
-// parameter gradients (dW, dbeta, dgamma, dbias) and the optimizer state stay fp32, every elementwise result is
-// computed in fp32 and rounded to the storage type once.  Same algorithms as train.hip (the fp32 step); a thread
-// owns 8 consecutive channels (one 16-byte load) wherever the channel count allows.
+// train_lp.hip — the HBM-bound ops of the training step for every storage type, and the filter gradient
+// of 16-bit storage (configs[2]: bf16 forward + backward).
+// Activations and activation gradients live in HBM as GV_F32, GV_BF16 or GV_F16; a kernel is templated on E, the element
+// in HBM (float, or unsigned short for the 16-bit types), and T, the type it stands for.  Batch statistics accumulate in
+// fp64, parameter gradients (dW, dbeta, dgamma, dbias) and the optimizer state stay fp32, every elementwise result is
+// computed in fp32 and rounded to the storage type once.  A thread owns one 16-byte quad of consecutive channels (4 fp32,
+// 8 16-bit) wherever the channel count and the operands allow.  train.hip holds the extern "C" entry points.
 //
 // The filter gradient runs on v_mfma_f32_32x32x16_{bf16,f16}.  Its reduction axis is the PIXEL axis while both
 // operands (the shifted input and dZ) are channel-contiguous in HBM, i.e. k-strided for the MFMA: the tiles are
@@ -23,11 +25,15 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-// dst[p][c] += src[p][c]
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void accumulate_lp(const unsigned short* __restrict__ src, int src_ld,
-                                                     unsigned short* __restrict__ dst, int dst_ld, int64_t npix,
-                                                     int c) {
+// ---- the scalar family: what the streaming kernels below decline -------------------------------------------------------
+// One body per op for every storage type: E is the element type in HBM (float, or unsigned short for the 16-bit types),
+// T the type it stands for (float, __bf16, _Float16), VEC = 16 / sizeof(E) channels per thread (one 16-byte access) where
+// the operands can be walked in quads, else 1.
+
+// dst[p][c] += src[p][c]  (gradient fan-in of the residual add, nets/resnet_v2.py:91)
+template <typename E, typename T, int VEC>
+__global__ __launch_bounds__(256) void accumulate_t(const E* __restrict__ src, int src_ld, E* __restrict__ dst, int dst_ld,
+                                                    int64_t npix, int c) {
     const int cg = c / VEC;
     const int64_t total = npix * cg;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -43,16 +49,19 @@ __global__ __launch_bounds__(256) void accumulate_lp(const unsigned short* __res
     }
 }
 
-// Per-(group, channel) sums, see grouped_sums_f32 in train.hip.  MODE 0: sum z, sum z^2; MODE 1: sum g, sum g*zhat with
-// g = dy*[y>0]; MODE 2: sum dz.  A thread owns VEC channels; 64 channels per block; grid (channel blocks, splits, G).
-template <typename T, int MODE, int VEC>
-__global__ __launch_bounds__(256) void grouped_sums_lp(const unsigned short* __restrict__ z, int z_ld,
-                                                       const unsigned short* __restrict__ dy, int dy_ld,
-                                                       const unsigned short* __restrict__ y, int y_ld,
-                                                       const float* __restrict__ mean, const float* __restrict__ inv,
-                                                       const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, int nb, int hw, int c, int G,
-                                                       double* __restrict__ acc) {
+// ---- grouped per-(group, channel) sums -----------------------------------------------------------
+// acc[g][c][0] += sum u,  acc[g][c][1] += sum u*w   over the pixels of images b with b % G == g.
+//   MODE 0 (BN forward stats):  u = z,            w = z                       -> sum z, sum z^2
+//   MODE 1 (BN backward):       u = dy*[y>0],     w = (z-mean)*inv            -> sum g, sum g*zhat
+//   MODE 2 (bias gradient):     u = dz,           w = 0
+// Thread layout: VEC consecutive channels per thread, 64 / VEC threads span 64 channels, the remaining threads of the
+// 256 are pixel lanes; grid (channel blocks, pixel splits, G).
+template <typename E, typename T, int MODE, int VEC>
+__global__ __launch_bounds__(256) void grouped_sums_t(const E* __restrict__ z, int z_ld, const E* __restrict__ dy, int dy_ld,
+                                                      const E* __restrict__ y, int y_ld, const float* __restrict__ mean,
+                                                      const float* __restrict__ inv, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, int nb, int hw, int c, int G,
+                                                      double* __restrict__ acc) {
     constexpr int TPC = 64 / VEC;
     constexpr int PL = 256 / TPC;
     const int cl = threadIdx.x % TPC;
@@ -77,7 +86,8 @@ __global__ __launch_bounds__(256) void grouped_sums_lp(const unsigned short* __r
             sc[e] = rmask ? scale[g * c + ch + e] : 0.f;
             sh[e] = rmask ? shift[g * c + ch + e] : 0.f;
         }
-        // fp32 partial sums over short runs (exact enough for 16-bit inputs), folded into fp64 every 16 pixels
+        // 16-bit storage: fp32 partial sums over short runs (exact enough for 16-bit inputs), folded into fp64 every 16
+        // pixels; fp32 storage: every value straight into fp64 (the split grouped_sums_v8 makes, for its reason)
         for (int64_t pb = p0 + pl; pb < p1; pb += (int64_t)PL * 16) {
             float f0[VEC], f1[VEC];
 #pragma unroll
@@ -94,22 +104,32 @@ __global__ __launch_bounds__(256) void grouped_sums_lp(const unsigned short* __r
                 if (MODE == 1 && y) load_v<T, VEC>(y + pix * y_ld + ch, yv);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
-                    if (MODE == 0) {
-                        f0[e] += zv[e];
-                        f1[e] = fmaf(zv[e], zv[e], f1[e]);
-                    } else if (MODE == 1) {
-                        float gr = gv[e];
-                        if (y && !(yv[e] > 0.f)) gr = 0.f;
-                        if (rmask && !(fmaf(zv[e], sc[e], sh[e]) > 0.f)) gr = 0.f;
-                        f0[e] += gr;
-                        f1[e] = fmaf(gr, (zv[e] - mu[e]) * iv[e], f1[e]);
+                    float gr = MODE == 0 ? 0.f : gv[e];
+                    if (MODE == 1 && y && !(yv[e] > 0.f)) gr = 0.f;
+                    if (rmask && !(fmaf(zv[e], sc[e], sh[e]) > 0.f)) gr = 0.f;
+                    if constexpr (sizeof(E) == 4) {
+                        if (MODE == 0) {
+                            s0[e] += zv[e];
+                            s1[e] += (double)zv[e] * zv[e];
+                        } else {
+                            s0[e] += gr;
+                            if (MODE == 1) s1[e] += (double)gr * ((zv[e] - mu[e]) * iv[e]);
+                        }
                     } else {
-                        f0[e] += gv[e];
+                        if (MODE == 0) {
+                            f0[e] += zv[e];
+                            f1[e] = fmaf(zv[e], zv[e], f1[e]);
+                        } else {
+                            f0[e] += gr;
+                            if (MODE == 1) f1[e] = fmaf(gr, (zv[e] - mu[e]) * iv[e], f1[e]);
+                        }
                     }
                 }
             }
+            if constexpr (sizeof(E) == 2) {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) { s0[e] += f0[e]; s1[e] += f1[e]; }
+                for (int e = 0; e < VEC; ++e) { s0[e] += f0[e]; s1[e] += f1[e]; }
+            }
         }
     }
     __shared__ double red[2][PL][64];
@@ -123,20 +143,20 @@ __global__ __launch_bounds__(256) void grouped_sums_lp(const unsigned short* __r
         double a = 0.0, b = 0.0;
         for (int q = 0; q < PL; ++q) { a += red[0][q][threadIdx.x]; b += red[1][q][threadIdx.x]; }
         const size_t o = ((size_t)g * c + blockIdx.x * 64 + threadIdx.x) * 2;
-        // the block's partial on the fixed grid of conv_stats.h: the fp64 additions are then exact, so the sums do not
-        // depend on the order the blocks arrive in (bitwise reproducible run to run)
-        const double q0 = MODE == 0 ? gvconv::STAT_Q_FWD0 : gvconv::STAT_Q_BWD, q1 = MODE == 0 ? gvconv::STAT_Q_FWD1 : gvconv::STAT_Q_BWD;
+        // the block's partial on the storage type's fixed grid (conv_stats.h; grouped_sums_v8 says why fp32 has its own):
+        // the fp64 additions are then exact, so the sums do not depend on the order the blocks arrive in
+        const double q0 = gvconv::stat_grid(sizeof(E), MODE == 0, 0), q1 = gvconv::stat_grid(sizeof(E), MODE == 0, 1);
         atomicAdd(&acc[o], rint(a * q0) / q0);
         if (MODE != 2) atomicAdd(&acc[o + 1], rint(b * q1) / q1);
     }
 }
 
 // y = act(x*scale[g][c] + shift[g][c]),  g = image % G
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void scale_shift_act_grouped_lp(const unsigned short* __restrict__ x, int nb, int hw,
-                                                                  int c, int x_ld, const float* __restrict__ scale,
-                                                                  const float* __restrict__ shift, int G, int relu,
-                                                                  unsigned short* __restrict__ y, int y_ld) {
+template <typename E, typename T, int VEC>
+__global__ __launch_bounds__(256) void scale_shift_act_grouped_t(const E* __restrict__ x, int nb, int hw, int c, int x_ld,
+                                                                 const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift, int G, int relu,
+                                                                 E* __restrict__ y, int y_ld) {
     const int cg = c / VEC;
     const int64_t total = (int64_t)nb * hw * cg;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -157,14 +177,17 @@ __global__ __launch_bounds__(256) void scale_shift_act_grouped_lp(const unsigned
     }
 }
 
-// dz += gamma*inv * (g - s1/m - zhat*s2/m),  g = dy*[y>0]
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void bn_bwd_apply_grouped_lp(
-    const unsigned short* __restrict__ dy, int dy_ld, const unsigned short* __restrict__ y, int y_ld,
-    const unsigned short* __restrict__ z, int z_ld, const float* __restrict__ mean, const float* __restrict__ inv,
-    const float* __restrict__ gamma, const double* __restrict__ acc, const int* __restrict__ counts,
-    const float* __restrict__ scale, const float* __restrict__ shift, int accumulate, int nb, int hw, int c, int G,
-    unsigned short* __restrict__ dz, int dz_ld) {
+// dz += gamma*inv * (g - s1/m - zhat*s2/m),  g = dy*[y>0]   (train-mode BN + ReLU backward)
+// Every storage type uses the form of bn_stream_v8 and bn_bwd_coeffs: rm = 1 / m once, products with rm, the recomputed
+// mask by fmaf.  (The fp32 kernel this one replaced divided by m twice, so on fp32 storage the last bits of dz can differ
+// from that kernel's — only for shapes the streaming kernel declines, c % 4 != 0 or operands that cannot be walked in
+// 16-byte quads, which no plan of either backbone produces.)
+template <typename E, typename T, int VEC>
+__global__ __launch_bounds__(256) void bn_bwd_apply_grouped_t(
+    const E* __restrict__ dy, int dy_ld, const E* __restrict__ y, int y_ld, const E* __restrict__ z, int z_ld,
+    const float* __restrict__ mean, const float* __restrict__ inv, const float* __restrict__ gamma,
+    const double* __restrict__ acc, const int* __restrict__ counts, const float* __restrict__ scale,
+    const float* __restrict__ shift, int accumulate, int nb, int hw, int c, int G, E* __restrict__ dz, int dz_ld) {
     const int cg = c / VEC;
     const int64_t total = (int64_t)nb * hw * cg;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -344,10 +367,7 @@ __global__ __launch_bounds__(256) void grouped_sums_v8(const E* __restrict__ z, 
         // totals below 2^13 / 2^17 / 2 add exactly (order-independent, bitwise reproducible); beyond them the additions
         // are ordinary fp64 additions, reproducible to 1e-16 relative.  Round 3's backward grid, 2^-60, was exact only
         // below 2^-7.)
-        const double q0 = sizeof(E) == 4 ? (MODE == 0 ? 1099511627776.0 : 4503599627370496.0)
-                                         : (MODE == 0 ? gvconv::STAT_Q_FWD0 : gvconv::STAT_Q_BWD);
-        const double q1 = sizeof(E) == 4 ? (MODE == 0 ? 68719476736.0 : 4503599627370496.0)
-                                         : (MODE == 0 ? gvconv::STAT_Q_FWD1 : gvconv::STAT_Q_BWD);
+        const double q0 = gvconv::stat_grid(sizeof(E), MODE == 0, 0), q1 = gvconv::stat_grid(sizeof(E), MODE == 0, 1);
         atomicAdd(&acc[o], rint(a * q0) / q0);
         if (MODE != 2) atomicAdd(&acc[o + 1], rint(b * q1) / q1);
     }
@@ -439,6 +459,7 @@ __global__ __launch_bounds__(256) void bn_stream_v8(const E* __restrict__ x, int
         const int cht = blockIdx.x * 64 + threadIdx.x;
         if (threadIdx.x < 64 && cht < c) {
             const int gi = g * c + cht;
+            // p0f = mean, p1f = inv; relu: GV_ACCUM_RAW_Z
             const float iv = p1f[gi], mu = p0f[gi];              // p0f = mean, p1f = inv
             const float rm = 1.f / (float)counts[g];
             const double a0 = acc[(size_t)gi * 2], a1 = acc[(size_t)gi * 2 + 1];
@@ -967,17 +988,19 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd_lp(const E* __restrict__ x
     }
 }
 
-// Backward of the fused view pooling + group fusion (view_pool_fuse_bwd_f32 in train.hip) with F and dF in the
-// storage type and dS in fp32.
-template <typename T>
-__global__ __launch_bounds__(256) void view_pool_fuse_bwd_lp(
-    const unsigned short* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
+// ---- grouping module backward (nets/model.py:44-102) ------------------------------------------------
+// dF[v] += w_g/sum(w) * dS / (#views of g tied at the maximum) for every view of g attaining the maximum
+// (tf.reduce_max splits the gradient equally among ties); mean pooling: w_g/sum(w) * dS / |g|.
+// F and dF in the storage type (SE the element in HBM, T the type it stands for), dS in fp32.
+template <typename SE, typename T>
+__global__ __launch_bounds__(256) void view_pool_fuse_bwd_t(
+    const SE* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
     int64_t shape_stride, const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode,
-    unsigned short* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
+    SE* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
     __shared__ unsigned long long s_mask[64];
     __shared__ float s_w[64];
     __shared__ float s_wsum;
-    const int n = blockIdx.y;
+    const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
     scheme += (size_t)n * scheme_stride;
     weight += (size_t)n * weight_stride;
     for (int g = threadIdx.x; g < G; g += 256) {
@@ -994,7 +1017,7 @@ __global__ __launch_bounds__(256) void view_pool_fuse_bwd_lp(
         s_wsum = ws;
     }
     __syncthreads();
-    if (s_wsum == 0.f) return;
+    if (s_wsum == 0.f) return;                      // (per-shape, mean-score weights) S = 0 for this shape: no gradient
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
         const size_t base = (size_t)n * shape_stride + e;
         const float ds = dS[(size_t)n * E + e];
@@ -1358,10 +1381,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_strip_lp(const unsigned short*
     }
 }
 
-// ---- launchers of the streaming kernels: one body for every storage type ---------------------------------------------
+// ---- launchers of the HBM-bound ops: one body for every storage type -------------------------------------------------
 // E is the element type in HBM (float, or unsigned short for the 16-bit types) and T the type it stands for (float,
-// __bf16, _Float16): GV_ST_DISPATCH below.  A shape the streaming kernels cannot take runs the scalar 16-bit kernel;
-// on fp32 storage the launcher answers GV_E_UNSUPPORTED and the caller (train.hip) launches its scalar fp32 kernel.
+// __bf16, _Float16): GV_ST_DISPATCH below.  The streaming kernel where the operands allow it, else the scalar kernel of
+// the same storage type.
 // every operand (nullptr: not used) can be walked in 16-byte quads (4 fp32 or 8 16-bit channels) ...
 inline bool stream_vec_ok(size_t elem_bytes, int c, const void* p0, int ld0, const void* p1, int ld1,
                           const void* p2 = nullptr, int ld2 = 0, const void* p3 = nullptr, int ld3 = 0) {
@@ -1370,11 +1393,13 @@ inline bool stream_vec_ok(size_t elem_bytes, int c, const void* p0, int ld0, con
 }
 // ... and a group's pixel index fits the int the streaming kernels count in
 inline bool stream_pix_ok(int nb, int hw, int G) { return (int64_t)((nb + G - 1) / G) * hw < 0x7fffffffll; }
+inline size_t elem_bytes(int dtype) { return dtype == GV_F32 ? 4 : 2; }
 
 template <typename E, typename T>
 int sums_t(int mode, const E* z, int z_ld, const E* dy, int dy_ld, const E* y, int y_ld, const float* mean,
            const float* inv, const float* scale, const float* shift, int nb, int hw, int c, int G, int splits, double* acc,
            hipStream_t st) {
+    constexpr int NE = 16 / sizeof(E);
     const bool v = stream_vec_ok(sizeof(E), c, z, z_ld, dy, dy_ld, y, y_ld);
     const dim3 grid((c + 63) / 64, splits, G);
     const bool stream = v && stream_pix_ok(nb, hw, G);
@@ -1384,9 +1409,8 @@ int sums_t(int mode, const E* z, int z_ld, const E* dy, int dy_ld, const E* y, i
 #define GV_SUMS(MODE)                                                                                                 \
     do {                                                                                                              \
         if (stream) GV_SUMS_LAUNCH(grouped_sums_v8<E, T, MODE>);                                                      \
-        else if constexpr (sizeof(E) != 2) return GV_E_UNSUPPORTED;                                                   \
-        else if (v) GV_SUMS_LAUNCH(grouped_sums_lp<T, MODE, 8>);                                                      \
-        else GV_SUMS_LAUNCH(grouped_sums_lp<T, MODE, 1>);                                                             \
+        else if (v) GV_SUMS_LAUNCH(grouped_sums_t<E, T, MODE, NE>);                                                   \
+        else GV_SUMS_LAUNCH(grouped_sums_t<E, T, MODE, 1>);                                                           \
     } while (0)
     if (mode == 0) GV_SUMS(0);
     else if (mode == 1) GV_SUMS(1);
@@ -1397,7 +1421,7 @@ int sums_t(int mode, const E* z, int z_ld, const E* dy, int dy_ld, const E* y, i
     return GV_OK;
 }
 
-// The arguments of bn_stream_v8 by name; what a launch does not use stays null.
+// The arguments of a BatchNorm apply by name; what a launch does not use stays null.
 struct StreamArgs {
     const void *x = nullptr, *dy = nullptr, *yact = nullptr;     // forward: x;  backward: z, dy and the kept activation
     int x_ld = 0, dy_ld = 0, y_ld = 0;                           // (nullptr: the ReLU mask is recomputed from scale / shift)
@@ -1413,31 +1437,28 @@ struct StreamArgs {
     BnExtra ex{};
 };
 
-// A BatchNorm apply, forward or backward: the streaming kernel when the operands allow it (*streamed says so), else the
-// scalar 16-bit kernel where `scalar_ok`, else GV_E_UNSUPPORTED and nothing launched.
+// bn_stream_v8 takes the launch; only it finalizes (forward), sums dbeta / dgamma and converts raw-z sums (backward)
+inline bool bn_streams(int dtype, const StreamArgs& a) {
+    return stream_vec_ok(elem_bytes(dtype), a.c, a.x, a.x_ld, a.dy, a.dy_ld, a.yact, a.y_ld, a.out, a.out_ld) &&
+           stream_pix_ok(a.nb, a.hw, a.G);
+}
+
+// A BatchNorm apply, forward or backward: the streaming kernel where bn_streams, else the scalar one (an element per thread)
 template <typename E, typename T, bool BWD>
-int launch_bn_stream(const StreamArgs& a, bool scalar_ok, bool* streamed, hipStream_t st) {
-    const bool v = stream_vec_ok(sizeof(E), a.c, a.x, a.x_ld, a.dy, a.dy_ld, a.yact, a.y_ld, a.out, a.out_ld) &&
-                   stream_pix_ok(a.nb, a.hw, a.G);
-    if (streamed) *streamed = v;
-    if (v) {
+int launch_bn_apply(const StreamArgs& a, hipStream_t st) {
+    const dim3 grid(gv_grid_for((int64_t)a.nb * a.hw * a.c));
+    if (bn_streams(sizeof(E) == 4 ? GV_F32 : GV_BF16, a))
         hipLaunchKernelGGL((bn_stream_v8<E, T, BWD>), dim3((a.c + 63) / 64, stream_splits(a.nb, a.hw, a.G, a.c), a.G),
                            dim3(256), 0, st, (const E*)a.x, a.x_ld, (const E*)a.dy, a.dy_ld, (const E*)a.yact, a.y_ld, a.p0,
                            a.p1, a.gamma, a.acc, a.counts, a.scale, a.shift, a.accumulate, a.nb, a.hw, a.c, a.G, a.flag,
                            (E*)a.out, a.out_ld, a.ex);
-    } else if constexpr (sizeof(E) != 2) {
-        return GV_E_UNSUPPORTED;
-    } else {
-        if (!scalar_ok) return GV_E_UNSUPPORTED;
-        const dim3 grid(gv_grid_for((int64_t)a.nb * a.hw * a.c));
-        if constexpr (BWD)
-            hipLaunchKernelGGL((bn_bwd_apply_grouped_lp<T, 1>), grid, dim3(256), 0, st, (const E*)a.dy, a.dy_ld,
-                               (const E*)a.yact, a.y_ld, (const E*)a.x, a.x_ld, a.p0, a.p1, a.gamma, a.acc, a.counts, a.scale,
-                               a.shift, a.accumulate, a.nb, a.hw, a.c, a.G, (E*)a.out, a.out_ld);
-        else
-            hipLaunchKernelGGL((scale_shift_act_grouped_lp<T, 1>), grid, dim3(256), 0, st, (const E*)a.x, a.nb, a.hw, a.c,
-                               a.x_ld, a.p0, a.p1, a.G, a.flag, (E*)a.out, a.out_ld);
-    }
+    else if constexpr (BWD)
+        hipLaunchKernelGGL((bn_bwd_apply_grouped_t<E, T, 1>), grid, dim3(256), 0, st, (const E*)a.dy, a.dy_ld,
+                           (const E*)a.yact, a.y_ld, (const E*)a.x, a.x_ld, a.p0, a.p1, a.gamma, a.acc, a.counts, a.scale,
+                           a.shift, a.accumulate, a.nb, a.hw, a.c, a.G, (E*)a.out, a.out_ld);
+    else
+        hipLaunchKernelGGL((scale_shift_act_grouped_t<E, T, 1>), grid, dim3(256), 0, st, (const E*)a.x, a.nb, a.hw, a.c,
+                           a.x_ld, a.p0, a.p1, a.G, a.flag, (E*)a.out, a.out_ld);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }
@@ -1826,16 +1847,15 @@ namespace gvlp {
     } while (0)
 
 int accumulate(int dtype, const void* src, int src_ld, void* dst, int dst_ld, int64_t npix, int c, hipStream_t st) {
-    const unsigned short* s = (const unsigned short*)src;
-    unsigned short* d = (unsigned short*)dst;
-    const bool v = stream_vec_ok(2, c, s, src_ld, d, dst_ld);
-    GV_LP_DISPATCH(dtype, {
+    const bool v = stream_vec_ok(elem_bytes(dtype), c, src, src_ld, dst, dst_ld);
+    GV_ST_DISPATCH(dtype, {
+        constexpr int NE = 16 / sizeof(E);
         if (v)
-            hipLaunchKernelGGL((accumulate_lp<T, 8>), dim3(gv_grid_for(npix * (c / 8))), dim3(256), 0, st, s, src_ld, d,
-                               dst_ld, npix, c);
+            hipLaunchKernelGGL((accumulate_t<E, T, NE>), dim3(gv_grid_for(npix * (c / NE))), dim3(256), 0, st, (const E*)src,
+                               src_ld, (E*)dst, dst_ld, npix, c);
         else
-            hipLaunchKernelGGL((accumulate_lp<T, 1>), dim3(gv_grid_for(npix * c)), dim3(256), 0, st, s, src_ld, d, dst_ld,
-                               npix, c);
+            hipLaunchKernelGGL((accumulate_t<E, T, 1>), dim3(gv_grid_for(npix * c)), dim3(256), 0, st, (const E*)src, src_ld,
+                               (E*)dst, dst_ld, npix, c);
         GV_LAUNCH_CHECK();
         return GV_OK;
     });
@@ -1853,7 +1873,7 @@ int scale_shift_act_grouped(int dtype, const void* x, int nb, int hw, int c, int
     StreamArgs a;
     a.x = x; a.x_ld = x_ld; a.p0 = scale; a.p1 = shift;
     a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = relu; a.out = y; a.out_ld = y_ld;
-    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, false>(a, true, nullptr, st)));
+    GV_ST_DISPATCH(dtype, return (launch_bn_apply<E, T, false>(a, st)));
 }
 
 // Fused finalize + apply (forward).  Returns GV_E_UNSUPPORTED when the shape needs the separate kernels.
@@ -1865,7 +1885,8 @@ int bn_finalize_apply_grouped(int dtype, const double* acc, const int* counts, c
     a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = relu; a.out = y; a.out_ld = y_ld;
     a.ex.fin_acc = acc; a.ex.beta = beta; a.ex.eps = eps;
     a.ex.mean = mean; a.ex.var = var; a.ex.inv = inv; a.ex.scale_out = scale; a.ex.shift_out = shift;
-    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, false>(a, false, nullptr, st)));
+    if (!bn_streams(dtype, a)) return GV_E_UNSUPPORTED;
+    GV_ST_DISPATCH(dtype, return (launch_bn_apply<E, T, false>(a, st)));
 }
 
 // *param_grads_done: the streaming kernel ran, which also sums dbeta / dgamma; else the caller launches bn_param_grads.
@@ -1874,14 +1895,14 @@ int bn_bwd_apply_grouped(int dtype, const void* dy, int dy_ld, const void* y, in
                          const float* mean, const float* inv, const float* gamma, const double* acc, const int* counts,
                          const float* scale, const float* shift, int accumulate, int nb, int hw, int c, int G, void* dz,
                          int dz_ld, float* dbeta, float* dgamma, bool* param_grads_done, hipStream_t st, int raw_z) {
-    *param_grads_done = false;
-    if (raw_z && dtype == GV_F32) return GV_E_UNSUPPORTED;
     StreamArgs a;
     a.x = z; a.x_ld = z_ld; a.dy = dy; a.dy_ld = dy_ld; a.yact = y; a.y_ld = y_ld; a.p0 = mean; a.p1 = inv;
     a.gamma = gamma; a.acc = acc; a.counts = counts; a.scale = scale; a.shift = shift; a.accumulate = accumulate;
     a.nb = nb; a.hw = hw; a.c = c; a.G = G; a.flag = raw_z ? 1 : 0; a.out = dz; a.out_ld = dz_ld;
     a.ex.dbeta = dbeta; a.ex.dgamma = dgamma;
-    GV_ST_DISPATCH(dtype, return (launch_bn_stream<E, T, true>(a, !raw_z, param_grads_done, st)));
+    *param_grads_done = bn_streams(dtype, a);
+    if (raw_z && (dtype == GV_F32 || !*param_grads_done)) return GV_E_UNSUPPORTED;
+    GV_ST_DISPATCH(dtype, return (launch_bn_apply<E, T, true>(a, st)));
 }
 
 int pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int dy_ld, void* dx, int dx_ld, hipStream_t st) {
@@ -2007,15 +2028,15 @@ int bn_bwd_coeffs_launch(const double* acc, const int* counts, const float* mean
     return GV_OK;
 }
 
-int view_pool_fuse_bwd(int dtype, const void* F, const float* dS, int V, int N, int64_t E, int64_t vs, int64_t ss,
+int view_pool_fuse_bwd(int dtype, const void* F, const float* dS, int V, int N, int64_t n_elem, int64_t vs, int64_t ss,
                        const int* scheme, int G, const float* weight, int mode, void* dF, hipStream_t st,
                        int64_t scheme_stride, int64_t weight_stride) {
-    int64_t bx = (E + 255) / 256;
+    int64_t bx = (n_elem + 255) / 256;
     if (bx > 1024) bx = 1024;
     const dim3 grid((unsigned)bx, (unsigned)N);
-    GV_LP_DISPATCH(dtype, {
-        hipLaunchKernelGGL(view_pool_fuse_bwd_lp<T>, grid, dim3(256), 0, st, (const unsigned short*)F, dS, V, N, E, vs, ss,
-                           scheme, G, weight, mode, (unsigned short*)dF, scheme_stride, weight_stride);
+    GV_ST_DISPATCH(dtype, {
+        hipLaunchKernelGGL((view_pool_fuse_bwd_t<E, T>), grid, dim3(256), 0, st, (const E*)F, dS, V, N, n_elem, vs, ss, scheme,
+                           G, weight, mode, (E*)dF, scheme_stride, weight_stride);
         GV_LAUNCH_CHECK();
         return GV_OK;
     });

@@ -898,10 +898,10 @@ int gv_dense_bwd(const float* x, const float* dy, const float* kernel, int32_t n
 int gv_sgd_momentum(float* w, const float* g, float* m, int64_t n, float lr, float mu, float wd,
                     void* stream);
 
-/* ---- the training step on 16-bit storage (configs[2]: bf16 forward + backward) --------------------------
+/* ---- the training step on any storage type (configs[2]: bf16 forward + backward) -----------------------
  * Storage-typed forms of the functions above: activations and activation gradients (z, y, dy, dz, F, dF, src, dst)
- * are `dtype` elements (GV_BF16 / GV_F16; with GV_F32 the function above, which forwards here), arithmetic is fp32 with one
- * rounding per stored element, batch statistics accumulate in fp64, parameter gradients (dbeta, dgamma, dbias, dW),
+ * are `dtype` elements (GV_F32, GV_BF16 or GV_F16; the fp32 functions above forward here with GV_F32), arithmetic is
+ * fp32 with one rounding per stored element, batch statistics accumulate in fp64, parameter gradients (dbeta, dgamma, dbias, dW),
  * dS and the optimizer state stay fp32.  gv_conv2d_fwd (forward and data gradient), gv_conv2d_wgrad,
  * gv_pool2d_fwd/_bwd, gv_global_avg_pool, gv_view_score_partial and gv_view_pool_fuse_fwd take the storage type
  * from their descriptor / dtype argument. */

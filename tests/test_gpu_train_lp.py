@@ -146,11 +146,12 @@ BN_CASES = {
     "D": (40, 2, 2, 2, 72, 80),        # 2 / 2: hw = 4, 80 pixels per block
     "E": (6, 5, 3, 3, 136, 136),       # 1 / 1: hw = 9, five views, ragged third channel block
     "F": (3, 4, 7, 7, 6, 7),           # 2 / -: no 16-byte walk: the scalar kernels of every type (their apply has a flat grid)
+    "I": (3, 4, 7, 7, 8, 9),           # 2 / -: the channels fill a quad but the leading dimension does not: the scalar kernels again
     "G": (2, 12, 25, 32, 2048, 2048),  # 3 / 3: 534 pixels per block (ragged last), block 1 crosses into the next image at
 }                                      #        pixel 800; 16-bit: 17 steps per lane = 4 unrolled trips + 1, the fold at step 12
 # (case, operands start 16 bytes into their buffers, storage); G has 39 M elements: bf16 and fp32 only
 BN_SWEEP = [(case, off, t) for case, off in [("A", 0), ("A", 1), ("B", 0), ("B", 1), ("C", 0), ("H", 0), ("D", 0), ("E", 0),
-                                             ("F", 0), ("G", 0)] for t in BN_TYPES if (case, t) != ("G", "f16")]
+                                             ("F", 0), ("I", 0), ("G", 0)] for t in BN_TYPES if (case, t) != ("G", "f16")]
 NAN, SENTINEL = float("nan"), -7.0
 
 
@@ -225,6 +226,7 @@ def test_bn_kernels_over_their_launch_geometries_against_fp64(case, off, tname):
       var            5.2e-8    7.4e-8    8.8e-8     (1e-5)
       y              1.0e-7    3.5e-3    4.2e-4     (1e-5 / 2^-8 = 3.9e-3 / 2^-11 = 4.9e-4: half an ulp at the foot of a binade)
       dz             1.4e-7    3.8e-3    4.6e-4     (1e-4 / 2^-7 = 7.8e-3 / 2^-10 = 9.8e-4)
+      dz, F and I    1.2e-7    3.8e-3    4.3e-4     (the scalar apply of every type: 1 / m once, as the streaming kernel has it)
       dbeta          8.4e-8    8.3e-8    9.1e-8     (1e-5)
       dgamma         8.2e-8    1.0e-7    9.6e-8     (1e-4)
       totals         8.0e-8    9.1e-8    9.2e-8     (1e-6; the backward ones carry the fp32 rounding of zhat)"""
@@ -237,7 +239,7 @@ def test_bn_kernels_over_their_launch_geometries_against_fp64(case, off, tname):
     zs, dys = z.v.reshape(shape), dy.v.reshape(shape)            # the stored values
     pre = ((torch.rand(npix, c, generator=g, device=DEV) - 0.5) / 2).to(tdt)
     db0, dg0 = torch.randn(c, generator=g, device=DEV), torch.randn(c, generator=g, device=DEV)
-    no_f32_apply = dt == _lib.GV_F32 and c % 4 != 0              # fp32 storage has no forward apply for such a shape
+    no_f32_apply = dt == _lib.GV_F32 and (c % 4 != 0 or ld % 4 != 0)   # fp32 storage has no forward apply for such a shape
 
     def slab(fill, values=None):
         return _Slab(npix, c, ld, o, tdt, fill, values)
@@ -490,7 +492,7 @@ def test_accumulate_and_bias_grad_typed(dt, tdt, eps):
 
 
 @pytest.mark.parametrize("tname", list(BN_TYPES))
-@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7)])
+@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7), (8, 9)])
 def test_bias_grad_over_several_pixel_splits(tname, c, ld):
     """gv_bias_grad_t with more than one pixel split (fp32: 2100 pixels = 2 workgroups of 2048; 16-bit: 300 pixels = 3 of
     128), on the streaming and on the scalar kernel, a slice of a wider buffer whose other channels hold NaN: dbias, which
@@ -509,7 +511,7 @@ def test_bias_grad_over_several_pixel_splits(tname, c, ld):
 
 
 @pytest.mark.parametrize("tname", list(BN_TYPES))
-@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7)])
+@pytest.mark.parametrize("c,ld", [(72, 80), (5, 7), (8, 9)])
 def test_accumulate_is_the_exact_sum_rounded_once(tname, c, ld):
     """gv_accumulate_t at 300 pixels (more than one workgroup), vector and scalar kernel, slices of wider buffers: dst is the
     sum formed in fp64 and rounded once to the storage type, bit for bit; the other channels of dst keep their sentinel."""

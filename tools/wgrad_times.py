@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-layer time of the filter-gradient kernel (v1 vs v2) on the Inception training geometry.
+"""Per-layer time of the filter gradient on the training geometry: the fp32 MFMA; on 16-bit storage the fp32 MFMA with
+typed loads beside the 16-bit MFMA kernels.
     python tools/wgrad_times.py [--shapes 32]"""
 import argparse
 import ctypes as C
@@ -25,7 +26,8 @@ eng.forward(x, torch.zeros(a.shapes, dtype=torch.int64), check=False)
 eng.backward()
 torch.cuda.synchronize()
 st = torch.cuda.current_stream().cuda_stream
-tot = [0.0, 0.0]
+forms = ["f32 mfma"] if a.storage == "f32" else ["f32 mfma", "16-bit mfma"]
+tot = [0.0] * len(forms)
 for op in eng.plan.ops:
     if op["kind"] != "conv":
         continue
@@ -33,11 +35,8 @@ for op in eng.plan.ops:
     d = eng._conv_desc(op)
     dw = eng._dw(op)
     res = []
-    for v1 in (1, 0):
-        if a.storage == "f32":
-            lib.gv_conv2d_wgrad_set_v1(v1)
-        else:                                    # 16-bit storage: column 1 = fp32 MFMA with typed loads, column 2 = 16-bit MFMA
-            lib.gv_conv2d_wgrad_set_lp_f32(v1)
+    for form in forms:
+        lib.gv_conv2d_wgrad_set_lp_f32(1 if a.storage != "f32" and form == "f32 mfma" else 0)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         lib.gv_conv2d_wgrad(C.byref(d), eng._ptr(xx), eng._ptr(y, True), y.ld, dw.data_ptr(), st)
         e0.record()
@@ -46,11 +45,9 @@ for op in eng.plan.ops:
         e1.record()
         torch.cuda.synchronize()
         res.append(e0.elapsed_time(e1) / 3)
-    lib.gv_conv2d_wgrad_set_v1(0)
     lib.gv_conv2d_wgrad_set_lp_f32(0)
-    tot[0] += res[0]
-    tot[1] += res[1]
+    tot = [t + r for t, r in zip(tot, res)]
     fl = op["flops"]
-    print("%-55s M=%8d cin=%4d cout=%4d k=%dx%d  v1 %7.3f ms %6.1f TF   v2 %7.3f ms %6.1f TF" % (
-        op["name"][-55:], y.npix, xx.c, y.c, op["kh"], op["kw"], res[0], fl / res[0] / 1e9, res[1], fl / res[1] / 1e9))
-print("total v1 %.2f ms, v2 %.2f ms" % tuple(tot))
+    print("%-55s M=%8d cin=%4d cout=%4d k=%dx%d" % (op["name"][-55:], y.npix, xx.c, y.c, op["kh"], op["kw"]) +
+          "".join("  %s %7.3f ms %6.1f TF" % (f, r, fl / r / 1e9) for f, r in zip(forms, res)))
+print("total " + ", ".join("%s %.2f ms" % (f, t) for f, t in zip(forms, tot)))
