@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _plan_layout as L
 
 INCEPTION_BN_EPS = 0.001   # nets/inception_utils.py:33
 RESNET_BN_EPS = 1e-5       # nets/resnet_utils.py:200
@@ -88,42 +89,32 @@ class DeferredPreact:
         self.t, self.scale_off, self.shift_off = t, scale_off, shift_off
 
 
-class BackbonePlan:
-    """Collects ops symbolically, then lowers them to a native gv_plan."""
+class SymbolicPlan:
+    """What a plan is before anything touches the library: an op list over virtual tensors, launch lanes, end points,
+    and the fusion switches at their neutral values.  BackbonePlan (inference) and training.TrainPlan record into it."""
 
-    def __init__(self, nb, height, width, dtype=_lib.GV_F32, math_mode=_lib.GV_MATH_F32):
-        self.lib = _lib.load()
+    def __init__(self, nb, height, width, dtype, math_mode):
         self.nb, self.height, self.width, self.dtype = nb, height, width, dtype
         self.esz = 4 if dtype == _lib.GV_F32 else 2          # bytes per stored activation / filter element
         self.math_mode = math_mode
         self.ops = []            # dict records
-        self.vbufs = []          # [size_elems, persistent]
-        self.filters = []        # (weights_name, kh, kw, cin, cout, w_off)
-        self.ss_specs = []       # (kind, name, c, eps, has_gamma, scale_off, shift_off)
-        self._ss_cache = {}
-        self.w_elems = 0
-        self.ss_elems = 0
+        self.vbufs = []          # [size_elems, persistent, three-plane]
         self.end_points = {}
         self.input = TRef(-1, 0, nb, height, width, 3, 3)    # vbuf -1 = SLOT_INPUT
-        self._plan = None
-        self._phys = None
-        self._bufs = None
-        self._ptrs = None
-        self.keepalive = []
         self.cur_lane = 0
-        self.use_lanes = True
+        self.use_lanes = False
         # fp32 storage + GV_MATH_BF16X3: conv -> conv intermediates are kept as three bf16 planes so that the consumer's
         # LDS-DMA loader only moves bytes (csrc/conv_dma.hip); everything a pool, the grouping module or a caller reads
         # stays fp32
-        self.use_p3 = dtype == _lib.GV_F32 and math_mode == _lib.GV_MATH_BF16X3
+        self.use_p3 = False
         self.p3_blocks = None             # None: every block; else the set of block / stem-layer names that use it
         # 16-bit storage: the pre-activation of a ResNet-v2 identity unit is applied by the loader of the unit's conv1
         # (gv_conv2d_fwd_xpre) instead of being stored by the unit before it: that conv3 is HBM-bound and writes 9 instead
         # of 13 channel-quanta per pixel.  Off: the second-output form everywhere (A/B switch; fp32 storage always)
-        self.defer_preact = dtype != _lib.GV_F32
+        self.defer_preact = False
         # 16-bit storage: Conv2d_2b_3x3 -> MaxPool_3a_3x3 as one launch that writes only the pooled tensor
         # (GV_CONV_MAXPOOL3S2); off: the two launches (A/B switch)
-        self.fuse_maxpool = dtype != _lib.GV_F32 or math_mode == _lib.GV_MATH_BF16X3
+        self.fuse_maxpool = False
         # 16-bit storage, inference plans (make_plan turns it on): conv3 of a ResNet-v2 unit + the next unit's
         # pre-activation + conv1 as ONE launch (gv_bottleneck_chain_fwd) where the bottleneck depth is 64 or 128
         self.fuse_chain = False
@@ -136,7 +127,6 @@ class BackbonePlan:
         # ... and a depth-changing unit's projection shortcut inside its conv3 GEMM (GV_CHAIN_PROJ: ResNet-v2-50's first unit)
         self.fuse_proj = False
 
-    # ---- symbolic construction ----------------------------------------------------------------
     def lane(self, k):
         """Context manager: ops recorded inside go to launch lane k (gv_plan_set_schedule)."""
         plan = self
@@ -164,29 +154,65 @@ class BackbonePlan:
             self.vbufs[t.vbuf][1] = True
         return t
 
-    def _packed_elems(self, kh, kw, cin, cout):
-        """Size of a packed filter in 4-byte units of the weights arena."""
-        nbytes = int(self.lib.gv_packed_filter_bytes(kh, kw, cin, cout, self.dtype, self.math_mode))
-        assert nbytes > 0 and nbytes % 4 == 0
-        return nbytes // 4
+    def fused_maxpool_ok(self, x, cout, k, padding, stride=1, pool_padding="VALID"):
+        """May `conv(x, ..., cout, k, stride, padding, maxpool=pool_padding)` be one launch (_plan_layout.fused_maxpool_ok)?"""
+        pads = padding if isinstance(padding, tuple) else (padding, padding)
+        oh = _out_size(x.h, k, stride, pads[0])[0]
+        ow = _out_size(x.w, k, stride, pads[1])[0]
+        return bool(self.fuse_maxpool) and L.fused_maxpool_ok(
+            cout, k, stride, oh, ow, pool_padding, x.c, x.ld, x.vbuf < 0, x.p3, self.dtype != _lib.GV_F32,
+            self.math_mode == _lib.GV_MATH_BF16X3)
+
+    @property
+    def total_flops(self):
+        return sum(op["flops"] for op in self.ops)
+
+
+class BackbonePlan(SymbolicPlan):
+    """Collects ops symbolically, then lowers them to a native gv_plan."""
+
+    def __init__(self, nb, height, width, dtype=_lib.GV_F32, math_mode=_lib.GV_MATH_F32):
+        super().__init__(nb, height, width, dtype, math_mode)
+        self.lib = _lib.load()
+        self.filters = []        # (weights_name, kh, kw, cin, cout, w_off)
+        self.ss_specs = []       # (kind, name, c, eps, has_gamma, scale_off, shift_off)
+        self._ss_cache = {}
+        self.w_elems = 0
+        self.ss_elems = 0
+        self._plan = None
+        self._phys = None
+        self._bufs = None
+        self._ptrs = None
+        self.keepalive = []
+        self.use_lanes = True
+        self.use_p3 = dtype == _lib.GV_F32 and math_mode == _lib.GV_MATH_BF16X3
+        self.defer_preact = dtype != _lib.GV_F32
+        self.fuse_maxpool = dtype != _lib.GV_F32 or math_mode == _lib.GV_MATH_BF16X3
+
+    # ---- symbolic construction ----------------------------------------------------------------
+    def _filters(self, group):
+        """The filters of one launch, [(name, kh, kw, cin, cout)], back to back in the weights arena -> the first's offset."""
+        sized = []
+        for name, kh, kw, cin, cout in group:
+            nbytes = int(self.lib.gv_packed_filter_bytes(kh, kw, cin, cout, self.dtype, self.math_mode))
+            assert nbytes > 0 and nbytes % 4 == 0
+            sized.append((name, kh, kw, cin, cout, nbytes // 4))
+        off, self.w_elems = L.place_filters(self.filters, self.w_elems, sized)
+        return off
 
     def _filter(self, name, kh, kw, cin, cout):
-        n = self._packed_elems(kh, kw, cin, cout)
-        off = self.w_elems
-        self.filters.append((name, kh, kw, cin, cout, off))
-        self.w_elems += (n + 63) // 64 * 64          # keep every filter 256-byte aligned
-        return off
+        return self._filters([(name, kh, kw, cin, cout)])
+
+    def _scale_shifts(self, cols):
+        """The (scale, shift) columns of one launch, [(kind, name, c, eps, has_gamma)], side by side -> their offsets."""
+        so, ho, self.ss_elems = L.place_scale_shift(self.ss_specs, self.ss_elems, cols)
+        return so, ho
 
     def _scale_shift(self, kind, name, c, eps=0.0, has_gamma=False):
         key = (kind, name)
-        if key in self._ss_cache:
-            return self._ss_cache[key]
-        cpad = (c + 3) // 4 * 4
-        so, ho = self.ss_elems, self.ss_elems + cpad
-        self.ss_elems += 2 * cpad
-        self.ss_specs.append((kind, name, c, eps, has_gamma, so, ho))
-        self._ss_cache[key] = (so, ho)
-        return so, ho
+        if key not in self._ss_cache:
+            self._ss_cache[key] = self._scale_shifts([(kind, name, c, eps, has_gamma)])
+        return self._ss_cache[key]
 
     def conv_siblings(self, x, branches, first_out, norm, relu=True, pooled=None):
         """Several 1x1/stride-1 slim.conv2d that read the SAME input, as ONE implicit GEMM over their
@@ -207,20 +233,8 @@ class BackbonePlan:
         total = sum(couts)
         rest = total - couts[0]
         assert (first_out.nb, first_out.h, first_out.w, first_out.c) == (x.nb, x.h, x.w, couts[0])
-        n_each = [self._packed_elems(1, 1, x.c, c) for c in couts]
-        w_off = self.w_elems
-        off = w_off
-        for (scope, c), n in zip(branches, n_each):
-            self.filters.append((scope + "/weights", 1, 1, x.c, c, off))
-            off += n
-        self.w_elems = (off + 63) // 64 * 64
-        cpad = (total + 3) // 4 * 4
-        so, ho = self.ss_elems, self.ss_elems + cpad
-        self.ss_elems += 2 * cpad
-        cum = 0
-        for scope, c in branches:
-            self.ss_specs.append(("bn", scope + "/BatchNorm", c, norm[1], norm[2], so + cum, ho + cum))
-            cum += c
+        w_off = self._filters([(scope + "/weights", 1, 1, x.c, c) for scope, c in branches])
+        so, ho = self._scale_shifts([("bn", scope + "/BatchNorm", c, norm[1], norm[2]) for scope, c in branches])
         # the members other than the first feed 3x3 / 5x5 / 1x7 convs (and the commuted average pool): three-plane storage
         scratch = self.new_tensor(x.nb, x.h, x.w, rest, p3=all(c % 16 == 0 for c in couts[1:]) and couts[0] % 8 == 0)
         self._record(dict(kind="conv", name="+".join(sc for sc, _ in branches), x=x, y=first_out,
@@ -252,16 +266,9 @@ class BackbonePlan:
         total = d + depth
         y1 = self.new_tensor(x.nb, x.h, x.w, d)
         y2 = self.new_tensor(x.nb, x.h, x.w, depth)
-        n1, n2 = self._packed_elems(1, 1, x.c, d), self._packed_elems(1, 1, x.c, depth)
-        w_off = self.w_elems
-        self.filters.append((scope1 + "/weights", 1, 1, x.c, d, w_off))
-        self.filters.append((scope_sc + "/weights", 1, 1, x.c, depth, w_off + n1))
-        self.w_elems = (w_off + n1 + n2 + 63) // 64 * 64
-        cpad = (total + 3) // 4 * 4
-        so, ho = self.ss_elems, self.ss_elems + cpad
-        self.ss_elems += 2 * cpad
-        self.ss_specs.append(("bn", scope1 + "/BatchNorm", d, norm1[1], norm1[2], so, ho))
-        self.ss_specs.append(("bias", scope_sc + "/biases", depth, 0.0, False, so + d, ho + d))
+        w_off = self._filters([(scope1 + "/weights", 1, 1, x.c, d), (scope_sc + "/weights", 1, 1, x.c, depth)])
+        so, ho = self._scale_shifts([("bn", scope1 + "/BatchNorm", d, norm1[1], norm1[2]),
+                                     ("bias", scope_sc + "/biases", depth, 0.0, False)])
         self._record(dict(kind="conv", name=scope1 + "+" + scope_sc, x=x, y=y1, y2=y2, res=None, w_off=w_off,
                           scale_off=so, shift_off=ho, scale2_off=0, shift2_off=0, kh=1, kw=1, stride=1, pad_t=0, pad_l=0,
                           relu=True, split=d, cout=total, relu_cols=d, xpre=None, maxpool=None,
@@ -330,7 +337,7 @@ class BackbonePlan:
 
     def chain_ok(self, x):
         """May conv3 over `x` (d channels -> 4d) and the next unit's preact + conv1 be one launch (csrc/conv_chain.hip)?"""
-        return bool(self.fuse_chain) and self.dtype != _lib.GV_F32 and x.c in (64, 128) and x.ld % 8 == 0 and not x.p3
+        return bool(self.fuse_chain) and L.chain_ok(x.c, x.ld, x.p3, self.dtype != _lib.GV_F32)
 
     def unit(self, x, scope2, norm2, scope3, shortcut, pre_scope, pre_eps, scope1, norm1):
         """chain() with the unit's conv2 (3x3 / 1 SAME + BatchNorm + ReLU, nets/resnet_v2.py:85-86) in front: x is the unit's
@@ -377,24 +384,6 @@ class BackbonePlan:
                           bytes=float(self.esz) * (x.npix * (x.c + (0 if proj else cout) + cout + d) + (x.c + d) * cout)))
         return out, z
 
-    def fused_maxpool_ok(self, x, cout, k, padding, stride=1, pool_padding="VALID"):
-        """May `conv(x, ..., cout, k, stride, padding, maxpool=pool_padding)` be one launch?  The classes
-        GV_CONV_MAXPOOL3S2 / _SAME serve (include/gvcnn_hip.h), 16-bit storage: 3x3 / stride 1 from 32 to 64 channels
-        (VALID pool), or a 3x3 / 7x7 stride-2 stem on the fp32 images at 64 channels (VALID, or SAME on an even map)."""
-        pads = padding if isinstance(padding, tuple) else (padding, padding)
-        oh = _out_size(x.h, k, stride, pads[0])[0]
-        ow = _out_size(x.w, k, stride, pads[1])[0]
-        if not (self.fuse_maxpool and cout == 64 and not x.p3 and min(oh, ow) >= 3):
-            return False
-        if self.dtype == _lib.GV_F32:                         # three-plane math: the halo kernel's 30-pixel strip form, VALID pool
-            return (self.math_mode == _lib.GV_MATH_BF16X3 and pool_padding == "VALID" and k == 3 and stride == 1 and x.c == 32
-                    and x.vbuf >= 0 and x.ld % 4 == 0 and -(-ow // 16) * 16 * 5 > -(-ow // 30) * 32 * 4)
-        if pool_padding == "SAME" and (oh % 2 or ow % 2):
-            return False
-        if x.vbuf < 0:                                        # the network input: the stem strip kernel
-            return k in (3, 7) and stride == 2 and x.c == 3
-        return pool_padding == "VALID" and k == 3 and stride == 1 and x.c == 32 and x.ld % 8 == 0
-
     def pool(self, x, k, stride, padding, mode, out=None, name="pool", p3=False):
         oh, pad_t = _out_size(x.h, k, stride, padding)
         ow, pad_l = _out_size(x.w, k, stride, padding)
@@ -423,201 +412,102 @@ class BackbonePlan:
         return out
 
     # ---- lowering ----------------------------------------------------------------------------
-    def _assign_buffers(self):
-        last_use = {}
-        first_def = {}
-        lanes_of = {}
-        for i, op in enumerate(self.ops):
-            for key in ("x", "y", "y2", "res"):
-                t = op.get(key)
-                if t is not None and t.vbuf >= 0:
-                    last_use[t.vbuf] = i
-                    first_def.setdefault(t.vbuf, i)
-                    lanes_of.setdefault(t.vbuf, set()).add(op.get("lane", 0))
-        phys_sizes = []
-        phys_p3 = []               # a physical buffer holds either fp32 / 16-bit tensors or three-plane tensors
-        self._phys_p3 = phys_p3
-        free = []                  # (physical id, op index at which it was released, lanes that touched it)
-        vmap = {}
-        # A buffer released by one lane is not handed to ANOTHER lane for REUSE_DELAY ops: immediate
-        # reuse would order the independent branches behind each other (a write-after-read hazard the
-        # schedule then has to honour).  Memory is not the constraint here (288 GB of HBM).
-        REUSE_DELAY = 16 if self.use_lanes else 0
-        for i, op in enumerate(self.ops):
-            lane = op.get("lane", 0)
-            for key in ("y", "y2"):
-                t = op.get(key)
-                if t is None or t.vbuf in vmap:
-                    continue
-                need = self.vbufs[t.vbuf][0]
-                fmt = self.vbufs[t.vbuf][2]
-                ok = [f for f in free if (f[2] == {lane} or f[1] <= i - REUSE_DELAY) and phys_p3[f[0]] == fmt]
-                cand = [f for f in ok if phys_sizes[f[0]] >= need]
-                if cand:
-                    f = min(cand, key=lambda q: phys_sizes[q[0]])
-                    free.remove(f)
-                    p = f[0]
-                elif ok:                           # enlarge the biggest reusable buffer instead of adding one
-                    f = max(ok, key=lambda q: phys_sizes[q[0]])
-                    free.remove(f)
-                    p = f[0]
-                    phys_sizes[p] = need
-                else:
-                    p = len(phys_sizes)
-                    phys_sizes.append(need)
-                    phys_p3.append(fmt)
-                vmap[t.vbuf] = p
-            for v, lu in list(last_use.items()):
-                if lu == i and v in vmap and not self.vbufs[v][1]:
-                    free.append((vmap[v], i, lanes_of[v]))
-                    del last_use[v]
-        return vmap, phys_sizes
-
     def lower(self, device):
         """Create the native plan and the device buffers."""
         assert self._plan is None
-        lib = self.lib
-        vmap, phys_sizes = self._assign_buffers()
+        acc = [L.accesses(op) for op in self.ops]
+        lanes = [op["lane"] for op in self.ops]
+        vmap, phys_sizes, phys_p3 = L.assign_buffers(acc, lanes, self.vbufs, L.REUSE_DELAY if self.use_lanes else 0)
         self._phys = vmap
-        plan = C.c_void_p()
-        _lib.check(lib.gv_plan_create(C.byref(plan)), "gv_plan_create")
-        self._plan = plan
+        self._plan = C.c_void_p()
+        _lib.check(self.lib.gv_plan_create(C.byref(self._plan)), "gv_plan_create")
 
         def ref(t):
+            """(slot, element offset) of a plan tensor; (-1, 0): no such operand."""
             if t is None:
                 return -1, 0
             if t.vbuf < 0:
                 return SLOT_INPUT, t.off
             return SLOT_ACT0 + vmap[t.vbuf], t.off
 
-        lowp = self.dtype != _lib.GV_F32
-        wmul = 2 if lowp else 1                               # arena offsets are 4-byte units; plan offsets are elements
         for op in self.ops:
-            x, y = op["x"], op["y"]
-            xs, xo = ref(x)
-            ys, yo = ref(y)
-            if op["kind"] == "conv" and op.get("chain") and op["chain"].get("front"):
-                ch, res, y2 = op["chain"], op["res"], op["y2"]
-                fr = ch["front"]
-                d = _lib.UnitDesc(x.nb, x.h, x.w, x.c, x.ld, res.ld, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2, 0)
-                rs, ro = ref(res)
-                y2s, y2o = ref(y2)
-                _lib.check(lib.gv_plan_add_unit(plan, C.byref(d), xs, xo, SLOT_WEIGHTS, fr["w_off"] * wmul, op["w_off"] * wmul,
-                                                ch["w1_off"] * wmul, SLOT_SS, fr["scale_off"], fr["shift_off"], op["scale_off"],
-                                                op["shift_off"], op["scale2_off"], op["shift2_off"], ch["scale1_off"],
-                                                ch["shift1_off"], rs, ro, ys, yo, y2s, y2o), "gv_plan_add_unit(%s)" % op["name"])
-            elif op["kind"] == "conv" and op.get("chain"):
-                ch, res, y2 = op["chain"], op["res"], op["y2"]
-                if ch.get("proj"):                            # GV_CHAIN_PROJ: x = [conv2 output | pre-activation], no shortcut operand
-                    d = _lib.ChainDesc(x.npix, x.c // 2, x.ld, 0, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2 | _lib.GV_CHAIN_PROJ, 0)
-                    rs, ro = -1, 0
-                else:
-                    d = _lib.ChainDesc(x.npix, x.c, x.ld, res.ld, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2, 0)
-                    rs, ro = ref(res)
-                y2s, y2o = ref(y2)
-                _lib.check(lib.gv_plan_add_chain(plan, C.byref(d), xs, xo, SLOT_WEIGHTS, op["w_off"] * wmul,
-                                                 ch["w1_off"] * wmul, SLOT_SS, op["scale_off"], op["shift_off"],
-                                                 op["scale2_off"], op["shift2_off"], ch["scale1_off"], ch["shift1_off"],
-                                                 rs, ro, ys, yo, y2s, y2o), "gv_plan_add_chain(%s)" % op["name"])
-            elif op["kind"] == "conv":
-                y2, res = op["y2"], op["res"]
-                split = op["split"]
-                flags = _lib.GV_CONV_RELU if op["relu"] else 0
-                if split:
-                    flags |= _lib.GV_CONV_SPLIT
-                elif y2 is not None:
-                    flags |= _lib.GV_CONV_RELU2
-                if lowp and x.vbuf < 0:
-                    flags |= _lib.GV_CONV_X_F32               # the images stay fp32; the stem's loader rounds them
-                if x.p3:
-                    flags |= _lib.GV_CONV_X_P3
-                if y.p3:
-                    flags |= _lib.GV_CONV_Y_P3
-                if y2 is not None and y2.p3:
-                    assert split, "a three-plane second destination exists only for fused sibling convs"
-                    flags |= _lib.GV_CONV_Y2_P3
-                if op.get("maxpool"):                         # y is the pooled tensor; oh / ow stay the convolution's
-                    flags |= _lib.GV_CONV_MAXPOOL3S2_SAME if op["maxpool"] == "SAME" else _lib.GV_CONV_MAXPOOL3S2
-                    if op.get("pool_act"):                    # ... stored through a second BatchNorm + ReLU
-                        flags |= _lib.GV_CONV_POOL_ACT2 | _lib.GV_CONV_RELU2
-                d = _lib.ConvDesc(x.nb, x.h, x.w, x.c, x.ld, op["kh"], op["kw"], op["stride"],
-                                  op["pad_t"], op["pad_l"], op.get("oh", y.h), op.get("ow", y.w), op["cout"], y.ld,
-                                  res.ld if res is not None else 0, y2.ld if y2 is not None else 0,
-                                  flags, self.dtype, split, op.get("tile", 0), self.math_mode, 0,
-                                  op.get("relu_cols", 0))
-                rs, ro = ref(res)
-                y2s, y2o = ref(y2)
-                _lib.check(lib.gv_plan_add_conv(plan, C.byref(d), xs, xo, SLOT_WEIGHTS, op["w_off"] * wmul,
-                                                SLOT_SS, op["scale_off"], op["shift_off"], rs, ro,
-                                                ys, yo, y2s, y2o, op["scale2_off"], op["shift2_off"]),
-                           "gv_plan_add_conv(%s)" % op["name"])
-                if op.get("xpre") is not None:
-                    _lib.check(lib.gv_plan_set_conv_xpre(plan, lib.gv_plan_num_ops(plan) - 1, *op["xpre"]),
-                               "gv_plan_set_conv_xpre(%s)" % op["name"])
-            elif op["kind"] == "pool":
-                d = _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, op["k"], op["k"], op["stride"],
-                                  op["pad_t"], op["pad_l"], y.h, y.w, y.ld, op["mode"], self.dtype)
-                _lib.check(lib.gv_plan_add_pool(plan, C.byref(d), xs, xo, ys, yo),
-                           "gv_plan_add_pool(%s)" % op["name"])
-            else:
-                _lib.check(lib.gv_plan_add_scale_shift_act(plan, x.npix, x.c, x.ld, y.ld, 1, self.dtype,
-                                                           xs, xo, SLOT_SS, op["scale_off"],
-                                                           op["shift_off"], ys, yo),
-                           "gv_plan_add_scale_shift_act(%s)" % op["name"])
-        self._schedule(vmap)
+            chain = op["kind"] == "conv" and op.get("chain")
+            step = self._LOWER["unit" if chain and chain.get("front") else "chain" if chain else op["kind"]]
+            step(self, op, ref)
+        self.lanes_used = len(set(lanes))
+        if self.use_lanes and self.lanes_used > 1:
+            for i, (op, deps) in enumerate(zip(self.ops, L.lane_deps(acc, lanes, vmap))):
+                op["deps"] = deps
+                arr = (C.c_int32 * max(len(deps), 1))(*deps)
+                _lib.check(self.lib.gv_plan_set_schedule(self._plan, i, op["lane"], arr, len(deps)),
+                           "gv_plan_set_schedule(%s)" % op["name"])
+        self._alloc(device, phys_sizes, phys_p3)
+        return self
+
+    @property
+    def _wmul(self):
+        return 1 if self.dtype == _lib.GV_F32 else 2          # arena offsets are 4-byte units; plan offsets are elements
+
+    def _lower_conv(self, op, ref):
+        x, y, y2, res = op["x"], op["y"], op["y2"], op["res"]
+        d = _lib.ConvDesc(x.nb, x.h, x.w, x.c, x.ld, op["kh"], op["kw"], op["stride"],
+                          op["pad_t"], op["pad_l"], op.get("oh", y.h), op.get("ow", y.w), op["cout"], y.ld,
+                          res.ld if res is not None else 0, y2.ld if y2 is not None else 0,
+                          L.conv_flags(op, self.dtype != _lib.GV_F32, _lib), self.dtype, op["split"], op.get("tile", 0),
+                          self.math_mode, 0, op.get("relu_cols", 0))
+        _lib.check(self.lib.gv_plan_add_conv(self._plan, C.byref(d), *ref(x), SLOT_WEIGHTS, op["w_off"] * self._wmul,
+                                                 SLOT_SS, op["scale_off"], op["shift_off"], *ref(res), *ref(y), *ref(y2),
+                                                 op["scale2_off"], op["shift2_off"]), "gv_plan_add_conv(%s)" % op["name"])
+        if op.get("xpre") is not None:
+            _lib.check(self.lib.gv_plan_set_conv_xpre(self._plan, self.lib.gv_plan_num_ops(self._plan) - 1, *op["xpre"]),
+                       "gv_plan_set_conv_xpre(%s)" % op["name"])
+
+    def _lower_chain(self, op, ref):
+        x, y, y2, res, ch = op["x"], op["y"], op["y2"], op["res"], op["chain"]
+        if ch.get("proj"):                                    # GV_CHAIN_PROJ: x = [conv2 output | pre-activation], no shortcut operand
+            d = _lib.ChainDesc(x.npix, x.c // 2, x.ld, 0, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2 | _lib.GV_CHAIN_PROJ, 0)
+        else:
+            d = _lib.ChainDesc(x.npix, x.c, x.ld, res.ld, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2, 0)
+        _lib.check(self.lib.gv_plan_add_chain(self._plan, C.byref(d), *ref(x), SLOT_WEIGHTS, op["w_off"] * self._wmul,
+                                          ch["w1_off"] * self._wmul, SLOT_SS, op["scale_off"], op["shift_off"],
+                                          op["scale2_off"], op["shift2_off"], ch["scale1_off"], ch["shift1_off"],
+                                          *ref(res), *ref(y), *ref(y2)), "gv_plan_add_chain(%s)" % op["name"])
+
+    def _lower_unit(self, op, ref):
+        x, y, y2, res, ch = op["x"], op["y"], op["y2"], op["res"], op["chain"]
+        fr = ch["front"]
+        d = _lib.UnitDesc(x.nb, x.h, x.w, x.c, x.ld, res.ld, y.ld, y2.ld, self.dtype, _lib.GV_CONV_RELU2, 0)
+        _lib.check(self.lib.gv_plan_add_unit(self._plan, C.byref(d), *ref(x), SLOT_WEIGHTS, fr["w_off"] * self._wmul,
+                                         op["w_off"] * self._wmul, ch["w1_off"] * self._wmul, SLOT_SS, fr["scale_off"],
+                                         fr["shift_off"], op["scale_off"], op["shift_off"], op["scale2_off"],
+                                         op["shift2_off"], ch["scale1_off"], ch["shift1_off"], *ref(res), *ref(y), *ref(y2)),
+                   "gv_plan_add_unit(%s)" % op["name"])
+
+    def _lower_pool(self, op, ref):
+        x, y = op["x"], op["y"]
+        d = _lib.PoolDesc(x.nb, x.h, x.w, x.c, x.ld, op["k"], op["k"], op["stride"],
+                          op["pad_t"], op["pad_l"], y.h, y.w, y.ld, op["mode"], self.dtype)
+        _lib.check(self.lib.gv_plan_add_pool(self._plan, C.byref(d), *ref(x), *ref(y)), "gv_plan_add_pool(%s)" % op["name"])
+
+    def _lower_scale_shift_act(self, op, ref):
+        x, y = op["x"], op["y"]
+        _lib.check(self.lib.gv_plan_add_scale_shift_act(self._plan, x.npix, x.c, x.ld, y.ld, 1, self.dtype, *ref(x), SLOT_SS,
+                                                    op["scale_off"], op["shift_off"], *ref(y)),
+                   "gv_plan_add_scale_shift_act(%s)" % op["name"])
+
+    _LOWER = {"conv": _lower_conv, "chain": _lower_chain, "unit": _lower_unit, "pool": _lower_pool,
+              "ssa": _lower_scale_shift_act}
+
+    def _alloc(self, device, phys_sizes, phys_p3):
+        """The arenas and one device buffer per physical buffer (a three-plane one holds 3 x int16 per value)."""
         self.tdtype = TORCH_DTYPES[self.dtype]
         self.weights = torch.zeros(max(self.w_elems, 4), dtype=torch.float32, device=device)   # 4-byte units
         self.ss = torch.zeros(max(self.ss_elems, 4), dtype=torch.float32, device=device)
         self.act = [torch.empty(((n + 7) // 8 * 8) * 3, dtype=torch.int16, device=device) if p3_ else
                     torch.empty((n + 7) // 8 * 8, dtype=self.tdtype, device=device)
-                    for n, p3_ in zip(phys_sizes, self._phys_p3)]
+                    for n, p3_ in zip(phys_sizes, phys_p3)]
         self._bufs = [None, self.weights, self.ss] + self.act
-        self.act_bytes = sum(n * (6 if p3_ else self.esz) for n, p3_ in zip(phys_sizes, self._phys_p3))
-        return self
-
-    def _schedule(self, vmap):
-        """Cross-lane dependencies: an op waits for every earlier op whose access to the same physical
-        buffer conflicts with its own (read-after-write, write-after-read, write-after-write);
-        accesses to disjoint channel slices of one tensor do not conflict."""
-        lanes = sorted({op["lane"] for op in self.ops})
-        self.lanes_used = len(lanes)
-        if not self.use_lanes or len(lanes) == 1:
-            return
-        history = {}                      # phys -> [(op, is_write, vbuf, lo, hi)]
-        hb = []                           # hb[i]: ops known complete before op i starts
-        last_on_lane = {}
-        for i, op in enumerate(self.ops):
-            acc = []
-            for key, is_w in (("x", False), ("res", False), ("y", True), ("y2", True)):
-                t = op.get(key)
-                if t is not None and t.vbuf >= 0:
-                    lo = t.off % t.ld
-                    acc.append((vmap[t.vbuf], is_w, t.vbuf, lo, lo + t.c))
-            need = set()
-            for ph, is_w, vb, lo, hi in acc:
-                for (j, jw, jvb, jlo, jhi) in history.get(ph, ()):
-                    if not (is_w or jw):
-                        continue
-                    if jvb == vb and (hi <= jlo or jhi <= lo):
-                        continue
-                    need.add(j)
-            prev = last_on_lane.get(op["lane"])
-            known = set() if prev is None else (hb[prev] | {prev})
-            deps = []
-            for j in sorted(need, reverse=True):          # latest first: it usually implies the older ones
-                if j in known:
-                    continue
-                assert self.ops[j]["lane"] != op["lane"]
-                deps.append(j)
-                known |= hb[j] | {j}
-            hb.append(known)
-            last_on_lane[op["lane"]] = i
-            for ph, is_w, vb, lo, hi in acc:
-                history.setdefault(ph, []).append((i, is_w, vb, lo, hi))
-            op["deps"] = sorted(deps)
-            arr = (C.c_int32 * max(len(deps), 1))(*sorted(deps))
-            _lib.check(self.lib.gv_plan_set_schedule(self._plan, i, op["lane"], arr, len(deps)),
-                       "gv_plan_set_schedule(%s)" % op["name"])
+        self.act_bytes = sum(n * (6 if p3_ else self.esz) for n, p3_ in zip(phys_sizes, phys_p3))
 
     def view(self, t):
         """torch view [nb,h,w,c] of a plan tensor (strided when it is a channel slice)."""
@@ -747,61 +637,69 @@ class BackbonePlan:
         (profiles/r3_conv_probe_bf16.txt against r3_step_times_*).  So (2) the `in_sequence` best configurations of pass 1
         are timed IN SEQUENCE (gv_plan_time_each: an event pair behind every op over whole passes of the plan; round r
         gives every launch its r-th candidate) and each launch keeps the candidate that was fastest where it actually
-        runs.  in_sequence <= 1: pass 1 only (round 3's behaviour)."""
+        runs.  in_sequence <= 1: pass 1 only (round 3's behaviour).  The selection rules: _plan_layout."""
+        self.run(x)
+        chosen, cands = self._tune_warm(x, iters, in_sequence, verbose)
+        rounds = L.in_sequence_rounds(in_sequence, cands)
+        if rounds:
+            self._tune_in_sequence(x, iters, rounds, cands, chosen, verbose)
+        return chosen
+
+    def _set_tile(self, i, tile):
+        self.ops[i]["tile"] = tile + 1
+        _lib.check(self.lib.gv_plan_set_conv_tile(self._plan, i, tile + 1), "gv_plan_set_conv_tile")
+
+    def _time_tile(self, x, i, tile, iters, looks=1):
+        """ms of launch i under tile `tile` as a warm repeat of itself: the fastest of `looks` measurements."""
+        self.lib.gv_conv2d_set_tile_override(tile)
+        return min([self.time_range(x, i, 1, iters) for _ in range(looks)])
+
+    def _tune_warm(self, x, iters, in_sequence, verbose):
+        """Pass 1 -> ({op name: (tile, ms)}, {op index: candidate tiles of pass 2}); the winners are installed."""
         lib = self.lib
         ncfg_plan = lib.gv_conv2d_num_tile_cfgs(self.math_mode if self.dtype == _lib.GV_F32 else -1)   # -1: 16-bit storage
         ncfg_p3 = lib.gv_conv2d_num_tile_cfgs(-3)             # three-plane input: the LDS-DMA kernel's own table
-        self.run(x)
         chosen, cands = {}, {}
         try:
             for i, op in enumerate(self.ops):
                 if op["kind"] != "conv" or op.get("chain"):
                     continue
-                ncfg = ncfg_p3 if op["x"].p3 else ncfg_plan
                 timed = []
-                for t in range(ncfg):
-                    lib.gv_conv2d_set_tile_override(t)
+                for t in range(ncfg_p3 if op["x"].p3 else ncfg_plan):
                     try:
-                        timed.append((self.time_range(x, i, 1, iters), t))
-                    except _lib.GvError:
+                        timed.append((self._time_tile(x, i, t, iters), t))
+                    except _lib.GvError:                      # (the launch declines this tile)
                         continue
-                # a second, longer look at the three fastest: one noisy sample must not pick the tile of a 0.1 ms launch
-                finals = []
-                for _, t in sorted(timed)[:3]:
-                    lib.gv_conv2d_set_tile_override(t)
-                    finals.append((min(self.time_range(x, i, 1, 2 * iters), self.time_range(x, i, 1, 2 * iters)), t))
-                best_ms, best = min(finals) if finals else (float("inf"), 0)
-                op["tile"] = best + 1
+                finals = [(self._time_tile(x, i, t, 2 * iters, looks=2), t) for t in L.warm_finalists(timed)]
+                best, best_ms, cands[i] = L.warm_order(timed, finals, in_sequence)
                 chosen[op["name"]] = (best, best_ms)
-                order = [best] + [t for _, t in sorted(timed) if t != best]
-                cands[i] = order[:max(int(in_sequence), 1)]
-                _lib.check(lib.gv_plan_set_conv_tile(self._plan, i, best + 1), "gv_plan_set_conv_tile")
+                self._set_tile(i, best)
                 if verbose:
                     print("autotune %-60s cfg %2d  %.4f ms" % (op["name"][-60:], best, best_ms))
         finally:
             lib.gv_conv2d_set_tile_override(-1)
-        if int(in_sequence) > 1 and cands:
-            seq = {i: {} for i in cands}                          # op -> {tile: in-sequence ms}
-            for r in range(int(in_sequence)):
-                for i, c in cands.items():
-                    _lib.check(lib.gv_plan_set_conv_tile(self._plan, i, c[min(r, len(c) - 1)] + 1), "gv_plan_set_conv_tile")
-                each = [min(a, b) for a, b in zip(self.time_each(x, 2 * iters), self.time_each(x, 2 * iters))]
-                for i, c in cands.items():
-                    t = c[min(r, len(c) - 1)]
-                    seq[i][t] = min(each[i], seq[i].get(t, float("inf")))
-            moved = 0
+        return chosen, cands
+
+    def _tune_in_sequence(self, x, iters, rounds, cands, chosen, verbose):
+        """Pass 2: round r times every launch under its r-th candidate (its last where it has fewer)."""
+        seq = {i: {} for i in cands}                              # op -> {tile: in-sequence ms}
+        for r in range(rounds):
             for i, c in cands.items():
-                op = self.ops[i]
-                best = min(c, key=lambda t: (seq[i][t], c.index(t)))
-                moved += best != c[0]
-                op["tile"] = best + 1
-                chosen[op["name"]] = (best, seq[i][best])
-                _lib.check(lib.gv_plan_set_conv_tile(self._plan, i, best + 1), "gv_plan_set_conv_tile")
-                if verbose:
-                    print("in sequence %-57s cfg %2d  %.4f ms  (warm-repeat choice cfg %2d: %.4f ms in sequence)"
-                          % (op["name"][-57:], best, seq[i][best], c[0], seq[i][c[0]]))
-            self.autotune_moved = moved                           # launches whose in-sequence winner is not the warm-repeat one
-        return chosen
+                _lib.check(self.lib.gv_plan_set_conv_tile(self._plan, i, c[min(r, len(c) - 1)] + 1), "gv_plan_set_conv_tile")
+            each = [min(a, b) for a, b in zip(self.time_each(x, 2 * iters), self.time_each(x, 2 * iters))]
+            for i, c in cands.items():
+                t = c[min(r, len(c) - 1)]
+                seq[i][t] = min(each[i], seq[i].get(t, float("inf")))
+        moved = 0
+        for i, c in cands.items():
+            best = L.pick_in_sequence(c, seq[i])
+            moved += best != c[0]
+            chosen[self.ops[i]["name"]] = (best, seq[i][best])
+            self._set_tile(i, best)
+            if verbose:
+                print("in sequence %-57s cfg %2d  %.4f ms  (warm-repeat choice cfg %2d: %.4f ms in sequence)"
+                      % (self.ops[i]["name"][-57:], best, seq[i][best], c[0], seq[i][c[0]]))
+        self.autotune_moved = moved                               # launches whose in-sequence winner is not the warm-repeat one
 
     def time_range(self, x, first, count, iters, stream=None):
         """Average ms of ops [first, first+count) via hipEvents on the launch stream."""
@@ -826,10 +724,6 @@ class BackbonePlan:
                 self._plan = None
         except Exception:
             pass
-
-    @property
-    def total_flops(self):
-        return sum(op["flops"] for op in self.ops)
 
 
 def _stream_ptr(stream):
@@ -1018,117 +912,83 @@ RESNET50_BLOCKS = (("block1", 64, 3, 2), ("block2", 128, 4, 2), ("block3", 256, 
 def build_resnet_v2_50(b, keep=("resnet_v2_50/block3", "resnet_v2_50/block4"), scope="resnet_v2_50"):
     BN = ("bn", RESNET_BN_EPS, True)
     MAX = _lib.GV_POOL_MAX
-    # The first unit changes the depth at stride 1 and its pre-activation has as many channels as its bottleneck (64): its
-    # projection shortcut rides in conv3's GEMM (GV_CHAIN_PROJ, csrc/conv_chain.hip) — the pre-activation is written next to
-    # where conv2 will write, [conv2 | preact] is conv3's 128-channel input, and the 256-channel shortcut tensor never exists
-    b0 = RESNET50_BLOCKS[0]
-    proj0 = (getattr(b, "fuse_proj", False) and getattr(b, "fuse_chain", False) and b.dtype != _lib.GV_F32 and b0[1] == 64 and
-             b0[2] >= 2 and scope + "/pool1" not in keep and "%s/%s/unit_1/bottleneck_v2" % (scope, b0[0]) not in keep)
-    xb = None
-
-    def first_preact_out(h, w):
-        nonlocal xb
-        if not proj0:
-            return None
-        xb = b.new_tensor(b.nb, h, w, 128)
-        return xb.channels(64, 128)
-    # conv1: explicit pad 3 + VALID, bias, no BN/ReLU (resnet_v2.py:178-180, resnet_utils.py:94-105)
-    if scope + "/conv1" not in keep and getattr(b, "fuse_maxpool", False) and \
-            b.fused_maxpool_ok(b.input, 64, 7, ((3, 3), (3, 3)), 2, "SAME"):
-        # conv1 -> pool1 (resnet_v2.py:178-181) as ONE launch: the un-pooled conv1 is never written (nobody taps it).  The first
-        # unit changes the depth, so pool1's only reader is that unit's `preact` BatchNorm + ReLU (:75): it rides on the
-        # pooled tensor's way out of the same launch (16-bit storage, GV_CONV_POOL_ACT2) and pool1 itself is never stored
-        first_pre = "%s/%s/unit_1/bottleneck_v2/preact" % (scope, RESNET50_BLOCKS[0][0])
-        fold_pre = (b.dtype != _lib.GV_F32 and getattr(b, "fuse_pool_act", False) and RESNET50_BLOCKS[0][1] * 4 != 64 and
-                    scope + "/pool1" not in keep)
-        ph, pw = _out_size(b.height, 7, 2, (3, 3))[0] // 2, _out_size(b.width, 7, 2, (3, 3))[0] // 2
-        net = b.conv(b.input, scope + "/conv1", 64, 7, 2, ((3, 3), (3, 3)), norm=None, relu=False, maxpool="SAME",
-                     pool_act=(first_pre, RESNET_BN_EPS) if fold_pre else None, out=first_preact_out(ph, pw) if fold_pre else None)
-        pre_folded = fold_pre
-    else:
-        net = b.conv(b.input, scope + "/conv1", 64, 7, 2, ((3, 3), (3, 3)), norm=None, relu=False)
-        b.end_points[scope + "/conv1"] = net
-        net = b.pool(net, 3, 2, "SAME", MAX, name=scope + "/pool1")                    # resnet_v2.py:181
-        pre_folded = False
+    lowp = b.dtype != _lib.GV_F32
     units = []
     for bname, base, n_units, bstride in RESNET50_BLOCKS:
         for u in range(n_units):
             units.append((bname, base, u, n_units, bstride if u == n_units - 1 else 1))
-    first_sc = "%s/%s/unit_1/bottleneck_v2" % (scope, units[0][0])
-    # (pre_folded: `net` already IS the first pre-activation; nothing reads the raw pool1 — the first unit's shortcut is a
-    # projection of the pre-activation, resnet_v2.py:79-81)
-    if not pre_folded:
-        o = first_preact_out(net.h, net.w)                 # (a training plan's bn_relu has no `out`: it never asks for one)
-        preact = b.bn_relu(net, first_sc + "/preact", RESNET_BN_EPS, first_sc + "/preact", **({"out": o} if o is not None else {}))
+
+    def unit_scope(i):
+        return "%s/%s/unit_%d/bottleneck_v2" % (scope, units[i][0], units[i][2] + 1)
+
+    # The first unit changes the depth at stride 1 and its pre-activation has as many channels as its bottleneck (64): its
+    # projection shortcut rides in conv3's GEMM (GV_CHAIN_PROJ, csrc/conv_chain.hip) — the pre-activation is written next to
+    # where conv2 will write, [conv2 | preact] is conv3's 128-channel input, and the 256-channel shortcut tensor never exists
+    b0 = RESNET50_BLOCKS[0]
+    proj0 = (b.fuse_proj and b.fuse_chain and lowp and b0[1] == 64 and b0[2] >= 2 and scope + "/pool1" not in keep and
+             unit_scope(0) not in keep)
+    forms = L.resnet_unit_forms(units, lowp, proj0, b.fuse_chain, b.fuse_unit, b.fuse_pair, b.defer_preact)
+
+    def preact_home(h, w):
+        """-> ([conv2 | preact] tensor of the first unit, its pre-activation half), allocated just before its writer."""
+        if not proj0:
+            return None, None
+        both = b.new_tensor(b.nb, h, w, 128)
+        return both, both.channels(64, 128)
+
+    # conv1: explicit pad 3 + VALID, bias, no BN/ReLU (resnet_v2.py:178-180, resnet_utils.py:94-105)
+    fold_pre = False
+    if scope + "/conv1" not in keep and b.fuse_maxpool and b.fused_maxpool_ok(b.input, 64, 7, ((3, 3), (3, 3)), 2, "SAME"):
+        # conv1 -> pool1 (resnet_v2.py:178-181) as ONE launch: the un-pooled conv1 is never written (nobody taps it).  The first
+        # unit changes the depth, so pool1's only reader is that unit's `preact` BatchNorm + ReLU (:75): it rides on the
+        # pooled tensor's way out of the same launch (16-bit storage, GV_CONV_POOL_ACT2) and pool1 itself is never stored
+        fold_pre = lowp and b.fuse_pool_act and b0[1] * 4 != 64 and scope + "/pool1" not in keep
+        ph, pw = _out_size(b.height, 7, 2, (3, 3))[0] // 2, _out_size(b.width, 7, 2, (3, 3))[0] // 2
+        xb, o = preact_home(ph, pw) if fold_pre else (None, None)
+        net = b.conv(b.input, scope + "/conv1", 64, 7, 2, ((3, 3), (3, 3)), norm=None, relu=False, maxpool="SAME",
+                     pool_act=(unit_scope(0) + "/preact", RESNET_BN_EPS) if fold_pre else None, out=o)
     else:
-        preact = net
-    c1_ready = None                                     # this unit's conv1 output, when the previous unit's chain launch made it
-    for i, (bname, base, u, n_units, stride) in enumerate(units):
-        sc = "%s/%s/unit_%d/bottleneck_v2" % (scope, bname, u + 1)
-        depth, depth_in = base * 4, net.c
-        pair = None
-        proj = i == 0 and xb is not None and stride == 1 and depth != depth_in and depth_in == base and \
-            units[1][1] * 4 == depth and preact.vbuf == xb.vbuf
-        if proj:
-            shortcut = None                                                        # (inside conv3's GEMM)
-        elif depth == depth_in:                                                    # resnet_v2.py:76-77
-            shortcut = net if stride == 1 else b.pool(net, 1, stride, "VALID", MAX, name=sc + "/shortcut")
-        elif (stride == 1 and getattr(b, "fuse_pair", False) and not isinstance(preact, DeferredPreact) and base % 8 == 0
-              and c1_ready is None and base >= 128):
-            # (block1's pair — 64 + 256 columns over K = 64 — measured slower than its two launches: 0.283 against 0.269 ms)
-            # the projection shortcut and conv1 read the same pre-activation: one GEMM (16-bit inference plans)
-            pair = b.resnet_unit1_pair(preact, sc + "/conv1", base, BN, sc + "/shortcut", depth)
-            shortcut = pair[1]
+        net = b.conv(b.input, scope + "/conv1", 64, 7, 2, ((3, 3), (3, 3)), norm=None, relu=False)
+        b.end_points[scope + "/conv1"] = net
+        net = b.pool(net, 3, 2, "SAME", MAX, name=scope + "/pool1")                    # resnet_v2.py:181
+    # (fold_pre: `net` already IS the first pre-activation; nothing reads the raw pool1 — the first unit's shortcut is a
+    # projection of the pre-activation, resnet_v2.py:79-81)
+    preact = net
+    if not fold_pre:
+        xb, o = preact_home(net.h, net.w)
+        preact = b.bn_relu(net, unit_scope(0) + "/preact", RESNET_BN_EPS, unit_scope(0) + "/preact", out=o)
+    c1 = None                                           # this unit's conv1 output, when the previous unit's launch made it
+    for i, ((bname, base, u, n_units, stride), (shortcut_form, tail)) in enumerate(zip(units, forms)):
+        sc, depth = unit_scope(i), base * 4
+        if shortcut_form == "in_gemm":
+            shortcut = None
+        elif shortcut_form == "identity":                                          # resnet_v2.py:76-77
+            shortcut = net
+        elif shortcut_form == "subsampled":
+            shortcut = b.pool(net, 1, stride, "VALID", MAX, name=sc + "/shortcut")
+        elif shortcut_form == "pair":                   # the projection and conv1 read the same pre-activation: one GEMM
+            c1, shortcut = b.resnet_unit1_pair(preact, sc + "/conv1", base, BN, sc + "/shortcut", depth)
         else:                                                                      # resnet_v2.py:79-81
             shortcut = b.conv(preact, sc + "/shortcut", depth, 1, stride, "VALID", norm=None, relu=False)
-        if c1_ready is not None:
-            r, c1_ready = c1_ready, None
-        elif pair is not None:
-            r = pair[0]
-        else:
-            r = b.conv(preact, sc + "/conv1", base, 1, 1, "SAME", norm=BN, relu=True)  # :83-84
-        pad = "SAME" if stride == 1 else ((1, 1), (1, 1))                          # resnet_utils.py:94-105
-        # conv3 + the next unit's preact + conv1 as ONE launch (csrc/conv_chain.hip): the next unit keeps this depth
-        # (identity shortcut, conv1 the pre-activation's only reader) and the bottleneck depth is one the kernel serves;
-        # with fuse_unit this unit's conv2 (stride 1 here: the strided unit is a block's last) runs in front of it
-        chains = i + 1 < len(units) and units[i + 1][1] * 4 == depth and getattr(b, "fuse_chain", False) and b.chain_ok(r)
-        assert chains or not proj
-        # (whole units where that pays: d = 64.  At d = 128 the unit launch measured level with chain + conv2 — 0.276 against
-        # 0.166 + 0.107 ms, profiles/r6_seq_vs_warm_c4_*.txt — its conv2 phase is matrix-heavy and its one 8-wave workgroup per
-        # CU runs the phases in lockstep; fuse_unit="all" asks for it anyway)
-        fu = getattr(b, "fuse_unit", False)
-        whole = chains and bool(fu) and stride == 1 and (r.c <= 64 or fu == "all") and not proj
-        if not whole:
+        r = c1 if c1 is not None else b.conv(preact, sc + "/conv1", base, 1, 1, "SAME", norm=BN, relu=True)   # :83-84
+        c1 = preact = None
+        if tail != "unit":
+            pad = "SAME" if stride == 1 else ((1, 1), (1, 1))                      # resnet_utils.py:94-105
             r = b.conv(r, sc + "/conv2", base, 3, stride, pad, norm=BN, relu=True,      # :85-86
-                       out=xb.channels(0, 64) if proj else None)
-        nxt = None
-        kw = {}
-        if i + 1 < len(units):
-            nb_, nbase, nu, _, _ = units[i + 1]
-            nxt = ("%s/%s/unit_%d/bottleneck_v2/preact" % (scope, nb_, nu + 1), RESNET_BN_EPS)
-            if chains:
-                nsc = "%s/%s/unit_%d/bottleneck_v2" % (scope, nb_, nu + 1)
-                if whole:
-                    net, c1_ready = b.unit(r, sc + "/conv2", BN, sc + "/conv3", shortcut, nxt[0], nxt[1], nsc + "/conv1", BN)
-                elif proj:
-                    net, c1_ready = b.chain(xb, sc + "/conv3", None, nxt[0], nxt[1], nsc + "/conv1", BN, proj=sc + "/shortcut")
-                else:
-                    net, c1_ready = b.chain(r, sc + "/conv3", shortcut, nxt[0], nxt[1], nsc + "/conv1", BN)
-                preact = None
-                b.end_points[sc] = net
-                if u == n_units - 1:
-                    b.end_points["%s/%s" % (scope, bname)] = net
-                    if "%s/%s" % (scope, bname) in keep:
-                        b.keep(net)
-                continue
-            # the next unit keeps this depth (identity shortcut): its conv1 is the pre-activation's only reader.  Not in
-            # block4 (2048 channels over 7x7 maps): its conv3 is no longer HBM-bound and the conv1 loses more on the
-            # register-staged loader than the conv3 gains (measured: gpurun_out/r2/lt_res_xpre.txt vs lt_res_stored.txt)
-            if getattr(b, "defer_preact", False) and nbase * 4 == depth and depth <= 1024:
-                kw["defer"] = True
-        res = b.conv(r, sc + "/conv3", depth, 1, 1, "SAME", norm=None, relu=False,
-                     residual=shortcut, next_preact=nxt, **kw)                     # :87-91
-        net, preact = res if nxt is not None else (res, None)
+                       out=xb.channels(0, 64) if shortcut_form == "in_gemm" else None)
+        if tail == "last":
+            net = b.conv(r, sc + "/conv3", depth, 1, 1, "SAME", norm=None, relu=False, residual=shortcut)   # :87-91
+        else:
+            nsc = unit_scope(i + 1)
+            if tail == "unit":
+                net, c1 = b.unit(r, sc + "/conv2", BN, sc + "/conv3", shortcut, nsc + "/preact", RESNET_BN_EPS, nsc + "/conv1", BN)
+            elif tail == "chain_proj":
+                net, c1 = b.chain(xb, sc + "/conv3", None, nsc + "/preact", RESNET_BN_EPS, nsc + "/conv1", BN, proj=sc + "/shortcut")
+            elif tail == "chain":
+                net, c1 = b.chain(r, sc + "/conv3", shortcut, nsc + "/preact", RESNET_BN_EPS, nsc + "/conv1", BN)
+            else:
+                net, preact = b.conv(r, sc + "/conv3", depth, 1, 1, "SAME", norm=None, relu=False, residual=shortcut,
+                                     next_preact=(nsc + "/preact", RESNET_BN_EPS), **({"defer": True} if tail == "deferred" else {}))
         b.end_points[sc] = net
         if u == n_units - 1:
             b.end_points["%s/%s" % (scope, bname)] = net                           # resnet_utils.py:181
@@ -1159,6 +1019,31 @@ MATH_MODES = {"f32": _lib.GV_MATH_F32, "bf16x3": _lib.GV_MATH_BF16X3, "bf16x2": 
               "bf16x1": _lib.GV_MATH_BF16X1}
 
 
+def resolve_switches(dtype, math_mode, lanes=True, p3=True, defer_preact=True, fuse_maxpool=True, fuse_chain=True,
+                     fuse_unit=True, fuse_proj=True, env=None):
+    """make_plan's keywords and the whole-plan A/B environment switches (GV_NO_CHAIN, GV_NO_UNIT, GV_UNIT_ALL, GV_NO_PAIR,
+    GV_NO_POOL_ACT, GV_NO_PROJ: set to anything = in force) -> {BackbonePlan attribute: value}."""
+    unset = lambda name: (os.environ if env is None else env).get(name) is None
+    lowp, x3 = dtype != _lib.GV_F32, math_mode == _lib.GV_MATH_BF16X3
+    s = dict(use_lanes=bool(lanes), use_p3=not lowp and x3 and bool(p3),
+             defer_preact=lowp and bool(defer_preact),           # (A/B switch: False = every pre-activation stored)
+             fuse_maxpool=(lowp or x3) and bool(fuse_maxpool))   # (A/B switch: False = Conv2d_2b and MaxPool_3a as two launches)
+    # conv3 + next preact + conv1 as one launch (ResNet-v2 blocks 1 and 2 on 16-bit storage)
+    s["fuse_chain"] = bool(fuse_chain) and lowp and unset("GV_NO_CHAIN")
+    s["fuse_unit"] = fuse_unit if s["fuse_chain"] and fuse_unit and unset("GV_NO_UNIT") else False   # (off: chain only)
+    if s["fuse_unit"] and not unset("GV_UNIT_ALL"):
+        s["fuse_unit"] = "all"
+    s["fuse_pair"] = bool(fuse_chain) and lowp and unset("GV_NO_PAIR")
+    s["fuse_pool_act"] = s["fuse_maxpool"] and lowp and unset("GV_NO_POOL_ACT")
+    # the first ResNet unit's projection shortcut inside its conv3 GEMM (GV_CHAIN_PROJ)
+    s["fuse_proj"] = s["fuse_chain"] and bool(fuse_proj) and unset("GV_NO_PROJ")
+    if isinstance(p3, (set, frozenset, list, tuple)):
+        s["p3_blocks"] = set(p3)
+    else:
+        s["p3_blocks"] = set(P3_DEFAULT_BLOCKS) if p3 is True else None     # None ("all"): every conv -> conv intermediate
+    return s
+
+
 def make_plan(backbone, nb, height, width, device, raw_tap=None, final_tap=None, dtype=_lib.GV_F32,
               math="f32", lanes=True, p3=True, defer_preact=True, fuse_maxpool=True, fuse_chain=True, fuse_unit=True,
               fuse_proj=True):
@@ -1168,46 +1053,33 @@ def make_plan(backbone, nb, height, width, device, raw_tap=None, final_tap=None,
     fuse_maxpool: 16-bit storage issues `Conv2d_2b_3x3 -> MaxPool_3a_3x3` (Inception) / `conv1 -> pool1` (ResNet) as ONE
     launch that writes only the pooled tensor (GV_CONV_MAXPOOL3S2[_SAME]; bit-identical; False = the two launches)."""
     dtype = DTYPES[dtype] if isinstance(dtype, str) else dtype
-    b = BackbonePlan(nb, height, width, dtype, MATH_MODES[math] if isinstance(math, str) else math)
-    b.use_lanes = bool(lanes)
-    b.use_p3 = b.use_p3 and bool(p3)
-    b.defer_preact = b.defer_preact and bool(defer_preact)      # (A/B switch: False = every pre-activation stored)
-    b.fuse_maxpool = b.fuse_maxpool and bool(fuse_maxpool)      # (A/B switch: False = Conv2d_2b and MaxPool_3a as two launches)
-    # conv3 + next preact + conv1 as one launch (ResNet-v2 blocks 1 and 2 on 16-bit storage); GV_NO_CHAIN=1: whole-plan A/B
-    b.fuse_chain = bool(fuse_chain) and dtype != _lib.GV_F32 and os.environ.get("GV_NO_CHAIN") is None
-    b.fuse_unit = (fuse_unit if b.fuse_chain and fuse_unit and os.environ.get("GV_NO_UNIT") is None else False)   # (GV_NO_UNIT=1: chain only, A/B)
-    if b.fuse_unit and os.environ.get("GV_UNIT_ALL") is not None:
-        b.fuse_unit = "all"
-    b.fuse_pair = bool(fuse_chain) and dtype != _lib.GV_F32 and os.environ.get("GV_NO_PAIR") is None
-    b.fuse_pool_act = b.fuse_maxpool and dtype != _lib.GV_F32 and os.environ.get("GV_NO_POOL_ACT") is None
-    # the first ResNet unit's projection shortcut inside its conv3 GEMM (GV_CHAIN_PROJ; GV_NO_PROJ=1: whole-plan A/B)
-    b.fuse_proj = b.fuse_chain and bool(fuse_proj) and os.environ.get("GV_NO_PROJ") is None
-    if isinstance(p3, (set, frozenset, list, tuple)):
-        b.p3_blocks = set(p3)
-    elif p3 is True:
-        b.p3_blocks = set(P3_DEFAULT_BLOCKS)
-    else:
-        b.p3_blocks = None                 # "all": every conv -> conv intermediate
+    math_mode = MATH_MODES[math] if isinstance(math, str) else math
     raw_tap = raw_tap or TAPS[backbone][0]
     final_tap = final_tap or TAPS[backbone][1]
-    if backbone == "inception_v3":
-        build_inception_v3(b, final_endpoint=final_tap if final_tap in INCEPTION_ENDPOINTS else "Mixed_7c",
-                           keep=(raw_tap, final_tap))
-    elif backbone == "resnet_v2_50":
-        build_resnet_v2_50(b, keep=(raw_tap, final_tap))
-    else:
+    if backbone not in BACKBONES:
         raise ValueError("unknown backbone %r" % backbone)
-    for t in (raw_tap, final_tap):
-        if t not in b.end_points:
-            raise ValueError("end point %r not in backbone %s" % (t, backbone))
-        b.keep(b.end_points[t])
-    b.raw_tap, b.final_tap = raw_tap, final_tap
-    plan = b.lower(device)
+    asked = dict(lanes=lanes, p3=p3, defer_preact=defer_preact, fuse_maxpool=fuse_maxpool, fuse_chain=fuse_chain,
+                 fuse_unit=fuse_unit, fuse_proj=fuse_proj)
     # The builder decides a conv -> max-pool fusion from a Python copy of the kernels' predicates (fused_maxpool_ok) and
     # never allocates the un-pooled tensor; the KERNEL is the authority.  On a device, ask it once (one launch of each
-    # fused op on the plan's own buffers): if it declines (GV_E_UNSUPPORTED), rebuild the plan with the two launches.
-    if (b.fuse_maxpool or b.fuse_chain) and torch.device(device).type == "cuda" and plan.declined_fused_pools():
-        del plan
-        return make_plan(backbone, nb, height, width, device, raw_tap=raw_tap, final_tap=final_tap, dtype=dtype, math=math,
-                         lanes=lanes, p3=p3, defer_preact=defer_preact, fuse_maxpool=False, fuse_chain=False, fuse_unit=False)
-    return plan
+    # fused op on the plan's own buffers): if it declines (GV_E_UNSUPPORTED), rebuild the plan with the separate launches.
+    attempts = [asked, dict(asked, fuse_maxpool=False, fuse_chain=False, fuse_unit=False)]
+    while True:
+        b = BackbonePlan(nb, height, width, dtype, math_mode)
+        for k, v in resolve_switches(dtype, math_mode, **attempts.pop(0)).items():
+            setattr(b, k, v)
+        if backbone == "inception_v3":
+            build_inception_v3(b, final_endpoint=final_tap if final_tap in INCEPTION_ENDPOINTS else "Mixed_7c",
+                               keep=(raw_tap, final_tap))
+        else:
+            build_resnet_v2_50(b, keep=(raw_tap, final_tap))
+        for t in (raw_tap, final_tap):
+            if t not in b.end_points:
+                raise ValueError("end point %r not in backbone %s" % (t, backbone))
+            b.keep(b.end_points[t])
+        b.raw_tap, b.final_tap = raw_tap, final_tap
+        b.lower(device)
+        if not (attempts and (b.fuse_maxpool or b.fuse_chain) and torch.device(device).type == "cuda"
+                and b.declined_fused_pools()):
+            return b
+        del b

@@ -35,16 +35,13 @@ def _bn_ptrs(st, *keys):
     return [st[k].data_ptr() for k in keys or _BN_STAT_KEYS]
 
 
-class TrainPlan(backbones.BackbonePlan):
-    """Symbolic op list for training: un-fused, nothing recycled."""
+class TrainPlan(backbones.SymbolicPlan):
+    """Symbolic op list for training: un-fused, nothing recycled.  Every inference switch stays at its neutral value: each
+    tensor keeps its storage type (no three-plane intermediates), BatchNorm is its own op (batch statistics), and the
+    pool -> BatchNorm form of TrainGVCNN is the training path's fusion."""
 
     def __init__(self, nb, height, width, math_mode, dtype=_lib.GV_F32):
-        # (the training plan keeps every tensor in its storage type: no three-plane intermediates)
         super().__init__(nb, height, width, dtype, math_mode)
-        self.use_lanes = False
-        self.use_p3 = False
-        self.defer_preact = False          # BatchNorm is its own op here (batch statistics)
-        self.fuse_maxpool = False          # (the pool -> BatchNorm form of TrainGVCNN is the training path's fusion)
 
     def conv(self, x, scope, cout, k, stride=1, padding="SAME", out=None, norm=None, relu=True,
              residual=None, next_preact=None):
@@ -126,7 +123,8 @@ class TrainPlan(backbones.BackbonePlan):
                              mode=mode))
         return out
 
-    def bn_relu(self, x, bn_scope, eps, name):
+    def bn_relu(self, x, bn_scope, eps, name, out=None):
+        assert out is None, "a training plan places its own tensors"
         out = self.new_tensor(x.nb, x.h, x.w, x.c)
         self.ops.append(dict(lane=self.cur_lane, kind="bn", name=bn_scope, x=x, y=out, eps=eps, has_gamma=True, relu=True))
         return out
