@@ -245,8 +245,7 @@ SIGNATURES = {
 # tuning hooks (exported, not part of the drop-in surface)
 TUNING = {
     "gv_conv2d_set_tile_override": (None, [C.c_int]),
-    "gv_conv2d_set_debug": (None, [C.c_int]),
-    "gv_bottleneck_chain_set_debug": (None, [C.c_int]),
+    "gv_conv2d_set_debug": (None, [C.c_int]),      # probe bits: csrc/conv_probe.h, PROBE_* below
     "gv_conv2d_num_tile_cfgs": (C.c_int, [C.c_int]),
     "gv_conv2d_special_tile_cfg": (C.c_int, [C.c_int]),
     "gv_conv2d_wgrad_set_lp_f32": (None, [C.c_int]),
@@ -254,6 +253,9 @@ TUNING = {
     "gv_conv2d_wgrad_set_strip_taps": (None, [C.c_int]),
     "gv_pool2d_set_rows": (None, [C.c_int]),
 }
+# gv_conv2d_set_debug bits that tests may use: each selects another CORRECT product path (gvconv::Probe, csrc/conv_probe.h)
+PROBE_TAP_MAJOR = 128               # conv_dma: k-tiles tap-major where channel-chunk-major would be taken
+PROBE_GENERAL_EPILOGUE = 1048576    # conv_ws: the general staged epilogue where the pipelined fast one would be taken
 
 _lib = None
 

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_bf16s(const ConvArgs 
                 // divergent branch => the compiler can count vmcnt and leave the younger tile's loads in flight.
                 aok[RS][i] = a_ok[i];
                 const float* p = a.x + a_off[i];
-                if (!(a.dbg & 16)) {                          // (timing ablation 16: no A loads)
+                if (!(a.dbg & gvconv::PROBE_NO_A_LOADS)) {         // (timing ablation)
                     v0 = *reinterpret_cast<const f32x4*>(p);
                     v1 = *reinterpret_cast<const f32x4*>(p + 4);
                 }
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_bf16s(const ConvArgs 
     };
     auto store_tile = [&](auto rsc, int buf) {
         constexpr int RS = decltype(rsc)::value;
-        if (a.dbg & 32) {                                      // timing ablation 32: no LDS writes (operands stay live)
+        if (a.dbg & gvconv::PROBE_NO_LDS_WRITES) {                // timing ablation: operands stay live
 #pragma unroll
             for (int i = 0; i < A_SLOTS; ++i) asm volatile("" ::"v"(ra[RS][i][0]), "v"(ra[RS][i][1]));
 #pragma unroll
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_bf16s(const ConvArgs 
             const int idx = tid + i * NT;
             if (A_SLOTS * NT == BM * 2 || idx < BM * 2) {
                 u32x4 pl[NP];
-                if (a.dbg & 8) {                              // timing ablation: no plane split (wrong values)
+                if (a.dbg & gvconv::PROBE_NO_SPLIT) {               // timing ablation: wrong values
 #pragma unroll
                     for (int p = 0; p < NP; ++p) pl[p] = __builtin_bit_cast(u32x4, ra[RS][i][p & 1]);
                 } else {
@@ -368,33 +368,31 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_bf16s(const ConvArgs 
 // Conv2d_2a_3x3 / Conv2d_2b_3x3), GV_MATH_BF16X3.  The implicit-GEMM kernel above fetches AND SPLITS every input
 // element once per filter tap (9x); with 32 or 64 output channels that split costs as many VALU cycles as the
 // MFMAs it feeds, and the LDS-DMA kernel (conv_dma.hip) would move 9x the input through L2 -> LDS for 32 columns of
-// arithmetic.  Here a workgroup owns a 30-pixel-wide column strip of one image (a 32-pixel halo row: exactly two
-// 8-channel loader chunks per thread) and 32 output channels and walks down the strip 4 output rows (one per wave) at a
-// time over a ROLLING RING of 10 halo rows in LDS:
+// arithmetic.  Here a workgroup owns a column strip of one image and 32 output channels and walks down the strip one
+// tile of output rows at a time over a ROLLING RING of halo rows in LDS:
 //   * every input row is fetched and split into its three bf16 planes ONCE per strip (208-byte pixels: conflict-free
-//     ds_read_b128 fragments at any tap shift); the 4 new rows of the next tile are split and written into the ring
+//     ds_read_b128 fragments at any tap shift); the new rows of the next tile are split and written into the ring
 //     slots the previous tile released WHILE this tile's MFMAs run (same instruction stream, no staging phase), and
-//     the 4 rows after those are fetched into registers under the rest of the tile: one barrier per tile;
+//     the rows after those are fetched into registers under the rest of the tile: one barrier per tile;
 //   * every tap's A fragments are ds_read_b128 at a shifted pixel of the ring, one k-step ahead of their MFMAs;
 //   * the packed filter ([n][k-tile][plane][16], 55 KB for 32 columns) is LDS resident for the life of the workgroup.
-// Accumulation order (tap, channel half, plane product) is that of the implicit-GEMM kernels: bitwise the same result.
-// RW output rows per wave: 1 = 30-pixel strips (32-pixel halo rows: exactly 2 loader chunks per thread, 4 rows per tile),
-// 2 = 16-pixel strips (18-pixel halo rows, an MFMA block = 2 output rows x 16 pixels, 8 rows per tile, 18-row ring):
-// the narrow form where it saves >= 20 % of the MFMA rows on the image width (narrow images); at 109 columns (4 x 32 = 128
-// rows against 7 x 16 = 112) the two measured equal — the chip holds a higher clock with fewer MFMAs per second.
-constexpr int halo_tw(int rw) { return rw == 1 ? 30 : 16; }
-// ABL: timing ablations (gv_conv2d_set_debug): 4 no epilogue, 16 no fetch, 32 no split / ring stores.
+// Two kernels, chosen by launch_halo_x3 on the image width:
+//   conv3x3_halo_x3      16-pixel strips on v_mfma_f32_32x32x16_bf16: 18-pixel halo rows, an MFMA block = 2 output rows
+//                        x 16 pixels, one block per wave = 8 rows per tile, an 18-row ring; per thread three loader
+//                        chunks, the last one a quarter full.  For narrow images, where it saves >= 20 % of the MFMA rows.
+//                        Accumulation order (tap, channel half, plane product) is that of the implicit-GEMM kernels:
+//                        bitwise the same result.
+//   conv3x3_halo_x3_k32  30-pixel strips on v_mfma_f32_16x16x32_bf16 (below): everything else, and the fused max pool.
 // PLAIN: 32 | cout, 16-byte aligned rows, no residual, output < 4 GiB: the epilogue is branch-free (buffer stores drop
 // the lanes past the strip / image), so it too issues between the MFMAs; otherwise the general epilogue.
-template <int ABL, bool PLAIN, int RW>
+template <bool PLAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_halo_x3(const ConvArgs a) {
-    constexpr int TH = 4 * RW, TW = halo_tw(RW), HW = RW == 1 ? 32 : 18, PB = 3 * 64 + 16;  // halo pixel: 3 planes x 32 ch + pad
+    constexpr int TH = 8, TW = 16, HW = 18, PB = 3 * 64 + 16;       // halo pixel: 3 planes x 32 ch + pad
     constexpr int R = 2 * TH + 2;                                   // ring rows: TH + 2 in use + TH being written
-    constexpr int ROWB = RW == 1 ? HW * PB : (HW * PB + 255) / 256 * 256;   // RW 2: a fragment spans two ring rows, whose
-                                                                            // banks interleave when the pitch is 0 mod 256 B
+    constexpr int ROWB = (HW * PB + 255) / 256 * 256;               // a fragment spans two ring rows, whose banks interleave
+                                                                    // when the pitch is 0 mod 256 B
     constexpr int NCH = TH * HW * 4;                                // 8-channel chunks of the TH new rows of a tile
-    constexpr int SL = (NCH + 255) / 256;                           // per thread: 2 (RW 1), 3 with the last one 1/4 full (RW 2)
-    constexpr int DUMP = RW == 1 ? 0 : 64 * 16 * 3;                 // where the idle lanes of the last chunk store
+    constexpr int SL = (NCH + 255) / 256;                           // per thread: 3, the last one 1/4 full
     constexpr int WB = 18 * 96 + 16;                                // LDS filter row: 18 k-tiles x 3 planes
     constexpr int SW = 32 + 4;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -481,8 +479,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         (void*)a.y, 0, PLAIN ? (int)(unsigned)((size_t)a.M * a.y_ld * 4) : 0, 0x00020000);
     auto finish_pass = [&](int pass, int oy0, f32x4 v4) {       // oy0: the wave's first output row of that tile
         const int mrow = pass * 8 + rrow;                   // MFMA row -> (output row, column in the strip)
-        const int oy = RW == 1 ? oy0 : oy0 + (mrow >> 4);
-        const int row = RW == 1 ? mrow : (mrow & 15);
+        const int oy = oy0 + (mrow >> 4);
+        const int row = mrow & 15;
         float v[4] = {v4[0], v4[1], v4[2], v4[3]};
         if constexpr (PLAIN) {
 #pragma unroll
@@ -525,8 +523,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int k = 0; k < SL; ++k) fetch_one(k, TH + 2, hr, hok);   // split and stored under tile 0
 
-    const int a_lane = (RW == 1 ? li : (li & 15)) * PB + 16 * lh;
-    const int a_row = RW == 1 ? wave : 2 * wave + (li >> 4);    // this lane's output row within the tile
+    const int a_lane = (li & 15) * PB + 16 * lh;
+    const int a_row = 2 * wave + (li >> 4);                 // this lane's output row within the tile
     const char* b_lane = sW + li * WB + 16 * lh;
     float accv[16];                                         // the previous tile's accumulators: stored under this tile
 #pragma unroll
@@ -534,7 +532,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     int rbase = 0;                                          // (TH t) % R
     for (int t = 0; t < ntiles; ++t, rbase = rbase + TH >= R ? rbase + TH - R : rbase + TH) {
         __syncthreads();                                    // ring rows of this tile written; previous tile's reads done
-        const int oy = t * TH + RW * wave;
+        const int oy = t * TH + 2 * wave;
         const int hput = TH * t + TH + 2;                   // rows past the last tile's need go to released slots: harmless
         const char* ar[3];
 #pragma unroll
@@ -578,8 +576,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int q = 0; q < 6; ++q)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[cur][prod_pa(3, q)]),
                                                               __builtin_bit_cast(bf16x8, fb[cur][prod_pb(3, q)]), acc, 0, 0, 0);
-            if (ks >= 6 && ks < 6 + SL && !(ABL & 16)) fetch_one(ks - 6, hput + TH, hn, hnok);
-            if (ks < SL * 5 && !(ABL & 32)) {               // unit u = ks / 5: pieces 0..3 split a pair each, piece 4 stores
+            if (ks >= 6 && ks < 6 + SL) fetch_one(ks - 6, hput + TH, hn, hnok);
+            if (ks < SL * 5) {                              // unit u = ks / 5: pieces 0..3 split a pair each, piece 4 stores
                 const int u = ks / 5, pc = ks - u * 5;
                 if (pc < 4) {
 #pragma unroll
@@ -606,7 +604,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4*>(dst + p * ps) = ppl[u][p];
                 }
             }
-            if (!(ABL & 4) && t > 0) {
+            if (t > 0) {
                 if (ks == 0) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) stage[(4 * lh + (r & 3) + 8 * (r >> 2)) * SW + li] = accv[r];
@@ -619,12 +617,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (ABL & 4) {
-            float tsum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tsum += acc[r];
-            if (tsum == 1.2345e-30f) a.y[0] = tsum;
-        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) accv[r] = acc[r];
 #pragma unroll
@@ -634,16 +626,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             hok[k] = hnok[k];
         }
     }
-    if (!(ABL & 4)) {                                       // the last tile's epilogue
-        const int oy = (ntiles - 1) * TH + RW * wave;
-        __builtin_amdgcn_wave_barrier();
+    // the last tile's epilogue
+    const int oy = (ntiles - 1) * TH + 2 * wave;
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) stage[(4 * lh + (r & 3) + 8 * (r >> 2)) * SW + li] = accv[r];
-        __builtin_amdgcn_wave_barrier();
+    for (int r = 0; r < 16; ++r) stage[(4 * lh + (r & 3) + 8 * (r >> 2)) * SW + li] = accv[r];
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int pass = 0; pass < 4; ++pass)
-            finish_pass(pass, oy, *reinterpret_cast<const f32x4*>(stage + (pass * 8 + rrow) * SW + col4));
-    }
+    for (int pass = 0; pass < 4; ++pass)
+        finish_pass(pass, oy, *reinterpret_cast<const f32x4*>(stage + (pass * 8 + rrow) * SW + col4));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -651,7 +642,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // 2 x 2 blocks of 16 x 16, the LDS images keep a plane's 32 channels contiguous (64 bytes; halo pixels 192 bytes with
 // the 8-channel chunks XOR-swizzled by (column >> 1) & 3, filter rows [tap][plane][32] at a 1760-byte pitch: both
 // conflict-free for the 16-lane groups of ds_read_b128 at every tap shift).  Same bytes read from LDS per FLOP and the
-// same cycles per FLOP as the 32x32x16 form; the chip holds a higher clock on this shape (MI355X_MICROARCH.md, DVFS (7)).
+// same cycles per FLOP as a 32x32x16 form of these strips, which it superseded; the chip holds a higher clock on this
+// shape (MI355X_MICROARCH.md, DVFS (7)).  One k-step sums 32 channels: fp32-rounding-level agreement with the implicit-GEMM
+// kernels, not bitwise.
 // POOL (GV_CONV_MAXPOOL3S2 on fp32 storage; Conv2d_2b_3x3 -> MaxPool_3a_3x3, nets/inception_v3.py:111-113): the 3x3 / 2
 // VALID max pool of the output is taken inside the workgroup and only the pooled tensor is written — a quarter of the
 // bytes, and the pool's launch (which re-read all of them from HBM: the largest tensor of the fp32 plan) disappears.  A
@@ -660,7 +653,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // LDS ring of [14 pooled pixels][32 channels], and two tiles later — behind the tile loop's own barrier, no extra one —
 // 224 threads take the two pooled rows a tile completed: bitwise the two launches' values.  (Whole rows in a six-row ring
 // with a barrier in the middle of the tile cost the convolution +15 %.)
-template <int ABL, bool PLAIN, bool POOL = false>
+template <bool PLAIN, bool POOL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_halo_x3_k32(const ConvArgs a) {
     constexpr int TH = 4, TW = 30, HW = 32, PB = 192;
     constexpr int R = 2 * TH + 2;
@@ -903,8 +896,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                                        __builtin_bit_cast(bf16x8, fb[tp][j][prod_pb(3, q)]),
                                                                        acc[i][j], 0, 0, 0);
             const int ks = hs;
-            if (ks >= 6 && ks < 6 + SL && !(ABL & 16)) fetch_one(ks - 6, hput + TH, hn, hnok);
-            if (ks < SL * 5 && !(ABL & 32)) {
+            if (ks >= 6 && ks < 6 + SL) fetch_one(ks - 6, hput + TH, hn, hnok);
+            if (ks < SL * 5) {
                 const int u = ks / 5, pc = ks - u * 5;
                 if (pc < 4) {
 #pragma unroll
@@ -930,7 +923,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4*>(dst + p * 64) = ppl[u][p];
                 }
             }
-            if (!(ABL & 4) && t > 0) {
+            if (t > 0) {
                 if (ks == 0) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {          // acc[i][j][v]: pixel 16 i + 4 lg + v, channel 16 j + l16
@@ -955,16 +948,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (ABL & 4) {
-            float tsum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) tsum += acc[i][j][v];
-            if (tsum == 1.2345e-30f) a.y[0] = tsum;
-        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) accv[r] = acc[r >> 3][(r >> 2) & 1][r & 3];
 #pragma unroll
@@ -974,81 +957,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             hok[k] = hnok[k];
         }
     }
-    if (!(ABL & 4)) {
-        const int oy = (ntiles - 1) * TH + wave;
-        __builtin_amdgcn_wave_barrier();
+    // the last tile's epilogue
+    const int oy = (ntiles - 1) * TH + wave;
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jc = (r >> 2) & 1;
-            stage[(16 * (r >> 3) + 4 * lg + (r & 3)) * SW + 16 * jc + l16] = POOL ? fmaxf(accv[r] * scp[jc] + shp[jc], rlop[jc]) : accv[r];
-        }
-        __builtin_amdgcn_wave_barrier();
-        if constexpr (POOL) {
-            // (a wave still in the last iteration's pool_rows reads ring slots this tile's rows are about to take: in the
-            // loop the next iteration's barrier stands between the two)
-            __syncthreads();
-            hpass(0, oy);
-            hpass(1, oy);
-            __syncthreads();
-            if (ntiles >= 2) pool_rows(ntiles - 2);
-            pool_rows(ntiles - 1);
-        } else {
+    for (int r = 0; r < 16; ++r) {
+        const int jc = (r >> 2) & 1;
+        stage[(16 * (r >> 3) + 4 * lg + (r & 3)) * SW + 16 * jc + l16] = POOL ? fmaxf(accv[r] * scp[jc] + shp[jc], rlop[jc]) : accv[r];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if constexpr (POOL) {
+        // (a wave still in the last iteration's pool_rows reads ring slots this tile's rows are about to take: in the
+        // loop the next iteration's barrier stands between the two)
+        __syncthreads();
+        hpass(0, oy);
+        hpass(1, oy);
+        __syncthreads();
+        if (ntiles >= 2) pool_rows(ntiles - 2);
+        pool_rows(ntiles - 1);
+    } else {
 #pragma unroll
-            for (int pass = 0; pass < 4; ++pass)
-                finish_pass(pass, oy, *reinterpret_cast<const f32x4*>(stage + (pass * 8 + rrow) * SW + col4));
-        }
+        for (int pass = 0; pass < 4; ++pass)
+            finish_pass(pass, oy, *reinterpret_cast<const f32x4*>(stage + (pass * 8 + rrow) * SW + col4));
     }
 }
 
 int launch_halo_x3(const ConvArgs& a, hipStream_t st) {
-    // strips of 30 (one output row per wave) or 16 pixels (two): whichever covers the width with fewer MFMA rows
+    // strips of 30 (conv3x3_halo_x3_k32) or 16 pixels (conv3x3_halo_x3): whichever covers the width with fewer MFMA rows
     // (measured equal at 12 % fewer rows — Conv2d_2a/2b, 109 columns — so the narrow form needs a 20 % saving)
-    const int rw = gv_ceil_div(a.ow, 16) * 16 * 5 <= gv_ceil_div(a.ow, 30) * 32 * 4 ? 2 : 1;
-    const int tw = halo_tw(rw), hw = rw == 1 ? 32 : 18, ring = 8 * rw + 2;
-    const int tiles_x = (a.ow + tw - 1) / tw, nct = (a.cout + 31) / 32;
-    const size_t lds = (size_t)ring * (rw == 1 ? hw * 208 : (hw * 208 + 255) / 256 * 256) + 4 * 32 * 36 * 4 + 32 * (18 * 96 + 16) +
-                       (rw == 1 ? 0 : 64 * 16 * 3);
-    const dim3 grid((unsigned)(a.nb * tiles_x * nct));
+    const bool narrow = gv_ceil_div(a.ow, 16) * 16 * 5 <= gv_ceil_div(a.ow, 30) * 32 * 4;
+    const int nct = (a.cout + 31) / 32;
     const bool plain = a.cout % 32 == 0 && a.y_ld % 4 == 0 && ((((uintptr_t)a.y) & 15) == 0) && a.res == nullptr &&
                        (uint64_t)a.M * a.y_ld * 4 < 0xffffffffull;
-#define GV_HALO_LAUNCH(B, P, W) return gv_launch<conv3x3_halo_x3<B, P, W>>(grid, dim3(256), lds, st, a);
-#define GV_HALO_K32(B, P) return gv_launch<conv3x3_halo_x3_k32<B, P>>(grid, dim3(256), lds32, st, a);
     const size_t lds32 = (size_t)10 * 32 * 192 + 4 * 32 * 36 * 4 + 32 * (9 * 192 + 32);
     if (a.pool) {                                     // conv -> max pool 3x3 / 2 VALID: the 30-pixel strip form only
-        if (rw != 1 || a.pool != 1 || a.res != nullptr || a.cout % 4 != 0) return GV_E_UNSUPPORTED;
+        if (narrow || a.pool != 1 || a.res != nullptr || a.cout % 4 != 0) return GV_E_UNSUPPORTED;
         const dim3 pgrid((unsigned)(a.nb * ((a.pw + 13) / 14) * nct));
         const size_t ldsp = lds32 + (size_t)10 * 14 * 32 * 4;
-        return gv_launch<conv3x3_halo_x3_k32<0, false, true>>(pgrid, dim3(256), ldsp, st, a);
+        return gv_launch<conv3x3_halo_x3_k32<false, true>>(pgrid, dim3(256), ldsp, st, a);
     }
-    if (rw == 1 && !(a.dbg & 8)) {                    // (debug bit 8: the 32x32x16 form, for A/B timing)
-        if (a.dbg & (4 | 16 | 32)) {
-            if (!plain) return GV_E_UNSUPPORTED;
-            switch (a.dbg & 52) {
-                case 4: GV_HALO_K32(4, true)
-                case 52: GV_HALO_K32(52, true)
-            }
-            return GV_E_UNSUPPORTED;
-        }
-        if (plain) GV_HALO_K32(0, true)
-        GV_HALO_K32(0, false)
+    if (narrow) {
+        // 18-row ring of 18-pixel rows at a pitch of 0 mod 256 bytes, staging blocks, filter, the idle loader lanes' dump
+        const size_t lds = (size_t)18 * ((18 * 208 + 255) / 256 * 256) + 4 * 32 * 36 * 4 + 32 * (18 * 96 + 16) + 64 * 16 * 3;
+        const dim3 grid((unsigned)(a.nb * gv_ceil_div(a.ow, 16) * nct));
+        if (plain) return gv_launch<conv3x3_halo_x3<true>>(grid, dim3(256), lds, st, a);
+        return gv_launch<conv3x3_halo_x3<false>>(grid, dim3(256), lds, st, a);
     }
-    if (a.dbg & (4 | 16 | 32)) {                      // timing experiments only
-        if (!plain || rw != 1) return GV_E_UNSUPPORTED;
-        switch (a.dbg & 52) {
-            case 4: GV_HALO_LAUNCH(4, true, 1)
-            case 48: GV_HALO_LAUNCH(48, true, 1)
-            case 52: GV_HALO_LAUNCH(52, true, 1)
-        }
-        return GV_E_UNSUPPORTED;
-    }
-    if (rw == 2) {
-        if (plain) GV_HALO_LAUNCH(0, true, 2)
-        GV_HALO_LAUNCH(0, false, 2)
-    }
-    if (plain) GV_HALO_LAUNCH(0, true, 1)
-    GV_HALO_LAUNCH(0, false, 1)
-#undef GV_HALO_LAUNCH
-#undef GV_HALO_K32
+    const dim3 grid((unsigned)(a.nb * gv_ceil_div(a.ow, 30) * nct));
+    if (plain) return gv_launch<conv3x3_halo_x3_k32<true>>(grid, dim3(256), lds32, st, a);
+    return gv_launch<conv3x3_halo_x3_k32<false>>(grid, dim3(256), lds32, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -45,7 +45,6 @@ struct ChainArgs {
     unsigned short* z;             // [M][z_ld]   d channels: relu(bn(conv1(relu(bn(y)))))
     int M, x_ld, res_ld, y_ld, z_ld;
     int relu2;
-    int dbg;
     // FRONT (gv_bottleneck_unit_fwd): x is the unit's conv1 output and the kernel begins with the unit's conv2 — 3x3, stride 1,
     // SAME, BatchNorm + ReLU (nets/resnet_v2.py:85-86) — whose 32 rows per wave never leave the registers
     const unsigned short* w0;      // packed [d][9 * d]: conv2 (k = tap * d + channel)
@@ -543,8 +542,6 @@ int launch_tail_d(int d, const ChainArgs& a, hipStream_t st) {
     return GV_E_UNSUPPORTED;
 }
 
-int g_chain_debug = 0;
-
 }  // namespace
 
 namespace gvconv {
@@ -570,14 +567,11 @@ int chain_tail_launch(int dtype, const ConvArgs& a, hipStream_t st) {
     c.z = reinterpret_cast<unsigned short*>(a.y);
     c.M = a.M; c.x_ld = 0; c.res_ld = a.x_ld; c.y_ld = 0; c.z_ld = a.y_ld;
     c.relu2 = 1;
-    c.dbg = g_chain_debug;
     c.w0 = nullptr; c.sc0 = c.sh0 = nullptr; c.zeros = nullptr; c.ih = c.iw = 0;
     GV_LP_DISPATCH(dtype, return launch_tail_d<T>(a.cout, c, st));
 }
 
 }  // namespace gvconv
-
-extern "C" void gv_bottleneck_chain_set_debug(int bits) { g_chain_debug = bits; }
 
 extern "C" int gv_bottleneck_chain_fwd(const gv_chain_desc* d, const void* x, const void* w3_packed, const float* scale3,
                                        const float* shift3, const void* shortcut, void* y, const float* pre_scale,
@@ -603,7 +597,6 @@ extern "C" int gv_bottleneck_chain_fwd(const gv_chain_desc* d, const void* x, co
     a.w2 = (const unsigned short*)w1_packed; a.sc2 = scale1; a.sh2 = shift1; a.z = (unsigned short*)z;
     a.M = d->m; a.x_ld = d->x_ld; a.res_ld = d->res_ld; a.y_ld = d->y_ld; a.z_ld = d->z_ld;
     a.relu2 = (d->flags & GV_CONV_RELU2) ? 1 : 0;
-    a.dbg = g_chain_debug;
     a.w0 = nullptr; a.sc0 = a.sh0 = nullptr; a.zeros = nullptr; a.ih = a.iw = 0;
     if (d->dtype == GV_BF16) return launch_chain_d<__bf16>(d->d, a, (hipStream_t)stream, proj);
     return launch_chain_d<_Float16>(d->d, a, (hipStream_t)stream, proj);
@@ -633,7 +626,6 @@ extern "C" int gv_bottleneck_unit_fwd(const gv_unit_desc* d, const void* x, cons
     a.w2 = (const unsigned short*)w1_packed; a.sc2 = scale1; a.sh2 = shift1; a.z = (unsigned short*)z;
     a.M = (int)M64; a.x_ld = d->x_ld; a.res_ld = d->res_ld; a.y_ld = d->y_ld; a.z_ld = d->z_ld;
     a.relu2 = (d->flags & GV_CONV_RELU2) ? 1 : 0;
-    a.dbg = g_chain_debug;
     a.w0 = (const unsigned short*)w2_packed; a.sc0 = scale2; a.sh0 = shift2;
     a.zeros = (const char*)gvconv::dma_zero_page();
     if (!a.zeros) return GV_E_UNSUPPORTED;

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "gv_common.h"
+#include "conv_probe.h"
 #include "conv_stats.h"
 
 namespace gvconv {
@@ -29,7 +30,7 @@ struct ConvArgs {
 #ifdef GV_PHASE_TIMES
     unsigned long long* phase_buf = nullptr;   // profiling build: per-wave phase timestamps (conv_dma.hip)
 #endif
-    int dbg;                    // ablation bit (timing experiments only): 4 = no epilogue stores
+    int dbg;                    // probe bits (gv_conv2d_set_debug): gvconv::Probe, conv_probe.h
     const void* zeros;          // conv_dma.hip: a zero page for the padding taps of the gather
     int y_p3, y2_p3;            // destination format: 0 = fp32, 1 = three bf16 planes (conv_x3_epi.h)
     int korder;                 // conv_dma.hip: 0 = k-tiles tap-major, 1 = channel-chunk-major (filter taps innermost)
@@ -44,14 +45,14 @@ struct ConvArgs {
     int ph = 0, pw = 0;         //    output, ph x pw pixels per image
 };
 
-// May this launch take the lean 16-bit staged epilogue (conv_stats.h STAT_LEAN)?  dbg bit 2: always the full one (A/B).
+// May this launch take the lean 16-bit staged epilogue (conv_stats.h STAT_LEAN)?  PROBE_FULL_EPILOGUE: always the full one.
 inline bool lp_epilogue_lean_ok(const ConvArgs& a) {
     const bool one = a.y2 == nullptr && a.split == 0;
     // ... or the two destinations of a fused sibling GEMM, split on a chunk boundary (no second ACTIVATION: that is the
     // full epilogue's dual output)
     const bool two = a.y2 != nullptr && a.split > 0 && a.split % 8 == 0 && a.y2_ld % 8 == 0 && (((uintptr_t)a.y2) & 15) == 0 &&
                      !a.y2_p3;
-    return !(a.dbg & 2) && (one || two) && a.cout % 8 == 0 && a.y_ld % 8 == 0 &&
+    return !(a.dbg & PROBE_FULL_EPILOGUE) && (one || two) && a.cout % 8 == 0 && a.y_ld % 8 == 0 &&
            (((uintptr_t)a.y) & 15) == 0 && (a.res == nullptr || (a.res_ld % 8 == 0 && (((uintptr_t)a.res) & 15) == 0)) &&
            (!a.relu || a.relu_limit >= a.cout || a.relu_limit % 8 == 0);
 }
@@ -62,7 +63,7 @@ inline bool lp_epilogue_lean_ok(const ConvArgs& a) {
 template <int TM, int TN>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x16 (&acc)[TM][TN], int m0,
                                               int n0, int wm, int wn, int lane) {
-    if (a.dbg & 4) {            // keep the accumulators live without storing the tile
+    if (a.dbg & PROBE_NO_STORES) {            // keep the accumulators live without storing the tile
         float t = 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i)

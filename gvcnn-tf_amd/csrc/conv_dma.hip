@@ -136,7 +136,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_dma(const ConvArgs a) {
     constexpr bool LATE_SS = dma_late_ss<NP, WM, WN, TM, TN, ST, EPI, KTX>();
     constexpr int LATE_OFF = dma_late_off<NP, WM, WN, TM, TN, ST, EPI, KTX>();
     constexpr bool ANY_SS = USE_SS || LATE_SS;
-    float* sstab = ANY_SS && !(a.dbg & 512) ? reinterpret_cast<float*>(smem + (LATE_SS ? LATE_OFF : SS_OFF)) : nullptr;   // dbg 512: constants from global (A/B)
+    float* sstab = ANY_SS && !(a.dbg & gvconv::PROBE_SS_FROM_GLOBAL) ? reinterpret_cast<float*>(smem + (LATE_SS ? LATE_OFF : SS_OFF)) : nullptr;   // (A/B)
     float ss_v[4] = {0.f, 0.f, 0.f, 0.f};
     const bool ss_dual = EPI == 0 && a.y2 != nullptr && a.split == 0;
     if (ANY_SS && tid < WN * TN * 32) {
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_dma(const ConvArgs a) {
     // Eight waves = two per SIMD (waves w and w+4: a workgroup's waves go to the SIMDs in a cyclic order), and the k-tile
     // barrier makes both arrive at their MFMAs together: they then share the matrix pipe and idle together through the next
     // barrier / fragment reads / DMA issue.  A higher issue priority for one of the two staggers them inside a k-tile —
-    // one runs its MFMAs while the other does everything else: -2 .. -3.5 % on the 256-row tiles (debug bit 256: off, A/B).
-    if (NW == 8 && NP == 1 && wave >= 4 && !(a.dbg & 256)) __builtin_amdgcn_s_setprio(2);
+    // one runs its MFMAs while the other does everything else: -2 .. -3.5 % on the 256-row tiles (PROBE_DMA_NO_PHASING: off, A/B).
+    if (NW == 8 && NP == 1 && wave >= 4 && !(a.dbg & gvconv::PROBE_DMA_NO_PHASING)) __builtin_amdgcn_s_setprio(2);
 
     const int lid = gv_xcd_remap(blockIdx.x, gridDim.x);
     const int tile_n = lid % a.tiles_n;
@@ -549,9 +549,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_dma(const ConvArgs a) {
         // 0-3 pass the tile barrier in front of the first half, waves 4-7 between the halves.  The barrier releases both at
         // once, so one wave of each SIMD is in its pure-MFMA half while its partner does everything else, and they swap.
         // (Same barrier count for every wave; tile kt's stage is overwritten only behind barrier kt+1, by which time both
-        // groups have consumed their fragments of tile kt.)  Debug bit 256: everyone passes the barrier in front (A/B).
+        // groups have consumed their fragments of tile kt.)  PROBE_DMA_NO_PHASING: everyone passes the barrier in front (A/B).
         constexpr bool PHASED = NW == 8 && KS == 1 && (NMFS % 2 == 0);
-        const bool late_barrier = PHASED && wave >= NW / 2 && !(a.dbg & 256);
+        const bool late_barrier = PHASED && wave >= NW / 2 && !(a.dbg & gvconv::PROBE_DMA_NO_PHASING);
         auto mfmas_half = [&](auto setc, auto halfc, bool do_issue, char* nb, bool do_read, int rstage) {
             constexpr int S = decltype(setc)::value;
             constexpr int HALF = decltype(halfc)::value;
@@ -658,7 +658,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_dma(const ConvArgs a) {
         lp_epilogue_staged<T, TM, TN, STATS>(a, acc, m0, n0, wm, wn, lane, reinterpret_cast<float*>(smem + wave * EpiGeom<TN>::BYTES), 32,
                                              sstab, BN, smem, st_b0 * (HAS_SUMS ? a.st.hw : 0));
         if constexpr (HAS_SUMS) {
-            if (!(a.st.dbg & 16384)) __syncthreads();              // every lane's runs are in the table
+            if (!(a.st.dbg & gvconv::PROBE_STAT_NO_BARRIER)) __syncthreads();              // every lane's runs are in the table
             const int last = (m0 + BM < a.M ? m0 + BM : a.M) - 1;
             gvconv::stat_publish<STATS>(a.st, smem, tid, BN, n0, a.cout, st_b0, min(last / a.st.hw - st_b0 + 1, a.st.slots));
         }
@@ -723,7 +723,7 @@ int launch_dma(const ConvArgs& a0, hipStream_t st) {
     if (nwg < 0) return GV_E_UNSUPPORTED;
     a.zeros = zero_page_for_current_device();
     if (!a.zeros) return GV_E_UNSUPPORTED;
-    a.korder = (a.kh * a.kw > 1 && a.kh * a.kw <= 32 && a.kw < 32 && a.cin % G::KT == 0 && a.dil_shift == 0 && !(a.dbg & 128)) ? 1 : 0;   // dbg 128: tap-major (A/B)
+    a.korder = (a.kh * a.kw > 1 && a.kh * a.kw <= 32 && a.kw < 32 && a.cin % G::KT == 0 && a.dil_shift == 0 && !(a.dbg & gvconv::PROBE_TAP_MAJOR)) ? 1 : 0;
     const size_t ring = (size_t)ST * NP * (BM + BN) * G::RBYTES;
     const size_t epi = EPI == 1 ? 0 : (size_t)(WM * WN) * (EPI == 0 ? EpiGeom<TN>::BYTES : X3EpiGeom<TN>::BYTES);
     static_assert(dma_ss_off<NP, WM, WN, TM, TN, ST, EPI, KTX>() >= (int)((size_t)ST * NP * (BM + BN) * G::RBYTES), "table behind the ring");
@@ -820,11 +820,11 @@ int launch_dma_x3_e(int cfg, const ConvArgs& a, hipStream_t st) {
 }
 
 int launch_dma_x3(int cfg, const ConvArgs& a, hipStream_t st) {
-    // fp32 destinations with 16-byte aligned rows also take the staged epilogue (16-byte stores); dbg bit 64 forces the
-    // direct one (A/B)
+    // fp32 destinations with 16-byte aligned rows also take the staged epilogue (16-byte stores); PROBE_X3_DIRECT_EPILOGUE forces the
+    // direct one
     const bool vec = (a.y_ld % 4 == 0) && gv_aligned16(a.y) && a.cout % 8 == 0 && (a.res == nullptr || (a.res_ld % 4 == 0 && gv_aligned16(a.res)));
     if (a.split > 0) return launch_dma_x3_e<2>(cfg, a, st);      // fused siblings: the staged epilogue routes the columns
-    return (a.y_p3 || (vec && !(a.dbg & 64))) ? launch_dma_x3_e<2>(cfg, a, st) : launch_dma_x3_e<1>(cfg, a, st);
+    return (a.y_p3 || (vec && !(a.dbg & gvconv::PROBE_X3_DIRECT_EPILOGUE))) ? launch_dma_x3_e<2>(cfg, a, st) : launch_dma_x3_e<1>(cfg, a, st);
 }
 
 }  // namespace

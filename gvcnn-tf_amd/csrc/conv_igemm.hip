@@ -282,7 +282,7 @@ __global__ void pack_filter_hwio_f32(const float* __restrict__ w, int K, int Kpa
 }
 
 int g_tile_override = -1;   // tuning hook: force a tile configuration (see gv_conv2d_set_tile_override)
-int g_debug = 0;            // ablation bits, see ConvArgs::dbg
+int g_debug = 0;            // probe bits: gvconv::Probe, conv_probe.h
 
 struct TileCfg { int bm, bn, nch; };
 constexpr TileCfg kTiles[] = {{128, 128, 1}, {128, 64, 1}, {128, 96, 1}, {128, 32, 1}, {64, 64, 1}, {64, 128, 1},

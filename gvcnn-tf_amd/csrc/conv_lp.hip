@@ -367,17 +367,17 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? (TM * TN <= 4 && STAT
 
     __syncthreads();                                  // every wave is done with the main-loop buffers
     if constexpr (HAS_SUMS) {                         // the sums table (in the freed main-loop space where it fits)
-        if (!(a.st.dbg & 16384)) {
+        if (!(a.st.dbg & gvconv::PROBE_STAT_NO_BARRIER)) {
         gvconv::stat_table_init<STATS>(a.st, smem_raw, tid, NT, BN, n0, a.cout, st_b0);
         __syncthreads();
         }
     }
     lp_epilogue_staged<T, TM, TN, STATS>(a, acc, m0, n0, wm, wn, lane,
                                          reinterpret_cast<float*>(smem_raw + wave * EpiGeom<TN>::BYTES), 32,
-                                         (a.dbg & 512) ? nullptr : sstab, BN,      // dbg 512: constants from global memory (A/B)
+                                         (a.dbg & gvconv::PROBE_SS_FROM_GLOBAL) ? nullptr : sstab, BN,   // (A/B)
                                          smem_raw, st_b0 * (HAS_SUMS ? a.st.hw : 0));
     if constexpr (HAS_SUMS) {
-        if (!(a.st.dbg & 16384)) __syncthreads();     // every lane's runs are in the table
+        if (!(a.st.dbg & gvconv::PROBE_STAT_NO_BARRIER)) __syncthreads();     // every lane's runs are in the table
         const int last = (m0 + BM < a.M ? m0 + BM : a.M) - 1;
         gvconv::stat_publish<STATS>(a.st, smem_raw, tid, BN, n0, a.cout, st_b0, min(last / a.st.hw - st_b0 + 1, a.st.slots));
     }
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_lp(const ConvArgs a) {
                     for (int e = 0; e < 8; ++e) v[e] = (colj + e < a.relu_limit) ? fmaxf(v[e], 0.f) : v[e];
                 }
                 if constexpr (STATS != 0) {               // sums of the values exactly as stored below
-                    if (nvalid == 8 && !(a.st.dbg & 8192)) {
+                    if (nvalid == 8 && !(a.st.dbg & gvconv::PROBE_STAT_NO_SUMS)) {
                         float rr[8];
                         unsigned zq[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -921,7 +921,7 @@ __global__ __launch_bounds__(256, POOL ? 3 : 2) void conv_stem_patch_lp(const Co
                     if (a.relu && colj + e < a.relu_limit) v[e] = fmaxf(v[e], 0.f);
                 }
                 if constexpr (STATS != 0) {               // sums of the values exactly as stored below
-                    if (nvalid == 8 && !(a.st.dbg & 8192)) {
+                    if (nvalid == 8 && !(a.st.dbg & gvconv::PROBE_STAT_NO_SUMS)) {
                         float rr[8];
                         const unsigned zq[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -1105,8 +1105,8 @@ int launch_halo_s(const ConvArgs& a, hipStream_t st) {
     if (a.cin == 64) return launch_halo64<T, STATS>(a, st);
     // two rows per wave wherever the map has them: Conv2d_2a 0.225 -> 0.150 ms.  With the 64-column filter in LDS the taller
     // halo would cost the second resident workgroup (84 KB: Conv2d_2b 0.295 -> 0.385 ms), so that form lets the staging
-    // blocks alias the halo (65 KB): 0.335 -> 0.283 ms.  Debug bit 1024: one row per wave (A/B)
-    return (a.oh >= 8 && !(a.dbg & 1024)) ? launch_halo_r<T, 2, STATS>(a, st) : launch_halo_r<T, 1, STATS>(a, st);
+    // blocks alias the halo (65 KB): 0.335 -> 0.283 ms.  PROBE_HALO_ONE_ROW: one row per wave
+    return (a.oh >= 8 && !(a.dbg & gvconv::PROBE_HALO_ONE_ROW)) ? launch_halo_r<T, 2, STATS>(a, st) : launch_halo_r<T, 1, STATS>(a, st);
 }
 
 template <typename T>

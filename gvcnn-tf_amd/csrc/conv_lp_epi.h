@@ -98,7 +98,7 @@ __device__ __forceinline__ void lp_epilogue_staged(const ConvArgs& a, const f32x
                                                    int wm, int wn, int lane, float* stage, int rows_valid = 32,
                                                    const float* sstab = nullptr, int bn = 0, char* smem = nullptr,
                                                    int mbase = 0) {
-    if (a.dbg & 4) {            // timing ablation: keep the accumulators live without storing the tile
+    if (a.dbg & gvconv::PROBE_NO_STORES) {            // timing ablation: keep the accumulators live without storing the tile
         float t = 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -318,7 +318,7 @@ __device__ __forceinline__ void lp_epilogue_staged(const ConvArgs& a, const f32x
                 if constexpr (HAS) {                              //  the same words are summed and stored)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) packed[j] = pack2<T>(v[2 * j], v[2 * j + 1]);
-                    if (st_on && !(st_dbg & 8192)) {              // sums of the values exactly as stored below
+                    if (st_on && !(st_dbg & gvconv::PROBE_STAT_NO_SUMS)) {              // sums of the values exactly as stored below
                         float rr[8], zv[8];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {

@@ -20,6 +20,7 @@
 // run — as long as a total stays below 2^53 grid steps (beyond that they degrade to ordinary fp64 rounding).
 #pragma once
 #include "gv_common.h"
+#include "conv_probe.h"
 
 namespace gvconv {
 
@@ -63,7 +64,7 @@ struct ConvStats {
     int lds_off;                // byte offset of the tables in dynamic LDS (set by the launcher)
     int slots;                  // table rows: images one row tile can span, at most G (image b0 + r and b0 + r + G share row r)
     int fold;                   // the tile can span more than G images: slot indices are reduced modulo G
-    int dbg, pad_;              // timing experiments (gv_conv2d_set_debug): 2048 no publish, 4096 no table adds, 8192 no sums
+    int dbg, pad_;              // probe bits (gv_conv2d_set_debug): the PROBE_STAT_* of conv_probe.h
     StatSeg seg[STAT_MAX_SEG];
 };
 
@@ -215,7 +216,7 @@ struct StatWave {
                                               int lcol0, bool col_ok, bool has_b, int dbg) {
         constexpr int NR = 64 / (CW / 8);
         const double q0 = MODE == STAT_FWD ? STAT_Q_FWD0 : STAT_Q_BWD, q1 = MODE == STAT_FWD ? STAT_Q_FWD1 : STAT_Q_BWD;
-        if (dbg & 4096) return;
+        if (dbg & PROBE_STAT_NO_TABLE) return;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (half == 1 && !has_b) break;                          // (uniform) the wave's rows lie in one image
@@ -291,7 +292,7 @@ struct StatStrip {
     }
     // stage: the wave's private block (>= 1024 floats); lane = (row lane rrow = lane >> 2, chunk c4 = lane & 3)
     __device__ __forceinline__ void finish(const ConvStats& s, float* stage, int lane, int g, int cout) {
-        if (s.dbg & 4096) return;
+        if (s.dbg & PROBE_STAT_NO_TABLE) return;
         const double q0 = MODE == STAT_FWD ? STAT_Q_FWD0 : STAT_Q_BWD, q1 = MODE == STAT_FWD ? STAT_Q_FWD1 : STAT_Q_BWD;
         const int rrow = lane >> 2, c4 = lane & 3;
 #pragma unroll
@@ -326,7 +327,7 @@ static inline bool stat_strip_ok_host(const ConvStats& s, int cout) {
 template <int MODE>
 __device__ __forceinline__ void stat_publish(const ConvStats& s, const char* smem, int tid, int bn, int n0, int cout, int b0,
                                              int slots_used) {
-    if (tid >= bn || (s.dbg & 2048)) return;
+    if (tid >= bn || (s.dbg & PROBE_STAT_NO_PUBLISH)) return;
     const int col = n0 + tid;
     if (col >= cout) return;
     const int k = stat_seg_of(s, col);

@@ -24,7 +24,6 @@
 // ds_read_b128 service group distinct modulo 16, so the shifted reads stay conflict-free.
 // k order: channel chunk outer, filter tap inner (conv_dma.hip's chunk-major order): k-step (c, t) multiplies strip c
 // at shift(t) with filter columns [t*cin + 32c, +32) of the packed [cout][Kpad] filter.
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_common.h"
@@ -49,8 +48,6 @@ struct WsArgs {
     int halo_lo;                               // strip rows in front of the tile's first pixel
     int strip_blocks, strip_bytes;             // 16-row blocks per strip buffer, bytes per buffer
     int na;                                    // strip buffers
-    int strip_off;                             // bytes in front of a strip buffer's rows (DIET: its own zero row, 128)
-    int tab_off;                               // DIET: LDS offset of the tap table [taps][BM] of 16-bit entries
     int pad_;
 };
 
@@ -129,12 +126,7 @@ __device__ __forceinline__ void ws_epilogue_fast(const ConvArgs& a, const f32x16
 // NL loader waves.  Eight consumers + four loaders = one 768-thread workgroup per CU; four consumers + two loaders = a
 // 384-thread workgroup, two per CU (three waves per SIMD either way: 168 registers) — the second workgroup's k-loop
 // covers the first one's epilogue, at twice the filter traffic per flop.
-// DIET (round 6, strip mode): the consumers' per-k-step address arithmetic — strip row of the tap, swizzle, out-of-image
-// select: ~20 vector instructions per k-step and row block — is replaced by a per-tile TABLE in LDS: entry [tap][row] is the
-// fragment's byte offset / 16 inside a strip buffer, or 0 = the buffer's own zero row; a k-step then needs one ds_read_u16
-// and two vector instructions per row block.  Loop body: ~15 vector + ~18 scalar instructions instead of ~34 + ~25 (12 MFMAs,
-// 10 ds_read_b128 either way).  Selected by debug bit 2097152 / GV_WS_DIET=1 — see launch_ws for the measurement.
-template <typename T, int WM, int WN, int TM, int TN, int NB, int STATS, bool GEMM, int KT = 32, int NL = 4, bool DIET = false>
+template <typename T, int WM, int WN, int TM, int TN, int NB, int STATS, bool GEMM, int KT = 32, int NL = 4>
 __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void conv_ws(const ConvArgs a, const WsArgs w) {
     constexpr int WS_NLW = NL;
     using G = WsGeom<KT>;
@@ -186,11 +178,11 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
     if (wave >= NC) {
         // =================================================== loader ===================================================
         const int lw = wave - NC;
-        if (!(a.dbg & 16384)) {                                    // (debug bit 16384: consumers alone, no loads, no barriers — timing only)
+        if (!(a.dbg & gvconv::PROBE_WS_CONSUMERS_ALONE)) {                  // (consumers alone, no loads, no barriers — timing only)
         // A loader shares its SIMD with two consumers whose MFMA / LDS / VALU streams never pause, and issue arbitration
         // goes by priority, then age — the loaders are the workgroup's youngest waves.  Their few instructions per k-step
-        // go first (debug bit 4096: no priority, A/B).
-        if (!(a.dbg & 4096)) __builtin_amdgcn_s_setprio(3);
+        // go first (PROBE_WS_NO_PRIO: no priority, A/B).
+        if (!(a.dbg & gvconv::PROBE_WS_NO_PRIO)) __builtin_amdgcn_s_setprio(3);
         const int lrow = lane / CPR;                               // row inside a row block
         // logical 16-byte chunk this lane fetches (swizzle at the source) in row block `blk`: with 128-byte rows the swizzle
         // reaches the block's parity
@@ -214,8 +206,8 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
         {
             int bq_t = 0, bq_c = 0, bq_slot = 0;                       // next filter slice to issue: tap, chunk, ring slot
             int sq_c = 0, sq_buf = 0;                                  // next strip to issue: chunk, buffer
-            // timing ablations (results garbage): 32768 barriers but no loads; 65536 loads but no barriers anywhere
-            const bool nodma = (a.dbg & 32768) != 0, nobar = (a.dbg & 65536) != 0;
+            // timing ablations (results garbage): barriers but no loads; loads but no barriers anywhere
+            const bool nodma = (a.dbg & gvconv::PROBE_WS_NO_LOADS) != 0, nobar = (a.dbg & gvconv::PROBE_WS_NO_BARRIERS) != 0;
             auto issue_b = [&]() {
                 const unsigned koff = (unsigned)(bq_t * a.cin + bq_c * KT) * 2u;
                 char* sb = smem + bq_slot * B_SLOT;
@@ -241,7 +233,7 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
                     for (int blk = lw; blk < w.strip_blocks; blk += WS_NLW) {
                         int p = m0 - w.halo_lo + blk * RPI + lrow;     // rows outside [0, M) are only ever read by masked taps
                         p = p < 0 ? 0 : (p < a.M ? p : a.M - 1);
-                        if (!nodma) ws_dma16(xb + (size_t)(unsigned)p * pix_bytes + coff, sb + w.strip_off + blk * 1024);
+                        if (!nodma) ws_dma16(xb + (size_t)(unsigned)p * pix_bytes + coff, sb + blk * 1024);
                     }
                 }
                 ++sq_c;
@@ -266,7 +258,7 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
                 for (int i = 0; i < ppi && sp_blk < w.strip_blocks; ++i, sp_blk += WS_NLW) {
                     int p = m0 - w.halo_lo + sp_blk * RPI + lrow;
                     p = p < 0 ? 0 : (p < a.M ? p : a.M - 1);
-                    if (!nodma) ws_dma16(xb + (size_t)(unsigned)p * pix_bytes + coff, sb + w.strip_off + sp_blk * 1024);
+                    if (!nodma) ws_dma16(xb + (size_t)(unsigned)p * pix_bytes + coff, sb + sp_blk * 1024);
                 }
             };
             // prologue: strip 0 and filter slice 0 first (the consumers' first fragments), then the rest of both rings
@@ -315,9 +307,6 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
         const int wm = wave / WN, wn = wave % WN;
         const int r = lane & 31, h = lane >> 5;
         if (tid < 32) reinterpret_cast<unsigned*>(smem)[tid] = 0u; // the zero row: bytes [0, 128)
-        if constexpr (DIET) {                                      // ... and one in front of each of the two strip buffers
-            if (tid < 64) reinterpret_cast<unsigned*>(smem + OFF_S + (tid >> 5) * w.strip_bytes)[tid & 31] = 0u;
-        }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -354,26 +343,6 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
             const int brow = (wn * TN + j) * 32 + r;
             b0[j] = OFF_B + brow * WS_RB + ((G::swz(brow) ^ h) << 4);
         }
-        // DIET: the tap table.  The WN waves that own the same rows share the taps between them; an entry is the same for
-        // both k halves (h is folded in by the reader)
-        int tab0 = 0;                                              // this lane's first row's column of the table
-        if constexpr (DIET) {
-            tab0 = w.tab_off + ((wm * TM) * 32 + r) * 2;
-            int fr = 0, fs = wn;                                   // tap wn, wn + WN, ...: (fr, fs) kept by increments
-            while (fs >= a.kw) { fs -= a.kw; ++fr; }
-            for (int t = wn; t < NTAP; t += WN) {
-                const int off = (fr - a.pad_t) * a.iw + (fs - a.pad_l);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int row = rbase[i] + off;
-                    const int rel = (128 + row * WS_RB + (G::swz(row) << 4)) >> 4;
-                    const int e = ((tapmask[i] >> t) & 1u) ? rel : 0;
-                    if (h == 0) *reinterpret_cast<unsigned short*>(smem + tab0 + t * (BM * 2) + i * 64) = (unsigned short)e;
-                }
-                fs += WN;
-                while (fs >= a.kw) { fs -= a.kw; ++fr; }
-            }
-        }
         // A fragment address (k16-step 0; step 1 is this ^ 32) of row block i for the tap at row shift `off` / mask bit
         // `bit`, strip buffer at byte `sbase`; a tap outside the image reads the zero row
         // (bit arithmetic, not a select: hipcc turns the select into exec-masked branches that cut the k-step's basic block)
@@ -387,15 +356,7 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
         int sbase = OFF_S, sbuf = 0, bslot = 0;                    // its strip buffer / filter slot (bytes)
         int aa[TM];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if constexpr (DIET) {                                  // (tap 0, straight from the arithmetic: the table is not published yet)
-                const int row = rbase[i] - (a.pad_t * a.iw + a.pad_l);
-                const int ad = sbase + 128 + row * WS_RB + ((G::swz(row) ^ h) << 4);
-                aa[i] = (tapmask[i] & 1u) ? ad : sbase + (h << 4);
-            } else {
-                aa[i] = a_addr(i, -(a.pad_t * a.iw + a.pad_l), 0, sbase);
-            }
-        }
+        for (int i = 0; i < TM; ++i) aa[i] = a_addr(i, -(a.pad_t * a.iw + a.pad_l), 0, sbase);
         u32x4 fa[2][TM], fb[2][TN];
         auto lds16 = [&](int addr) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + addr); };
         // one fragment read (q-th of the TM + TN of a k16-step) into register set S
@@ -438,50 +399,36 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
         using FF = std::false_type;
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
-        const bool nosync = (a.dbg & (16384 | 65536)) != 0;
+        const bool nosync = (a.dbg & (gvconv::PROBE_WS_CONSUMERS_ALONE | gvconv::PROBE_WS_NO_BARRIERS)) != 0;
         ws_wait_lds();
         WS_PT(1);
         if (!nosync) __builtin_amdgcn_s_barrier();                 // strip 0, filter slices 0 and 1 and the zero row are in LDS
         WS_PT(2);
 #pragma unroll
         for (int q = 0; q < TM + TN; ++q) read_one(S0{}, q, 0, aa, 0);
-        // Stagger (debug bit 8192: off, A/B).  The two consumers of a SIMD are waves w and w + 4; run in lockstep they reach
+        // Stagger (PROBE_WS_STAGGER turns it on, A/B).  The two consumers of a SIMD are waves w and w + 4; run in lockstep they reach
         // their MFMA bursts, their LDS reads and the barrier together and idle together.  Waves 4-7 therefore take the
         // k-step's barrier HALF A K-STEP LATER in their own instruction stream (in the middle of the following k-step's
         // first half instead of this one's last): every SIMD then has one wave in front of the barrier and one behind it.
         // Legal: a wave's reads of k-step j have returned long before either point, and k-step j+2 — published by barrier j
         // — is first read behind both.
-        const bool late = wave >= NC / 2 && (a.dbg & 8192) != 0;      // (debug bit 8192: the stagger, A/B — measured neutral to negative)
+        const bool late = wave >= NC / 2 && (a.dbg & gvconv::PROBE_WS_STAGGER) != 0;   // (A/B — measured neutral to negative)
         const bool early = !late && !nosync, lateb = late && !nosync;
         for (int j = 0; j + 1 < nk; ++j) {
             // the next k-step's tap, strip buffer and slot (selects, no branches: a branch here would cut the basic block
             // and keep this arithmetic from being scheduled between the MFMAs below)
             int an[TM];
-            if constexpr (DIET) {
-                const bool wrap = q_tap + 1 == NTAP;
-                q_tap = wrap ? 0 : q_tap + 1;
-                const int sb1 = sbuf + 1 == w.na ? 0 : sbuf + 1;
-                sbuf = wrap ? sb1 : sbuf;
-                sbase = OFF_S + sbuf * w.strip_bytes;
-                const int tp = tab0 + q_tap * (BM * 2);
+            const bool wrap = q_tap + 1 == NTAP;
+            const bool row_end = q_fs + 1 == a.kw;
+            q_tap = wrap ? 0 : q_tap + 1;
+            q_fr = wrap ? 0 : (row_end ? q_fr + 1 : q_fr);
+            q_fs = (wrap || row_end) ? 0 : q_fs + 1;
+            const int sb1 = sbuf + 1 == w.na ? 0 : sbuf + 1;
+            sbuf = wrap ? sb1 : sbuf;
+            sbase = OFF_S + sbuf * w.strip_bytes;
+            const int off = (q_fr - a.pad_t) * a.iw + (q_fs - a.pad_l);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int e = *reinterpret_cast<const unsigned short*>(smem + tp + i * 64);
-                    an[i] = ((e ^ h) << 4) + sbase;
-                }
-            } else {
-                const bool wrap = q_tap + 1 == NTAP;
-                const bool row_end = q_fs + 1 == a.kw;
-                q_tap = wrap ? 0 : q_tap + 1;
-                q_fr = wrap ? 0 : (row_end ? q_fr + 1 : q_fr);
-                q_fs = (wrap || row_end) ? 0 : q_fs + 1;
-                const int sb1 = sbuf + 1 == w.na ? 0 : sbuf + 1;
-                sbuf = wrap ? sb1 : sbuf;
-                sbase = OFF_S + sbuf * w.strip_bytes;
-                const int off = (q_fr - a.pad_t) * a.iw + (q_fs - a.pad_l);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) an[i] = a_addr(i, off, q_tap, sbase);
-            }
+            for (int i = 0; i < TM; ++i) an[i] = a_addr(i, off, q_tap, sbase);
             const int bnext = bslot + B_SLOT == NB * B_SLOT ? 0 : bslot + B_SLOT;
             // the k-step's first KS - 1 MFMA k-steps; behind each one's MFMAs the next one's fragments (same strip rows and
             // filter slot, the chunk index advanced by XOR); the late waves' barrier j-1 sits in number KS/2 - 1
@@ -517,7 +464,7 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
     // ====================================================== epilogue ======================================================
     __syncthreads();                                               // every wave is done with the ring: the staging blocks alias it
     constexpr int SS_OFF = NC * 8192;                              // (two staging blocks per wave, whatever the epilogue)
-    float* sstab = !(a.dbg & 512) ? reinterpret_cast<float*>(smem + SS_OFF) : nullptr;   // dbg 512: constants from global (A/B)
+    float* sstab = !(a.dbg & gvconv::PROBE_SS_FROM_GLOBAL) ? reinterpret_cast<float*>(smem + SS_OFF) : nullptr;   // (A/B)
     if (sstab != nullptr && tid < BN) {
         sstab[tid] = ss_v[0];
         sstab[BN + tid] = ss_v[1];
@@ -526,9 +473,9 @@ __global__ __launch_bounds__((WM * WN + NL) * 64, (WM * WN + NL) * 3 / 12) void 
     __syncthreads();
     if (wave < NC) {
         const int wm = wave / WN, wn = wave % WN;
-        // interior tile, one plain destination: the pipelined straight-line epilogue (debug bit 1048576: the general one, A/B)
+        // interior tile, one plain destination: the pipelined straight-line epilogue (PROBE_GENERAL_EPILOGUE: the general one)
         const bool fast = STATS == gvconv::STAT_LEAN && sstab != nullptr && a.res == nullptr && a.y2 == nullptr && a.split == 0 &&
-                          m0 + BM <= a.M && (!a.relu || a.relu_limit >= a.cout) && !(a.dbg & (4 | 1048576));
+                          m0 + BM <= a.M && (!a.relu || a.relu_limit >= a.cout) && !(a.dbg & (gvconv::PROBE_NO_STORES | gvconv::PROBE_GENERAL_EPILOGUE));
         if (fast)
             ws_epilogue_fast<T, TM, TN>(a, acc, m0, n0, wm, wn, lane, smem + wave * 8192, sstab, BN);
         else
@@ -575,24 +522,10 @@ int launch_ws(const ConvArgs& a0, hipStream_t st) {
     w.strip_blocks = gemm ? BM / RPI : gv_ceil_div(w.halo_lo + BM + halo_hi, RPI);
     w.na = gemm ? NB : 2;
     w.pad_ = 0;
-    // strip mode: the tap-table form (DIET), when asked for, where its table and the strip buffers' zero rows still fit the
-    // workgroup's LDS share
-    const size_t lds_cap = (size_t)(NL == 2 ? 80 : 160) * 1024;
-    // Measured NEUTRAL (profiles/r6_ws_diet_ab.txt: whole plans c3 0.249 -> 0.247, c5 0.283 -> 0.282; single layers +4 ... +6 %
-    // as warm repeats): the consumers' instruction count is not what bounds this kernel.  Kept behind debug bit 2097152 /
-    // GV_WS_DIET=1 with its parity tests; the arithmetic form stays the product.
-    static const bool env_on = getenv("GV_WS_DIET") != nullptr;
-    bool diet = !gemm && ((a.dbg & 2097152) || env_on);
-    if (diet && (size_t)WS_ZERO + (size_t)NB * BN * WS_RB + 2 * ((size_t)128 + w.strip_blocks * 1024) +
-                    ((size_t)w.taps * BM * 2 + 127) / 128 * 128 > lds_cap)
-        diet = false;
-    w.strip_off = diet ? 128 : 0;
-    w.strip_bytes = w.strip_off + w.strip_blocks * 1024;
+    w.strip_bytes = w.strip_blocks * 1024;
     const int64_t nwg = gvconv::conv_grid(a, BM, BN);
     if (nwg < 0) return GV_E_UNSUPPORTED;
-    size_t ring = (size_t)WS_ZERO + (size_t)NB * BN * WS_RB + (size_t)w.na * w.strip_bytes;
-    w.tab_off = (int)ring;
-    if (diet) ring += ((size_t)w.taps * BM * 2 + 127) / 128 * 128;   // (16-bit entries: offsets / 16 — any strip fits)
+    const size_t ring = (size_t)WS_ZERO + (size_t)NB * BN * WS_RB + (size_t)w.na * w.strip_bytes;
     const size_t epi = (size_t)ws_epi_bytes<WM, WN, TN>();
     const size_t lds = ring > epi ? ring : epi;
     if (lds > (NL == 2 ? 80 : 160) * 1024) return GV_E_UNSUPPORTED;   // (two of the small workgroups per CU)
@@ -600,7 +533,6 @@ int launch_ws(const ConvArgs& a0, hipStream_t st) {
         constexpr int MODE = decltype(mode)::value;
         constexpr bool GM = decltype(gm)::value;
         const dim3 grid((unsigned)nwg), block((NC + NL) * 64);
-        if (!GM && diet) return gv_launch<conv_ws<T, WM, WN, TM, TN, NB, MODE, false, KT, NL, true>>(grid, block, lds, st, a, w);
         return gv_launch<conv_ws<T, WM, WN, TM, TN, NB, MODE, GM, KT, NL>>(grid, block, lds, st, a, w);
     };
     const bool lean = gvconv::lp_epilogue_lean_ok(a);

@@ -96,7 +96,7 @@ __global__ __launch_bounds__((WM * WN + X3W_NL) * 64, 3) void conv_ws_x3(const C
     const int nk = w.nk, NTAP = w.taps;
     // timing ablations (results garbage): 16384 consumers alone (no loads, no barriers); 32768 barriers but no loads;
     // 65536 loads but no barriers
-    const bool nosync = (a.dbg & (16384 | 65536)) != 0;
+    const bool nosync = (a.dbg & (gvconv::PROBE_WS_CONSUMERS_ALONE | gvconv::PROBE_WS_NO_BARRIERS)) != 0;
 
     // the epilogue's per-column constants: requested now, published into LDS once the ring is free
     // (by the LOADER waves: two registers a consumer cannot spare)
@@ -112,12 +112,12 @@ __global__ __launch_bounds__((WM * WN + X3W_NL) * 64, 3) void conv_ws_x3(const C
             ss_v[0] = a.scale[cc];
             ss_v[1] = a.shift[cc];
         }
-        if (!(a.dbg & 16384)) {
+        if (!(a.dbg & gvconv::PROBE_WS_CONSUMERS_ALONE)) {
             // (conv_ws.hip: the loaders' few instructions go first.  Measured here and neutral: no priority; a higher priority
             // for one of a SIMD's two consumers; an s_sleep behind every DMA instruction, -1 ... -3 %:
             // profiles/r5_x3ws_priority_and_pacing_ab.txt)
             __builtin_amdgcn_s_setprio(3);
-            const bool nodma = (a.dbg & 32768) != 0, nobar = (a.dbg & 65536) != 0;
+            const bool nodma = (a.dbg & gvconv::PROBE_WS_NO_LOADS) != 0, nobar = (a.dbg & gvconv::PROBE_WS_NO_BARRIERS) != 0;
             const int lrow = lane >> 1;                            // row inside a 32-row block
             const int lc16 = (((lane & 1) ^ ((lrow >> 3) & 1)) << 4);   // byte offset of the logical chunk this lane fetches
             const char* xb = reinterpret_cast<const char*>(a.x);

@@ -97,7 +97,7 @@ template <int TM, int TN>
 __device__ __forceinline__ void x3_epilogue_staged(const gvconv::ConvArgs& a, const f32x16 (&acc)[TM][TN], int m0, int n0,
                                                    int wm, int wn, int lane, float* stage, const float* sstab = nullptr,
                                                    int bn = 0) {
-    if (a.dbg & 4) {            // timing ablation: keep the accumulators live without storing the tile
+    if (a.dbg & gvconv::PROBE_NO_STORES) {            // timing ablation: keep the accumulators live without storing the tile
         float t = 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i)

@@ -528,8 +528,17 @@ def test_per_shape_assign_and_fuse_vs_oracle(weight_mode, pool):
     assert int(status.item()) & 1
 
 
-@pytest.mark.parametrize("cout,pad,hw", [(32, 0, (23, 41)), (64, 1, (23, 41)), (64, 1, (8, 32)), (48, 0, (5, 70)), (64, 1, (61, 95)),
-                                         (32, 0, (3, 3)), (32, 1, (1, 1)), (32, 0, (21, 32)), (64, 1, (13, 60)), (64, 0, (9, 92))])
+HALO_STEM_CASES = [(32, 0, (23, 41)), (64, 1, (23, 41)), (64, 1, (8, 32)), (48, 0, (5, 70)), (64, 1, (61, 95)),
+                   (32, 0, (3, 3)), (32, 1, (1, 1)), (32, 0, (21, 32)), (64, 1, (13, 60)), (64, 0, (9, 92))]
+
+
+def halo_narrow(ow):
+    """launch_halo_x3's rule (csrc/conv_bf16s.hip): 16-pixel strips (conv3x3_halo_x3, 32x32x16 MFMAs) where they cover the
+    output width with at least 20 % fewer MFMA rows than 30-pixel strips (conv3x3_halo_x3_k32, 32 rows per strip)."""
+    return -(-ow // 16) * 16 * 5 <= -(-ow // 30) * 32 * 4
+
+
+@pytest.mark.parametrize("cout,pad,hw", HALO_STEM_CASES)
 def test_halo_stem_kernel_fp32_storage(cout, pad, hw):
     """The halo-tiled 3x3 kernel of Conv2d_2a/2b on fp32 storage (GV_MATH_BF16X3, tile configuration 11): ragged
     strips (widths that pick the 16-pixel two-rows-per-wave form and widths that pick the 30-pixel form), VALID and SAME,
@@ -552,15 +561,13 @@ def test_halo_stem_kernel_fp32_storage(cout, pad, hw):
         yq = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, relu, tile=0, math=1)
         np.testing.assert_allclose(yp, yq, rtol=1e-5, atol=1e-5)
     ys = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=11, math=1, y_ld=cout + 32, y_off=16)
-    assert np.array_equal(ys, run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=11, math=1))
-    # the 32x32x16 form of the wide-strip kernel (debug bit 8; the default is the 16x16x32 form) accumulates the plane
-    # products in the implicit-GEMM kernel's order: BITWISE the same result
-    lib().gv_conv2d_set_debug(8)
-    try:
-        y8 = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=11, math=1)
-    finally:
-        lib().gv_conv2d_set_debug(0)
-    assert np.array_equal(y8, run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=0, math=1))
+    y11 = run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=11, math=1)
+    assert np.array_equal(ys, y11)
+    # the 32x32x16 halo kernel (the 16-pixel strips; wider maps take the 16x16x32 form) accumulates the plane products in
+    # the implicit-GEMM kernel's order: BITWISE the same result, wherever the output width selects it
+    assert sum(halo_narrow(w_ + 2 * p_ - 2) for _, p_, (_, w_) in HALO_STEM_CASES) >= 3 and halo_narrow(41 - 2)
+    if halo_narrow(ow):
+        assert np.array_equal(y11, run_conv(x, w, 1, (pad, pad), (oh, ow), scale, shift, True, tile=0, math=1))
 
 
 @pytest.mark.parametrize("k,pad,cout,hw", [(3, 0, 32, (47, 75)), (7, 3, 64, (47, 75)), (7, 3, 64, (224, 64)), (3, 0, 24, (9, 131))])

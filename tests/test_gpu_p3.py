@@ -136,8 +136,8 @@ def test_dma_conv_on_three_plane_input(k, stride, padding, cin, cout, tile):
     yp = conv(x, w, stride, pads, hw, scale, shift, True, x_p3=True, y_p3=True, tile=tile, x_ld=cin + 32, x_off=16,
               y_ld=cout + 32, y_off=16)
     assert torch.equal(yp, y)
-    # ... and BITWISE agreement in the tap-major order (debug bit 128)
-    lib().gv_conv2d_set_debug(128)
+    # ... and BITWISE agreement in the tap-major order (`_lib.PROBE_TAP_MAJOR`)
+    lib().gv_conv2d_set_debug(_lib.PROBE_TAP_MAJOR)
     try:
         yt = conv(x, w, stride, pads, hw, scale, shift, True, x_p3=True, tile=tile, x_ld=cin + 32, x_off=16, y_ld=cout + 8, y_off=4)
     finally:

@@ -16,10 +16,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--d", type=int, default=0)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--only", default="")
-ap.add_argument("--dbg", type=int, default=0)
 a = ap.parse_args()
 lib = _lib.load()
-lib.gv_bottleneck_chain_set_debug(a.dbg)
 dev = torch.device("cuda:0")
 st = torch.cuda.current_stream().cuda_stream
 code, td = _lib.GV_BF16, torch.bfloat16
