@@ -140,11 +140,17 @@ __global__ void group_weight_kernel(const int* __restrict__ scheme, int G, int V
 // Fused view pooling + group fusion.  Thread per (shape n, VEC consecutive descriptor elements).
 // Group membership is turned into per-group 64-bit view masks held in LDS; each view of each
 // group is loaded once, so a one-hot scheme costs exactly V loads per output element.
+// Order of the fp32 operations (numpy float32 reproduces it bit for bit): mean = views added in ascending v, one division
+// by the count; S = fl(w_g * D_g) added in ascending g, one division by wsum (the ascending sum of the weights).  The
+// header's __fmul_rn / __fadd_rn are plain operators that hipcc contracts into one FMA by default, wherever they are called
+// from (render.hip), so the kernel body turns contraction off and spells the fusion with plain operators: the product is
+// rounded before it is added, as tf.multiply + tf.add_n round it.
 template <int VEC>
 __global__ __launch_bounds__(256) void view_pool_fuse_f32(
     const float* __restrict__ F, int V, int N, int64_t E, int64_t view_stride, int64_t shape_stride,
     const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode, float fill,
     float* __restrict__ D, float* __restrict__ S, int64_t scheme_stride, int64_t weight_stride) {
+#pragma clang fp contract(off)
     using Vt = typename std::conditional<VEC == 4, f32x4, float>::type;
     __shared__ unsigned long long s_mask[64];
     __shared__ float s_w[64];
@@ -213,9 +219,9 @@ __global__ __launch_bounds__(256) void view_pool_fuse_f32(
             const float w = s_w[g];
             if constexpr (VEC == 4) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(w, d[k]));   // multiply, add_n
+                for (int k = 0; k < 4; ++k) acc[k] = acc[k] + w * d[k];   // multiply, add_n: two roundings (contraction is off)
             } else {
-                acc = __fadd_rn(acc, __fmul_rn(w, d));
+                acc = acc + w * d;
             }
         }
         if (S) {

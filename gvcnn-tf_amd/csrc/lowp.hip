@@ -347,7 +347,8 @@ __global__ __launch_bounds__(256) void view_score_partial_lp(const unsigned shor
     if (threadIdx.x == 0) r_img[b] = (part[0] + part[1] + part[2] + part[3]) / (float)hw + bias[v];
 }
 
-// nets/model.py:44-102 fused, one read of every descriptor element (view_pool_fuse_f32 in grouping.hip)
+// nets/model.py:44-102 fused, one read of every descriptor element (view_pool_fuse_f32 in grouping.hip): the same fp32
+// operations in the same order, contraction off, then one rounding of D and of S into the storage type
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void view_pool_fuse_lp(const unsigned short* __restrict__ F, int V, int N, int64_t E,
                                                          int64_t view_stride, int64_t shape_stride,
@@ -355,6 +356,7 @@ __global__ __launch_bounds__(256) void view_pool_fuse_lp(const unsigned short* _
                                                          const float* __restrict__ weight, int mode, float fill,
                                                          unsigned short* __restrict__ D, unsigned short* __restrict__ S,
                                                          int64_t scheme_stride, int64_t weight_stride) {
+#pragma clang fp contract(off)
     __shared__ unsigned long long s_mask[64];
     __shared__ float s_w[64];
     __shared__ float s_wsum;
@@ -412,7 +414,7 @@ __global__ __launch_bounds__(256) void view_pool_fuse_lp(const unsigned short* _
             if (D) store_v<T, VEC>(D + ((size_t)g * N + n) * E + e, d);
             const float w = s_w[g];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(w, d[k]));
+            for (int k = 0; k < VEC; ++k) acc[k] = acc[k] + w * d[k];   // two roundings: contraction is off in this body
         }
         if (S) {
 #pragma unroll

@@ -122,11 +122,13 @@ def view_score(raw_descriptor, kernel, bias):
 
 
 def score_from_r(r):
-    """sigmoid(log(abs(r))) in fp32 (model.py:147); r == 0 -> 0."""
-    r = np.abs(np.asarray(r, dtype=F32))
-    with np.errstate(divide="ignore"):
-        lg = np.log(r).astype(F32)
-    return (F32(1) / (F32(1) + np.exp(-lg).astype(F32))).astype(F32)
+    """sigmoid(log(abs(r))) of an fp32 r (model.py:147); r == 0 -> 0.  (fp64 inside, one rounding to fp32, like dense and
+    view_score: TF evaluates the graph in fp32, where the rounding of log r alone costs up to 2^-24 |ln r| of the score —
+    10 fp32 ulps at r = 1e-4 — so an fp32 restatement here was that far from the value both it and the kernel stand for.)"""
+    r = np.abs(np.asarray(r, dtype=F32)).astype(np.float64)
+    with np.errstate(divide="ignore", over="ignore"):
+        lg = np.log(r)
+        return (1.0 / (1.0 + np.exp(-lg))).astype(F32)
 
 
 def dense(x, kernel, bias):

@@ -17,6 +17,7 @@ from gvcnn_tf_amd import _lib                       # noqa: E402
 from gvcnn_tf_amd.training import TrainGVCNN        # noqa: E402
 from oracle import backbone as OB                   # noqa: E402
 import bn_ref                                       # noqa: E402   (tests/bn_ref.py)
+from slab import NAN, SENTINEL, _Slab, _hold        # noqa: E402   (tests/slab.py)
 
 DEV = "cuda:0"
 TYPES = [(_lib.GV_BF16, torch.bfloat16, 2.0 ** -8), (_lib.GV_F16, torch.float16, 2.0 ** -11)]
@@ -152,37 +153,6 @@ BN_CASES = {
 # (case, operands start 16 bytes into their buffers, storage); G has 39 M elements: bf16 and fp32 only
 BN_SWEEP = [(case, off, t) for case, off in [("A", 0), ("A", 1), ("B", 0), ("B", 1), ("C", 0), ("H", 0), ("D", 0), ("E", 0),
                                              ("F", 0), ("I", 0), ("G", 0)] for t in BN_TYPES if (case, t) != ("G", "f16")]
-NAN, SENTINEL = float("nan"), -7.0
-
-
-class _Slab:
-    """An [npix, c] operand of pixel stride ld that starts `off` elements into a flat buffer filled with `fill` (NaN for an
-    input: the neighbours must not leak in; a sentinel for an output: they must stay as they are)."""
-
-    def __init__(self, npix, c, ld, off, tdt, fill, values=None):
-        self.buf = torch.full((npix * ld + off,), fill, dtype=tdt, device=DEV)
-        self.v = self.buf.as_strided((npix, c), (ld, 1), off)
-        self.fill = fill
-        if values is not None:
-            self.v.copy_(values.reshape(npix, c))
-        self.ptr = self.v.data_ptr()
-
-    def outside_intact(self):
-        if self.v.numel() == self.buf.numel():
-            return True
-        m = torch.ones(self.buf.shape, dtype=torch.bool, device=DEV)
-        m.as_strided(self.v.shape, self.v.stride(), self.v.storage_offset()).fill_(False)
-        out = self.buf[m]
-        return bool(torch.isnan(out).all()) if self.fill != self.fill else bool((out == self.fill).all())
-
-
-def _hold(tag, what, got, want, tol, floor=0.0):
-    """max |got - want| <= tol * max |want| + floor, in float64 on the device; the figure is printed first."""
-    got, want = got.double(), want.double()
-    scale = max(float(want.abs().max()), 1e-30)
-    err = float((got.reshape(want.shape) - want).abs().max())
-    print("%s %-12s rel %.3e (bound %.1e)" % (tag, what, err / scale, tol))
-    assert err <= tol * scale + floor, "%s %s: max|diff| %.3e vs scale %.3e (%.2e rel)" % (tag, what, err, scale, err / scale)
 
 
 def _hold_totals(tag, what, acc, want0, want1):
