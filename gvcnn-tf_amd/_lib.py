@@ -174,6 +174,10 @@ SIGNATURES = {
                                            _L, _P, _L, _P]),
     "gv_render_draw_smooth": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L,
                                         _I, _P, _P, _P, _I, C.POINTER(RenderShading), _P, _P, _P, _L, _P]),
+    "gv_points_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "gv_points_prepare": (C.c_int, [_P, _P, _I, _L, _I, _P, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _P, _P]),
+    "gv_points_draw": (C.c_int, [_P, _P, _I, _L, _I, C.POINTER(RenderDesc), _P, _P, _P, _L, _P, _L, _L, _I, _P, _P, _P,
+                                 _P, C.POINTER(RenderShading), _P, _P, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

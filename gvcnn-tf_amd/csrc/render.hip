@@ -1,7 +1,8 @@
 // render.hip — multi-view rasteriser: a batch of triangle meshes -> the backbone's input views [N, V, H, W, 3] on the
 // device (the rendering contract is in include/gvcnn_hip.h, "meshes in").
 //
-//   gv_render_prepare   normalise_kernel   one workgroup per mesh: bbox midpoint c, radius r, scale = fit / r, status.
+//   gv_render_prepare   normalise_kernel   (render_common.h, as the scans) one workgroup per mesh: bbox midpoint c, radius
+//                                          r, scale = fit / r, status.
 //                       bin_kernel<false>  grid (triangle chunks, view, mesh): every thread sets up its triangles for
 //                                          the view (vertex transform, snap, orientation, pixel-centre bbox) and counts
 //                                          them into the image's 16x16-pixel tiles with LDS atomics; the workgroup then
@@ -35,40 +36,15 @@
 // view, triangle), recomputed where needed (count, scatter, raster), so the bins hold 4-byte ids only.
 #include <math.h>
 
-#include "gv_common.h"
+// the fp32 discipline (mul_rn / add_rn, no contraction), MeshXf, world, project, snap, dot3, normalise_kernel and the two
+// scan kernels are shared with render_points.hip
+#include "render_common.h"
 
-// Every fp32 step rounds on its own, so numpy float32 reproduces it.  hipcc contracts a * b + c into one FMA by default,
-// the header's __fmul_rn / __fadd_rn included (they are plain operators there): this file turns contraction off and
-// spells each step with the helpers below.  The one fused step, the quantised output, is an explicit fmaf.  Division is
-// IEEE (HIP's default); the square root is __builtin_sqrtf, correctly rounded (__fsqrt_rn is the native approximation).
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-
-typedef unsigned long long u64;
-
-constexpr int TS = 16;                                           // tile edge in pixels
-constexpr int RT = 256;                                          // threads of every kernel but the scans
-constexpr int SCAN_T = 1024;                                     // threads of the scan kernels
-constexpr int CHUNK = 1024;                                      // triangles per binning workgroup and pass
-constexpr int MAX_SIDE = 512;
-constexpr int MAX_TILES = (MAX_SIDE / TS) * (MAX_SIDE / TS);     // 1024
-constexpr int MAX_TRIS = 1 << 24;
-// snapped coordinates are clamped to +-2^18 (+-1024 pixels; a vertex of the unit sphere lands inside the image): a
-// triangle then spans at most 2^19 per axis, twice its area is below 2^38 and e0*Z0 + e1*Z1 + e2*Z2 <= area * (2^24-1)
-// stays below 2^62, whatever the input
-constexpr float SNAP_LIM = 262144.0f;
-constexpr u64 BG_KEY = ~0ull;
-
-struct MeshXf {                                                  // per mesh, written by normalise_kernel
-    float cx, cy, cz, scale;
-    int status, pad0, pad1, pad2;
-};
-
-struct Args {                                                    // everything a triangle setup needs
+struct Args : View {                                             // everything a triangle setup needs
     const float* verts;
     const long long* voff;
     const int* tris;
@@ -76,8 +52,6 @@ struct Args {                                                    // everything a
     const float* cams;                                           // [V, 3, 3]
     const float* rots;                                           // [N, 3, 3] or null
     const MeshXf* xf;
-    int V, H, W, tiles_x, tiles_y, persp;
-    float k, D, da, db, cxs, cys;                                // projection constants, image centre
 };
 
 struct Tri {
@@ -87,50 +61,6 @@ struct Tri {
     long long area;
     int flip;                                                    // vertices 1 and 2 were swapped (smooth shading)
 };
-
-__device__ __forceinline__ float dot3(const float* r, float a, float b, float c) {
-    return add_rn(add_rn(mul_rn(r[0], a), mul_rn(r[1], b)), mul_rn(r[2], c));
-}
-
-// normalised (and rotated) world position w of a vertex
-__device__ __forceinline__ void world(const MeshXf& x, const float* M, const float* p, float w[3]) {
-    const float u0 = mul_rn(add_rn(p[0], -x.cx), x.scale);
-    const float u1 = mul_rn(add_rn(p[1], -x.cy), x.scale);
-    const float u2 = mul_rn(add_rn(p[2], -x.cz), x.scale);
-    if (M) {
-        w[0] = dot3(M, u0, u1, u2);
-        w[1] = dot3(M + 3, u0, u1, u2);
-        w[2] = dot3(M + 6, u0, u1, u2);
-    } else {
-        w[0] = u0;
-        w[1] = u1;
-        w[2] = u2;
-    }
-}
-
-__device__ __forceinline__ int snap(float s) {
-    return (int)rintf(fminf(fmaxf(mul_rn(s, 256.0f), -SNAP_LIM), SNAP_LIM));
-}
-
-// camera transform, projection, 1/256-pixel snap, 24-bit depth
-__device__ __forceinline__ void project(const Args& a, const float* C, const float w[3], int& X, int& Y, unsigned& Z) {
-    const float q0 = dot3(C, w[0], w[1], w[2]), q1 = dot3(C + 3, w[0], w[1], w[2]), q2 = dot3(C + 6, w[0], w[1], w[2]);
-    float sx, sy, t;
-    if (a.persp) {
-        const float z = add_rn(q2, a.D);
-        sx = add_rn(a.cxs, __fdiv_rn(mul_rn(q0, a.k), z));
-        sy = add_rn(a.cys, -__fdiv_rn(mul_rn(q1, a.k), z));
-        t = add_rn(a.da, -__fdiv_rn(a.db, z));
-    } else {
-        sx = add_rn(a.cxs, mul_rn(q0, a.k));
-        sy = add_rn(a.cys, -mul_rn(q1, a.k));
-        t = mul_rn(add_rn(q2, 1.0f), 0.5f);
-    }
-    X = snap(sx);
-    Y = snap(sy);
-    t = fminf(fmaxf(t, 0.0f), 1.0f);
-    Z = (unsigned)rintf(mul_rn(t, 16777215.0f));
-}
 
 __device__ __forceinline__ bool load_tri(const Args& a, int m, int t, const float*& p0, const float*& p1,
                                          const float*& p2) {
@@ -273,71 +203,6 @@ __global__ __launch_bounds__(RT) void vertex_normals_kernel(Args a, int n, long 
     o[2] = g[2];
 }
 
-// ---- normalisation -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RT) void normalise_kernel(const float* __restrict__ verts, const long long* __restrict__ voff,
-                                                       const long long* __restrict__ toff, long long total_verts,
-                                                       long long total_tris, float fit, MeshXf* __restrict__ xf,
-                                                       int* __restrict__ status) {
-    __shared__ float s_red[6][RT];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const long long v0 = voff[m] - voff[0], v1 = voff[m + 1] - voff[0];
-    const long long t0 = toff[m] - toff[0], t1 = toff[m + 1] - toff[0];
-    int st = GV_RENDER_OK;
-    if (v0 < 0 || v1 < v0 || v1 > total_verts || t0 < 0 || t1 < t0 || t1 > total_tris) st = GV_RENDER_BAD_OFFSETS;
-    else if (t1 - t0 > MAX_TRIS) st = GV_RENDER_TOO_LARGE;
-    else if (t1 == t0 || v1 == v0) st = GV_RENDER_EMPTY;
-    MeshXf x = {0.f, 0.f, 0.f, 0.f, st, 0, 0, 0};
-    if (st == GV_RENDER_OK) {                                    // (uniform)
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (long long i = v0 + tid; i < v1; i += RT)
-            for (int c = 0; c < 3; ++c) {
-                const float p = verts[i * 3 + c];
-                mn[c] = fminf(mn[c], p);
-                mx[c] = fmaxf(mx[c], p);
-            }
-        for (int c = 0; c < 3; ++c) {
-            s_red[c][tid] = mn[c];
-            s_red[3 + c][tid] = mx[c];
-        }
-        __syncthreads();
-        for (int s = RT / 2; s > 0; s >>= 1) {
-            if (tid < s)
-                for (int c = 0; c < 3; ++c) {
-                    s_red[c][tid] = fminf(s_red[c][tid], s_red[c][tid + s]);
-                    s_red[3 + c][tid] = fmaxf(s_red[3 + c][tid], s_red[3 + c][tid + s]);
-                }
-            __syncthreads();
-        }
-        x.cx = mul_rn(add_rn(s_red[0][0], s_red[3][0]), 0.5f);
-        x.cy = mul_rn(add_rn(s_red[1][0], s_red[4][0]), 0.5f);
-        x.cz = mul_rn(add_rn(s_red[2][0], s_red[5][0]), 0.5f);
-        __syncthreads();
-        float r2 = 0.0f;                                         // max of the squared distances: sqrt is monotone
-        for (long long i = v0 + tid; i < v1; i += RT) {
-            const float dx = add_rn(verts[i * 3], -x.cx), dy = add_rn(verts[i * 3 + 1], -x.cy);
-            const float dz = add_rn(verts[i * 3 + 2], -x.cz);
-            r2 = fmaxf(r2, add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));
-        }
-        s_red[0][tid] = r2;
-        __syncthreads();
-        for (int s = RT / 2; s > 0; s >>= 1) {
-            if (tid < s) s_red[0][tid] = fmaxf(s_red[0][tid], s_red[0][tid + s]);
-            __syncthreads();
-        }
-        const float r = __builtin_sqrtf(s_red[0][0]);
-        if (!isfinite(r)) x.status = GV_RENDER_NONFINITE;
-        else if (r == 0.0f) x.status = GV_RENDER_ZERO_RADIUS;
-        else {
-            x.scale = __fdiv_rn(fit, r);
-            if (!isfinite(x.scale)) x.status = GV_RENDER_NONFINITE;
-        }
-    }
-    if (tid == 0) {
-        xf[m] = x;
-        status[m] = x.status;
-    }
-}
-
 // ---- binning: count (SCATTER = false) and scatter (SCATTER = true) --------------------------------------------------
 template <bool SCATTER, int LS>
 __global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_count, long long* __restrict__ image_total,
@@ -404,50 +269,6 @@ __global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_
         }
         __syncthreads();                                         // s_cnt / s_sum are reused by the next chunk
     }
-}
-
-// exclusive scan of the per-image totals (one workgroup); *total = their sum
-__global__ __launch_bounds__(SCAN_T) void scan_images_kernel(const long long* __restrict__ image_total, long long nimg,
-                                                             long long* __restrict__ image_base,
-                                                             long long* __restrict__ total) {
-    __shared__ long long s[SCAN_T];
-    const int tid = threadIdx.x;
-    long long carry = 0;
-    for (long long b = 0; b < nimg; b += SCAN_T) {
-        const long long i = b + tid;
-        const long long v = i < nimg ? image_total[i] : 0;
-        s[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < SCAN_T; o <<= 1) {
-            const long long add = tid >= o ? s[tid - o] : 0;
-            __syncthreads();
-            s[tid] += add;
-            __syncthreads();
-        }
-        if (i < nimg) image_base[i] = carry + s[tid] - v;
-        carry += s[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry;
-}
-
-// tile list starts of one image: image base + exclusive scan of its tile counts (T <= 1024)
-__global__ __launch_bounds__(SCAN_T) void scan_tiles_kernel(const int* __restrict__ tile_count,
-                                                            const long long* __restrict__ image_base, int T,
-                                                            long long* __restrict__ tile_start) {
-    __shared__ long long s[SCAN_T];
-    const int tid = threadIdx.x;
-    const long long img = blockIdx.x;
-    const long long v = tid < T ? tile_count[img * T + tid] : 0;
-    s[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < SCAN_T; o <<= 1) {
-        const long long add = tid >= o ? s[tid - o] : 0;
-        __syncthreads();
-        s[tid] += add;
-        __syncthreads();
-    }
-    if (tid < T) tile_start[img * T + tid] = image_base[img] + s[tid] - v;
 }
 
 // ---- raster + resolve ----------------------------------------------------------------------------------------------
@@ -701,8 +522,6 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 struct WsLayout {
     int64_t xf, shade, tile_count, tile_fill, tile_start, image_total, image_base, bytes;
 };
@@ -723,22 +542,13 @@ WsLayout ws_layout(int32_t n, int32_t v, int32_t h, int32_t w, int64_t total_tri
     return L;
 }
 
-bool finite3(const float* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
 // the checks every entry point shares
 int check_common(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
                  int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* d,
                  const float* cameras, const void* workspace, int64_t workspace_bytes) {
     if (!verts || !vert_offsets || !tris || !tri_offsets || !d || !cameras || !workspace) return GV_E_BADARG;
     if (n <= 0 || total_verts < 0 || total_tris < 0 || max_tris < 0) return GV_E_BADARG;
-    if (d->height <= 0 || d->width <= 0 || d->num_views <= 0 || (d->flags & ~(GV_RENDER_PERSPECTIVE | GV_RENDER_TWO_SIDED)))
-        return GV_E_BADARG;
-    if (!(d->fit > 0.0f && d->fit <= 1.0f) || !(d->ambient >= 0.0f && d->ambient <= 1.0f)) return GV_E_BADARG;
-    if (!(d->proj_scale > 0.0f) || !isfinite(d->proj_scale)) return GV_E_BADARG;
-    if ((d->flags & GV_RENDER_PERSPECTIVE) &&
-        !(d->persp_dist > 1.0f && isfinite(d->persp_dist) && isfinite(d->depth_a) && isfinite(d->depth_b)))
-        return GV_E_BADARG;
-    if (!finite3(d->light) || !finite3(d->color) || !finite3(d->background)) return GV_E_BADARG;
+    if (check_desc(d) != GV_OK) return GV_E_BADARG;
     if (d->height > MAX_SIDE || d->width > MAX_SIDE || d->num_views > 64 || n > 65535 || max_tris > MAX_TRIS)
         return GV_E_UNSUPPORTED;
     if (workspace_bytes < ws_layout(n, d->num_views, d->height, d->width, total_tris).bytes) return GV_E_BADARG;
@@ -749,6 +559,7 @@ int check_common(const float* verts, const int64_t* vert_offsets, const int32_t*
 Args make_args(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
                const gv_render_desc* d, const float* cameras, const float* rotations, const MeshXf* xf) {
     Args a;
+    static_cast<View&>(a) = make_view(d);
     a.verts = verts;
     a.voff = (const long long*)vert_offsets;
     a.tris = tris;
@@ -756,18 +567,6 @@ Args make_args(const float* verts, const int64_t* vert_offsets, const int32_t* t
     a.cams = cameras;
     a.rots = rotations;
     a.xf = xf;
-    a.V = d->num_views;
-    a.H = d->height;
-    a.W = d->width;
-    a.tiles_x = (d->width + TS - 1) / TS;
-    a.tiles_y = (d->height + TS - 1) / TS;
-    a.persp = (d->flags & GV_RENDER_PERSPECTIVE) ? 1 : 0;
-    a.k = d->proj_scale;
-    a.D = d->persp_dist;
-    a.da = d->depth_a;
-    a.db = d->depth_b;
-    a.cxs = (float)d->width * 0.5f;                              // exact: w <= 512
-    a.cys = (float)d->height * 0.5f;
     return a;
 }
 
@@ -861,16 +660,6 @@ int64_t normal_tables(const gv_render_desc* d) { return (d->flags & GV_RENDER_TW
 
 int64_t normals_bytes(int64_t tables, int64_t total_verts) {
     return round_up((total_verts > 0 ? tables * total_verts : 1) * 12, 256);
-}
-
-// shininess -> the number of squarings; -1 for a power of two above 128 (GV_E_UNSUPPORTED once the shared checks have
-// passed); false for anything else (GV_E_BADARG)
-bool shininess_shift(int32_t shininess, int* k) {
-    if (shininess <= 0 || (shininess & (shininess - 1))) return false;
-    *k = -1;
-    for (int i = 0; i <= 7; ++i)
-        if (shininess == 1 << i) *k = i;
-    return true;
 }
 
 struct SmoothCall {                                              // what gv_render_draw_smooth adds to a draw call

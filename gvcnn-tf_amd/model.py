@@ -578,6 +578,11 @@ class GVCNN:
 
     # -- meshes in (render.py): render into an engine-owned view buffer, then the view entry points ---------------
     def _render_meshes(self, batch, renderer, rotations):
+        return self._render_shapes(batch, renderer, "render", "meshes", rotations=rotations)
+
+    def _render_shapes(self, batch, renderer, method, what, **kw):
+        """renderer.<method>(batch, out=the engine's view buffer, quantize=True, **kw): the body of the mesh and the
+        point entry points."""
         from . import render as _render
         if renderer is None:
             renderer = getattr(self, "_renderer", None)
@@ -588,11 +593,29 @@ class GVCNN:
                              % ((renderer.V, renderer.H, renderer.W), (self.V, self.H, self.W)))
         n = len(batch)
         if n != self.N:
-            raise ValueError("the batch holds %d meshes, the engine was built for %d" % (n, self.N))
+            raise ValueError("the batch holds %d %s, the engine was built for %d" % (n, what, self.N))
         if getattr(self, "_mesh_views", None) is None:
             self._mesh_views = torch.empty((self.N, self.V, self.H, self.W, 3), dtype=torch.float32,
                                            device=self.device)
-        return renderer.render(batch, rotations=rotations, out=self._mesh_views, quantize=True)
+        return getattr(renderer, method)(batch, out=self._mesh_views, quantize=True, **kw)
+
+    # -- points in: the same three entry points on splatted point clouds (render.ViewRenderer.render_points) ----------
+    def _render_points(self, batch, renderer, rotations, radius, shading):
+        return self._render_shapes(batch, renderer, "render_points", "point clouds", rotations=rotations, radius=radius,
+                                   shading=shading)
+
+    def forward_points(self, batch, renderer=None, rotations=None, check=True, radius="auto", shading="depth"):
+        """forward() on the views of N point clouds splatted on the device (see forward_meshes; batch: a
+        render.PointBatch or a list of points / (points, normals); radius, shading: render_points)."""
+        return self.forward(self._render_points(batch, renderer, rotations, radius, shading), check=check)
+
+    def embed_points(self, batch, renderer=None, rotations=None, check=True, basic=False, radius="auto", shading="depth"):
+        """embed() on the splatted views of N point clouds (see forward_points)."""
+        return self.embed(self._render_points(batch, renderer, rotations, radius, shading), check=check, basic=basic)
+
+    def explain_points(self, batch, renderer=None, rotations=None, radius="auto", shading="depth", **kw):
+        """explain() on the splatted views of N point clouds (see forward_points)."""
+        return self.explain(self._render_points(batch, renderer, rotations, radius, shading), **kw)
 
     def forward_meshes(self, batch, renderer=None, rotations=None, check=True):
         """forward() on the views of N meshes rendered on the device (render.ViewRenderer; default: V x H x W of this

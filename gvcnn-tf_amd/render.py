@@ -40,6 +40,21 @@ reproducible bit for bit:
     rounded to fp32.  A sample whose interpolated normal has no finite positive length takes its triangle's flat
     factor (the table of the flat mode: wrap or |s|, the world light; DEFAULT_LIGHT with light="camera").  With
     samples > 1 every sample is shaded at its own position.
+Points in (csrc/render_points.hip; contract: include/gvcnn_hip.h, "points in"; restated in tests/render_points_oracle.py):
+
+    pts = load_points("scan.xyz")                                # [P, 3], or (points, normals) from six columns
+    pts, normals = sample_surface(verts, tris, 20000, seed=0)    # ... or a cloud from a mesh
+    batch = PointBatch([pts, ...], device)
+    views = r.render_points(batch)                               # the same [N, 12, 224, 224, 3]
+
+  - the cloud is normalised, rotated, projected and snapped exactly as a mesh's vertices are; point i becomes a disc
+    around its snapped centre, parallel to the screen, at the point's 24-bit depth: R = rint(min(max((radius * k) * 256,
+    1), 8192)) in 1/256 pixel (perspective: (radius * k) / z), radius per cloud in normalised units ("auto":
+    auto_point_radius); pixel centre P is covered when |P - centre|^2 <= R^2 in int64 (the boundary belongs to the
+    disc); the pixel keeps the smallest (depth << 32 | point id).  A disc under about 0.71 pixel can miss every centre.
+  - shading="depth": f = ambient + (1 - ambient) * (1 - Z / (2^24 - 1)), colour = color * f, nearer is brighter;
+    shading="normal": the reflection model above on the point's own (rotated) normal, with l_v and m_v as above; a
+    normal without a finite positive length takes the depth factor.  One sample per pixel only.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
@@ -55,6 +70,7 @@ from . import model as _model
 MAX_SIDE = 512
 MAX_VIEWS = 64
 MAX_TRIS = 1 << 24
+MAX_POINTS = 1 << 24
 DEFAULT_COLOR = (31 / 255.0, 119 / 255.0, 180 / 255.0)         # matplotlib C0
 DEFAULT_BACKGROUND = (1.0, 1.0, 1.0)
 DEFAULT_MAX_WORKSPACE = 2 << 30
@@ -321,6 +337,163 @@ class MeshBatch:
         return off.data_ptr() + int(vo[a]) * 8, tid.data_ptr() + c0 * 4, c1 - c0
 
 
+# ---- point clouds ----------------------------------------------------------------------------------------------------
+def load_points(path):
+    """A point cloud file -> points float32 [P, 3], or (points, normals) when the file has six columns (x y z nx ny nz,
+    the resampled ModelNet40 layout).  .xyz / .pts / .txt: one point per line, values separated by whitespace or commas,
+    '#' starts a comment; .npy: an array [P, 3] or [P, 6].  ValueError for anything else: an unknown extension, no
+    points, a line with another number of columns, a token that is no number, a non-finite value."""
+    p = str(path).lower()
+    if p.endswith(".npy"):
+        try:
+            a = np.load(path, allow_pickle=False)
+        except Exception as e:
+            raise ValueError("%s: not a readable .npy array (%s)" % (path, e))
+        if a.ndim != 2 or a.shape[1] not in (3, 6) or not (np.issubdtype(a.dtype, np.floating)
+                                                            or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("%s: expected a numeric array [P, 3] or [P, 6], got %s %s" % (path, a.dtype, a.shape))
+    elif p.endswith((".xyz", ".pts", ".txt")):
+        with open(path) as f:
+            rows = [line.replace(",", " ").split() for line in _lines(f.read())]
+        if not rows:
+            raise ValueError("%s: no points" % path)
+        cols = len(rows[0])
+        if cols not in (3, 6):
+            raise ValueError("%s: %d columns (expected 3 or 6)" % (path, cols))
+        for i, r in enumerate(rows):
+            if len(r) != cols:
+                raise ValueError("%s: point %d has %d columns, the first has %d" % (path, i, len(r), cols))
+        try:
+            a = np.array(rows, dtype=np.float64)
+        except ValueError:
+            raise ValueError("%s: a value is not a number" % path)
+    else:
+        raise ValueError("unknown point cloud format: %s" % path)
+    if len(a) == 0:
+        raise ValueError("%s: no points" % path)
+    with np.errstate(over="ignore"):
+        a = a.astype(np.float32)
+    if not np.isfinite(a).all():
+        raise ValueError("%s: non-finite value" % path)
+    if a.shape[1] == 3:
+        return np.ascontiguousarray(a)
+    return np.ascontiguousarray(a[:, :3]), np.ascontiguousarray(a[:, 3:])
+
+
+def sample_surface(verts, tris, n, seed=0, return_faces=False):
+    """n points on the surface of a mesh, uniform by area, and the unit normal of the face each one lies on (winding
+    defined): (points float32 [n, 3], normals float32 [n, 3]), with return_faces also the face ids int64 [n].  Host
+    numpy in float64, np.random.RandomState(seed): the same arguments give the same cloud.  How a mesh becomes a cloud."""
+    v = np.asarray(verts, np.float64)
+    t = np.asarray(tris, np.int64).reshape(-1, 3)
+    n = int(n)
+    if v.ndim != 2 or v.shape[1] != 3 or not np.isfinite(v).all():
+        raise ValueError("verts must be finite [nv, 3]")
+    if n < 0 or len(t) == 0 or t.min() < 0 or t.max() >= len(v):
+        raise ValueError("sample_surface needs n >= 0 and triangles with indices in [0, %d)" % len(v))
+    a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
+    cr = np.cross(b - a, c - a)
+    area2 = np.linalg.norm(cr, axis=1)
+    if not area2.sum() > 0:
+        raise ValueError("the mesh has no area")
+    rng = np.random.RandomState(seed)
+    cdf = np.cumsum(area2) / area2.sum()
+    f = np.minimum(np.searchsorted(cdf, rng.uniform(size=n), side="right"), len(t) - 1)
+    f = np.where(area2[f] > 0, f, int(np.argmax(area2)))             # (a rounding step onto a zero-area face)
+    s, r2 = np.sqrt(rng.uniform(size=n)), rng.uniform(size=n)
+    w0, w1, w2 = 1.0 - s, s * (1.0 - r2), s * r2
+    p = w0[:, None] * a[f] + w1[:, None] * b[f] + w2[:, None] * c[f]
+    out = (p.astype(np.float32), (cr[f] / area2[f][:, None]).astype(np.float32))
+    return out + (f,) if return_faces else out
+
+
+def auto_point_radius(P, fit, k):
+    """The radius="auto" of render_points for a cloud of P points, in normalised units: min(max(2 * fit / sqrt(P), 1 / k),
+    32 / k), float64 rounded to fp32.  2 * fit / sqrt(P) is about the spacing of P points spread over a disc of radius
+    fit (twice it closes the gaps of an uneven sampling); the clamps keep the disc between 1 and 32 pixels.  fit, k: the
+    renderer's descriptor()['fit'] and ['proj_scale']."""
+    return np.float32(min(max(2.0 * float(fit) / math.sqrt(max(int(P), 1)), 1.0 / float(k)), 32.0 / float(k)))
+
+
+def pack_points(clouds):
+    """[points [P, 3] or (points, normals [P, 3]), ...] -> dict of host arrays: points float32 [sum P, 3], normals float32
+    [sum P, 3] or None, point_offsets int64 [N + 1].  A cloud with normals is a tuple; normals are all or none across
+    the list.  Every cloud is checked here, before any upload: shapes, finite values, at most 2^24 points."""
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError("no point clouds")
+    ps, ns = [], []
+    for i, c in enumerate(clouds):
+        g = None
+        if isinstance(c, tuple):
+            if len(c) != 2:
+                raise ValueError("cloud %d is not points or a (points, normals) pair" % i)
+            c, g = c
+        p = np.asarray(c)
+        if p.size == 0:
+            p = p.reshape(0, 3)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("cloud %d: points must be [P, 3], got %s" % (i, p.shape))
+        with np.errstate(over="ignore"):
+            p = p.astype(np.float32)
+        if not np.isfinite(p).all():
+            raise ValueError("cloud %d: non-finite point" % i)
+        if len(p) > MAX_POINTS:
+            raise ValueError("cloud %d: %d points (at most 2^24)" % (i, len(p)))
+        if g is not None:
+            g = np.asarray(g)
+            if g.size == 0:
+                g = g.reshape(0, 3)
+            if g.shape != p.shape:
+                raise ValueError("cloud %d: normals must be %s like the points, got %s" % (i, p.shape, g.shape))
+            with np.errstate(over="ignore"):
+                g = g.astype(np.float32)
+            if not np.isfinite(g).all():
+                raise ValueError("cloud %d: non-finite normal" % i)
+        if ns and (g is None) != (ns[0] is None):
+            raise ValueError("cloud %d: normals are all or none across a batch" % i)
+        ps.append(p)
+        ns.append(g)
+    po = np.zeros(len(clouds) + 1, np.int64)
+    po[1:] = np.cumsum([len(p) for p in ps])
+    return {"points": np.concatenate(ps).reshape(-1, 3),
+            "normals": None if ns[0] is None else np.concatenate(ns).reshape(-1, 3), "point_offsets": po}
+
+
+class PointBatch:
+    """Point clouds packed and uploaded once, as MeshBatch does for meshes.  clouds: a list of points [P, 3] or of
+    (points, normals [P, 3]) tuples."""
+
+    def __init__(self, clouds, device=None):
+        p = pack_points(clouds)
+        self.device = _device(device)
+        self.n = len(p["point_offsets"]) - 1
+        self.point_offsets_host = p["point_offsets"]
+        self.num_points = np.diff(p["point_offsets"])
+        # one element at least: an empty tensor has no address to hand to the library
+        pts = p["points"] if len(p["points"]) else np.zeros((1, 3), np.float32)
+        self.points = torch.from_numpy(np.ascontiguousarray(pts)).to(self.device)
+        self.normals = None
+        if p["normals"] is not None:
+            nr = p["normals"] if len(p["normals"]) else np.zeros((1, 3), np.float32)
+            self.normals = torch.from_numpy(np.ascontiguousarray(nr)).to(self.device)
+        self.point_offsets = torch.from_numpy(p["point_offsets"]).to(self.device)
+
+    def __len__(self):
+        return self.n
+
+    def group(self, a, b):
+        """The C-ABI arguments of clouds [a, b): pointers into the packed arrays (no copy); the last is the grid-size
+        hint (the largest cloud)."""
+        po = self.point_offsets_host
+        return (self.points.data_ptr() + int(po[a]) * 12, self.point_offsets.data_ptr() + a * 8, b - a,
+                int(po[b] - po[a]), int(self.num_points[a:b].max()))
+
+    def group_normals(self, a):
+        """The normals pointer of the group that starts at cloud a (None without normals)."""
+        return None if self.normals is None else self.normals.data_ptr() + int(self.point_offsets_host[a]) * 12
+
+
 def random_rotations(n, mode="z", seed=0):
     """[n, 3, 3] float32 rotation matrices, built in float64 from np.random.RandomState(seed) and rounded once.
     mode 'z': about the up axis by a uniform angle; 'so3': uniform over all rotations (unit quaternions)."""
@@ -421,6 +594,26 @@ def projection(height, width, fov):
     return _lib.GV_RENDER_PERSPECTIVE, half / math.tan(t), D, (D + 1.0) / 2.0, (D * D - 1.0) / 2.0
 
 
+def _check_reflection(diffuse, specular, shininess, light):
+    """The reflection keywords of ViewRenderer (and of its point_reflection), each on its own."""
+    if diffuse not in ("wrap", "lambert"):
+        raise ValueError("diffuse must be 'wrap' or 'lambert'")
+    if isinstance(light, str) and light != "camera":
+        raise ValueError("light must be a nonzero 3-vector or 'camera'")
+    if isinstance(specular, bool) or not isinstance(specular, numbers.Real) or not 0.0 <= specular <= 1.0:
+        raise ValueError("specular must be in [0, 1]")
+    if (isinstance(shininess, bool) or not isinstance(shininess, numbers.Integral)
+            or shininess not in (1, 2, 4, 8, 16, 32, 64, 128)):
+        raise ValueError("shininess must be one of 1, 2, 4, ..., 128")
+
+
+def _unit_light(light):
+    lt = np.asarray(light, np.float64)
+    if lt.shape != (3,) or not np.isfinite(lt).all() or not np.linalg.norm(lt) > 0:
+        raise ValueError("light must be a nonzero 3-vector")
+    return lt / np.linalg.norm(lt)
+
+
 class ViewRenderer:
     """V views of H x W per mesh (rendering contract: the module docstring).  elevation: degrees, one for all views or
     one per view; azimuths: degrees (default (i + 1) * 360 / V); fov: 0 (orthographic) or a perspective field of view
@@ -430,12 +623,14 @@ class ViewRenderer:
     at the pixel centre); shading: "flat" (one factor per triangle) or "smooth" (Phong reflection on interpolated vertex
     normals, per sample).  Smooth only: light="camera" (a headlight that travels with the view), diffuse="lambert"
     (max(s, 0); "wrap" is matplotlib's (s + 1) / 2; two_sided makes both |s|), specular in [0, 1] with shininess 1, 2,
-    4, ..., 128 (the exponent of the highlight)."""
+    4, ..., 128 (the exponent of the highlight).  point_reflection: a dict with any of diffuse, specular, shininess, light,
+    two_sided for render_points(shading="normal") alone (it may hold what a flat mesh renderer refuses); without it the
+    splatter reflects as the renderer does."""
 
     def __init__(self, num_views, height, width, elevation=30.0, azimuths=None, fov=0.0, fit=0.9,
                  color=DEFAULT_COLOR, background=DEFAULT_BACKGROUND, light=DEFAULT_LIGHT, ambient=0.3,
                  two_sided=False, device=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE, samples=1, shading="flat",
-                 diffuse="wrap", specular=0.0, shininess=16):
+                 diffuse="wrap", specular=0.0, shininess=16, point_reflection=None):
         if not 1 <= int(num_views) <= MAX_VIEWS:
             raise ValueError("num_views must be in [1, %d]" % MAX_VIEWS)
         if not (1 <= int(height) <= MAX_SIDE and 1 <= int(width) <= MAX_SIDE):
@@ -450,15 +645,15 @@ class ViewRenderer:
             raise ValueError("samples must be 1, 2 or 4")
         if shading not in ("flat", "smooth"):
             raise ValueError("shading must be 'flat' or 'smooth'")
-        if diffuse not in ("wrap", "lambert"):
-            raise ValueError("diffuse must be 'wrap' or 'lambert'")
-        if isinstance(light, str) and light != "camera":
-            raise ValueError("light must be a nonzero 3-vector or 'camera'")
-        if isinstance(specular, bool) or not isinstance(specular, numbers.Real) or not 0.0 <= specular <= 1.0:
-            raise ValueError("specular must be in [0, 1]")
-        if (isinstance(shininess, bool) or not isinstance(shininess, numbers.Integral)
-                or shininess not in (1, 2, 4, 8, 16, 32, 64, 128)):
-            raise ValueError("shininess must be one of 1, 2, 4, ..., 128")
+        _check_reflection(diffuse, specular, shininess, light)
+        # render_points(shading="normal") reflects as the renderer does, or as point_reflection says: a dict with any of
+        # diffuse, specular, shininess, light, two_sided (so a flat mesh renderer can still splat with a headlight)
+        pr = {"diffuse": diffuse, "specular": specular, "shininess": shininess, "light": light, "two_sided": two_sided}
+        if point_reflection is not None:
+            if not isinstance(point_reflection, dict) or set(point_reflection) - set(pr):
+                raise ValueError("point_reflection is a dict with keys among %s" % sorted(pr))
+            pr.update(point_reflection)
+            _check_reflection(pr["diffuse"], pr["specular"], pr["shininess"], pr["light"])
         if shading == "flat":
             # the flat table is per triangle and view-independent, and stays so
             for bad, what in ((isinstance(light, str), "light='camera'"), (diffuse != "wrap", "diffuse='lambert'"),
@@ -479,10 +674,7 @@ class ViewRenderer:
         self.elevation = elevation
         self.device = _device(device)
         self.cameras_host = camera_matrices(elevation, self.azimuths)
-        lt = np.asarray(light, np.float64)
-        if lt.shape != (3,) or not np.isfinite(lt).all() or not np.linalg.norm(lt) > 0:
-            raise ValueError("light must be a nonzero 3-vector")
-        lt = lt / np.linalg.norm(lt)
+        lt = _unit_light(light)
         flags, k, D, a, b = projection(self.H, self.W, fov)
         d = _lib.RenderDesc()
         d.height, d.width, d.num_views = self.H, self.W, self.V
@@ -507,6 +699,26 @@ class ViewRenderer:
             self.shade_desc = sh
             self.lights = torch.from_numpy(self.lights_host).to(self.device)
             self.halfs = torch.from_numpy(self.halfs_host).to(self.device)
+        # the point splatter's reflection: its own descriptor copy (two_sided), shading descriptor, lights and halfs
+        self.point = pr
+        self.point_desc = _lib.RenderDesc.from_buffer_copy(d)
+        self.point_desc.flags = flags | (_lib.GV_RENDER_TWO_SIDED if pr["two_sided"] else 0)
+        sh = _lib.RenderShading()
+        sh.flags = _lib.GV_RENDER_LAMBERT if pr["diffuse"] == "lambert" else 0
+        sh.shininess, sh.specular = int(pr["shininess"]), float(pr["specular"])
+        self.point_shade_desc = sh
+        self.point_lights_host, self.point_halfs_host = shading_vectors(
+            elevation, self.azimuths, "camera" if isinstance(pr["light"], str) else _unit_light(pr["light"]))
+        self._point_vectors = None                       # (lights, halfs) on the device, on the first "normal" render
+
+    def point_descriptor(self):
+        """descriptor() with the reflection fields render_points(shading="normal") uses, for an oracle."""
+        d = self.descriptor()
+        d.update({"flags": self.point_desc.flags, "diffuse": self.point["diffuse"],
+                  "light_mode": "camera" if isinstance(self.point["light"], str) else "world",
+                  "specular": float(np.float32(self.point["specular"])), "shininess": int(self.point["shininess"]),
+                  "lights": self.point_lights_host.copy(), "halfs": self.point_halfs_host.copy()})
+        return d
 
     def descriptor(self):
         """The descriptor's fields as Python values (fp32-rounded), for an oracle."""
@@ -592,9 +804,11 @@ class ViewRenderer:
             rc = lib.gv_render_draw_ss(*args, *tail, S, _model._st())
         _lib.check(rc, "gv_render_draw")
 
-    def _render(self, batch, rotations, out, output, return_buffers):
+    def _render(self, batch, rotations, out, output, return_buffers, to_batch=None, draw=None):
+        """The body of every render call: to_batch / draw are the mesh pair (_batch, _draw) or the point pair."""
         with torch.cuda.device(self.device):
-            batch = self._batch(batch)
+            batch = (to_batch or self._batch)(batch)
+            draw = draw or self._draw
             n = batch.n
             rot = self._rotations(rotations, n)
             shape = (n, self.V, self.H, self.W, 3)
@@ -610,11 +824,118 @@ class ViewRenderer:
                 face_id = torch.empty(grid, dtype=torch.int32, device=self.device)
                 depth = torch.empty(grid, dtype=torch.int32, device=self.device)        # uint32 bits
             status = np.zeros(n, np.int32)
-            self._draw(batch, 0, n, rot, output, out, face_id, depth, status)
+            draw(batch, 0, n, rot, output, out, face_id, depth, status)
             self.status = status
             if return_buffers:
                 return out, face_id, depth
             return out
+
+    # -- points in (csrc/render_points.hip; contract: include/gvcnn_hip.h, "points in") ---------------------------------
+    def _point_radii(self, batch, radius):
+        """radius -> float32 [N] in normalised units: "auto" (auto_point_radius per cloud), one positive number, or one
+        per cloud."""
+        n = batch.n
+        if isinstance(radius, str):
+            if radius != "auto":
+                raise ValueError("radius must be 'auto', a positive number or one per cloud")
+            r = [auto_point_radius(p, self.desc.fit, self.desc.proj_scale) for p in batch.num_points]
+            return np.ascontiguousarray(r, dtype=np.float32)
+        try:
+            r = np.asarray(radius, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("radius must be 'auto', a positive number or one per cloud")
+        if isinstance(radius, bool) or r.dtype == bool or (r.ndim != 0 and r.shape != (n,)):
+            raise ValueError("radius must be 'auto', a positive number or one per cloud (%d)" % n)
+        r = np.ascontiguousarray(np.broadcast_to(r, (n,)), dtype=np.float32)
+        if not (np.isfinite(r).all() and (r > 0).all()):
+            raise ValueError("radius must be finite and positive in fp32")
+        return r
+
+    def _draw_points(self, batch, a, b, rot, output, out, point_id, depth, status, radii, normal):
+        """Render clouds [a, b) into out[a:b] (and the buffers); halves the group when its tile lists would pass the
+        workspace cap.  The steps of _draw."""
+        lib, d = self.lib, self.point_desc
+        args = batch.group(a, b)
+        n = args[2]
+
+        def halves():
+            h = (a + b) // 2
+            self._draw_points(batch, a, h, rot, output, out, point_id, depth, status, radii, normal)
+            self._draw_points(batch, h, b, rot, output, out, point_id, depth, status, radii, normal)
+        ws_bytes = lib.gv_points_workspace_bytes(n, self.V, self.H, self.W)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_workspace_bytes")
+        if ws_bytes > self.max_workspace_bytes and n > 1:
+            return halves()
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        info = torch.empty(1 + (n + 1) // 2, dtype=torch.int64, device=self.device)     # pair total, then status
+        st_dev = info[1:].view(torch.int32)
+        rp = None if rot is None else rot.data_ptr() + a * 36
+        rad = radii[a:b]                                                 # host memory, alive past the read below
+        rc = lib.gv_points_prepare(*args, rad.ctypes.data, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
+                                   info.data_ptr(), st_dev.data_ptr(), _model._st())
+        _lib.check(rc, "gv_points_prepare")
+        host = info.cpu().numpy()                                        # the one host read of a render
+        total = int(host[0])
+        status[a:b] = host[1:].view(np.int32)[:n]
+        bins_bytes = lib.gv_render_bins_bytes(total)
+        _lib.check(bins_bytes if bins_bytes < 0 else 0, "gv_render_bins_bytes")
+        if ws_bytes + bins_bytes > self.max_workspace_bytes and n > 1:
+            del ws, info
+            return halves()
+        bins = torch.empty(bins_bytes, dtype=torch.uint8, device=self.device)
+        img = self.V * self.H * self.W
+        esz = 1 if output == _lib.GV_RENDER_OUT_U8 else 4
+        shade = (None, None, None, None)
+        if normal:
+            if self._point_vectors is None:
+                self._point_vectors = (torch.from_numpy(self.point_lights_host).to(self.device),
+                                       torch.from_numpy(self.point_halfs_host).to(self.device))
+            shade = (batch.group_normals(a), self.point_shade_desc, self._point_vectors[0].data_ptr(),
+                     self._point_vectors[1].data_ptr())
+        rc = lib.gv_points_draw(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, bins.data_ptr(),
+                                bins_bytes, total, output, out.data_ptr() + a * img * 3 * esz,
+                                None if point_id is None else point_id.data_ptr() + a * img * 4,
+                                None if depth is None else depth.data_ptr() + a * img * 4, *shade, _model._st())
+        _lib.check(rc, "gv_points_draw")
+
+    def _render_points(self, batch, rotations, out, output, return_buffers, radius, shading):
+        if self.samples != 1:
+            raise ValueError("render_points draws one sample per pixel: the renderer has samples=%d" % self.samples)
+        if shading not in ("depth", "normal"):
+            raise ValueError("shading must be 'depth' or 'normal'")
+        if isinstance(batch, PointBatch):
+            if batch.device != self.device:
+                raise ValueError("the batch lives on %s, the renderer on %s" % (batch.device, self.device))
+        else:
+            with torch.cuda.device(self.device):
+                batch = PointBatch(batch, self.device)
+        if shading == "normal" and batch.normals is None:
+            raise ValueError("shading='normal' needs a batch with normals")
+        radii = self._point_radii(batch, radius)
+
+        def draw(*a):
+            self._draw_points(*a, radii, shading == "normal")
+        return self._render(batch, rotations, out, output, return_buffers, to_batch=lambda b: b, draw=draw)
+
+    def render_points(self, batch, rotations=None, out=None, quantize=True, return_buffers=False, radius="auto",
+                      shading="depth"):
+        """views fp32 [N, V, H, W, 3] of N point clouds splatted as screen-parallel discs (and (point_id int32, depth)
+        [N, V, H, W] with return_buffers, as render returns face_id and depth).  batch: a PointBatch or a list of points
+        [P, 3] / (points, normals) tuples.  radius: the disc's radius in normalised units (the unit sphere has radius 1;
+        one pixel is 1 / proj_scale): a positive number, one per cloud, or "auto" (auto_point_radius).  shading:
+        "depth" (nearer is brighter: f = ambient + (1 - ambient) * (1 - depth)) or "normal" (the reflection model of
+        shading="smooth" on the points' normals, with this renderer's diffuse / specular / shininess / light /
+        two_sided or its point_reflection).  The renderer must have samples=1.  Sets `status` as render does."""
+        output = _lib.GV_RENDER_OUT_F32_QUANTIZED if quantize else _lib.GV_RENDER_OUT_F32
+        return self._render_points(batch, rotations, out, output, return_buffers, radius, shading)
+
+    def render_points_uint8(self, batch, rotations=None, out=None, return_buffers=False, radius="auto", shading="depth"):
+        """render_points as uint8 [N, V, H, W, 3] on the device (what a PNG of the render holds)."""
+        return self._render_points(batch, rotations, out, _lib.GV_RENDER_OUT_U8, return_buffers, radius, shading)
+
+    def render_points_png(self, batch, rotations=None, filter="adaptive", color="auto", radius="auto", shading="depth"):
+        """One list of V PNG files (bytes) per cloud: render_points_uint8, then the device encoder, as render_png."""
+        return self._encode_png(self.render_points_uint8(batch, rotations, radius=radius, shading=shading), filter, color)
 
     def render(self, batch, rotations=None, out=None, quantize=True, return_buffers=False):
         """views fp32 [N, V, H, W, 3] on the device (and (face_id int32, depth) [N, V, S*H, S*W] with return_buffers, one
@@ -632,8 +953,10 @@ class ViewRenderer:
     def render_png(self, batch, rotations=None, filter="adaptive", color="auto"):
         """One list of V PNG files (bytes) per mesh: render_uint8, then the device encoder (records.encode_png_batch:
         the pixels stay on the device, the finished zlib streams come back).  Sets `status` as render_uint8 does."""
+        return self._encode_png(self.render_uint8(batch, rotations), filter, color)
+
+    def _encode_png(self, views, filter, color):
         from . import records
-        views = self.render_uint8(batch, rotations)
         n = views.shape[0]
         with torch.cuda.device(self.device):
             pngs = records.encode_png_batch(views.view(n * self.V, self.H, self.W, 3), filter, color)

@@ -732,6 +732,59 @@ int gv_render_draw_smooth(const float* verts, const int64_t* vert_offsets, const
                           const gv_render_shading* shading, const float* lights, const float* halfs,
                           const float* normals, int64_t normals_bytes, void* stream);
 
+/* ---- points in: multi-view point splatter (scans, LiDAR crops, sampled meshes: shapes that are not triangulated) -----
+ * Turns N point clouds into the same views [N, V, H, W, 3] as "meshes in", under the same discipline: fp32 with every
+ * step rounded on its own (no FMA), integer coverage, results defined bit for bit and independent of scheduling.
+ *  - clouds: fp32 points [sum P, 3] concatenated, int64 point_offsets [N+1] (offsets[0] need not be 0, as for meshes).
+ *    The index of a point within its cloud is its id.  Optional unit-free normals [sum P, 3], one per point, laid out
+ *    like the points.
+ *  - normalisation, rotation, cameras, projection, snap and depth: exactly those of "meshes in", applied to the cloud's
+ *    points (c = bbox midpoint, r = max |p - c|, u = (p - c) * (fit / r), w = M u, q = C_v w, X, Y in 1/256 pixel, Z in
+ *    24 bits).  Status GV_RENDER_* per cloud: GV_RENDER_EMPTY for a cloud without points, GV_RENDER_ZERO_RADIUS when
+ *    all its points coincide (a single point included), GV_RENDER_TOO_LARGE above 2^24 points.
+ *  - splat: point i of cloud m is a disc around (X, Y), parallel to the screen, at depth Z over its whole area.  Its
+ *    radius in 1/256 pixel, every step rounded: orthographic R = rint(min(max((radius_m * k) * 256, 1), 8192));
+ *    GV_RENDER_PERSPECTIVE R = rint(min(max(((radius_m * k) / z) * 256, 1), 8192)) with z = q2 + D of the projection
+ *    (min / max as fminf / fmaxf: a NaN gives 1).  radius [N] is per cloud, in normalised units (the unit sphere has
+ *    radius 1), HOST memory: gv_points_prepare checks it, copies it into the workspace on the stream (keep it alive
+ *    until the stream has passed that copy) and gv_points_draw reads it there.  R <= 8192 (32 pixels) bounds the tiles
+ *    a splat touches; R >= 1 only: a disc under about 0.71 pixel (R < 182) can miss every pixel centre and then leaves
+ *    no trace.  A point whose world position w is not finite has no snapped position or depth and is skipped.
+ *  - coverage, int64: pixel centre P = (256 i + 128, 256 j + 128) is covered when dx*dx + dy*dy <= R*R with
+ *    d = P - (X, Y): the boundary is inclusive.  The pixel keeps the smallest key (Z << 32) | id: the nearest splat,
+ *    the lower id at equal depth.
+ *  - binning: a splat belongs to the 16x16-pixel tiles of the pixels i0 = max((X - R + 127) >> 8, 0) .. i1 =
+ *    min((X + R - 128) >> 8, W - 1) (rows likewise); it is dropped when that box is empty.
+ *  - shading of the winning splat.  normals == NULL ("depth"): t = float(Z) / 16777215, f = ambient + (1 - ambient) *
+ *    (1 - t), channel = color * f: nearer is brighter.  normals != NULL ("normal"): n = M g (g the point's normal; the
+ *    rotation's sum order; n = g without rotations), nn = (n0*n0 + n1*n1) + n2*n2, and the reflection model of "smooth
+ *    shading" evaluated on n: s = ((l0*n0 + l1*n1) + l2*n2) / sqrt(nn) with l = lights[v]; h = (s+1)*0.5, or
+ *    max(s, 0) with GV_RENDER_LAMBERT, or |s| with GV_RENDER_TWO_SIDED; f = ambient + (1-ambient) * h; t = (m.n) /
+ *    sqrt(nn) with m = halfs[v], max(t, 0) (|t| with GV_RENDER_TWO_SIDED); p = t squared log2(shininess) times;
+ *    channel = min(color * f + specular * p, 1).  A normal whose nn is not finite and > 0 takes the depth factor.
+ *    desc->light is not used.
+ *  - output, point_id int32 [N,V,H,W] (-1 background) and depth uint32 [N,V,H,W] (0xFFFFFFFF background): as "meshes
+ *    in" (one sample per pixel only).
+ * Sequence: ws = gv_points_workspace_bytes(...); gv_points_prepare(...) writes *pair_total and status[N] (device
+ * memory); the host reads the total; bins = gv_render_bins_bytes(total) bytes; gv_points_draw(...) writes the views.
+ * max_points (the largest P of the batch) only sizes the binning grid: any value >= 0 gives the same results.
+ * Limits: H, W <= 512, V <= 64, N <= 65535, max_points <= 2^24 (GV_E_UNSUPPORTED beyond).  GV_E_BADARG before any HIP
+ * call: a NULL required pointer (shading / lights / halfs are required with normals), a size <= 0, the descriptor
+ * errors of "meshes in", a radius that is not finite or not > 0, unknown shading flags, specular outside [0, 1], a
+ * shininess that is no power of two (GV_E_UNSUPPORTED above 128), an unknown output, a workspace / bins buffer smaller
+ * than the size query's answer; GV_E_ALIGN for a workspace / bins pointer that is not 16-byte aligned or a 4-byte
+ * buffer that is not 4-byte aligned. */
+int64_t gv_points_workspace_bytes(int32_t n, int32_t num_views, int32_t height, int32_t width);
+int gv_points_prepare(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                      int32_t max_points, const float* radius, const gv_render_desc* desc, const float* cameras,
+                      const float* rotations, void* workspace, int64_t workspace_bytes, int64_t* pair_total,
+                      int32_t* status, void* stream);
+int gv_points_draw(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                   int32_t max_points, const gv_render_desc* desc, const float* cameras, const float* rotations,
+                   void* workspace, int64_t workspace_bytes, void* bins, int64_t bins_bytes, int64_t total,
+                   int32_t output, void* out, int32_t* point_id, uint32_t* depth, const float* normals,
+                   const gv_render_shading* shading, const float* lights, const float* halfs, void* stream);
+
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
  * consumers (an Inception block input, a ResNet shortcut) sums their gradients.
