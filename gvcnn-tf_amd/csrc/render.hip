@@ -1,26 +1,22 @@
 // render.hip — multi-view rasteriser: a batch of triangle meshes -> the backbone's input views [N, V, H, W, 3] on the
 // device (the rendering contract is in include/gvcnn_hip.h, "meshes in").
 //
-//   gv_render_prepare   normalise_kernel   (render_common.h, as the scans) one workgroup per mesh: bbox midpoint c, radius
-//                                          r, scale = fit / r, status.
-//                       bin_kernel<false>  grid (triangle chunks, view, mesh): every thread sets up its triangles for
-//                                          the view (vertex transform, snap, orientation, pixel-centre bbox) and counts
-//                                          them into the image's 16x16-pixel tiles with LDS atomics; the workgroup then
-//                                          adds its nonzero tile counts to the global counters (one atomic per
-//                                          workgroup and tile, never per fragment).  View 0 also writes every triangle's
-//                                          flat shading factor (world-space normal, view independent).
-//                       scan_images_kernel one workgroup: exclusive scan of the per-image pair totals, the grand total.
-//                       scan_tiles_kernel  one workgroup per image: tile list starts = image base + scan of its tiles.
-//   gv_render_draw      bin_kernel<true>   the same setup and the same LDS counts; each workgroup reserves a run of
-//                                          every tile list it feeds (one atomic per workgroup and tile) and places its
-//                                          triangle ids there through LDS cursors.  List order is scheduling dependent;
-//                                          nothing downstream depends on it.
-//                       raster_kernel      one workgroup per tile (256 threads = 16 x 16 pixels): the tile's list is
-//                                          streamed through LDS 256 setups at a time; each pixel keeps the smallest
-//                                          64-bit key (Z << 32 | triangle id) in a register and writes its outputs once.
+//   gv_render_prepare   normalise_kernel       (render_common.h, as the scans) one workgroup per mesh: bbox midpoint c,
+//                                              radius r, scale = fit / r, status.
+//                       tile_bin_kernel<false> (render_tiles.h, over MeshPrim<LS>) grid (triangle chunks, view, mesh): every
+//                                              thread sets up its triangles for the view (vertex transform, snap,
+//                                              orientation, pixel-centre bbox) and counts them into the image's
+//                                              16x16-pixel tiles.  View 0 also writes every triangle's flat shading factor
+//                                              (world-space normal, view independent).
+//                       scan_images_kernel     one workgroup: exclusive scan of the per-image pair totals, the grand total.
+//                       scan_tiles_kernel      one workgroup per image: tile list starts = image base + scan of its tiles.
+//   gv_render_draw      tile_bin_kernel<true>  the same setup; places the triangle ids in the tile lists.
+//                       raster_kernel          one workgroup per tile (256 threads = 16 x 16 pixels): the tile's list is
+//                                              streamed through LDS 256 setups at a time; each pixel keeps the smallest
+//                                              64-bit key (Z << 32 | triangle id) in a register and writes its outputs once.
 //
 // gv_render_prepare_ss / gv_render_draw_ss: the same launches with S x S samples per pixel (S = 1 << LS = 1, 2, 4; LS is a
-// template parameter of tri_setup, bin_kernel and raster_kernel; LS = 0 is the code behind the original pair).  The
+// template parameter of tri_setup, MeshPrim and raster_kernel; LS = 0 is the code behind the original pair).  The
 // triangle's box is taken over the sample grid, so binning depends on S; a raster thread still owns one pixel and keeps
 // its S * S keys in registers, and resolves them to the pixel in the same launch.
 //
@@ -29,16 +25,16 @@
 //                          host-built CSR in ascending triangle order and normalises the sum.
 //   raster_kernel<.., SM = true>  the same raster loop; the resolve recomputes the winning triangle's setup and edge
 //                          functions per covered sample, interpolates the three vertex normals and shades the sample
-//                          (smooth_colour).  SM = false is the flat code, instantiated from the same source as before.
+//                          (smooth_colour, the reflection model of render_common.h).  SM = false is the flat code, instantiated from the same source as before.
 //
 // No thread walks more than one tile's pixels: a triangle that covers the whole screen sits in every tile list it
 // touches and each tile's threads test it against their own pixel.  The triangle setup is a pure function of (mesh,
 // view, triangle), recomputed where needed (count, scatter, raster), so the bins hold 4-byte ids only.
 #include <math.h>
 
-// the fp32 discipline (mul_rn / add_rn, no contraction), MeshXf, world, project, snap, dot3, normalise_kernel and the two
-// scan kernels are shared with render_points.hip
-#include "render_common.h"
+// the fp32 discipline (mul_rn / add_rn, no contraction), MeshXf, world, project, snap, dot3, the reflection model, the pixel
+// store, normalise_kernel, the binning kernel and the two scan kernels are shared with render_points.hip
+#include "render_tiles.h"
 
 #pragma clang fp contract(off)
 
@@ -115,27 +111,7 @@ __device__ bool tri_setup(const Args& a, int m, int v, int t, Tri& T) {
     return gx0 <= gx1 && gy0 <= gy1;
 }
 
-// flat shading factor of a triangle (winding-defined world normal)
-__device__ float shade_factor(const MeshXf& x, const float* M, const float* p0, const float* p1, const float* p2,
-                              float3 light, float ambient, int two_sided) {
-    float w0[3], w1[3], w2[3];
-    world(x, M, p0, w0);
-    world(x, M, p1, w1);
-    world(x, M, p2, w2);
-    const float a0 = add_rn(w1[0], -w0[0]), a1 = add_rn(w1[1], -w0[1]), a2 = add_rn(w1[2], -w0[2]);
-    const float b0 = add_rn(w2[0], -w0[0]), b1 = add_rn(w2[1], -w0[1]), b2 = add_rn(w2[2], -w0[2]);
-    const float n0 = add_rn(mul_rn(a1, b2), -mul_rn(a2, b1));
-    const float n1 = add_rn(mul_rn(a2, b0), -mul_rn(a0, b2));
-    const float n2 = add_rn(mul_rn(a0, b1), -mul_rn(a1, b0));
-    const float nl = add_rn(add_rn(mul_rn(n0, light.x), mul_rn(n1, light.y)), mul_rn(n2, light.z));
-    const float nn = add_rn(add_rn(mul_rn(n0, n0), mul_rn(n1, n1)), mul_rn(n2, n2));
-    const float s = nn > 0.0f ? __fdiv_rn(nl, __builtin_sqrtf(nn)) : 0.0f;
-    const float h = two_sided ? fabsf(s) : mul_rn(add_rn(s, 1.0f), 0.5f);
-    return add_rn(ambient, mul_rn(add_rn(1.0f, -ambient), h));
-}
-
-// ---- smooth shading: vertex normals --------------------------------------------------------------------------------
-// face vector n = (w1 - w0) x (w2 - w0) of a triangle, unnormalised (the steps of shade_factor)
+// face vector n = (w1 - w0) x (w2 - w0) of a triangle, unnormalised
 __device__ __forceinline__ void face_vector(const MeshXf& x, const float* M, const float* p0, const float* p1,
                                             const float* p2, float n[3]) {
     float w0[3], w1[3], w2[3];
@@ -149,6 +125,43 @@ __device__ __forceinline__ void face_vector(const MeshXf& x, const float* M, con
     n[2] = add_rn(mul_rn(a0, b1), -mul_rn(a1, b0));
 }
 
+// flat shading factor of a triangle (winding-defined world normal)
+__device__ float shade_factor(const MeshXf& x, const float* M, const float* p0, const float* p1, const float* p2,
+                              float3 light, float ambient, int two_sided) {
+    float n[3];
+    face_vector(x, M, p0, p1, p2, n);
+    const float nl = add_rn(add_rn(mul_rn(n[0], light.x), mul_rn(n[1], light.y)), mul_rn(n[2], light.z));
+    const float nn = add_rn(add_rn(mul_rn(n[0], n[0]), mul_rn(n[1], n[1])), mul_rn(n[2], n[2]));
+    const float s = nn > 0.0f ? __fdiv_rn(nl, __builtin_sqrtf(nn)) : 0.0f;
+    const float h = two_sided ? fabsf(s) : mul_rn(add_rn(s, 1.0f), 0.5f);
+    return add_rn(ambient, mul_rn(add_rn(1.0f, -ambient), h));
+}
+
+// a mesh's triangles with S = 1 << LS samples per pixel and axis, as tile_bin_kernel sees them; the count pass of view 0
+// also fills the flat shade table [sum T]
+template <int LS>
+struct MeshPrim : Args {
+    float3 light;
+    float ambient;
+    int two_sided;
+    typedef float CountOut;
+    __device__ int status(int m) const { return xf[m].status; }
+    __device__ int count(int m) const { return (int)(toff[m + 1] - toff[m]); }
+    __device__ bool box(int m, int v, int t, int& px0, int& px1, int& py0, int& py1) const {
+        Tri q;
+        if (!tri_setup<LS>(*this, m, v, t, q)) return false;
+        px0 = q.px0, px1 = q.px1, py0 = q.py0, py1 = q.py1;
+        return true;
+    }
+    __device__ void counted(int m, int v, int t, float* shade) const {
+        const float *p0, *p1, *p2;
+        if (v == 0 && load_tri(*this, m, t, p0, p1, p2))
+            shade[toff[m] - toff[0] + t] =
+                shade_factor(xf[m], rots ? rots + (size_t)m * 9 : nullptr, p0, p1, p2, light, ambient, two_sided);
+    }
+};
+
+// ---- smooth shading: vertex normals --------------------------------------------------------------------------------
 // One thread per (table, vertex of the group): the face vectors of the vertex's corners (CSR: corner_off per vertex of
 // the packed arrays, re-based by corner_off[0] as the mesh offsets are; corner_tri the local triangle ids, ascending)
 // added in list order, then normalised.  Table v of a two-sided render turns every face vector towards view v's eye
@@ -203,74 +216,6 @@ __global__ __launch_bounds__(RT) void vertex_normals_kernel(Args a, int n, long 
     o[2] = g[2];
 }
 
-// ---- binning: count (SCATTER = false) and scatter (SCATTER = true) --------------------------------------------------
-template <bool SCATTER, int LS>
-__global__ __launch_bounds__(RT) void bin_kernel(Args a, int* __restrict__ tile_count, long long* __restrict__ image_total,
-                                                 float* __restrict__ shade, float3 light, float ambient, int two_sided,
-                                                 const long long* __restrict__ tile_start, int* __restrict__ tile_fill,
-                                                 int* __restrict__ bins, long long cap) {
-    __shared__ int s_cnt[MAX_TILES];
-    __shared__ long long s_base[SCATTER ? MAX_TILES : 1];
-    __shared__ long long s_sum[RT / 64];
-    const int m = blockIdx.z, v = blockIdx.y, tid = threadIdx.x;
-    if (a.xf[m].status != GV_RENDER_OK) return;                  // (uniform)
-    const int nt = (int)(a.toff[m + 1] - a.toff[m]);
-    const int T = a.tiles_x * a.tiles_y;
-    const long long img = (long long)m * a.V + v;
-    const int stride = gridDim.x * CHUNK;
-    for (int c0 = blockIdx.x * CHUNK; c0 < nt; c0 += stride) {
-        for (int i = tid; i < T; i += RT) s_cnt[i] = 0;
-        __syncthreads();
-        for (int t = c0 + tid; t < min(c0 + CHUNK, nt); t += RT) {
-            if (!SCATTER && v == 0) {
-                const float *p0, *p1, *p2;
-                if (load_tri(a, m, t, p0, p1, p2))
-                    shade[a.toff[m] - a.toff[0] + t] = shade_factor(a.xf[m], a.rots ? a.rots + (size_t)m * 9 : nullptr,
-                                                                    p0, p1, p2, light, ambient, two_sided);
-            }
-            Tri q;
-            if (!tri_setup<LS>(a, m, v, t, q)) continue;
-            for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
-                for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) atomicAdd(&s_cnt[ty * a.tiles_x + tx], 1);
-        }
-        __syncthreads();
-        long long local = 0;
-        for (int i = tid; i < T; i += RT) {
-            const int c = s_cnt[i];
-            if (!c) continue;
-            if (SCATTER) {
-                s_base[i] = tile_start[img * T + i] + atomicAdd(&tile_fill[img * T + i], c);
-                s_cnt[i] = 0;                                    // now the workgroup's cursor into its run
-            } else {
-                atomicAdd(&tile_count[img * T + i], c);
-                local += c;
-            }
-        }
-        if (!SCATTER) {
-            for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-            if ((tid & 63) == 0) s_sum[tid >> 6] = local;
-            __syncthreads();
-            if (tid == 0) {
-                const long long s = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-                if (s) atomicAdd((u64*)&image_total[img], (u64)s);
-            }
-        } else {
-            __syncthreads();
-            for (int t = c0 + tid; t < min(c0 + CHUNK, nt); t += RT) {
-                Tri q;
-                if (!tri_setup<LS>(a, m, v, t, q)) continue;
-                for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
-                    for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) {
-                        const int i = ty * a.tiles_x + tx;
-                        const long long pos = s_base[i] + atomicAdd(&s_cnt[i], 1);
-                        if (pos < cap) bins[pos] = t;
-                    }
-            }
-        }
-        __syncthreads();                                         // s_cnt / s_sum are reused by the next chunk
-    }
-}
-
 // ---- raster + resolve ----------------------------------------------------------------------------------------------
 struct LTri {                                                    // one setup in LDS (64 bytes)
     int x0, y0, x1, y1, x2, y2;
@@ -293,13 +238,9 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
 }
 
 // ---- smooth shading: per covered sample ------------------------------------------------------------------------------
-struct Smooth {                                                  // the extra kernel argument of a smooth raster_kernel
+struct Smooth : Reflect {                                        // the extra kernel argument of a smooth raster_kernel
     const float* normals;                                        // [tables, total_verts, 3], vertex_normals_kernel
-    const float* lights;                                         // [V, 3] unit light of every view
-    const float* halfs;                                          // [V, 3] unit half-vector of every view
     long long table_stride;                                      // vertices between two views' tables (0: one table)
-    float specular, ambient;
-    int squarings, lambert, two_sided;                           // squarings = log2(shininess)
 };
 struct SmoothTri {                                               // the recomputed setup of the last shaded triangle id
     int id, ok;
@@ -339,29 +280,9 @@ __device__ __forceinline__ void smooth_colour(const Args& a, const Smooth& sm, c
         float n[3];
         for (int c = 0; c < 3; ++c)
             n[c] = add_rn(add_rn(mul_rn(b0, st.g[0][c]), mul_rn(b1, st.g[1][c])), mul_rn(b2, st.g[2][c]));
-        const float nn = add_rn(add_rn(mul_rn(n[0], n[0]), mul_rn(n[1], n[1])), mul_rn(n[2], n[2]));
-        if (nn > 0.0f && nn < INFINITY) {
-            const float len = __builtin_sqrtf(nn);
-            const float s = __fdiv_rn(dot3(sm.lights + v * 3, n[0], n[1], n[2]), len);
-            const float h = sm.two_sided ? fabsf(s) : sm.lambert ? fmaxf(s, 0.0f) : mul_rn(add_rn(s, 1.0f), 0.5f);
-            const float f = add_rn(sm.ambient, mul_rn(add_rn(1.0f, -sm.ambient), h));
-            float sp = 0.0f;
-            if (sm.specular > 0.0f) {                            // (uniform; specular = 0 adds exactly nothing)
-                const float t = __fdiv_rn(dot3(sm.halfs + v * 3, n[0], n[1], n[2]), len);
-                float p = sm.two_sided ? fabsf(t) : fmaxf(t, 0.0f);
-                for (int k = 0; k < sm.squarings; ++k) p = mul_rn(p, p);
-                sp = mul_rn(sm.specular, p);
-            }
-            cs[0] = fminf(add_rn(mul_rn(color.x, f), sp), 1.0f);
-            cs[1] = fminf(add_rn(mul_rn(color.y, f), sp), 1.0f);
-            cs[2] = fminf(add_rn(mul_rn(color.z, f), sp), 1.0f);
-            return;
-        }
+        if (reflect(sm, v, n, color, cs)) return;
     }
-    const float f = shade[tb + id];
-    cs[0] = mul_rn(color.x, f);
-    cs[1] = mul_rn(color.y, f);
-    cs[2] = mul_rn(color.z, f);
+    scale_colour(color, shade[tb + id], cs);
 }
 
 // S = 1 << LS samples per pixel and axis.  The thread of pixel (px, py) holds the S * S keys of its samples (b rows,
@@ -484,10 +405,7 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
             if constexpr (SM) {
                 smooth_colour<LS>(a, sm, shade, m, v, id, PX + (s % S) * STEP, PY + (s / S) * STEP, color, st, cs);
             } else {
-                const float f = shade[a.toff[m] - a.toff[0] + id];
-                cs[0] = mul_rn(color.x, f);
-                cs[1] = mul_rn(color.y, f);
-                cs[2] = mul_rn(color.z, f);
+                scale_colour(color, shade[a.toff[m] - a.toff[0] + id], cs);
             }
         }
         if (face_id || depth) {
@@ -499,65 +417,29 @@ __global__ __launch_bounds__(RT) void raster_kernel(Args a, const float* __restr
             if (OUT == GV_RENDER_OUT_F32)
                 acc[c] = s == 0 ? cs[c] : add_rn(acc[c], cs[c]);
             else
-                sum[c] += (unsigned)(unsigned char)fminf(fmaxf(floorf(add_rn(mul_rn(cs[c], 255.0f), 0.5f)), 0.0f), 255.0f);
+                sum[c] += to_u8(cs[c]);
         }
     }
-    if (OUT == GV_RENDER_OUT_F32) {
-        float* o = static_cast<float*>(out) + p * 3;
-        for (int c = 0; c < 3; ++c) o[c] = add_rn(LS ? mul_rn(acc[c], 1.0f / NS) : acc[c], -0.5f);
-    } else {
-        unsigned char u[3];
-        for (int c = 0; c < 3; ++c) u[c] = (unsigned char)((sum[c] + NS / 2) >> (2 * LS));
-        if (OUT == GV_RENDER_OUT_U8) {
-            unsigned char* o = static_cast<unsigned char*>(out) + p * 3;
-            o[0] = u[0];
-            o[1] = u[1];
-            o[2] = u[2];
-        } else {
-            float* o = static_cast<float*>(out) + p * 3;
-            // what gv_preprocess_views computes from the PNG bytes (its u8 * (1/255) - 0.5 compiles to one FMA)
-            for (int c = 0; c < 3; ++c) o[c] = __builtin_fmaf((float)u[c], 1.0f / 255.0f, -0.5f);
-        }
-    }
+    store_pixel<OUT, LS>(out, p, acc, sum);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-struct WsLayout {
-    int64_t xf, shade, tile_count, tile_fill, tile_start, image_total, image_base, bytes;
-};
+int64_t shade_bytes(int64_t total_tris) { return (total_tris > 0 ? total_tris : 1) * 4; }   // the flat shade table
 
-WsLayout ws_layout(int32_t n, int32_t v, int32_t h, int32_t w, int64_t total_tris) {
-    const int64_t T = (int64_t)((h + TS - 1) / TS) * ((w + TS - 1) / TS);
-    const int64_t nimg = (int64_t)n * v;
-    WsLayout L;
-    int64_t o = 0;
-    L.xf = o;          o += round_up((int64_t)n * sizeof(MeshXf), 256);
-    L.shade = o;       o += round_up((total_tris > 0 ? total_tris : 1) * 4, 256);
-    L.tile_count = o;  o += round_up(nimg * T * 4, 256);
-    L.tile_fill = o;   o += round_up(nimg * T * 4, 256);
-    L.tile_start = o;  o += round_up(nimg * T * 8, 256);
-    L.image_total = o; o += round_up(nimg * 8, 256);
-    L.image_base = o;  o += round_up(nimg * 8, 256);
-    L.bytes = o;
-    return L;
+TileWs ws_layout(int32_t n, int32_t v, int32_t h, int32_t w, int64_t total_tris) {
+    return tile_ws_layout(n, v, h, w, shade_bytes(total_tris));
 }
 
 // the checks every entry point shares
 int check_common(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
                  int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* d,
                  const float* cameras, const void* workspace, int64_t workspace_bytes) {
-    if (!verts || !vert_offsets || !tris || !tri_offsets || !d || !cameras || !workspace) return GV_E_BADARG;
-    if (n <= 0 || total_verts < 0 || total_tris < 0 || max_tris < 0) return GV_E_BADARG;
-    if (check_desc(d) != GV_OK) return GV_E_BADARG;
-    if (d->height > MAX_SIDE || d->width > MAX_SIDE || d->num_views > 64 || n > 65535 || max_tris > MAX_TRIS)
-        return GV_E_UNSUPPORTED;
-    if (workspace_bytes < ws_layout(n, d->num_views, d->height, d->width, total_tris).bytes) return GV_E_BADARG;
-    if (!gv_aligned16(workspace)) return GV_E_ALIGN;
-    return GV_OK;
+    return check_tile_common(verts && vert_offsets && tris && tri_offsets, total_verts >= 0 && total_tris >= 0, n,
+                             max_tris, d, cameras, workspace, workspace_bytes, shade_bytes(total_tris));
 }
 
 Args make_args(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
-               const gv_render_desc* d, const float* cameras, const float* rotations, const MeshXf* xf) {
+               const gv_render_desc* d, const float* cameras, const float* rotations, void* workspace, const TileWs& L) {
     Args a;
     static_cast<View&>(a) = make_view(d);
     a.verts = verts;
@@ -566,13 +448,18 @@ Args make_args(const float* verts, const int64_t* vert_offsets, const int32_t* t
     a.toff = (const long long*)tri_offsets;
     a.cams = cameras;
     a.rots = rotations;
-    a.xf = xf;
+    a.xf = ws_at<const MeshXf>(workspace, L.xf);
     return a;
 }
 
-dim3 bin_grid(int32_t max_tris, int32_t v, int32_t n) {
-    const int chunks = max_tris > 0 ? (max_tris + CHUNK - 1) / CHUNK : 1;
-    return dim3((unsigned)chunks, (unsigned)v, (unsigned)n);
+template <int LS>
+MeshPrim<LS> make_prim(const Args& a, const gv_render_desc* d) {
+    MeshPrim<LS> p;
+    static_cast<Args&>(p) = a;
+    p.light = make_float3(d->light[0], d->light[1], d->light[2]);
+    p.ambient = d->ambient;
+    p.two_sided = (d->flags & GV_RENDER_TWO_SIDED) ? 1 : 0;
+    return p;
 }
 
 // samples per pixel and axis -> log2 (0, 1, 2); -1 for a power of two above 4 (GV_E_UNSUPPORTED once the shared checks
@@ -583,77 +470,25 @@ bool sample_shift(int32_t samples, int* ls) {
     return true;
 }
 
-template <int LS>
-void launch_count(dim3 grid, hipStream_t st, const Args& a, int* tile_count, long long* image_total, float* shade,
-                  const gv_render_desc* d) {
-    hipLaunchKernelGGL((bin_kernel<false, LS>), grid, dim3(RT), 0, st, a, tile_count, image_total, shade,
-                       make_float3(d->light[0], d->light[1], d->light[2]), d->ambient,
-                       (d->flags & GV_RENDER_TWO_SIDED) ? 1 : 0, nullptr, nullptr, nullptr, 0ll);
-}
-
-template <int LS, bool SM>
-int launch_draw(dim3 bgrid, dim3 grid, hipStream_t st, const Args& a, const float* shade, const int* tc,
-                const long long* ts, int* tile_fill, int* bins, long long cap, const gv_render_desc* d, int32_t output,
-                void* out, int32_t* face_id, uint32_t* depth, typename SmoothParam<SM>::type sm) {
-    hipLaunchKernelGGL((bin_kernel<true, LS>), bgrid, dim3(RT), 0, st, a, nullptr, nullptr, nullptr,
-                       make_float3(0.f, 0.f, 0.f), 0.f, 0, ts, tile_fill, bins, cap);
-    GV_LAUNCH_CHECK();
-    const float3 color = make_float3(d->color[0], d->color[1], d->color[2]);
-    const float3 bg = make_float3(d->background[0], d->background[1], d->background[2]);
-    const int* b = bins;
-    if (output == GV_RENDER_OUT_F32_QUANTIZED)
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32_QUANTIZED, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts,
-                           b, cap, color, bg, out, face_id, depth, sm);
-    else if (output == GV_RENDER_OUT_F32)
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_F32, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap,
-                           color, bg, out, face_id, depth, sm);
-    else
-        hipLaunchKernelGGL((raster_kernel<GV_RENDER_OUT_U8, LS, SM>), grid, dim3(RT), 0, st, a, shade, tc, ts, b, cap,
-                           color, bg, out, face_id, depth, sm);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
 int render_prepare(const float* verts, const int64_t* vert_offsets, const int32_t* tris, const int64_t* tri_offsets,
                    int32_t n, int64_t total_verts, int64_t total_tris, int32_t max_tris, const gv_render_desc* desc,
                    const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes,
                    int64_t* pair_total, int32_t* status, int ls, void* stream) {
     if (!pair_total || !status) return GV_E_BADARG;
-    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
-                                cameras, workspace, workspace_bytes);
+    int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                          workspace, workspace_bytes);
     if (rc != GV_OK) return rc;
     if (ls < 0) return GV_E_UNSUPPORTED;
     const hipStream_t st = (hipStream_t)stream;
-    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
-    char* ws = static_cast<char*>(workspace);
-    MeshXf* xf = reinterpret_cast<MeshXf*>(ws + L.xf);
-    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_count, 0, (size_t)nimg * T * 4, st));
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.image_total, 0, (size_t)nimg * 8, st));
-    hipLaunchKernelGGL(normalise_kernel, dim3(n), dim3(RT), 0, st, verts, (const long long*)vert_offsets,
-                       (const long long*)tri_offsets, (long long)total_verts, (long long)total_tris, desc->fit, xf,
-                       status);
-    GV_LAUNCH_CHECK();
-    const dim3 grid = bin_grid(max_tris, desc->num_views, n);
-    int* tc = reinterpret_cast<int*>(ws + L.tile_count);
-    long long* it = reinterpret_cast<long long*>(ws + L.image_total);
-    float* shade = reinterpret_cast<float*>(ws + L.shade);
-    if (ls == 0) launch_count<0>(grid, st, a, tc, it, shade, desc);
-    else if (ls == 1) launch_count<1>(grid, st, a, tc, it, shade, desc);
-    else launch_count<2>(grid, st, a, tc, it, shade, desc);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_images_kernel, dim3(1), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const long long*>(ws + L.image_total), nimg,
-                       reinterpret_cast<long long*>(ws + L.image_base), (long long*)pair_total);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)nimg), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const int*>(ws + L.tile_count),
-                       reinterpret_cast<const long long*>(ws + L.image_base), T,
-                       reinterpret_cast<long long*>(ws + L.tile_start));
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    const TileWs L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, workspace, L);
+    rc = start_prepare(st, a, n, workspace, L, verts, vert_offsets, tri_offsets, total_verts, total_tris, desc->fit, status);
+    if (rc != GV_OK) return rc;
+    rc = dispatch3<0, 1, 2>(ls, [&](auto LS) {
+        return launch_bin<false>(st, make_prim<decltype(LS)::value>(a, desc), max_tris, n, workspace, L, nullptr, 0ll,
+                                 ws_at<float>(workspace, L.extra));
+    });
+    return rc != GV_OK ? rc : finish_prepare(st, a, n, workspace, L, pair_total);
 }
 
 int64_t normal_tables(const gv_render_desc* d) { return (d->flags & GV_RENDER_TWO_SIDED) ? d->num_views : 1; }
@@ -673,59 +508,49 @@ int render_draw(const float* verts, const int64_t* vert_offsets, const int32_t* 
                 const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes, void* bins,
                 int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* face_id, uint32_t* depth, int ls,
                 void* stream, const SmoothCall* sc = nullptr) {
-    if (!bins || !out || total < 0) return GV_E_BADARG;
-    if (output != GV_RENDER_OUT_F32_QUANTIZED && output != GV_RENDER_OUT_F32 && output != GV_RENDER_OUT_U8)
-        return GV_E_BADARG;
     int squarings = 0;
-    if (sc) {
-        if (!sc->shading || !sc->lights || !sc->halfs || !sc->normals) return GV_E_BADARG;
-        if ((sc->shading->flags & ~GV_RENDER_LAMBERT) || !(sc->shading->specular >= 0.0f && sc->shading->specular <= 1.0f))
-            return GV_E_BADARG;
-        if (!shininess_shift(sc->shading->shininess, &squarings)) return GV_E_BADARG;
-    }
-    const int rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc,
-                                cameras, workspace, workspace_bytes);
+    int rc = check_draw_args(bins, out, total, output);
+    if (rc == GV_OK && sc) rc = sc->normals ? check_shading(sc->shading, sc->lights, sc->halfs, &squarings) : GV_E_BADARG;
+    if (rc == GV_OK)
+        rc = check_common(verts, vert_offsets, tris, tri_offsets, n, total_verts, total_tris, max_tris, desc, cameras,
+                          workspace, workspace_bytes);
     if (rc != GV_OK) return rc;
     if (ls < 0 || squarings < 0) return GV_E_UNSUPPORTED;
-    if (bins_bytes < gv_render_bins_bytes(total)) return GV_E_BADARG;
     if (sc && sc->normals_size < normals_bytes(normal_tables(desc), total_verts)) return GV_E_BADARG;
-    if (!gv_aligned16(bins) || (output != GV_RENDER_OUT_U8 && ((uintptr_t)out & 3u))) return GV_E_ALIGN;
+    rc = check_draw_buffers(bins, bins_bytes, total, output, out, face_id, depth);
+    if (rc != GV_OK) return rc;
     if (sc && !gv_aligned16(sc->normals)) return GV_E_ALIGN;
-    if (((uintptr_t)face_id & 3u) || ((uintptr_t)depth & 3u)) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
-    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
-    char* ws = static_cast<char*>(workspace);
-    const MeshXf* xf = reinterpret_cast<const MeshXf*>(ws + L.xf);
-    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
+    const TileWs L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, workspace, L);
     const long long cap = bins_bytes / 4;
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_fill, 0, (size_t)nimg * T * 4, st));
-    const dim3 bgrid = bin_grid(max_tris, desc->num_views, n);
-    const dim3 grid((unsigned)T, (unsigned)desc->num_views, (unsigned)n);
-    const float* shade = reinterpret_cast<const float*>(ws + L.shade);
-    const int* tc = reinterpret_cast<const int*>(ws + L.tile_count);
-    const long long* ts = reinterpret_cast<const long long*>(ws + L.tile_start);
-    int* tf = reinterpret_cast<int*>(ws + L.tile_fill);
-    int* b = static_cast<int*>(bins);
+    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y), (unsigned)desc->num_views, (unsigned)n);
+    const float3 color = make_float3(desc->color[0], desc->color[1], desc->color[2]);
+    const float3 bg = make_float3(desc->background[0], desc->background[1], desc->background[2]);
+    Smooth smooth = {};
     if (sc) {
-        const bool two = (desc->flags & GV_RENDER_TWO_SIDED) != 0;
-        const Smooth sm = {sc->normals, sc->lights, sc->halfs, two ? (long long)total_verts : 0ll, sc->shading->specular,
-                           desc->ambient, squarings, (sc->shading->flags & GV_RENDER_LAMBERT) ? 1 : 0, two ? 1 : 0};
-        if (ls == 0)
-            return launch_draw<0, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth,
-                                        sm);
-        if (ls == 1)
-            return launch_draw<1, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth,
-                                        sm);
-        return launch_draw<2, true>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, sm);
+        static_cast<Reflect&>(smooth) = make_reflect(desc, sc->shading, squarings, sc->lights, sc->halfs);
+        smooth.normals = sc->normals;
+        smooth.table_stride = (desc->flags & GV_RENDER_TWO_SIDED) ? (long long)total_verts : 0ll;
     }
-    const NoSmooth no;
-    if (ls == 0)
-        return launch_draw<0, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
-    if (ls == 1)
-        return launch_draw<1, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
-    return launch_draw<2, false>(bgrid, grid, st, a, shade, tc, ts, tf, b, cap, desc, output, out, face_id, depth, no);
+    // the one place that names the raster_kernel instantiations: S x shading x output
+    auto raster = [&](auto LS, auto SM, auto sm) {
+        dispatch_output(output, [&](auto OUT) {
+            hipLaunchKernelGGL((raster_kernel<decltype(OUT)::value, decltype(LS)::value, decltype(SM)::value>), grid,
+                               dim3(RT), 0, st, a, ws_at<const float>(workspace, L.extra),
+                               ws_at<const int>(workspace, L.tile_count), ws_at<const long long>(workspace, L.tile_start),
+                               static_cast<const int*>(bins), cap, color, bg, out, face_id, depth, sm);
+        });
+    };
+    return dispatch3<0, 1, 2>(ls, [&](auto LS) {
+        const int rc = launch_bin<true>(st, make_prim<decltype(LS)::value>(a, desc), max_tris, n, workspace, L,
+                                        static_cast<int*>(bins), cap);
+        if (rc != GV_OK) return rc;
+        if (sc) raster(LS, std::true_type{}, smooth);
+        else raster(LS, std::false_type{}, NoSmooth{});
+        GV_LAUNCH_CHECK();
+        return (int)GV_OK;
+    });
 }
 
 int render_vertex_normals(const float* verts, const int64_t* vert_offsets, const int32_t* tris,
@@ -741,9 +566,8 @@ int render_vertex_normals(const float* verts, const int64_t* vert_offsets, const
     if (normals_size < normals_bytes(normal_tables(desc), total_verts)) return GV_E_BADARG;
     if (!gv_aligned16(normals)) return GV_E_ALIGN;
     if (total_verts == 0) return GV_OK;
-    const WsLayout L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
-    const MeshXf* xf = reinterpret_cast<const MeshXf*>(static_cast<char*>(workspace) + L.xf);
-    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, xf);
+    const TileWs L = ws_layout(n, desc->num_views, desc->height, desc->width, total_tris);
+    const Args a = make_args(verts, vert_offsets, tris, tri_offsets, desc, cameras, rotations, workspace, L);
     const int64_t blocks = (total_verts + RT - 1) / RT;
     if (blocks > 0x7fffffffll) return GV_E_UNSUPPORTED;
     hipLaunchKernelGGL(vertex_normals_kernel, dim3((unsigned)blocks, (unsigned)normal_tables(desc)), dim3(RT), 0,

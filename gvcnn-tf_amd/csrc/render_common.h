@@ -1,5 +1,6 @@
 // What the two renderers share (render.hip: meshes in; render_points.hip: points in): the fp32 discipline, the per-shape
-// normalisation, the camera transform / projection / snap, and the scans that turn tile counts into tile list starts.
+// normalisation, the camera transform / projection / snap, the reflection model, the pixel store, and the scans that turn
+// tile counts into tile list starts (the tile binning built on them is in render_tiles.h).
 // Everything sits in the including file's unnamed namespace: each translation unit has its own copy of the kernels.
 #pragma once
 #include <math.h>
@@ -102,6 +103,73 @@ inline View make_view(const gv_render_desc* d) {
     a.cxs = (float)d->width * 0.5f;                              // exact: w <= 512
     a.cys = (float)d->height * 0.5f;
     return a;
+}
+
+// ---- reflection model (contract: include/gvcnn_hip.h, "smooth shading") ---------------------------------------------
+struct Reflect {                                                 // the head of both renderers' shading arguments
+    const float* lights;                                         // [V, 3] unit light of every view
+    const float* halfs;                                          // [V, 3] unit half-vector of every view
+    float specular, ambient;
+    int squarings, lambert, two_sided;                           // squarings = log2(shininess)
+};
+
+// colour cs of a surface with (unnormalised) normal n in view v.  False, cs untouched, when n has no finite positive
+// length: the caller then shades by its own fallback.
+__device__ __forceinline__ bool reflect(const Reflect& r, int v, const float n[3], float3 color, float cs[3]) {
+    const float nn = add_rn(add_rn(mul_rn(n[0], n[0]), mul_rn(n[1], n[1])), mul_rn(n[2], n[2]));
+    if (!(nn > 0.0f && nn < INFINITY)) return false;
+    const float len = __builtin_sqrtf(nn);
+    const float s = __fdiv_rn(dot3(r.lights + v * 3, n[0], n[1], n[2]), len);
+    const float h = r.two_sided ? fabsf(s) : r.lambert ? fmaxf(s, 0.0f) : mul_rn(add_rn(s, 1.0f), 0.5f);
+    const float f = add_rn(r.ambient, mul_rn(add_rn(1.0f, -r.ambient), h));
+    float sp = 0.0f;
+    if (r.specular > 0.0f) {                                     // (uniform; specular = 0 adds exactly nothing)
+        const float t = __fdiv_rn(dot3(r.halfs + v * 3, n[0], n[1], n[2]), len);
+        float p = r.two_sided ? fabsf(t) : fmaxf(t, 0.0f);
+        for (int k = 0; k < r.squarings; ++k) p = mul_rn(p, p);
+        sp = mul_rn(r.specular, p);
+    }
+    cs[0] = fminf(add_rn(mul_rn(color.x, f), sp), 1.0f);
+    cs[1] = fminf(add_rn(mul_rn(color.y, f), sp), 1.0f);
+    cs[2] = fminf(add_rn(mul_rn(color.z, f), sp), 1.0f);
+    return true;
+}
+
+// the unlit colour: one factor for the three channels (the flat table's entry, the splatter's depth factor)
+__device__ __forceinline__ void scale_colour(float3 color, float f, float cs[3]) {
+    cs[0] = mul_rn(color.x, f);
+    cs[1] = mul_rn(color.y, f);
+    cs[2] = mul_rn(color.z, f);
+}
+
+// ---- pixel store ---------------------------------------------------------------------------------------------------
+// the byte a PNG of the render holds for a colour channel in [0, 1]
+__device__ __forceinline__ unsigned to_u8(float c) {
+    return (unsigned)(unsigned char)fminf(fmaxf(floorf(add_rn(mul_rn(c, 255.0f), 0.5f)), 0.0f), 255.0f);
+}
+
+// pixel p of `out` from its NS = 1 << 2 * LS samples: acc holds their fp32 colours added in row-major sample order
+// (read by OUT_F32 alone), sum the exact sum of their to_u8 bytes (read by the other two modes)
+template <int OUT, int LS>
+__device__ __forceinline__ void store_pixel(void* out, size_t p, const float acc[3], const unsigned sum[3]) {
+    constexpr int NS = 1 << (2 * LS);
+    if (OUT == GV_RENDER_OUT_F32) {
+        float* o = static_cast<float*>(out) + p * 3;
+        for (int c = 0; c < 3; ++c) o[c] = add_rn(LS ? mul_rn(acc[c], 1.0f / NS) : acc[c], -0.5f);
+    } else {
+        unsigned char u[3];
+        for (int c = 0; c < 3; ++c) u[c] = (unsigned char)((sum[c] + NS / 2) >> (2 * LS));
+        if (OUT == GV_RENDER_OUT_U8) {
+            unsigned char* o = static_cast<unsigned char*>(out) + p * 3;
+            o[0] = u[0];
+            o[1] = u[1];
+            o[2] = u[2];
+        } else {
+            float* o = static_cast<float*>(out) + p * 3;
+            // what gv_preprocess_views computes from the PNG bytes (its u8 * (1/255) - 0.5 compiles to one FMA)
+            for (int c = 0; c < 3; ++c) o[c] = __builtin_fmaf((float)u[c], 1.0f / 255.0f, -0.5f);
+        }
+    }
 }
 
 // ---- normalisation -------------------------------------------------------------------------------------------------
@@ -239,6 +307,20 @@ inline bool shininess_shift(int32_t shininess, int* k) {
     for (int i = 0; i <= 7; ++i)
         if (shininess == 1 << i) *k = i;
     return true;
+}
+
+// the reflection arguments of a shaded draw: GV_E_BADARG or GV_OK, with *squarings as shininess_shift leaves it
+inline int check_shading(const gv_render_shading* s, const float* lights, const float* halfs, int* squarings) {
+    if (!s || !lights || !halfs) return GV_E_BADARG;
+    if ((s->flags & ~GV_RENDER_LAMBERT) || !(s->specular >= 0.0f && s->specular <= 1.0f)) return GV_E_BADARG;
+    return shininess_shift(s->shininess, squarings) ? GV_OK : GV_E_BADARG;
+}
+
+// s: null for a draw that reflects nothing (the splatter's "depth" shading reads ambient alone)
+inline Reflect make_reflect(const gv_render_desc* d, const gv_render_shading* s, int squarings, const float* lights,
+                            const float* halfs) {
+    return {lights, halfs, s ? s->specular : 0.0f, d->ambient, squarings, (s && (s->flags & GV_RENDER_LAMBERT)) ? 1 : 0,
+            (d->flags & GV_RENDER_TWO_SIDED) ? 1 : 0};
 }
 
 }  // namespace

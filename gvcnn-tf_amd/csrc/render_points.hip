@@ -1,26 +1,22 @@
 // render_points.hip — multi-view point splatter: a batch of point clouds -> the backbone's input views [N, V, H, W, 3]
-// on the device (the contract is in include/gvcnn_hip.h, "points in").  The launches mirror render.hip's:
+// on the device (the contract is in include/gvcnn_hip.h, "points in").  The launches are render.hip's with a splat for
+// a triangle:
 //
-//   gv_points_prepare   normalise_kernel    (render_common.h) one workgroup per cloud: c, r, scale = fit / r, status.
-//                       pbin_kernel<false>  grid (point chunks, view, cloud): every thread sets up its points for the view
-//                                           (world position, project, snap, radius, pixel-centre box of the disc) and
-//                                           counts them into the image's 16x16-pixel tiles with LDS atomics; the workgroup
-//                                           then adds its nonzero tile counts to the global counters (one atomic per
-//                                           workgroup and tile, never per fragment).
+//   gv_points_prepare   normalise_kernel        (render_common.h) one workgroup per cloud: c, r, scale = fit / r, status.
+//                       tile_bin_kernel<false>  (render_tiles.h, over PointPrim) counts every point's disc (world position,
+//                                               project, snap, radius, pixel-centre box) into the image's tiles.
 //                       scan_images_kernel, scan_tiles_kernel  (render_common.h) tile list starts.
-//   gv_points_draw      pbin_kernel<true>   the same setup and LDS counts; each workgroup reserves a run of every tile
-//                                           list it feeds and places its point ids there through LDS cursors.  List order
-//                                           is scheduling dependent; nothing downstream depends on it.
-//                       splat_kernel        one workgroup per tile (256 threads = 16 x 16 pixels): the tile's list is
-//                                           streamed through LDS 256 setups at a time; each pixel tests its centre against
-//                                           the disc in int64, keeps the smallest key (Z << 32 | point id) in a register,
-//                                           shades the winner and writes its outputs once.
+//   gv_points_draw      tile_bin_kernel<true>   the same setup; places the point ids in the tile lists.
+//                       splat_kernel            one workgroup per tile (256 threads = 16 x 16 pixels): the tile's list is
+//                                               streamed through LDS 256 setups at a time; each pixel tests its centre
+//                                               against the disc in int64, keeps the smallest key (Z << 32 | point id) in
+//                                               a register, shades the winner and writes its outputs once.
 //
 // The splat setup is a pure function of (cloud, view, point), recomputed where needed (count, scatter, raster), so the
 // bins hold 4-byte ids only.  A disc reaches at most R_MAX = 32 pixels from its centre: at most 6 x 6 tiles.
 #include <math.h>
 
-#include "render_common.h"
+#include "render_tiles.h"
 
 #pragma clang fp contract(off)
 
@@ -68,68 +64,18 @@ __device__ bool splat_setup(const PArgs& a, int m, int v, int i, Splat& s) {
     return s.px0 <= s.px1 && s.py0 <= s.py1;
 }
 
-// ---- binning: count (SCATTER = false) and scatter (SCATTER = true) --------------------------------------------------
-// gridDim.x is a hint: the loop strides over every chunk of the cloud whatever the grid holds.
-template <bool SCATTER>
-__global__ __launch_bounds__(RT) void pbin_kernel(PArgs a, int* __restrict__ tile_count, long long* __restrict__ image_total,
-                                                  const long long* __restrict__ tile_start, int* __restrict__ tile_fill,
-                                                  int* __restrict__ bins, long long cap) {
-    __shared__ int s_cnt[MAX_TILES];
-    __shared__ long long s_base[SCATTER ? MAX_TILES : 1];
-    __shared__ long long s_sum[RT / 64];
-    const int m = blockIdx.z, v = blockIdx.y, tid = threadIdx.x;
-    if (a.xf[m].status != GV_RENDER_OK) return;                  // (uniform)
-    const int np = (int)(a.poff[m + 1] - a.poff[m]);             // <= 2^24 (status OK)
-    const int T = a.tiles_x * a.tiles_y;
-    const long long img = (long long)m * a.V + v;
-    const long long stride = (long long)gridDim.x * CHUNK;
-    for (long long c0 = (long long)blockIdx.x * CHUNK; c0 < np; c0 += stride) {
-        const int lo = (int)c0, hi = min(lo + CHUNK, np);
-        for (int i = tid; i < T; i += RT) s_cnt[i] = 0;
-        __syncthreads();
-        for (int t = lo + tid; t < hi; t += RT) {
-            Splat q;
-            if (!splat_setup(a, m, v, t, q)) continue;
-            for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
-                for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) atomicAdd(&s_cnt[ty * a.tiles_x + tx], 1);
-        }
-        __syncthreads();
-        long long local = 0;
-        for (int i = tid; i < T; i += RT) {
-            const int c = s_cnt[i];
-            if (!c) continue;
-            if (SCATTER) {
-                s_base[i] = tile_start[img * T + i] + atomicAdd(&tile_fill[img * T + i], c);
-                s_cnt[i] = 0;                                    // now the workgroup's cursor into its run
-            } else {
-                atomicAdd(&tile_count[img * T + i], c);
-                local += c;
-            }
-        }
-        if (!SCATTER) {
-            for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-            if ((tid & 63) == 0) s_sum[tid >> 6] = local;
-            __syncthreads();
-            if (tid == 0) {
-                const long long s = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-                if (s) atomicAdd((u64*)&image_total[img], (u64)s);
-            }
-        } else {
-            __syncthreads();
-            for (int t = lo + tid; t < hi; t += RT) {
-                Splat q;
-                if (!splat_setup(a, m, v, t, q)) continue;
-                for (int ty = q.py0 >> 4; ty <= q.py1 >> 4; ++ty)
-                    for (int tx = q.px0 >> 4; tx <= q.px1 >> 4; ++tx) {
-                        const int i = ty * a.tiles_x + tx;
-                        const long long pos = s_base[i] + atomicAdd(&s_cnt[i], 1);
-                        if (pos >= 0 && pos < cap) bins[pos] = t;
-                    }
-            }
-        }
-        __syncthreads();                                         // s_cnt / s_sum are reused by the next chunk
+struct PointPrim : PArgs {                                       // a cloud's points, as tile_bin_kernel sees them
+    __device__ int status(int m) const { return xf[m].status; }
+    __device__ int count(int m) const { return (int)(poff[m + 1] - poff[m]); }
+    __device__ bool box(int m, int v, int i, int& px0, int& px1, int& py0, int& py1) const {
+        Splat s;
+        if (!splat_setup(*this, m, v, i, s)) return false;
+        px0 = s.px0, px1 = s.px1, py0 = s.py0, py1 = s.py1;
+        return true;
     }
-}
+    typedef void CountOut;                                       // the count pass has nothing else to do
+    __device__ void counted(int, int, int, void*) const {}
+};
 
 // ---- raster + shade ------------------------------------------------------------------------------------------------
 struct LSplat {                                                  // one setup in LDS (20 bytes)
@@ -139,12 +85,8 @@ struct LSplat {                                                  // one setup in
     int id;
 };
 
-struct PShade {
+struct PShade : Reflect {
     const float* normals;                                        // [sum P, 3] per point, or null: "depth" shading
-    const float* lights;                                         // [V, 3] unit light of every view
-    const float* halfs;                                          // [V, 3] unit half-vector of every view
-    float specular, ambient;
-    int squarings, lambert, two_sided;                           // squarings = log2(shininess)
 };
 
 // colour of the pixel whose winning splat is point id at depth Z
@@ -155,36 +97,14 @@ __device__ __forceinline__ void splat_colour(const PArgs& a, const PShade& sh, i
         float n[3] = {g[0], g[1], g[2]};
         if (a.rots) {
             const float* M = a.rots + (size_t)m * 9;
-            const float n0 = dot3(M, g[0], g[1], g[2]), n1 = dot3(M + 3, g[0], g[1], g[2]);
-            const float n2 = dot3(M + 6, g[0], g[1], g[2]);
-            n[0] = n0;
-            n[1] = n1;
-            n[2] = n2;
+            n[0] = dot3(M, g[0], g[1], g[2]);
+            n[1] = dot3(M + 3, g[0], g[1], g[2]);
+            n[2] = dot3(M + 6, g[0], g[1], g[2]);
         }
-        const float nn = add_rn(add_rn(mul_rn(n[0], n[0]), mul_rn(n[1], n[1])), mul_rn(n[2], n[2]));
-        if (nn > 0.0f && nn < INFINITY) {
-            const float len = __builtin_sqrtf(nn);
-            const float s = __fdiv_rn(dot3(sh.lights + v * 3, n[0], n[1], n[2]), len);
-            const float h = sh.two_sided ? fabsf(s) : sh.lambert ? fmaxf(s, 0.0f) : mul_rn(add_rn(s, 1.0f), 0.5f);
-            const float f = add_rn(sh.ambient, mul_rn(add_rn(1.0f, -sh.ambient), h));
-            float sp = 0.0f;
-            if (sh.specular > 0.0f) {                            // (uniform; specular = 0 adds exactly nothing)
-                const float t = __fdiv_rn(dot3(sh.halfs + v * 3, n[0], n[1], n[2]), len);
-                float p = sh.two_sided ? fabsf(t) : fmaxf(t, 0.0f);
-                for (int k = 0; k < sh.squarings; ++k) p = mul_rn(p, p);
-                sp = mul_rn(sh.specular, p);
-            }
-            cs[0] = fminf(add_rn(mul_rn(color.x, f), sp), 1.0f);
-            cs[1] = fminf(add_rn(mul_rn(color.y, f), sp), 1.0f);
-            cs[2] = fminf(add_rn(mul_rn(color.z, f), sp), 1.0f);
-            return;
-        }
+        if (reflect(sh, v, n, color, cs)) return;
     }
     const float t = __fdiv_rn((float)Z, 16777215.0f);            // Z < 2^24: exact in fp32
-    const float f = add_rn(sh.ambient, mul_rn(add_rn(1.0f, -sh.ambient), add_rn(1.0f, -t)));
-    cs[0] = mul_rn(color.x, f);
-    cs[1] = mul_rn(color.y, f);
-    cs[2] = mul_rn(color.z, f);
+    scale_colour(color, add_rn(sh.ambient, mul_rn(add_rn(1.0f, -sh.ambient), add_rn(1.0f, -t))), cs);
 }
 
 template <int OUT>
@@ -241,76 +161,33 @@ __global__ __launch_bounds__(RT) void splat_kernel(PArgs a, PShade sh, const int
     if (best != BG_KEY) splat_colour(a, sh, m, v, (int)(best & 0xffffffffu), (unsigned)(best >> 32), color, cs);
     if (point_id) point_id[p] = best == BG_KEY ? -1 : (int)(best & 0xffffffffu);
     if (depth) depth[p] = best == BG_KEY ? 0xFFFFFFFFu : (unsigned)(best >> 32);
-    if (OUT == GV_RENDER_OUT_F32) {
-        float* o = static_cast<float*>(out) + p * 3;
-        for (int c = 0; c < 3; ++c) o[c] = add_rn(cs[c], -0.5f);
-    } else {
-        unsigned char u[3];
-        for (int c = 0; c < 3; ++c)
-            u[c] = (unsigned char)fminf(fmaxf(floorf(add_rn(mul_rn(cs[c], 255.0f), 0.5f)), 0.0f), 255.0f);
-        if (OUT == GV_RENDER_OUT_U8) {
-            unsigned char* o = static_cast<unsigned char*>(out) + p * 3;
-            o[0] = u[0];
-            o[1] = u[1];
-            o[2] = u[2];
-        } else {
-            float* o = static_cast<float*>(out) + p * 3;
-            // what gv_preprocess_views computes from the PNG bytes (its u8 * (1/255) - 0.5 compiles to one FMA)
-            for (int c = 0; c < 3; ++c) o[c] = __builtin_fmaf((float)u[c], 1.0f / 255.0f, -0.5f);
-        }
-    }
+    const unsigned u[3] = {to_u8(cs[0]), to_u8(cs[1]), to_u8(cs[2])};
+    store_pixel<OUT, 0>(out, p, cs, u);                          // one sample per pixel
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-struct PWsLayout {
-    int64_t xf, radius, tile_count, tile_fill, tile_start, image_total, image_base, bytes;
-};
-
-PWsLayout pws_layout(int32_t n, int32_t v, int32_t h, int32_t w) {
-    const int64_t T = (int64_t)((h + TS - 1) / TS) * ((w + TS - 1) / TS);
-    const int64_t nimg = (int64_t)n * v;
-    PWsLayout L;
-    int64_t o = 0;
-    L.xf = o;          o += round_up((int64_t)n * sizeof(MeshXf), 256);
-    L.radius = o;      o += round_up((int64_t)n * 4, 256);
-    L.tile_count = o;  o += round_up(nimg * T * 4, 256);
-    L.tile_fill = o;   o += round_up(nimg * T * 4, 256);
-    L.tile_start = o;  o += round_up(nimg * T * 8, 256);
-    L.image_total = o; o += round_up(nimg * 8, 256);
-    L.image_base = o;  o += round_up(nimg * 8, 256);
-    L.bytes = o;
-    return L;
+TileWs pws_layout(int32_t n, int32_t v, int32_t h, int32_t w) {  // extra: the clouds' radii
+    return tile_ws_layout(n, v, h, w, (int64_t)n * 4);
 }
 
 // the checks both entry points share
 int pcheck_common(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points, int32_t max_points,
                   const gv_render_desc* d, const float* cameras, const void* workspace, int64_t workspace_bytes) {
-    if (!points || !point_offsets || !d || !cameras || !workspace) return GV_E_BADARG;
-    if (n <= 0 || total_points < 0 || max_points < 0) return GV_E_BADARG;
-    if (check_desc(d) != GV_OK) return GV_E_BADARG;
-    if (d->height > MAX_SIDE || d->width > MAX_SIDE || d->num_views > 64 || n > 65535 || max_points > MAX_TRIS)
-        return GV_E_UNSUPPORTED;
-    if (workspace_bytes < pws_layout(n, d->num_views, d->height, d->width).bytes) return GV_E_BADARG;
-    if (!gv_aligned16(workspace)) return GV_E_ALIGN;
-    return GV_OK;
+    return check_tile_common(points && point_offsets, total_points >= 0, n, max_points, d, cameras, workspace,
+                             workspace_bytes, (int64_t)n * 4);
 }
 
-PArgs make_pargs(const float* points, const int64_t* point_offsets, const gv_render_desc* d, const float* cameras,
-                 const float* rotations, const MeshXf* xf, const float* radius) {
-    PArgs a;
+PointPrim make_prim(const float* points, const int64_t* point_offsets, const gv_render_desc* d, const float* cameras,
+                     const float* rotations, void* workspace, const TileWs& L) {
+    PointPrim a;
     static_cast<View&>(a) = make_view(d);
     a.pts = points;
     a.poff = (const long long*)point_offsets;
     a.cams = cameras;
     a.rots = rotations;
-    a.xf = xf;
-    a.radius = radius;
+    a.xf = ws_at<const MeshXf>(workspace, L.xf);
+    a.radius = ws_at<const float>(workspace, L.extra);
     return a;
-}
-
-dim3 pbin_grid(int32_t max_points, int32_t v, int32_t n) {
-    const int chunks = max_points > 0 ? (max_points + CHUNK - 1) / CHUNK : 1;
-    return dim3((unsigned)chunks, (unsigned)v, (unsigned)n);
 }
 
 }  // namespace
@@ -326,40 +203,18 @@ extern "C" int gv_points_prepare(const float* points, const int64_t* point_offse
                                  const float* cameras, const float* rotations, void* workspace, int64_t workspace_bytes,
                                  int64_t* pair_total, int32_t* status, void* stream) {
     if (!pair_total || !status || !radius) return GV_E_BADARG;
-    const int rc = pcheck_common(points, point_offsets, n, total_points, max_points, desc, cameras, workspace,
-                                 workspace_bytes);
+    int rc = pcheck_common(points, point_offsets, n, total_points, max_points, desc, cameras, workspace, workspace_bytes);
     if (rc != GV_OK) return rc;
     for (int32_t i = 0; i < n; ++i)                              // radius is host memory
         if (!(radius[i] > 0.0f) || !isfinite(radius[i])) return GV_E_BADARG;
     const hipStream_t st = (hipStream_t)stream;
-    const PWsLayout L = pws_layout(n, desc->num_views, desc->height, desc->width);
-    char* ws = static_cast<char*>(workspace);
-    MeshXf* xf = reinterpret_cast<MeshXf*>(ws + L.xf);
-    const PArgs a = make_pargs(points, point_offsets, desc, cameras, rotations, xf,
-                               reinterpret_cast<const float*>(ws + L.radius));
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
-    GV_HIP_CHECK(hipMemcpyAsync(ws + L.radius, radius, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_count, 0, (size_t)nimg * T * 4, st));
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.image_total, 0, (size_t)nimg * 8, st));
-    hipLaunchKernelGGL(normalise_kernel, dim3(n), dim3(RT), 0, st, points, (const long long*)point_offsets,
-                       (const long long*)point_offsets, (long long)total_points, (long long)total_points, desc->fit, xf,
-                       status);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pbin_kernel<false>, pbin_grid(max_points, desc->num_views, n), dim3(RT), 0, st, a,
-                       reinterpret_cast<int*>(ws + L.tile_count), reinterpret_cast<long long*>(ws + L.image_total),
-                       nullptr, nullptr, nullptr, 0ll);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_images_kernel, dim3(1), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const long long*>(ws + L.image_total), nimg,
-                       reinterpret_cast<long long*>(ws + L.image_base), (long long*)pair_total);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)nimg), dim3(SCAN_T), 0, st,
-                       reinterpret_cast<const int*>(ws + L.tile_count),
-                       reinterpret_cast<const long long*>(ws + L.image_base), T,
-                       reinterpret_cast<long long*>(ws + L.tile_start));
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    const TileWs L = pws_layout(n, desc->num_views, desc->height, desc->width);
+    const PointPrim a = make_prim(points, point_offsets, desc, cameras, rotations, workspace, L);
+    GV_HIP_CHECK(hipMemcpyAsync(ws_at<char>(workspace, L.extra), radius, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    rc = start_prepare(st, a, n, workspace, L, points, point_offsets, point_offsets, total_points, total_points,
+                       desc->fit, status);
+    if (rc == GV_OK) rc = launch_bin<false>(st, a, max_points, n, workspace, L, nullptr, 0ll);
+    return rc != GV_OK ? rc : finish_prepare(st, a, n, workspace, L, pair_total);
 }
 
 extern "C" int gv_points_draw(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
@@ -368,54 +223,34 @@ extern "C" int gv_points_draw(const float* points, const int64_t* point_offsets,
                               int64_t bins_bytes, int64_t total, int32_t output, void* out, int32_t* point_id,
                               uint32_t* depth, const float* normals, const gv_render_shading* shading,
                               const float* lights, const float* halfs, void* stream) {
-    if (!bins || !out || total < 0) return GV_E_BADARG;
-    if (output != GV_RENDER_OUT_F32_QUANTIZED && output != GV_RENDER_OUT_F32 && output != GV_RENDER_OUT_U8)
-        return GV_E_BADARG;
     int squarings = 0;
-    if (normals) {                                               // "normal" shading
-        if (!shading || !lights || !halfs) return GV_E_BADARG;
-        if ((shading->flags & ~GV_RENDER_LAMBERT) || !(shading->specular >= 0.0f && shading->specular <= 1.0f))
-            return GV_E_BADARG;
-        if (!shininess_shift(shading->shininess, &squarings)) return GV_E_BADARG;
-    }
-    const int rc = pcheck_common(points, point_offsets, n, total_points, max_points, desc, cameras, workspace,
-                                 workspace_bytes);
+    int rc = check_draw_args(bins, out, total, output);
+    if (rc == GV_OK && normals) rc = check_shading(shading, lights, halfs, &squarings);      // "normal" shading
+    if (rc == GV_OK)
+        rc = pcheck_common(points, point_offsets, n, total_points, max_points, desc, cameras, workspace, workspace_bytes);
     if (rc != GV_OK) return rc;
     if (squarings < 0) return GV_E_UNSUPPORTED;
-    if (bins_bytes < gv_render_bins_bytes(total)) return GV_E_BADARG;
-    if (!gv_aligned16(bins) || (output != GV_RENDER_OUT_U8 && ((uintptr_t)out & 3u))) return GV_E_ALIGN;
-    if (((uintptr_t)point_id & 3u) || ((uintptr_t)depth & 3u) || ((uintptr_t)normals & 3u)) return GV_E_ALIGN;
+    rc = check_draw_buffers(bins, bins_bytes, total, output, out, point_id, depth);
+    if (rc != GV_OK) return rc;
+    if ((uintptr_t)normals & 3u) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
-    const PWsLayout L = pws_layout(n, desc->num_views, desc->height, desc->width);
-    char* ws = static_cast<char*>(workspace);
-    const PArgs a = make_pargs(points, point_offsets, desc, cameras, rotations, reinterpret_cast<const MeshXf*>(ws + L.xf),
-                               reinterpret_cast<const float*>(ws + L.radius));
-    const int T = a.tiles_x * a.tiles_y;
-    const long long nimg = (long long)n * desc->num_views;
+    const TileWs L = pws_layout(n, desc->num_views, desc->height, desc->width);
+    const PointPrim a = make_prim(points, point_offsets, desc, cameras, rotations, workspace, L);
     const long long cap = bins_bytes / 4;
-    const int* tc = reinterpret_cast<const int*>(ws + L.tile_count);
-    const long long* ts = reinterpret_cast<const long long*>(ws + L.tile_start);
     int* b = static_cast<int*>(bins);
-    GV_HIP_CHECK(hipMemsetAsync(ws + L.tile_fill, 0, (size_t)nimg * T * 4, st));
-    hipLaunchKernelGGL(pbin_kernel<true>, pbin_grid(max_points, desc->num_views, n), dim3(RT), 0, st, a, nullptr, nullptr,
-                       ts, reinterpret_cast<int*>(ws + L.tile_fill), b, cap);
-    GV_LAUNCH_CHECK();
-    const bool two = (desc->flags & GV_RENDER_TWO_SIDED) != 0;
-    const PShade sh = {normals, lights, halfs, normals ? shading->specular : 0.0f, desc->ambient, squarings,
-                       (normals && (shading->flags & GV_RENDER_LAMBERT)) ? 1 : 0, two ? 1 : 0};
+    rc = launch_bin<true>(st, a, max_points, n, workspace, L, b, cap);
+    if (rc != GV_OK) return rc;
+    PShade sh;
+    static_cast<Reflect&>(sh) = make_reflect(desc, normals ? shading : nullptr, squarings, lights, halfs);
+    sh.normals = normals;
     const float3 color = make_float3(desc->color[0], desc->color[1], desc->color[2]);
     const float3 bg = make_float3(desc->background[0], desc->background[1], desc->background[2]);
-    const dim3 grid((unsigned)T, (unsigned)desc->num_views, (unsigned)n);
-    const int* cb = b;
-    if (output == GV_RENDER_OUT_F32_QUANTIZED)
-        hipLaunchKernelGGL(splat_kernel<GV_RENDER_OUT_F32_QUANTIZED>, grid, dim3(RT), 0, st, a, sh, tc, ts, cb, cap, color,
-                           bg, out, point_id, depth);
-    else if (output == GV_RENDER_OUT_F32)
-        hipLaunchKernelGGL(splat_kernel<GV_RENDER_OUT_F32>, grid, dim3(RT), 0, st, a, sh, tc, ts, cb, cap, color, bg, out,
-                           point_id, depth);
-    else
-        hipLaunchKernelGGL(splat_kernel<GV_RENDER_OUT_U8>, grid, dim3(RT), 0, st, a, sh, tc, ts, cb, cap, color, bg, out,
-                           point_id, depth);
+    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y), (unsigned)desc->num_views, (unsigned)n);
+    dispatch_output(output, [&](auto OUT) {
+        hipLaunchKernelGGL(splat_kernel<decltype(OUT)::value>, grid, dim3(RT), 0, st, static_cast<const PArgs&>(a), sh,
+                           ws_at<const int>(workspace, L.tile_count), ws_at<const long long>(workspace, L.tile_start),
+                           static_cast<const int*>(b), cap, color, bg, out, point_id, depth);
+    });
     GV_LAUNCH_CHECK();
     return GV_OK;
 }

@@ -614,6 +614,81 @@ def _unit_light(light):
     return lt / np.linalg.norm(lt)
 
 
+def _shading_desc(diffuse, specular, shininess):
+    sh = _lib.RenderShading()
+    sh.flags = _lib.GV_RENDER_LAMBERT if diffuse == "lambert" else 0
+    sh.shininess, sh.specular = int(shininess), float(specular)
+    return sh
+
+
+class _MeshKind:
+    """What ViewRenderer._draw_group calls to draw meshes: gv_render_* (csrc/render.hip).  args: the batch's group(a, b);
+    ws_args: the five arguments from the descriptor to the workspace size, which every call takes after args."""
+    batch, prefix = MeshBatch, "gv_render"
+
+    def __init__(self, r):
+        self.r, self.desc, self.samples = r, r.desc, r.samples
+
+    def workspace_bytes(self, args):
+        """(workspace bytes, what else counts against the cap: the normal table of a smooth render)."""
+        r = self.r
+        ws_bytes = r.lib.gv_render_workspace_bytes(args[4], r.V, r.H, r.W, args[6])
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_render_workspace_bytes")
+        nb = 0
+        if r.shading == "smooth":
+            nb = r.lib.gv_render_normals_bytes(r.V, r.desc.flags, args[5])
+            _lib.check(nb if nb < 0 else 0, "gv_render_normals_bytes")
+        return ws_bytes, nb
+
+    def prepare(self, args, a, b, ws_args, info):
+        r = self.r
+        if not r._ss:
+            return r.lib.gv_render_prepare(*args, *ws_args, *info, _model._st())
+        return r.lib.gv_render_prepare_ss(*args, *ws_args, *info, r.samples, _model._st())
+
+    def draw(self, batch, args, a, b, ws_args, out_args, nb):
+        r = self.r
+        if r.shading == "smooth":
+            normals = torch.empty(nb, dtype=torch.uint8, device=r.device)
+            rc = r.lib.gv_render_vertex_normals(*args, *ws_args, *batch.group_adjacency(a, b), normals.data_ptr(), nb,
+                                                _model._st())
+            _lib.check(rc, "gv_render_vertex_normals")
+            return r.lib.gv_render_draw_smooth(*args, *ws_args, *out_args, r.samples, r.shade_desc, r.lights.data_ptr(),
+                                               r.halfs.data_ptr(), normals.data_ptr(), nb, _model._st())
+        if not r._ss:
+            return r.lib.gv_render_draw(*args, *ws_args, *out_args, _model._st())
+        return r.lib.gv_render_draw_ss(*args, *ws_args, *out_args, r.samples, _model._st())
+
+
+class _PointKind:
+    """... and to splat point clouds: gv_points_* (csrc/render_points.hip), one sample per pixel.  radii: float32 [N] on
+    the host; normal: shading="normal"."""
+    batch, prefix = PointBatch, "gv_points"
+
+    def __init__(self, r, radii, normal):
+        self.r, self.desc, self.samples, self.radii, self.normal = r, r.point_desc, 1, radii, normal
+
+    def workspace_bytes(self, args):
+        r = self.r
+        ws_bytes = r.lib.gv_points_workspace_bytes(args[2], r.V, r.H, r.W)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_workspace_bytes")
+        return ws_bytes, 0
+
+    def prepare(self, args, a, b, ws_args, info):
+        rad = self.radii[a:b]                                            # host memory: self.radii outlives the call
+        return self.r.lib.gv_points_prepare(*args, rad.ctypes.data, *ws_args, *info, _model._st())
+
+    def draw(self, batch, args, a, b, ws_args, out_args, extra):
+        r, shade = self.r, (None, None, None, None)
+        if self.normal:
+            if r._point_vectors is None:
+                r._point_vectors = (torch.from_numpy(r.point_lights_host).to(r.device),
+                                    torch.from_numpy(r.point_halfs_host).to(r.device))
+            shade = (batch.group_normals(a), r.point_shade_desc, r._point_vectors[0].data_ptr(),
+                     r._point_vectors[1].data_ptr())
+        return r.lib.gv_points_draw(*args, *ws_args, *out_args, *shade, _model._st())
+
+
 class ViewRenderer:
     """V views of H x W per mesh (rendering contract: the module docstring).  elevation: degrees, one for all views or
     one per view; azimuths: degrees (default (i + 1) * 360 / V); fov: 0 (orthographic) or a perspective field of view
@@ -693,20 +768,14 @@ class ViewRenderer:
         self.lights_host, self.halfs_host = shading_vectors(elevation, self.azimuths,
                                                             "camera" if self.light_mode == "camera" else lt)
         if shading == "smooth":
-            sh = _lib.RenderShading()
-            sh.flags = _lib.GV_RENDER_LAMBERT if diffuse == "lambert" else 0
-            sh.shininess, sh.specular = shininess, self.specular
-            self.shade_desc = sh
+            self.shade_desc = _shading_desc(diffuse, specular, shininess)
             self.lights = torch.from_numpy(self.lights_host).to(self.device)
             self.halfs = torch.from_numpy(self.halfs_host).to(self.device)
         # the point splatter's reflection: its own descriptor copy (two_sided), shading descriptor, lights and halfs
         self.point = pr
         self.point_desc = _lib.RenderDesc.from_buffer_copy(d)
         self.point_desc.flags = flags | (_lib.GV_RENDER_TWO_SIDED if pr["two_sided"] else 0)
-        sh = _lib.RenderShading()
-        sh.flags = _lib.GV_RENDER_LAMBERT if pr["diffuse"] == "lambert" else 0
-        sh.shininess, sh.specular = int(pr["shininess"]), float(pr["specular"])
-        self.point_shade_desc = sh
+        self.point_shade_desc = _shading_desc(pr["diffuse"], pr["specular"], pr["shininess"])
         self.point_lights_host, self.point_halfs_host = shading_vectors(
             elevation, self.azimuths, "camera" if isinstance(pr["light"], str) else _unit_light(pr["light"]))
         self._point_vectors = None                       # (lights, halfs) on the device, on the first "normal" render
@@ -736,79 +805,56 @@ class ViewRenderer:
             return None
         return torch.from_numpy(check_rotations(rotations, n)).to(self.device)
 
-    def _batch(self, batch):
-        if not isinstance(batch, MeshBatch):
-            batch = MeshBatch(batch, self.device)
+    def _batch(self, cls, batch):
+        """batch as a MeshBatch / PointBatch (cls) on the renderer's device."""
+        if not isinstance(batch, cls):
+            batch = cls(batch, self.device)
         elif batch.device != self.device:
             raise ValueError("the batch lives on %s, the renderer on %s" % (batch.device, self.device))
         return batch
 
-    def _draw(self, batch, a, b, rot, output, out, face_id, depth, status):
-        """Render meshes [a, b) into out[a:b] (and the buffers); halves the group when its tile lists would pass the
-        workspace cap."""
-        lib, d = self.lib, self.desc
+    def _draw_group(self, kind, batch, a, b, rot, output, out, ids, depth, status):
+        """Render shapes [a, b) into out[a:b] (and the buffers); halves the group when its workspace or its tile lists
+        would pass the workspace cap.  kind: _MeshKind or _PointKind."""
+        lib, n = self.lib, b - a
         args = batch.group(a, b)
-        n, total_tris = args[4], args[6]
-        ws_bytes = lib.gv_render_workspace_bytes(n, self.V, self.H, self.W, total_tris)
-        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_render_workspace_bytes")
-        smooth = self.shading == "smooth"
-        nb = 0
-        if smooth:                                                       # the normal table counts as workspace
-            nb = lib.gv_render_normals_bytes(self.V, d.flags, args[5])
-            _lib.check(nb if nb < 0 else 0, "gv_render_normals_bytes")
-        if ws_bytes + nb > self.max_workspace_bytes and n > 1:
+
+        def halves():
             h = (a + b) // 2
-            self._draw(batch, a, h, rot, output, out, face_id, depth, status)
-            self._draw(batch, h, b, rot, output, out, face_id, depth, status)
-            return
+            self._draw_group(kind, batch, a, h, rot, output, out, ids, depth, status)
+            self._draw_group(kind, batch, h, b, rot, output, out, ids, depth, status)
+        ws_bytes, extra = kind.workspace_bytes(args)
+        if ws_bytes + extra > self.max_workspace_bytes and n > 1:
+            return halves()
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
         info = torch.empty(1 + (n + 1) // 2, dtype=torch.int64, device=self.device)     # pair total, then status
         st_dev = info[1:].view(torch.int32)
         rp = None if rot is None else rot.data_ptr() + a * 36
-        S = self.samples
-        if not self._ss:
-            rc = lib.gv_render_prepare(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, info.data_ptr(),
-                                       st_dev.data_ptr(), _model._st())
-        else:
-            rc = lib.gv_render_prepare_ss(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
-                                          info.data_ptr(), st_dev.data_ptr(), S, _model._st())
-        _lib.check(rc, "gv_render_prepare")
+        ws_args = (kind.desc, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes)
+        rc = kind.prepare(args, a, b, ws_args, (info.data_ptr(), st_dev.data_ptr()))
+        _lib.check(rc, kind.prefix + "_prepare")
         host = info.cpu().numpy()                                        # the one host read of a render
         total = int(host[0])
         status[a:b] = host[1:].view(np.int32)[:n]
         bins_bytes = lib.gv_render_bins_bytes(total)
         _lib.check(bins_bytes if bins_bytes < 0 else 0, "gv_render_bins_bytes")
-        if ws_bytes + nb + bins_bytes > self.max_workspace_bytes and n > 1:
+        if ws_bytes + extra + bins_bytes > self.max_workspace_bytes and n > 1:
             del ws, info
-            h = (a + b) // 2
-            self._draw(batch, a, h, rot, output, out, face_id, depth, status)
-            self._draw(batch, h, b, rot, output, out, face_id, depth, status)
-            return
+            return halves()
         bins = torch.empty(bins_bytes, dtype=torch.uint8, device=self.device)
         img = self.V * self.H * self.W
         esz = 1 if output == _lib.GV_RENDER_OUT_U8 else 4
-        tail = (d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, bins.data_ptr(), bins_bytes, total, output,
-                out.data_ptr() + a * img * 3 * esz,
-                None if face_id is None else face_id.data_ptr() + a * img * S * S * 4,        # the sample grid
-                None if depth is None else depth.data_ptr() + a * img * S * S * 4)
-        if smooth:
-            normals = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            rc = lib.gv_render_vertex_normals(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
-                                              *batch.group_adjacency(a, b), normals.data_ptr(), nb, _model._st())
-            _lib.check(rc, "gv_render_vertex_normals")
-            rc = lib.gv_render_draw_smooth(*args, *tail, S, self.shade_desc, self.lights.data_ptr(),
-                                           self.halfs.data_ptr(), normals.data_ptr(), nb, _model._st())
-        elif not self._ss:
-            rc = lib.gv_render_draw(*args, *tail, _model._st())
-        else:
-            rc = lib.gv_render_draw_ss(*args, *tail, S, _model._st())
-        _lib.check(rc, "gv_render_draw")
+        grid = img * kind.samples ** 2 * 4                               # ids and depth: one entry per sample
+        out_args = (bins.data_ptr(), bins_bytes, total, output, out.data_ptr() + a * img * 3 * esz,
+                    None if ids is None else ids.data_ptr() + a * grid,
+                    None if depth is None else depth.data_ptr() + a * grid)
+        _lib.check(kind.draw(batch, args, a, b, ws_args, out_args, extra), kind.prefix + "_draw")
 
-    def _render(self, batch, rotations, out, output, return_buffers, to_batch=None, draw=None):
-        """The body of every render call: to_batch / draw are the mesh pair (_batch, _draw) or the point pair."""
+    def _render(self, batch, rotations, out, output, return_buffers, kind=None):
+        """The body of every render call; kind: a _PointKind for render_points (default: meshes)."""
+        kind = kind or _MeshKind(self)
         with torch.cuda.device(self.device):
-            batch = (to_batch or self._batch)(batch)
-            draw = draw or self._draw
+            batch = self._batch(kind.batch, batch)
             n = batch.n
             rot = self._rotations(rotations, n)
             shape = (n, self.V, self.H, self.W, 3)
@@ -824,7 +870,7 @@ class ViewRenderer:
                 face_id = torch.empty(grid, dtype=torch.int32, device=self.device)
                 depth = torch.empty(grid, dtype=torch.int32, device=self.device)        # uint32 bits
             status = np.zeros(n, np.int32)
-            draw(batch, 0, n, rot, output, out, face_id, depth, status)
+            self._draw_group(kind, batch, 0, n, rot, output, out, face_id, depth, status)
             self.status = status
             if return_buffers:
                 return out, face_id, depth
@@ -851,71 +897,16 @@ class ViewRenderer:
             raise ValueError("radius must be finite and positive in fp32")
         return r
 
-    def _draw_points(self, batch, a, b, rot, output, out, point_id, depth, status, radii, normal):
-        """Render clouds [a, b) into out[a:b] (and the buffers); halves the group when its tile lists would pass the
-        workspace cap.  The steps of _draw."""
-        lib, d = self.lib, self.point_desc
-        args = batch.group(a, b)
-        n = args[2]
-
-        def halves():
-            h = (a + b) // 2
-            self._draw_points(batch, a, h, rot, output, out, point_id, depth, status, radii, normal)
-            self._draw_points(batch, h, b, rot, output, out, point_id, depth, status, radii, normal)
-        ws_bytes = lib.gv_points_workspace_bytes(n, self.V, self.H, self.W)
-        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_workspace_bytes")
-        if ws_bytes > self.max_workspace_bytes and n > 1:
-            return halves()
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        info = torch.empty(1 + (n + 1) // 2, dtype=torch.int64, device=self.device)     # pair total, then status
-        st_dev = info[1:].view(torch.int32)
-        rp = None if rot is None else rot.data_ptr() + a * 36
-        rad = radii[a:b]                                                 # host memory, alive past the read below
-        rc = lib.gv_points_prepare(*args, rad.ctypes.data, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes,
-                                   info.data_ptr(), st_dev.data_ptr(), _model._st())
-        _lib.check(rc, "gv_points_prepare")
-        host = info.cpu().numpy()                                        # the one host read of a render
-        total = int(host[0])
-        status[a:b] = host[1:].view(np.int32)[:n]
-        bins_bytes = lib.gv_render_bins_bytes(total)
-        _lib.check(bins_bytes if bins_bytes < 0 else 0, "gv_render_bins_bytes")
-        if ws_bytes + bins_bytes > self.max_workspace_bytes and n > 1:
-            del ws, info
-            return halves()
-        bins = torch.empty(bins_bytes, dtype=torch.uint8, device=self.device)
-        img = self.V * self.H * self.W
-        esz = 1 if output == _lib.GV_RENDER_OUT_U8 else 4
-        shade = (None, None, None, None)
-        if normal:
-            if self._point_vectors is None:
-                self._point_vectors = (torch.from_numpy(self.point_lights_host).to(self.device),
-                                       torch.from_numpy(self.point_halfs_host).to(self.device))
-            shade = (batch.group_normals(a), self.point_shade_desc, self._point_vectors[0].data_ptr(),
-                     self._point_vectors[1].data_ptr())
-        rc = lib.gv_points_draw(*args, d, self.cameras.data_ptr(), rp, ws.data_ptr(), ws_bytes, bins.data_ptr(),
-                                bins_bytes, total, output, out.data_ptr() + a * img * 3 * esz,
-                                None if point_id is None else point_id.data_ptr() + a * img * 4,
-                                None if depth is None else depth.data_ptr() + a * img * 4, *shade, _model._st())
-        _lib.check(rc, "gv_points_draw")
-
     def _render_points(self, batch, rotations, out, output, return_buffers, radius, shading):
         if self.samples != 1:
             raise ValueError("render_points draws one sample per pixel: the renderer has samples=%d" % self.samples)
         if shading not in ("depth", "normal"):
             raise ValueError("shading must be 'depth' or 'normal'")
-        if isinstance(batch, PointBatch):
-            if batch.device != self.device:
-                raise ValueError("the batch lives on %s, the renderer on %s" % (batch.device, self.device))
-        else:
-            with torch.cuda.device(self.device):
-                batch = PointBatch(batch, self.device)
+        batch = self._batch(PointBatch, batch)
         if shading == "normal" and batch.normals is None:
             raise ValueError("shading='normal' needs a batch with normals")
-        radii = self._point_radii(batch, radius)
-
-        def draw(*a):
-            self._draw_points(*a, radii, shading == "normal")
-        return self._render(batch, rotations, out, output, return_buffers, to_batch=lambda b: b, draw=draw)
+        kind = _PointKind(self, self._point_radii(batch, radius), shading == "normal")
+        return self._render(batch, rotations, out, output, return_buffers, kind)
 
     def render_points(self, batch, rotations=None, out=None, quantize=True, return_buffers=False, radius="auto",
                       shading="depth"):
