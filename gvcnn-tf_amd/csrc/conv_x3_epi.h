@@ -85,6 +85,39 @@ __device__ __forceinline__ void p3_store4(char* base, size_t pix, int ld, int c,
     }
 }
 
+// Pixel accessor of a P3 tensor (the interface of gvlp_elem::Px, lp_elem.h; base = the tensor's group-aligned base, ld and ch
+// in channels): NN = 4 through p3_load4 / p3_store4, NN = 8 (ch a multiple of 8) as three 16-byte plane accesses.
+template <int NN>
+struct P3Px {
+    using elem = char;
+    static constexpr int N = NN;
+    template <typename P>
+    static __device__ __forceinline__ P at(P base, size_t pix, int ld) { return base + pix * (size_t)ld * 6; }
+    static __device__ __forceinline__ void load(const char* base, size_t pix, int ld, int ch, float (&f)[NN]) {
+        if constexpr (NN == 4) {
+            const f32x4 v = p3_load4(base, pix, ld, ch);
+            f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
+        } else {
+            const char* src = base + p3_byte_off(pix, ld, ch);
+            p3_u32x4 pl[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) pl[p] = *reinterpret_cast<const p3_u32x4*>(src + p * 32);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int sh = (e & 1) * 16;
+                const float a0 = __builtin_bit_cast(float, ((pl[0][e >> 1] >> sh) & 0xffffu) << 16);
+                const float a1 = __builtin_bit_cast(float, ((pl[1][e >> 1] >> sh) & 0xffffu) << 16);
+                const float a2 = __builtin_bit_cast(float, ((pl[2][e >> 1] >> sh) & 0xffffu) << 16);
+                f[e] = (a2 + a1) + a0;                           // small terms first, as p3_load4
+            }
+        }
+    }
+    static __device__ __forceinline__ void store(char* base, size_t pix, int ld, int ch, const float (&f)[NN]) {
+        if constexpr (NN == 4) p3_store4(base, pix, ld, ch, f32x4{f[0], f[1], f[2], f[3]});
+        else p3_store8(base, pix, ld, ch, f);
+    }
+};
+
 template <int TN> struct X3EpiGeom {
     static constexpr int CW = (TN % 2 == 0) ? 64 : 32;     // columns per staging block
     static constexpr int JB = CW / 32;                     // MFMA tiles per block

@@ -1,4 +1,5 @@
-// grouping.hip — the grouping module of nets/model.py on device (fp32 path).
+// grouping.hip — the grouping module of nets/model.py on device (the scorer partial and the view pool + fusion for every
+// storage type; the rest is fp32).
 //
 //   scorer            model.py:144-147   GAP -> Dense(1) per view -> batch mean -> sigmoid(log|.|)
 //   group assignment  model.py:16-41     bin = (int)(score * 10f) ; weight = 1 + count
@@ -12,72 +13,89 @@
 // element is read exactly once (the algorithmic minimum; the TF graph makes >= 3 passes).
 #include <math.h>
 
-#include <type_traits>
-
 #include "gv_common.h"
-#include "lowp.h"
+#include "lp_elem.h"
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+using namespace gvlp_elem;
 
 __device__ __forceinline__ int view_of_image(int b, int num_views, int num_shapes, int order) {
     return order == GV_ORDER_SHAPE_MAJOR ? b % num_views : b / num_shapes;
 }
 
-// r_img[b] = (1/hw) * sum_{p,c} raw[b,p,c] * k[v(b)][c] + bias[v(b)]; one workgroup per image,
-// fixed reduction tree => bitwise reproducible.
-__global__ __launch_bounds__(256) void view_score_partial_f32(
-    const float* __restrict__ raw, int hw, int cr, int raw_ld, const float* __restrict__ kernel,
-    const float* __restrict__ bias, int num_views, int num_shapes, int order,
-    float* __restrict__ r_img) {
+// x[0] * k[0] + x[1] * k[1] + ... of one N-element chunk, left to right; k (16-byte aligned) is read in quads
+template <int N>
+__device__ __forceinline__ float chunk_dot(const float (&x)[8], const float* __restrict__ k) {
+    float t = 0.f;
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        const f32x4 kq = *reinterpret_cast<const f32x4*>(k + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t = q + e == 0 ? x[0] * kq[0] : t + x[4 * q + e] * kq[e];
+    }
+    return t;
+}
+
+// nets/model.py:144-145: r_img[b] = (1/hw) * sum_{p,c} raw[b,p,c] * k[v(b)][c] + bias[v(b)]; one workgroup per image,
+// fixed reduction tree => bitwise reproducible.  E the element type of the raw map in HBM, T the type it stands for.
+template <typename E, typename T>
+__global__ __launch_bounds__(256) void view_score_partial(const E* __restrict__ raw, int hw, int cr, int raw_ld,
+                                                          const float* __restrict__ kernel, const float* __restrict__ bias,
+                                                          int num_views, int num_shapes, int order,
+                                                          float* __restrict__ r_img) {
+    constexpr int N = 16 / sizeof(E);               // elements of a 16-byte chunk
     const int b = blockIdx.x;
     const int v = view_of_image(b, num_views, num_shapes, order);
     const float* kv = kernel + (size_t)v * cr;
-    const float* xb = raw + (size_t)b * hw * raw_ld;
+    const E* xb = raw + (size_t)b * hw * raw_ld;
     float s = 0.f;
-    if ((cr & 3) == 0 && (raw_ld & 3) == 0 && ((((uintptr_t)raw) | ((uintptr_t)kernel)) & 15) == 0) {
-        const int cg = cr >> 2;
+    if (cr % N == 0 && raw_ld % N == 0 && ((((uintptr_t)raw) | ((uintptr_t)kernel)) & 15) == 0) {
+        const int cg = cr / N;
         const int total = hw * cg;
-        // four chunks in flight per thread, each into its own partial sum (lowp.hip: view_score_partial_lp); fixed order
+        // four chunks in flight per thread, each into its own partial sum (one load at a time left this 85 MB read
+        // latency-bound: 69 us for the raw tap of 384 views, 1.2 TB/s); the order of the additions is fixed, so every rank
+        // of a sharded job still computes the same bits
         float sp[4] = {0.f, 0.f, 0.f, 0.f};
         int i = threadIdx.x;
         for (; i + 3 * 256 < total; i += 4 * 256) {
-            f32x4 q[4];
+            u32x4 q[4];
             int gq[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int ii = i + u * 256;
                 const int p = ii / cg;
                 gq[u] = ii - p * cg;
-                q[u] = *reinterpret_cast<const f32x4*>(xb + (size_t)p * raw_ld + 4 * gq[u]);
+                q[u] = *reinterpret_cast<const u32x4*>(xb + (size_t)p * raw_ld + N * gq[u]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const f32x4 k = *reinterpret_cast<const f32x4*>(kv + 4 * gq[u]);
-                sp[u] += q[u][0] * k[0] + q[u][1] * k[1] + q[u][2] * k[2] + q[u][3] * k[3];
+                float x[8];
+                unpackq<E, T>(q[u], x);
+                sp[u] += chunk_dot<N>(x, kv + N * gq[u]);
             }
         }
         for (; i < total; i += 256) {
             const int p = i / cg, g = i - p * cg;
-            const f32x4 x = *reinterpret_cast<const f32x4*>(xb + (size_t)p * raw_ld + 4 * g);
-            const f32x4 k = *reinterpret_cast<const f32x4*>(kv + 4 * g);
-            sp[0] += x[0] * k[0] + x[1] * k[1] + x[2] * k[2] + x[3] * k[3];
+            float x[8];
+            unpackq<E, T>(*reinterpret_cast<const u32x4*>(xb + (size_t)p * raw_ld + N * g), x);
+            if constexpr (sizeof(E) == 4) {
+                sp[0] += chunk_dot<N>(x, kv + N * g);
+            } else {                                // (16-bit storage adds a tail chunk's products to sp[0] one by one)
+#pragma unroll
+                for (int e = 0; e < N; ++e) sp[0] += x[e] * kv[N * g + e];
+            }
         }
         s = (sp[0] + sp[1]) + (sp[2] + sp[3]);
     } else {
         const int total = hw * cr;
         for (int i = threadIdx.x; i < total; i += 256) {
             const int p = i / cr, c = i - p * cr;
-            s += xb[(size_t)p * raw_ld + c] * kv[c];
+            s += up<T>(xb[(size_t)p * raw_ld + c]) * kv[c];
         }
     }
     __shared__ float part[4];
-    s = wave_sum(s);
+    s = gv_wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) r_img[b] = (part[0] + part[1] + part[2] + part[3]) / (float)hw + bias[v];
@@ -145,13 +163,16 @@ __global__ void group_weight_kernel(const int* __restrict__ scheme, int G, int V
 // header's __fmul_rn / __fadd_rn are plain operators that hipcc contracts into one FMA by default, wherever they are called
 // from (render.hip), so the kernel body turns contraction off and spells the fusion with plain operators: the product is
 // rounded before it is added, as tf.multiply + tf.add_n round it.
-template <int VEC>
-__global__ __launch_bounds__(256) void view_pool_fuse_f32(
-    const float* __restrict__ F, int V, int N, int64_t E, int64_t view_stride, int64_t shape_stride,
-    const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode, float fill,
-    float* __restrict__ D, float* __restrict__ S, int64_t scheme_stride, int64_t weight_stride) {
+// 16-bit storage: one rounding of D and of S into the storage type, each from the unrounded fp32 value.
+template <class A>
+__global__ __launch_bounds__(256) void view_pool_fuse(const typename A::elem* __restrict__ F, int V, int N, int64_t E,
+                                                      int64_t view_stride, int64_t shape_stride,
+                                                      const int* __restrict__ scheme, int G,
+                                                      const float* __restrict__ weight, int mode, float fill,
+                                                      typename A::elem* __restrict__ D, typename A::elem* __restrict__ S,
+                                                      int64_t scheme_stride, int64_t weight_stride) {
 #pragma clang fp contract(off)
-    using Vt = typename std::conditional<VEC == 4, f32x4, float>::type;
+    constexpr int VEC = A::N;
     __shared__ unsigned long long s_mask[64];
     __shared__ float s_w[64];
     __shared__ float s_wsum;
@@ -177,61 +198,44 @@ __global__ __launch_bounds__(256) void view_pool_fuse_f32(
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < eg;
          idx += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e = idx * VEC;
-        const float* base = F + (size_t)n * shape_stride + e;
-        Vt acc;
-        if constexpr (VEC == 4) acc = Vt{0.f, 0.f, 0.f, 0.f}; else acc = 0.f;
+        const typename A::elem* base = F + (size_t)n * shape_stride + e;
+        float acc[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
         for (int g = 0; g < G; ++g) {
             unsigned long long m = s_mask[g];
-            Vt d;
+            float d[VEC];
             if (m == 0) {
-                if constexpr (VEC == 4) d = Vt{fill, fill, fill, fill}; else d = fill;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) d[k] = fill;
             } else {
                 const int cnt = __popcll(m);
                 int v = __ffsll((long long)m) - 1;
                 m &= m - 1;
-                d = *reinterpret_cast<const Vt*>(base + (size_t)v * view_stride);
+                A::load(base + (size_t)v * view_stride, 0, 0, 0, d);
                 while (m) {
                     v = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    const Vt x = *reinterpret_cast<const Vt*>(base + (size_t)v * view_stride);
-                    if (mode == GV_VIEWPOOL_MAX) {
-                        if constexpr (VEC == 4) {
+                    float x[VEC];
+                    A::load(base + (size_t)v * view_stride, 0, 0, 0, x);
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) d[k] = fmaxf(d[k], x[k]);
-                        } else {
-                            d = fmaxf(d, x);
-                        }
-                    } else {
-                        d += x;
-                    }
+                    for (int k = 0; k < VEC; ++k) d[k] = mode == GV_VIEWPOOL_MAX ? fmaxf(d[k], x[k]) : d[k] + x[k];
                 }
                 if (mode == GV_VIEWPOOL_MEAN) {
                     const float c = (float)cnt;
-                    if constexpr (VEC == 4) {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) d[k] = d[k] / c;
-                    } else {
-                        d = d / c;
-                    }
+                    for (int k = 0; k < VEC; ++k) d[k] = d[k] / c;
                 }
             }
-            if (D) *reinterpret_cast<Vt*>(D + ((size_t)g * N + n) * E + e) = d;
+            if (D) A::store(D + ((size_t)g * N + n) * E + e, 0, 0, 0, d);
             const float w = s_w[g];
-            if constexpr (VEC == 4) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = acc[k] + w * d[k];   // multiply, add_n: two roundings (contraction is off)
-            } else {
-                acc = acc + w * d;
-            }
+            for (int k = 0; k < VEC; ++k) acc[k] = acc[k] + w * d[k];   // multiply, add_n: two roundings (contraction is off)
         }
         if (S) {
-            if constexpr (VEC == 4) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = wsum != 0.f ? __fdiv_rn(acc[k], wsum) : 0.f;   // tf.div
-            } else {
-                acc = wsum != 0.f ? __fdiv_rn(acc, wsum) : 0.f;
-            }
-            *reinterpret_cast<Vt*>(S + (size_t)n * E + e) = acc;
+            for (int k = 0; k < VEC; ++k) acc[k] = wsum != 0.f ? __fdiv_rn(acc[k], wsum) : 0.f;   // tf.div
+            A::store(S + (size_t)n * E + e, 0, 0, 0, acc);
         }
     }
 }
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(256) void dense_f32(const float* __restrict__ x, in
     float s = 0.f;
     for (int i = threadIdx.x; i < f; i += 256) s += xr[i] * kernel[(size_t)i * c + cc];
     __shared__ float part[4];
-    s = wave_sum(s);
+    s = gv_wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) y[(size_t)n * c + cc] = part[0] + part[1] + part[2] + part[3] + bias[cc];
@@ -263,14 +267,9 @@ extern "C" int gv_view_score_partial(const void* raw, int32_t nb, int32_t hw, in
         num_views <= 0 || nb % num_views != 0)
         return GV_E_BADARG;
     if (order != GV_ORDER_SHAPE_MAJOR && order != GV_ORDER_VIEW_MAJOR) return GV_E_BADARG;
-    if (dtype != GV_F32)
-        return gvlp::view_score_partial(dtype, raw, nb, hw, cr, raw_ld, kernel, bias, num_views, order, r_img,
-                                        (hipStream_t)stream);
-    hipLaunchKernelGGL(view_score_partial_f32, dim3(nb), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)raw, hw, cr, raw_ld, kernel, bias, num_views, nb / num_views,
-                       order, r_img);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    GV_ST_DISPATCH(dtype, return (gv_launch<view_score_partial<E, T>>(dim3(nb), dim3(256), 0, (hipStream_t)stream, (const E*)raw,
+                                                                      hw, cr, raw_ld, kernel, bias, num_views, nb / num_views,
+                                                                      order, r_img)));
 }
 
 extern "C" int gv_view_score_finalize(const float* r_img, int32_t num_shapes, int32_t num_views,
@@ -314,28 +313,21 @@ static int pool_fuse_launch(const void* F, int32_t num_views, int32_t num_shapes
         return GV_E_BADARG;
     if (mode != GV_VIEWPOOL_MAX && mode != GV_VIEWPOOL_MEAN) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
-    if (dtype != GV_F32)
-        return gvlp::view_pool_fuse(dtype, F, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups,
-                                    weight, mode, empty_fill, D, S, (hipStream_t)stream, scheme_stride, weight_stride);
-    const bool vec = (E % 4 == 0) && (view_stride % 4 == 0) && (shape_stride % 4 == 0) &&
+    const int quad = dtype == GV_F32 ? 4 : 8;
+    const bool vec = (E % quad == 0) && (view_stride % quad == 0) && (shape_stride % quad == 0) &&
                      gv_aligned16(F) && (!D || gv_aligned16(D)) && (!S || gv_aligned16(S));
-    const int64_t per_shape = vec ? E / 4 : E;
+    const int64_t per_shape = vec ? E / quad : E;
     int64_t bx = (per_shape + 255) / 256;
     if (bx > 1024) bx = 1024;
     const dim3 grid((unsigned)bx, (unsigned)num_shapes);
-    hipStream_t st = (hipStream_t)stream;
-    if (vec)
-        hipLaunchKernelGGL(view_pool_fuse_f32<4>, grid, dim3(256), 0, st,
-                           (const float*)F, num_views, num_shapes, E, view_stride, shape_stride,
-                           scheme, num_groups, weight, mode, empty_fill, (float*)D, (float*)S, scheme_stride,
-                           weight_stride);
-    else
-        hipLaunchKernelGGL(view_pool_fuse_f32<1>, grid, dim3(256), 0, st,
-                           (const float*)F, num_views, num_shapes, E, view_stride, shape_stride,
-                           scheme, num_groups, weight, mode, empty_fill, (float*)D, (float*)S, scheme_stride,
-                           weight_stride);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    const int64_t ne = E;                                        // (GV_ST_DISPATCH names the element type E)
+#define GV_FUSE(NN)                                                                                                       \
+    return (gv_launch<view_pool_fuse<Px<E, T, NN>>>(grid, dim3(256), 0, (hipStream_t)stream, (const E*)F, num_views,      \
+                                                     num_shapes, ne, view_stride, shape_stride, scheme, num_groups, weight, \
+                                                     mode, empty_fill, (E*)D, (E*)S, scheme_stride, weight_stride))
+    if (vec) GV_ST_DISPATCH(dtype, GV_FUSE(16 / sizeof(E)));
+    GV_ST_DISPATCH(dtype, GV_FUSE(1));
+#undef GV_FUSE
 }
 
 extern "C" int gv_view_pool_fuse_fwd(const void* F, int32_t num_views, int32_t num_shapes, int64_t E,

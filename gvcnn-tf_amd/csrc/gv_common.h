@@ -67,6 +67,14 @@ int gv_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... 
         if ((dtype) == GV_F16) { using T = _Float16; CALL; }  \
         return GV_E_UNSUPPORTED;                          \
     } while (0)
+// every storage type: E the element type in HBM, T the type it stands for
+#define GV_ST_DISPATCH(dtype, CALL)                                                   \
+    do {                                                                              \
+        if ((dtype) == GV_F32) { using E = float; using T = float; CALL; }            \
+        if ((dtype) == GV_BF16) { using E = unsigned short; using T = __bf16; CALL; } \
+        if ((dtype) == GV_F16) { using E = unsigned short; using T = _Float16; CALL; } \
+        return GV_E_UNSUPPORTED;                                                      \
+    } while (0)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -182,4 +190,11 @@ __device__ __forceinline__ int gv_xcd_remap(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// sum over the 64 lanes of a wave, valid in lane 0: a fixed tree, so the same bits every run
+__device__ __forceinline__ float gv_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
 }

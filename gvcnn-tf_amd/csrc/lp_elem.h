@@ -1,4 +1,4 @@
-// Element helpers of the storage-typed kernels (lowp.hip, train_lp.hip): a 16-bit element travels as an
+// Element helpers of the storage-typed kernels (pool.hip, grouping.hip, train_lp.hip): a 16-bit element travels as an
 // unsigned short, arithmetic is fp32, T = __bf16 or _Float16 selects the encoding; fp32 storage is E = T = float.
 #pragma once
 #include "gv_common.h"
@@ -89,5 +89,47 @@ __device__ __forceinline__ void store_v(float* p, const float (&f)[8]) {
         *p = f[0];
     }
 }
+
+// Pixel accessor of the forward kernels (pool.hip, grouping.hip): the NN channels from channel ch of pixel pix of a tensor
+// with pixel stride ld elements, as fp32 registers.  NN = 1 is the scalar access; a vector access (4 or 8 fp32, 8 of a
+// 16-bit type) moves whole 16-byte quads, which the host checks for.  at() advances the base by whole pixels.  The
+// three-plane accessor P3Px is in conv_x3_epi.h.
+template <typename E, typename T, int NN>
+struct Px {
+    using elem = E;
+    static constexpr int N = NN;
+    static constexpr int PER = 16 / sizeof(E);                   // elements of a quad
+    // the tensor from pixel pix on: a kernel that walks a row takes the row's address once
+    template <typename P>
+    static __device__ __forceinline__ P at(P base, size_t pix, int ld) { return base + pix * (size_t)ld; }
+    static __device__ __forceinline__ void load(const E* base, size_t pix, int ld, int ch, float (&f)[NN]) {
+        const E* p = base + pix * (size_t)ld + ch;
+        if constexpr (NN == 1) {
+            f[0] = up<T>(*p);
+        } else {
+#pragma unroll
+            for (int q = 0; q < NN / PER; ++q) {
+                float w[8];
+                unpackq<E, T>(*reinterpret_cast<const u32x4*>(p + q * PER), w);
+#pragma unroll
+                for (int e = 0; e < PER; ++e) f[q * PER + e] = w[e];
+            }
+        }
+    }
+    static __device__ __forceinline__ void store(E* base, size_t pix, int ld, int ch, const float (&f)[NN]) {
+        E* p = base + pix * (size_t)ld + ch;
+        if constexpr (NN == 1) {
+            *p = down<T>(f[0]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < NN / PER; ++q) {
+                float w[8];
+#pragma unroll
+                for (int e = 0; e < PER; ++e) w[e] = f[q * PER + e];
+                *reinterpret_cast<u32x4*>(p + q * PER) = packq<E, T>(w);
+            }
+        }
+    }
+};
 
 }  // namespace gvlp_elem

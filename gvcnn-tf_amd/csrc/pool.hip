@@ -1,35 +1,31 @@
-// pool.hip — HBM-bound NHWC window ops of the per-view backbone (fp32 path).
+// pool.hip — HBM-bound NHWC window ops of the per-view backbone, one kernel template per op for every storage:
 //   * max / average pooling (slim.max_pool2d / slim.avg_pool2d: nets/inception_v3.py:112,127,152,
 //     219,355; nets/resnet_v2.py:181; `subsample`, nets/resnet_utils.py:64-67)
 //   * per-channel scale/shift(+ReLU)  (stand-alone slim.batch_norm, nets/resnet_v2.py:75)
 //   * global average pool              (tf.keras GlobalAveragePooling2D, nets/model.py:144,163)
-// One thread per (output pixel, 4-channel group): 16-byte loads/stores, consecutive lanes on
-// consecutive channels, so every wave instruction moves whole 128-byte lines.  Input and output
-// carry an explicit pixel stride so a pool can read/write a channel slice of a concat buffer
-// (Mixed_6a / Mixed_7a max-pool branches write straight into the block's output).
+// A kernel reads and writes pixels through accessors (Px: fp32 and 16-bit storage, lp_elem.h; P3Px: the three-plane layout,
+// conv_x3_epi.h), its input's and its output's chosen independently.  One thread per (output pixel, N-channel group) with
+// 16-byte accesses (N = 4 fp32 or 8 16-bit channels), consecutive lanes on consecutive channels, so every wave instruction
+// moves whole 128-byte lines; N = 1 where the operands do not allow it.  Arithmetic is fp32 and an output is rounded to
+// its storage type exactly once (max pooling is rounding-free).  Input and output carry an explicit pixel stride so a
+// pool can read/write a channel slice of a concat buffer (Mixed_6a / Mixed_7a max-pool branches write straight into the
+// block's output).
 #include <math.h>
 
 #include "gv_common.h"
 #include "conv_x3_epi.h"
-#include "lowp.h"
+#include "lp_elem.h"
 
 namespace {
 
-template <int VEC>
-struct VecT;
-template <>
-struct VecT<4> { using type = f32x4; };
-template <>
-struct VecT<1> { using type = float; };
+using namespace gvlp_elem;
 
-// XP3 / YP3 (VEC = 4 only): input / output in the three-plane layout of conv_x3_epi.h (ld in channels, multiples of 16)
-template <int VEC, bool XP3 = false, bool YP3 = false>
-__global__ __launch_bounds__(256) void pool2d_f32(const float* __restrict__ x, float* __restrict__ y,
-                                                  int nb, int ih, int iw, int c, int x_ld, int kh,
-                                                  int kw, int stride, int pad_t, int pad_l, int oh,
-                                                  int ow, int y_ld, int mode) {
-    using V = typename VecT<VEC>::type;
-    const int cg = c / VEC;
+template <class XA, class YA>
+__global__ __launch_bounds__(256) void pool2d(const typename XA::elem* __restrict__ x, typename YA::elem* __restrict__ y,
+                                              int nb, int ih, int iw, int c, int x_ld, int kh, int kw, int stride,
+                                              int pad_t, int pad_l, int oh, int ow, int y_ld, int mode) {
+    constexpr int N = XA::N;
+    const int cg = c / N;
     const int64_t total = (int64_t)nb * oh * ow * cg;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
@@ -39,9 +35,9 @@ __global__ __launch_bounds__(256) void pool2d_f32(const float* __restrict__ x, f
         const int64_t t = pix / ow;
         const int oy = (int)(t % oh);
         const int n = (int)(t / oh);
-        V acc;
-        if constexpr (VEC == 4) acc = mode == GV_POOL_MAX ? V{-INFINITY, -INFINITY, -INFINITY, -INFINITY} : V{0.f, 0.f, 0.f, 0.f};
-        else acc = mode == GV_POOL_MAX ? -INFINITY : 0.f;
+        float acc[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) acc[e] = mode == GV_POOL_MAX ? -INFINITY : 0.f;
         int cnt = 0;
         for (int r = 0; r < kh; ++r) {
             const int iy = oy * stride + r - pad_t;
@@ -49,48 +45,38 @@ __global__ __launch_bounds__(256) void pool2d_f32(const float* __restrict__ x, f
             for (int s = 0; s < kw; ++s) {
                 const int ix = ox * stride + s - pad_l;
                 if ((unsigned)ix >= (unsigned)iw) continue;
-                V v;
-                if constexpr (XP3) v = p3_load4(reinterpret_cast<const char*>(x), (size_t)(n * ih + iy) * iw + ix, x_ld, g * 4);
-                else v = *reinterpret_cast<const V*>(x + ((size_t)(n * ih + iy) * iw + ix) * x_ld + g * VEC);
-                if (mode == GV_POOL_MAX) {
-                    if constexpr (VEC == 4) {
+                float v[N];
+                XA::load(x, (size_t)(n * ih + iy) * iw + ix, x_ld, g * N, v);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], v[e]);
-                    } else {
-                        acc = fmaxf(acc, v);
-                    }
-                } else {
-                    acc += v;
-                }
+                for (int e = 0; e < N; ++e) acc[e] = mode == GV_POOL_MAX ? fmaxf(acc[e], v[e]) : acc[e] + v[e];
                 ++cnt;
             }
         }
         if (mode != GV_POOL_MAX) {
-            const float inv = (float)cnt;     // divisor = number of valid taps (TF SAME semantics)
-            const bool relu = mode == GV_POOL_AVG_RELU;
-            if constexpr (VEC == 4) {
+            const float inv = (float)cnt;             // divisor = number of valid taps (TF SAME semantics)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[e] = acc[e] / inv;
-                    if (relu) acc[e] = fmaxf(acc[e], 0.f);
-                }
-            } else {
-                acc = acc / inv;
-                if (relu) acc = fmaxf(acc, 0.f);
+            for (int e = 0; e < N; ++e) {
+                acc[e] = acc[e] / inv;
+                if (mode == GV_POOL_AVG_RELU) acc[e] = fmaxf(acc[e], 0.f);
             }
         }
-        if constexpr (YP3) p3_store4(reinterpret_cast<char*>(y), (size_t)pix, y_ld, g * 4, acc);
-        else *reinterpret_cast<V*>(y + (size_t)pix * y_ld + g * VEC) = acc;
+        YA::store(y, (size_t)pix, y_ld, g * N, acc);
     }
 }
 
 // 3x3 / stride 2 / VALID max pool (MaxPool_3a / 5a and the pooled branches of Mixed_6a / 7a, nets/inception_v3.py:112,127,
-// 214,347) on fp32 storage, four vertically adjacent outputs of a 4-channel group per thread: 9 input rows instead of 12, and
-// the rows two outputs share are not fetched again by a workgroup on another XCD (lowp.hip: maxpool3x3s2_rows_lp).
-template <int RH>
-__global__ __launch_bounds__(256) void maxpool3x3s2_rows_f32(const float* __restrict__ x, float* __restrict__ y, int nb,
-                                                             int ih, int iw, int c, int x_ld, int oh, int ow, int y_ld) {
-    const int cg = c >> 2;
+// 214,347), RH vertically adjacent outputs of an N-channel group per thread: the window rows 2*oy .. 2*oy + 2 of
+// consecutive outputs share a row, so a thread that walks down RH outputs reads 2*RH + 1 input rows instead of 3*RH — and,
+// what matters more, the shared rows are not re-fetched by ANOTHER workgroup on another XCD (pool2d: one output per
+// thread, L2 hit 0.32, 1.5x the algorithmic bytes from the fabric; r3_pmc / r4_pmc).
+// Giving every workgroup one contiguous span of pool2d's index instead was measured and dropped (round 4: the pools
+// of a step 1.10 -> 1.25 ms — 4096 spans in flight at once walk 4096 far-apart regions).
+template <class A, int RH>
+__global__ __launch_bounds__(256) void maxpool3x3s2_rows(const typename A::elem* __restrict__ x,
+                                                         typename A::elem* __restrict__ y, int nb, int ih, int iw, int c,
+                                                         int x_ld, int oh, int ow, int y_ld) {
+    constexpr int N = A::N;
+    const int cg = c / N;
     const int nob = (oh + RH - 1) / RH;
     const int64_t total = (int64_t)nb * nob * ow * cg;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -102,189 +88,86 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_rows_f32(const float* __rest
         const int ob = (int)(t % nob);
         const int n = (int)(t / nob);
         const int oy0 = ob * RH;
-        const int nr = min(RH, oh - oy0);
-        const float* xp = x + ((size_t)(n * ih + 2 * oy0) * iw + 2 * ox) * x_ld + g * 4;
-        float* yp = y + ((size_t)(n * oh + oy0) * ow + ox) * y_ld + g * 4;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int nr = min(RH, oh - oy0);                          // output rows of this thread
+        const auto* xp = A::at(x, (size_t)(n * ih + 2 * oy0) * iw + 2 * ox, x_ld);
+        auto* yp = A::at(y, (size_t)(n * oh + oy0) * ow + ox, y_ld);
+        float acc[N];
 #pragma unroll
         for (int r = 0; r <= 2 * RH; ++r) {
-            if (r > 2 * nr) break;
-            const float* rp = xp + (size_t)r * iw * x_ld;
-            const f32x4 a = *reinterpret_cast<const f32x4*>(rp), b = *reinterpret_cast<const f32x4*>(rp + x_ld),
-                        d_ = *reinterpret_cast<const f32x4*>(rp + 2 * x_ld);
-            f32x4 hm;
+            if (r > 2 * nr) break;                                 // (VALID: input row 2*oy + 2 exists for every oy < oh)
+            const auto* rp = A::at(xp, (size_t)r * iw, x_ld);
+            float a[N], b[N], d_[N], hm[N];
+            A::load(rp, 0, x_ld, g * N, a);
+            A::load(rp, 1, x_ld, g * N, b);
+            A::load(rp, 2, x_ld, g * N, d_);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) hm[e] = fmaxf(fmaxf(a[e], b[e]), d_[e]);
+            for (int e = 0; e < N; ++e) hm[e] = fmaxf(fmaxf(a[e], b[e]), d_[e]);
             if (r == 0) {
-                acc = hm;
+#pragma unroll
+                for (int e = 0; e < N; ++e) acc[e] = hm[e];
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], hm[e]);
-                if ((r & 1) == 0) {
-                    *reinterpret_cast<f32x4*>(yp + (size_t)(r / 2 - 1) * ow * y_ld) = acc;
-                    acc = hm;
+                for (int e = 0; e < N; ++e) acc[e] = fmaxf(acc[e], hm[e]);
+                if ((r & 1) == 0) {                                // the third row of output r/2 - 1 = the first of output r/2
+                    A::store(yp, (size_t)(r / 2 - 1) * ow, y_ld, g * N, acc);
+#pragma unroll
+                    for (int e = 0; e < N; ++e) acc[e] = hm[e];
                 }
             }
         }
     }
 }
 
-// 3x3 / stride 1 / SAME average pool (slim.avg_pool2d under the Inception arg-scope,
-// nets/inception_v3.py:152,...): one thread produces 4 horizontally adjacent outputs of a 4-channel
-// group from a 3x6 input patch (column sums are shared), i.e. 18 16-byte loads for 4 outputs
-// instead of 36 — the generic kernel is L2-request bound on this op (2.4 TB/s).
-// XP3: the input is in the three-plane layout of GV_CONV_Y_P3 (conv_x3_epi.h); the sum of the planes is the fp32 value.
-template <bool XP3, bool YP3 = false>
-__global__ __launch_bounds__(256) void avgpool3x3s1_row4_f32(const float* __restrict__ x,
-                                                             float* __restrict__ y, int nb, int ih,
-                                                             int iw, int c, int x_ld, int y_ld, int relu) {
-    const int cg = c >> 2;
-    const int wg = (iw + 3) >> 2;
-    const int64_t total = (int64_t)nb * ih * wg * cg;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int g = (int)(idx % cg);
-        int64_t t = idx / cg;
-        const int xg = (int)(t % wg);
-        t /= wg;
-        const int oy = (int)(t % ih);
-        const int n = (int)(t / ih);
-        const int ox0 = xg * 4;
-        f32x4 col[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) col[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        int rows = 0;
-#pragma unroll
-        for (int r = -1; r <= 1; ++r) {
-            const int iy = oy + r;
-            if ((unsigned)iy >= (unsigned)ih) continue;
-            ++rows;
-            const float* rowp = x + ((size_t)(n * ih + iy) * iw) * x_ld + g * 4;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int ix = ox0 - 1 + j;
-                if ((unsigned)ix < (unsigned)iw) {
-                    if constexpr (XP3)
-                        col[j] += p3_load4(reinterpret_cast<const char*>(x), (size_t)(n * ih + iy) * iw + ix, x_ld, g * 4);
-                    else
-                        col[j] += *reinterpret_cast<const f32x4*>(rowp + (size_t)ix * x_ld);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ox = ox0 + j;
-            if (ox >= iw) break;
-            const int cols = 1 + (ox > 0 ? 1 : 0) + (ox + 1 < iw ? 1 : 0);
-            const float inv = (float)(rows * cols);           // valid taps only (TF SAME semantics)
-            f32x4 v = col[j] + col[j + 1] + col[j + 2];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = v[e] / inv;
-                if (relu) v[e] = fmaxf(v[e], 0.f);
-            }
-            if constexpr (YP3) p3_store4(reinterpret_cast<char*>(y), (size_t)(n * ih + oy) * iw + ox, y_ld, g * 4, v);
-            else *reinterpret_cast<f32x4*>(y + ((size_t)(n * ih + oy) * iw + ox) * y_ld + g * 4) = v;
-        }
-    }
+// (A 4 x 4 block of outputs per thread for the 3x3 / stride-1 AVERAGE pool — 36 loads for 16 outputs instead of the row
+// form's 18 for 4 — was measured and dropped in round 4: 0.027 -> 0.038 ms on a Mixed_5 branch, 0.018 -> 0.024 ms on a
+// Mixed_6 one: a quarter of the threads and 96 live partial sums each.)
+
+// sum / inv with rcp = 1 / inv, the correctly rounded reciprocal, taken once for several sums: a product and one
+// exact-remainder correction (Markstein) — the correctly rounded quotient, i.e. the bits of the division, at 3 instead of
+// ~10 instructions per value — for a FINITE sum; a non-finite one keeps sum * rcp (inf stays inf, NaN stays NaN, as the
+// division gives; the correction would turn inf into NaN)
+__device__ __forceinline__ float div_by_rcp(float sum, float inv, float rcp) {
+    const float q0 = sum * rcp;
+    const float qc = __builtin_fmaf(__builtin_fmaf(-inv, q0, sum), rcp, q0);
+    return __builtin_fabsf(q0) < __builtin_inff() ? qc : q0;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void scale_shift_act_f32(const float* __restrict__ x, int64_t npix,
-                                                           int c, int x_ld,
-                                                           const float* __restrict__ scale,
-                                                           const float* __restrict__ shift, int relu,
-                                                           float* __restrict__ y, int y_ld) {
-    using V = typename VecT<VEC>::type;
-    const int cg = c / VEC;
-    const int64_t total = npix * cg;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int g = (int)(idx % cg);
-        const int64_t pix = idx / cg;
-        V v = *reinterpret_cast<const V*>(x + (size_t)pix * x_ld + g * VEC);
-        const V sc = *reinterpret_cast<const V*>(scale + g * VEC);
-        const V sh = *reinterpret_cast<const V*>(shift + g * VEC);
-        v = v * sc + sh;
-        if (relu) {
-            if constexpr (VEC == 4) {
+// ROWS x 4 outputs (rows oy0 .., columns ox0 ..) of one N-channel group from a (ROWS + 2) x 6 input patch: the column sums
+// are shared by the outputs of a row, and an input row by the output rows it serves.  Per output the same additions in the
+// same order for every ROWS: per column the valid rows ascending, then (col[j] + col[j+1]) + col[j+2].
+template <class XA, class YA, int ROWS>
+__device__ __forceinline__ void avgpool3x3s1_tile(const typename XA::elem* __restrict__ x, typename YA::elem* __restrict__ y,
+                                                  int n, int oy0, int ox0, int ch, int ih, int iw, int x_ld, int y_ld,
+                                                  int relu) {
+    constexpr int N = XA::N;
+    float col[ROWS][6][N];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else {
-                v = fmaxf(v, 0.f);
-            }
-        }
-        *reinterpret_cast<V*>(y + (size_t)pix * y_ld + g * VEC) = v;
-    }
-}
-
-// y[b][c] = mean_p x[b][p][c]; thread per (b, c): lanes walk consecutive channels.
-__global__ __launch_bounds__(256) void global_avg_pool_f32(const float* __restrict__ x, int nb, int hw,
-                                                           int c, int x_ld, float* __restrict__ y) {
-    const int64_t total = (int64_t)nb * c;
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int ch = (int)(idx % c);
-    const int b = (int)(idx / c);
-    const float* p = x + (size_t)b * hw * x_ld + ch;
-    float s = 0.f;
-    for (int i = 0; i < hw; ++i) s += p[(size_t)i * x_ld];
-    y[idx] = s / (float)hw;
-}
-
-// The same pool on THREE-PLANE input, 8 channels and 2 x 4 outputs per thread: 16-byte plane loads (the form above reads a
-// pixel's 4 channels as three 8-byte loads), rows oy and oy + 1 of the pair shared in registers, and workgroups mapped so
-// that an XCD owns a contiguous range of them — the rows two outputs share are then in ITS L2 (round-robin dispatch put
-// vertical neighbours on different XCDs: the pooled branches of c2 fetched 3.5 x their input from beyond L2, at an L2
-// hit rate of 0.28).  Same additions in the same order as the form above: bitwise the same values.
-template <bool YP3>
-__global__ __launch_bounds__(256) void avgpool3x3s1_p3x8(const char* __restrict__ x, char* __restrict__ y, int nb, int ih,
-                                                         int iw, int c, int x_ld, int y_ld, int relu) {
-    const int cg = c >> 3, wg = (iw + 3) >> 2, hg = (ih + 1) >> 1;
-    const int64_t total = (int64_t)nb * hg * wg * cg;
-    const int64_t idx = (int64_t)gv_xcd_remap((int)blockIdx.x, (int)gridDim.x) * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int g = (int)(idx % cg);
-    int64_t t = idx / cg;
-    const int xg = (int)(t % wg);
-    t /= wg;
-    const int yg = (int)(t % hg);
-    const int n = (int)(t / hg);
-    const int oy0 = yg * 2, ox0 = xg * 4, ch = g * 8;
-    float col[2][6][8];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
+    for (int q = 0; q < ROWS; ++q)
 #pragma unroll
         for (int j = 0; j < 6; ++j)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) col[q][j][e] = 0.f;
-    const size_t choff = (size_t)(ch & ~15) * 6 + (size_t)(ch & 15) * 2;
+            for (int e = 0; e < N; ++e) col[q][j][e] = 0.f;
 #pragma unroll
-    for (int r = -1; r <= 2; ++r) {
+    for (int r = -1; r <= ROWS; ++r) {
         const int iy = oy0 + r;
         if ((unsigned)iy >= (unsigned)ih) continue;
+        const auto* xr = XA::at(x, (size_t)(n * ih + iy) * iw, x_ld);
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             const int ix = ox0 - 1 + j;
             if ((unsigned)ix >= (unsigned)iw) continue;
-            const char* src = x + ((size_t)(n * ih + iy) * iw + ix) * (size_t)x_ld * 6 + choff;
-            p3_u32x4 pl[3];
+            float v[N];
+            XA::load(xr, ix, x_ld, ch, v);
 #pragma unroll
-            for (int p = 0; p < 3; ++p) pl[p] = *reinterpret_cast<const p3_u32x4*>(src + p * 32);
+            for (int q = 0; q < ROWS; ++q)
+                if (r >= q - 1 && r <= q + 1) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int sh = (e & 1) * 16;
-                const float a0 = __builtin_bit_cast(float, ((pl[0][e >> 1] >> sh) & 0xffffu) << 16);
-                const float a1 = __builtin_bit_cast(float, ((pl[1][e >> 1] >> sh) & 0xffffu) << 16);
-                const float a2 = __builtin_bit_cast(float, ((pl[2][e >> 1] >> sh) & 0xffffu) << 16);
-                const float v = (a2 + a1) + a0;
-                if (r <= 1) col[0][j][e] += v;
-                if (r >= 0) col[1][j][e] += v;
-            }
+                    for (int e = 0; e < N; ++e) col[q][j][e] += v[e];
+                }
         }
     }
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < ROWS; ++q) {
         const int oy = oy0 + q;
         if (oy >= ih) break;
         const int rows = 1 + (oy > 0 ? 1 : 0) + (oy + 1 < ih ? 1 : 0);
@@ -294,30 +177,87 @@ __global__ __launch_bounds__(256) void avgpool3x3s1_p3x8(const char* __restrict_
             if (ox >= iw) break;
             const int cols = 1 + (ox > 0 ? 1 : 0) + (ox + 1 < iw ? 1 : 0);
             const float inv = (float)(rows * cols);           // valid taps only (TF SAME semantics)
-            // s / inv for eight values: the correctly rounded reciprocal once, then per value a product and one exact-remainder
-            // correction (Markstein) — the correctly rounded quotient, i.e. the bits of the division, at 3 instead of ~10
-            // instructions per value (the divisions were most of this kernel's vector instructions)
-            // — for a FINITE sum; a non-finite one keeps sum * rcp (inf stays inf, NaN stays NaN, as the division gives)
             const float rcp = 1.0f / inv;
-            float v[8];
+            float v[N];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
+            for (int e = 0; e < N; ++e) {
                 const float sum = col[q][j][e] + col[q][j + 1][e] + col[q][j + 2][e];
-                const float q0 = sum * rcp;
-                const float qc = __builtin_fmaf(__builtin_fmaf(-inv, q0, sum), rcp, q0);
-                v[e] = __builtin_fabsf(q0) < __builtin_inff() ? qc : q0;   // (+-inf / NaN sums: the correction would turn inf into NaN)
+                // (the divisions were most of the two-row form's vector instructions; the one-row form keeps them)
+                v[e] = ROWS == 2 ? div_by_rcp(sum, inv, rcp) : sum / inv;
                 if (relu) v[e] = fmaxf(v[e], 0.f);
             }
-            const size_t pix = (size_t)(n * ih + oy) * iw + ox;
-            if constexpr (YP3) {
-                p3_store8(y, pix, y_ld, ch, v);
-            } else {
-                float* yp = reinterpret_cast<float*>(y) + pix * (size_t)y_ld + ch;
-                *reinterpret_cast<f32x4*>(yp) = f32x4{v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(yp + 4) = f32x4{v[4], v[5], v[6], v[7]};
-            }
+            YA::store(y, (size_t)(n * ih + oy) * iw + ox, y_ld, ch, v);
         }
     }
+}
+
+// 3x3 / stride 1 / SAME average pool (slim.avg_pool2d under the Inception arg-scope, nets/inception_v3.py:152,...): 18
+// 16-byte loads for 4 outputs instead of 36 — the generic kernel is L2-request bound on this op (2.4 TB/s).
+// ROWS = 1: a grid-stride loop.  ROWS = 2: rows oy and oy + 1 of a pair are loaded once, and workgroups are mapped so that
+// an XCD owns a contiguous range of them — the rows two outputs share are then in ITS L2 (under round-robin dispatch
+// vertical neighbours sat on different XCDs: c5's nine pooled branches fetched 3.9 x their input from beyond L2, the pooled
+// branches of c2 3.5 x at an L2 hit rate of 0.28); launched with exactly ceil(total / 256) workgroups.
+template <class XA, class YA, int ROWS>
+__global__ __launch_bounds__(256) void avgpool3x3s1_rows(const typename XA::elem* __restrict__ x,
+                                                         typename YA::elem* __restrict__ y, int nb, int ih, int iw, int c,
+                                                         int x_ld, int y_ld, int relu) {
+    constexpr int N = XA::N;
+    const int cg = c / N, wg = (iw + 3) >> 2, hg = (ih + ROWS - 1) / ROWS;
+    const int64_t total = (int64_t)nb * hg * wg * cg;
+    const auto tile = [&](int64_t idx) {
+        const int g = (int)(idx % cg);
+        int64_t t = idx / cg;
+        const int xg = (int)(t % wg);
+        t /= wg;
+        const int yg = (int)(t % hg);
+        const int n = (int)(t / hg);
+        avgpool3x3s1_tile<XA, YA, ROWS>(x, y, n, yg * ROWS, xg * 4, g * N, ih, iw, x_ld, y_ld, relu);
+    };
+    if constexpr (ROWS == 2) {
+        const int64_t idx = (int64_t)gv_xcd_remap((int)blockIdx.x, (int)gridDim.x) * 256 + threadIdx.x;
+        if (idx < total) tile(idx);
+    } else {
+        for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+             idx += (int64_t)gridDim.x * blockDim.x)
+            tile(idx);
+    }
+}
+
+template <class A>
+__global__ __launch_bounds__(256) void scale_shift_act(const typename A::elem* __restrict__ x, int64_t npix, int c, int x_ld,
+                                                       const float* __restrict__ scale, const float* __restrict__ shift,
+                                                       int relu, typename A::elem* __restrict__ y, int y_ld) {
+    constexpr int N = A::N;
+    const int cg = c / N;
+    const int64_t total = npix * cg;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int g = (int)(idx % cg);
+        const int64_t pix = idx / cg;
+        float v[N];
+        A::load(x, (size_t)pix, x_ld, g * N, v);
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            v[e] = v[e] * scale[g * N + e] + shift[g * N + e];
+            if (relu) v[e] = fmaxf(v[e], 0.f);
+        }
+        A::store(y, (size_t)pix, y_ld, g * N, v);
+    }
+}
+
+// y[b][c] = mean_p x[b][p][c]; thread per (b, c): lanes walk consecutive channels.
+template <typename E, typename T>
+__global__ __launch_bounds__(256) void global_avg_pool(const E* __restrict__ x, int nb, int hw, int c, int x_ld,
+                                                       float* __restrict__ y) {
+    const int64_t total = (int64_t)nb * c;
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int ch = (int)(idx % c);
+    const int b = (int)(idx / c);
+    const E* p = x + (size_t)b * hw * x_ld + ch;
+    float s = 0.f;
+    for (int i = 0; i < hw; ++i) s += up<T>(p[(size_t)i * x_ld]);
+    y[idx] = s / (float)hw;
 }
 
 }  // namespace
@@ -368,6 +308,82 @@ extern "C" int gv_preprocess_views(const uint8_t* src, int32_t nimg, int32_t h0,
     return GV_OK;
 }
 
+namespace {
+
+int g_pool_rows = 1;      // multi-row form of the 3x3 / stride-2 max pool (gv_pool2d_set_rows: 0 = one output per thread; A/B)
+
+// The kernel form that serves a pool, and the channels a thread owns in it.
+enum PoolKind { POOL_GENERIC, POOL_AVG_ROWS1, POOL_AVG_ROWS2, POOL_MAX_ROWS };
+struct PoolForm {
+    PoolKind kind;
+    int n;                // 1: the scalar walk; 4 (fp32 values) / 8 (16-bit storage; the two-row form on three planes): 16-byte accesses
+};
+// mode without the three-plane bits; vec: c, both pixel strides and both bases allow the 16-byte walk of the storage
+// (always so for a three-plane operand: the entry point rejects the others); max_rows: gv_pool2d_set_rows
+PoolForm pool_form(const gv_pool_desc* d, int mode, bool xp3, bool yp3, bool vec, bool max_rows) {
+    const int n = !vec ? 1 : d->dtype == GV_F32 ? 4 : 8;
+    const bool k3 = d->kh == 3 && d->kw == 3;
+    if (vec && mode != GV_POOL_MAX && k3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->oh == d->ih &&
+        d->ow == d->iw) {
+        // two rows per thread, XCD-contiguous workgroups: 16-bit storage, and three-plane input in whole 8-channel chunks
+        const int64_t blk2 = ((int64_t)d->nb * ((d->ih + 1) / 2) * ((d->iw + 3) / 4) * (d->c / 8) + 255) / 256;
+        if ((d->dtype != GV_F32 || (xp3 && d->c % 8 == 0)) && blk2 < 0x7fffffff) return {POOL_AVG_ROWS2, 8};
+        return {POOL_AVG_ROWS1, n};
+    }
+    if (vec && max_rows && !xp3 && !yp3 && mode == GV_POOL_MAX && k3 && d->stride == 2 && d->pad_t == 0 && d->pad_l == 0 &&
+        d->oh == (d->ih - 3) / 2 + 1 && d->ow == (d->iw - 3) / 2 + 1)
+        return {POOL_MAX_ROWS, n};
+    return {POOL_GENERIC, n};
+}
+
+template <class XA, class YA>
+int launch_pool2d(const gv_pool_desc* d, int mode, const void* x, void* y, hipStream_t st) {
+    const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / XA::N);
+    return gv_launch<pool2d<XA, YA>>(dim3(gv_grid_for(total)), dim3(256), 0, st, (const typename XA::elem*)x,
+                                     (typename YA::elem*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride,
+                                     d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, mode);
+}
+
+template <class XA, class YA, int ROWS>
+int launch_avg_rows(const gv_pool_desc* d, int mode, const void* x, void* y, hipStream_t st) {
+    const int64_t total = (int64_t)d->nb * ((d->ih + ROWS - 1) / ROWS) * ((d->iw + 3) / 4) * (d->c / XA::N);
+    const dim3 grid(ROWS == 2 ? (unsigned)((total + 255) / 256) : gv_grid_for(total));
+    return gv_launch<avgpool3x3s1_rows<XA, YA, ROWS>>(grid, dim3(256), 0, st, (const typename XA::elem*)x,
+                                                      (typename YA::elem*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld,
+                                                      mode == GV_POOL_AVG_RELU ? 1 : 0);
+}
+
+template <class A>
+int launch_max_rows(const gv_pool_desc* d, const void* x, void* y, hipStream_t st) {
+    constexpr int RH = 4;
+    const int64_t total = (int64_t)d->nb * ((d->oh + RH - 1) / RH) * d->ow * (d->c / A::N);
+    return gv_launch<maxpool3x3s2_rows<A, RH>>(dim3(gv_grid_for(total)), dim3(256), 0, st, (const typename A::elem*)x,
+                                               (typename A::elem*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->oh, d->ow,
+                                               d->y_ld);
+}
+
+template <class A>
+int launch_ssa(const void* x, int64_t npix, int c, int x_ld, const float* scale, const float* shift, int relu, void* y,
+               int y_ld, void* stream) {
+    return gv_launch<scale_shift_act<A>>(dim3(gv_grid_for(npix * (c / A::N))), dim3(256), 0, (hipStream_t)stream,
+                                         (const typename A::elem*)x, npix, c, x_ld, scale, shift, relu,
+                                         (typename A::elem*)y, y_ld);
+}
+
+// fp32 values with three-plane input and / or output, 4 channels per thread: XA / YA the accessors of the two sides
+#define GV_P3_DISPATCH(xp3, yp3, CALL)                                              \
+    do {                                                                            \
+        using P = P3Px<4>;                                                          \
+        using Q = Px<float, float, 4>;                                              \
+        if ((xp3) && (yp3)) { using XA = P; using YA = P; CALL; }                   \
+        if (xp3) { using XA = P; using YA = Q; CALL; }                              \
+        { using XA = Q; using YA = P; CALL; }                                       \
+    } while (0)
+
+}  // namespace
+
+extern "C" void gv_pool2d_set_rows(int on) { g_pool_rows = on; }
+
 extern "C" int gv_pool2d_fwd(const gv_pool_desc* d, const void* x, void* y, void* stream) {
     if (!d || !x || !y) return GV_E_BADARG;
     if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->kh <= 0 || d->kw <= 0 ||
@@ -375,137 +391,52 @@ extern "C" int gv_pool2d_fwd(const gv_pool_desc* d, const void* x, void* y, void
         return GV_E_BADARG;
     if (d->x_ld < d->c || d->y_ld < d->c) return GV_E_BADARG;
     if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;             // (every dtype and storage form: checked before any branch)
-    const bool xp3 = (d->mode & GV_POOL_X_P3) != 0, yp3 = (d->mode & GV_POOL_Y_P3) != 0;
+    const bool xp3 = (d->mode & GV_POOL_X_P3) != 0, yp3 = (d->mode & GV_POOL_Y_P3) != 0, p3 = xp3 || yp3;
     const int mode = d->mode & ~(GV_POOL_X_P3 | GV_POOL_Y_P3);
     if (mode != GV_POOL_MAX && mode != GV_POOL_AVG && mode != GV_POOL_AVG_RELU) return GV_E_BADARG;
-    if (xp3 || yp3) {                            // three-plane input and / or output (fp32 values, GV_MATH_BF16X3 plans)
-        if (d->dtype != GV_F32 || d->c % 4 != 0 || !gv_aligned16(x) || !gv_aligned16(y) ||
-            (xp3 ? d->x_ld % 16 != 0 : d->x_ld % 4 != 0) || (yp3 ? d->y_ld % 16 != 0 : d->y_ld % 4 != 0))
-            return GV_E_UNSUPPORTED;
-        hipStream_t st = (hipStream_t)stream;
-        const float* xf = (const float*)x;
-        float* yf = (float*)y;
-        if (mode != GV_POOL_MAX && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-            d->oh == d->ih && d->ow == d->iw) {
-            const int64_t tot4 = (int64_t)d->nb * d->ih * ((d->iw + 3) / 4) * (d->c / 4);
-            const int relu = mode == GV_POOL_AVG_RELU ? 1 : 0;
-            const int64_t blk8 = ((int64_t)d->nb * ((d->ih + 1) / 2) * ((d->iw + 3) / 4) * (d->c / 8) + 255) / 256;
-            if (xp3 && d->c % 8 == 0 && blk8 < 0x7fffffff) {     // three-plane input, whole 8-channel chunks
-                if (yp3) hipLaunchKernelGGL((avgpool3x3s1_p3x8<true>), dim3((unsigned)blk8), dim3(256), 0, st, (const char*)x, (char*)y,
-                                            d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, relu);
-                else hipLaunchKernelGGL((avgpool3x3s1_p3x8<false>), dim3((unsigned)blk8), dim3(256), 0, st, (const char*)x, (char*)y,
-                                        d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, relu);
-                GV_LAUNCH_CHECK();
-                return GV_OK;
-            }
-#define GV_AVG4(XP, YP) hipLaunchKernelGGL((avgpool3x3s1_row4_f32<XP, YP>), dim3(gv_grid_for(tot4)), dim3(256), 0, st, xf, yf, \
-                                           d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, relu)
-            if (xp3 && yp3) GV_AVG4(true, true); else if (xp3) GV_AVG4(true, false); else GV_AVG4(false, true);
-#undef GV_AVG4
-        } else {
-            const int64_t total = (int64_t)d->nb * d->oh * d->ow * (d->c / 4);
-#define GV_POOL4(XP, YP) hipLaunchKernelGGL((pool2d_f32<4, XP, YP>), dim3(gv_grid_for(total)), dim3(256), 0, st, xf, yf, d->nb, \
-                                            d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride, d->pad_t, d->pad_l, d->oh, \
-                                            d->ow, d->y_ld, mode)
-            if (xp3 && yp3) GV_POOL4(true, true); else if (xp3) GV_POOL4(true, false); else GV_POOL4(false, true);
-#undef GV_POOL4
-        }
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    if (d->dtype != GV_F32) return gvlp::pool2d(d, x, y, (hipStream_t)stream);
-    const bool vec = (d->c % 4 == 0) && (d->x_ld % 4 == 0) && (d->y_ld % 4 == 0) && gv_aligned16(x) &&
-                     gv_aligned16(y);
-    const int64_t total = (int64_t)d->nb * d->oh * d->ow * (vec ? d->c / 4 : d->c);
+    // three-plane input and / or output (fp32 values, GV_MATH_BF16X3 plans): nothing but the 4-channel walk
+    if (p3 && (d->dtype != GV_F32 || d->c % 4 != 0 || !gv_aligned16(x) || !gv_aligned16(y) ||
+               (xp3 ? d->x_ld % 16 != 0 : d->x_ld % 4 != 0) || (yp3 ? d->y_ld % 16 != 0 : d->y_ld % 4 != 0)))
+        return GV_E_UNSUPPORTED;
+    const int quad = d->dtype == GV_F32 ? 4 : 8;
+    const bool vec = p3 || (d->c % quad == 0 && gv_vec_ok(x, d->x_ld, quad) && gv_vec_ok(y, d->y_ld, quad));
+    const PoolForm f = pool_form(d, mode, xp3, yp3, vec, g_pool_rows != 0);
     hipStream_t st = (hipStream_t)stream;
-    if (vec && d->mode != GV_POOL_MAX && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 &&
-        d->pad_l == 1 && d->oh == d->ih && d->ow == d->iw) {
-        const int64_t tot4 = (int64_t)d->nb * d->ih * ((d->iw + 3) / 4) * (d->c / 4);
-        hipLaunchKernelGGL((avgpool3x3s1_row4_f32<false, false>), dim3(gv_grid_for(tot4)), dim3(256), 0, st, (const float*)x,
-                           (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->y_ld, d->mode == GV_POOL_AVG_RELU ? 1 : 0);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
+    switch (f.kind) {
+    case POOL_AVG_ROWS2:
+        if (xp3 && yp3) return launch_avg_rows<P3Px<8>, P3Px<8>, 2>(d, mode, x, y, st);
+        if (xp3) return launch_avg_rows<P3Px<8>, Px<float, float, 8>, 2>(d, mode, x, y, st);
+        GV_LP_DISPATCH(d->dtype, return (launch_avg_rows<Px<unsigned short, T, 8>, Px<unsigned short, T, 8>, 2>(d, mode, x, y, st)));
+    case POOL_AVG_ROWS1:
+        if (p3) GV_P3_DISPATCH(xp3, yp3, return (launch_avg_rows<XA, YA, 1>(d, mode, x, y, st)));
+        GV_ST_DISPATCH(d->dtype, return (launch_avg_rows<Px<E, T, 16 / sizeof(E)>, Px<E, T, 16 / sizeof(E)>, 1>(d, mode, x, y, st)));
+    case POOL_MAX_ROWS:
+        GV_ST_DISPATCH(d->dtype, return (launch_max_rows<Px<E, T, 16 / sizeof(E)>>(d, x, y, st)));
+    case POOL_GENERIC:
+        break;
     }
-    if (vec && gvlp::pool_rows() && d->mode == GV_POOL_MAX && d->kh == 3 && d->kw == 3 && d->stride == 2 && d->pad_t == 0 &&
-        d->pad_l == 0 && d->oh == (d->ih - 3) / 2 + 1 && d->ow == (d->iw - 3) / 2 + 1) {
-        constexpr int RH = 4;
-        const int64_t tot = (int64_t)d->nb * ((d->oh + RH - 1) / RH) * d->ow * (d->c / 4);
-        hipLaunchKernelGGL(maxpool3x3s2_rows_f32<RH>, dim3(gv_grid_for(tot)), dim3(256), 0, st, (const float*)x, (float*)y,
-                           d->nb, d->ih, d->iw, d->c, d->x_ld, d->oh, d->ow, d->y_ld);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    }
-    if (vec)
-        hipLaunchKernelGGL(pool2d_f32<4>, dim3(gv_grid_for(total)), dim3(256), 0, st, (const float*)x,
-                           (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride,
-                           d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
-    else
-        hipLaunchKernelGGL(pool2d_f32<1>, dim3(gv_grid_for(total)), dim3(256), 0, st, (const float*)x,
-                           (float*)y, d->nb, d->ih, d->iw, d->c, d->x_ld, d->kh, d->kw, d->stride,
-                           d->pad_t, d->pad_l, d->oh, d->ow, d->y_ld, d->mode);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    if (p3) GV_P3_DISPATCH(xp3, yp3, return (launch_pool2d<XA, YA>(d, mode, x, y, st)));
+    if (f.n == 1) GV_ST_DISPATCH(d->dtype, return (launch_pool2d<Px<E, T, 1>, Px<E, T, 1>>(d, mode, x, y, st)));
+    GV_ST_DISPATCH(d->dtype, return (launch_pool2d<Px<E, T, 16 / sizeof(E)>, Px<E, T, 16 / sizeof(E)>>(d, mode, x, y, st)));
 }
 
 extern "C" int gv_scale_shift_act(const void* x, int64_t npix, int32_t c, int32_t x_ld,
                                   const float* scale, const float* shift, int32_t relu, void* y,
                                   int32_t y_ld, int32_t dtype, void* stream) {
     if (!x || !y || !scale || !shift || npix <= 0 || c <= 0 || x_ld < c || y_ld < c) return GV_E_BADARG;
-    if (dtype != GV_F32)
-        return gvlp::scale_shift_act(dtype, x, npix, c, x_ld, scale, shift, relu, y, y_ld, (hipStream_t)stream);
-    const bool vec = (c % 4 == 0) && (x_ld % 4 == 0) && (y_ld % 4 == 0) && gv_aligned16(x) &&
-                     gv_aligned16(y) && gv_aligned16(scale) && gv_aligned16(shift);
-    const int64_t total = npix * (vec ? c / 4 : c);
-    hipStream_t st = (hipStream_t)stream;
+    const int quad = dtype == GV_F32 ? 4 : 8;
+    // (fp32 storage takes the 16-byte walk only with 16-byte aligned coefficient rows as well)
+    const bool vec = c % quad == 0 && gv_vec_ok(x, x_ld, quad) && gv_vec_ok(y, y_ld, quad) &&
+                     (dtype != GV_F32 || (gv_aligned16(scale) && gv_aligned16(shift)));
     if (vec)
-        hipLaunchKernelGGL(scale_shift_act_f32<4>, dim3(gv_grid_for(total)), dim3(256), 0, st,
-                           (const float*)x, npix, c, x_ld, scale, shift, relu, (float*)y, y_ld);
-    else
-        hipLaunchKernelGGL(scale_shift_act_f32<1>, dim3(gv_grid_for(total)), dim3(256), 0, st,
-                           (const float*)x, npix, c, x_ld, scale, shift, relu, (float*)y, y_ld);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+        GV_ST_DISPATCH(dtype, return (launch_ssa<Px<E, T, 16 / sizeof(E)>>(x, npix, c, x_ld, scale, shift, relu, y, y_ld, stream)));
+    GV_ST_DISPATCH(dtype, return (launch_ssa<Px<E, T, 1>>(x, npix, c, x_ld, scale, shift, relu, y, y_ld, stream)));
 }
 
 extern "C" int gv_global_avg_pool(const void* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
                                   float* y, int32_t dtype, void* stream) {
     if (!x || !y || nb <= 0 || hw <= 0 || c <= 0 || x_ld < c) return GV_E_BADARG;
-    if (dtype != GV_F32) return gvlp::global_avg_pool(dtype, x, nb, hw, c, x_ld, y, (hipStream_t)stream);
-    const int64_t total = (int64_t)nb * c;
-    hipLaunchKernelGGL(global_avg_pool_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const float*)x, nb, hw, c, x_ld, y);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-// ---- PNG row un-filtering (host code: tf.image.decode_png of train_data.py:55 after zlib inflate) -------------------
-// raw: h rows of (1 filter byte + rowbytes data bytes); out: h x rowbytes.  Filters 0-4 of the PNG specification
-// (None, Sub, Up, Average, Paeth); bpp = bytes per pixel.  Sequential by definition (each byte depends on its left
-// neighbour), which is why it lives here and not in a Python loop.
-extern "C" int gv_png_unfilter(const uint8_t* raw, int32_t h, int32_t rowbytes, int32_t bpp, uint8_t* out) {
-    if (!raw || !out || h <= 0 || rowbytes <= 0 || bpp <= 0) return GV_E_BADARG;
-    const uint8_t* prev = nullptr;
-    for (int y = 0; y < h; ++y) {
-        const uint8_t* line = raw + (size_t)y * (rowbytes + 1);
-        uint8_t* cur = out + (size_t)y * rowbytes;
-        const int ft = line[0];
-        ++line;
-        if (ft > 4) return GV_E_BADARG;
-        for (int x = 0; x < rowbytes; ++x) {
-            const int a = x >= bpp ? cur[x - bpp] : 0;
-            const int b = prev ? prev[x] : 0;
-            const int c = (prev && x >= bpp) ? prev[x - bpp] : 0;
-            int p = 0;
-            if (ft == 1) p = a;
-            else if (ft == 2) p = b;
-            else if (ft == 3) p = (a + b) >> 1;
-            else if (ft == 4) {
-                const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
-                p = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-            }
-            cur[x] = (uint8_t)(line[x] + p);
-        }
-        prev = cur;
-    }
-    return GV_OK;
+    const dim3 grid((unsigned)(((int64_t)nb * c + 255) / 256));
+    GV_ST_DISPATCH(dtype, return (gv_launch<global_avg_pool<E, T>>(grid, dim3(256), 0, (hipStream_t)stream, (const E*)x, nb, hw,
+                                                                   c, x_ld, y)));
 }

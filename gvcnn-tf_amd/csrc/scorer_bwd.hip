@@ -19,15 +19,9 @@ namespace {
 
 using namespace gvlp_elem;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 constexpr int kGwChunk = 256;                         // element vectors per workgroup of group_weight_bwd (one per thread)
 
-// D_g of one element vector, exactly as view_pool_fuse_f32 / view_pool_fuse_lp form it (m != 0)
+// D_g of one element vector, exactly as view_pool_fuse (grouping.hip) forms it (m != 0)
 template <typename T, int VEC, typename E>
 __device__ __forceinline__ void pooled_group(const E* base, int64_t view_stride, unsigned long long m, int mode,
                                              float (&d)[8]) {
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(256) void group_weight_bwd_kernel(const E* __restri
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) t += ds[k] * (d[k] - s[k]);
             }
-            t = wave_sum(t);
+            t = gv_wave_sum(t);
         }
         if (lane == 0) s_part[g][wave] = t;
     }

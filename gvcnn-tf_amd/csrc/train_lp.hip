@@ -1383,7 +1383,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_strip_lp(const unsigned short*
 
 // ---- launchers of the HBM-bound ops: one body for every storage type -------------------------------------------------
 // E is the element type in HBM (float, or unsigned short for the 16-bit types) and T the type it stands for (float,
-// __bf16, _Float16): GV_ST_DISPATCH below.  The streaming kernel where the operands allow it, else the scalar kernel of
+// __bf16, _Float16): GV_ST_DISPATCH (gv_common.h).  The streaming kernel where the operands allow it, else the scalar kernel of
 // the same storage type.
 // every operand (nullptr: not used) can be walked in 16-byte quads (4 fp32 or 8 16-bit channels) ...
 inline bool stream_vec_ok(size_t elem_bytes, int c, const void* p0, int ld0, const void* p1, int ld1,
@@ -1836,15 +1836,6 @@ int wgrad_stem_rows(const gv_conv_desc* d, const unsigned short* x, const unsign
 }  // namespace
 
 namespace gvlp {
-
-// every storage type: E the element type in HBM, T the type it stands for
-#define GV_ST_DISPATCH(dtype, CALL)                                                   \
-    do {                                                                              \
-        if ((dtype) == GV_F32) { using E = float; using T = float; CALL; }            \
-        if ((dtype) == GV_BF16) { using E = unsigned short; using T = __bf16; CALL; } \
-        if ((dtype) == GV_F16) { using E = unsigned short; using T = _Float16; CALL; } \
-        return GV_E_UNSUPPORTED;                                                      \
-    } while (0)
 
 int accumulate(int dtype, const void* src, int src_ld, void* dst, int dst_ld, int64_t npix, int c, hipStream_t st) {
     const bool v = stream_vec_ok(elem_bytes(dtype), c, src, src_ld, dst, dst_ld);

@@ -1,5 +1,6 @@
 """Reference of the grouping head (helper, not collected): the operations between the backbone's last tap and the logits
-(csrc/grouping.hip, their 16-bit twins in csrc/lowp.hip and csrc/pool.hip), restated twice from the STORED values.
+(csrc/grouping.hip and csrc/pool.hip: one kernel template per op for every storage type), restated twice from the STORED
+values.
 
 fp64 (plain torch, on the device of the inputs; a bf16 / fp16 / fp32 tensor is widened exactly):
     r_img[b] = mean_p(raw[b,p,:] . k[v(b)]) + bias[v(b)]        v(b) = b % V (shape-major) or b // N (view-major)

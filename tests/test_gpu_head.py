@@ -1,5 +1,5 @@
-"""The grouping head's kernels over their launch geometries (csrc/grouping.hip, their 16-bit twins in csrc/lowp.hip, the
-element-wise ones in csrc/pool.hip, the pooling backward in csrc/train_lp.hip) against tests/head_ref.py: an fp64
+"""The grouping head's kernels over their launch geometries (csrc/grouping.hip, one template per op for every storage type;
+the element-wise ones in csrc/pool.hip, the pooling backward in csrc/train_lp.hip) against tests/head_ref.py: an fp64
 restatement of the stored values, and an ordered fp32 one where the kernel fixes the order of its operations.
 
 Operands are slices of wider flat buffers (tests/slab.py): inputs surrounded by NaN, outputs by a sentinel.  Reductions also
@@ -15,16 +15,16 @@ then carries 2 * 2^-23 |ln r| absolute, exp(-lg) that plus 2 * 2^-23 relative, 1
 held to 2^-126 absolute: the relative bound is one of normal numbers, and expf(-ln r) overflows for r < 2^-128.
 
 Case -> kernel form -> the condition that selects it (chunk = 4 elements of fp32, 8 of a 16-bit type; cg = cr / chunk):
-  score idle / tail3 / trip / straddle / trips / hw1   vector walk of view_score_partial_{f32,lp}   cr, raw_ld % chunk == 0
+  score idle / tail3 / trip / straddle / trips / hw1   vector walk of view_score_partial<E, T>      cr, raw_ld % chunk == 0
       and raw, kernel 16-byte aligned; hw * cg = 128 (idle threads), 600 (tail loop only, 3 trips), 1024 (one unrolled
       trip, no tail), 1176 (a trip, then a tail for threads < 152; hw = 49, cg = 24: a trip's 4 chunks in different
       pixels), 5000 (4 trips + tail), hw = 1;  +ld1 / +ld2: raw_ld = cr + 1 / 2 chunks;  +16B: operands 16 bytes in
   score cr30 / ld34 / base1                            scalar branch                               cr % chunk != 0 /
       raw_ld = 34 (fp32), 36 (16-bit) / raw one element off alignment
-  fuse A, B, F, Z, P, loopv                            view_pool_fuse_{f32<4>,lp<T,8>}              E, strides % chunk == 0,
+  fuse A, B, F, Z, P, loopv                            view_pool_fuse<Px<E, T, chunk>>              E, strides % chunk == 0,
       F, D, S aligned; loopv / loop1: E / chunk (E) > 1024 * 256 (the grid cap): the stride loop runs
   fuse C (stride E + 1), D (F one element off), E37, P37 (E % chunk != 0), N65535 (E = 3), loop1 (E = 262144 + 77)   view_pool_fuse_*<1>
-  ssa v64, v64o, loopv                                 scale_shift_act_{f32<4>,lp<T,8>}             c, x_ld, y_ld % chunk == 0
+  ssa v64, v64o, loopv                                 scale_shift_act<Px<E, T, chunk>>             c, x_ld, y_ld % chunk == 0
       and x, y (fp32: scale, shift too) aligned; loopv: npix * c / chunk > 4096 * 256 (gv_grid_for's cap)
   ssa s6, s8_9, sc4 (fp32: scale 4 bytes off), loops   scale_shift_act_*<1>
   gap / dense / metrics                                one kernel each; blocks below, at and above a multiple of 256

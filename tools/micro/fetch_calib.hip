@@ -4,7 +4,7 @@
 // on a known byte count in your own access pattern").  One kernel name per pattern, so that the per-kernel counter rows
 // can be compared with the bytes printed here:
 //   wide16      16 bytes per lane, lanes contiguous (the convolutions' loaders, the max pools' rows)
-//   planes16    the three-plane average pool's reads (csrc/pool.hip avgpool3x3s1_p3x8): thread t takes the 16-byte halves
+//   planes16    the three-plane average pool's reads (csrc/pool.hip avgpool3x3s1_rows on P3Px<8>): thread t takes the 16-byte halves
 //               (t & 1) of the three 32-byte plane rows of 16-channel group t >> 1 — a wave covers 3 KiB contiguous bytes
 //               with three loads of 16 bytes at a 32-byte pitch
 //   half64      only the first 64 bytes of every 128-byte line (4 lanes x 16 bytes), then — a second kernel, after the whole
