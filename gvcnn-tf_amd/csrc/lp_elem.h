@@ -1,4 +1,4 @@
-// Element helpers of the storage-typed kernels (pool.hip, grouping.hip, train_lp.hip): a 16-bit element travels as an
+// Element helpers of the storage-typed kernels (pool.hip, grouping.hip, train_lp.hip, pool_train.hip): a 16-bit element travels as an
 // unsigned short, arithmetic is fp32, T = __bf16 or _Float16 selects the encoding; fp32 storage is E = T = float.
 #pragma once
 #include "gv_common.h"
@@ -90,10 +90,10 @@ __device__ __forceinline__ void store_v(float* p, const float (&f)[8]) {
     }
 }
 
-// Pixel accessor of the forward kernels (pool.hip, grouping.hip): the NN channels from channel ch of pixel pix of a tensor
-// with pixel stride ld elements, as fp32 registers.  NN = 1 is the scalar access; a vector access (4 or 8 fp32, 8 of a
-// 16-bit type) moves whole 16-byte quads, which the host checks for.  at() advances the base by whole pixels.  The
-// three-plane accessor P3Px is in conv_x3_epi.h.
+// Pixel accessor of the forward kernels (pool.hip, grouping.hip) and the training pools (pool_train.hip): the NN channels
+// from channel ch of pixel pix of a tensor with pixel stride ld elements, as fp32 registers.  NN = 1 is the scalar access;
+// a vector access (4 or 8 fp32, 8 of a 16-bit type) moves whole 16-byte quads, which the host checks for.  at() advances
+// the base by whole pixels.  The three-plane accessor P3Px is in conv_x3_epi.h.
 template <typename E, typename T, int NN>
 struct Px {
     using elem = E;

@@ -5,8 +5,9 @@
 // update (train.py:171).  This file holds the extern "C" entry points of the step, the fp32-only kernels (BatchNorm
 // finalize / parameter gradients / moving averages, loss, dense backward, optimizer) and the fp32-MFMA filter gradient.
 // The HBM-bound ops that exist for every storage type (BatchNorm sums and applies, accumulate, the pool and view-pool
-// backward) are checked here and launched by gvlp:: in train_lp.hip.  Reductions accumulate in fp64 (HBM-bound
-// kernels, the fp64 adds are free) so that per-(view, channel) sums over up to 1.5e5 pixels are reproducible to fp32.
+// backward) are checked here and launched by gvlp:: in train_lp.hip and pool_train.hip.  Reductions accumulate in fp64
+// (HBM-bound kernels, the fp64 adds are free) so that per-(view, channel) sums over up to 1.5e5 pixels are reproducible
+// to fp32.
 #include <math.h>
 
 #include "gv_common.h"
@@ -637,24 +638,32 @@ extern "C" int gv_bias_grad(const float* dz, int32_t dz_ld, int64_t npix, int32_
     return gv_bias_grad_t(dz, dz_ld, npix, c, accum, dbias, GV_F32, stream);
 }
 
+// The descriptor checks of the training pools (pool_train.hip), after an entry point's null pointers: dimensions, the pixel
+// strides of its two activation operands, the mode (without GV_POOL_BWD_STORE; an average only where avg_ok), a valid tap
+// in every window, the storage type.
+static int pool_train_check(const gv_pool_desc* d, int mode, int ld0, int ld1, bool avg_ok) {
+    if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->oh <= 0 ||
+        d->ow <= 0 || d->pad_t < 0 || d->pad_l < 0 || ld0 < d->c || ld1 < d->c ||
+        (mode != GV_POOL_MAX && !(avg_ok && mode == GV_POOL_AVG)))
+        return GV_E_BADARG;
+    if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;
+    if (!storage_type(d->dtype)) return GV_E_UNSUPPORTED;
+    return GV_OK;
+}
+
 extern "C" int gv_pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int32_t dy_ld, void* dx,
                              int32_t dx_ld, void* stream) {
     if (!d || !dy || !dx) return GV_E_BADARG;
     const int mode = d->mode & ~GV_POOL_BWD_STORE;
-    if ((mode == GV_POOL_MAX && !x) || (mode != GV_POOL_MAX && mode != GV_POOL_AVG)) return GV_E_BADARG;
-    if (!storage_type(d->dtype)) return GV_E_UNSUPPORTED;
-    // one deterministic gather kernel family for all storage types (train_lp.hip)
+    if (mode == GV_POOL_MAX && !x) return GV_E_BADARG;
+    if (const int rc = pool_train_check(d, mode, dy_ld, dx_ld, true)) return rc;
     return gvlp::pool2d_bwd(d, x, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
 }
 
 extern "C" int gv_pool2d_fwd_argmax(const gv_pool_desc* d, const void* x, void* y, uint8_t* argmax, void* stream) {
     if (!d || !x || !y || !argmax) return GV_E_BADARG;
-    if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->oh <= 0 ||
-        d->ow <= 0 || d->pad_t < 0 || d->pad_l < 0 || d->x_ld < d->c || d->y_ld < d->c || d->mode != GV_POOL_MAX)
-        return GV_E_BADARG;
-    if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;
+    if (const int rc = pool_train_check(d, d->mode, d->x_ld, d->y_ld, false)) return rc;
     if (d->kh * d->kw > 255) return GV_E_UNSUPPORTED;               // the tap index is one byte
-    if (d->dtype != GV_F32 && d->dtype != GV_BF16 && d->dtype != GV_F16) return GV_E_UNSUPPORTED;
     return gvlp::pool2d_fwd_argmax(d, x, y, argmax, (hipStream_t)stream);
 }
 
@@ -671,12 +680,9 @@ extern "C" int gv_pool2d_bwd_argmax_bn(const gv_pool_desc* d, const uint8_t* arg
                                        const float* coef_b, const float* coef_c, const float* scale, const float* shift,
                                        void* dz, int32_t dz_ld, void* stream) {
     if (!d || !argmax || !dy || !z || !dz || !coef_a || !coef_b || !coef_c || num_groups <= 0) return GV_E_BADARG;
-    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-    if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->oh <= 0 || d->ow <= 0 || dy_ld < d->c || dz_ld < d->c ||
-        z_ld < d->c || (d->mode & ~GV_POOL_BWD_STORE) != GV_POOL_MAX)
-        return GV_E_BADARG;
-    if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;
-    if (d->dtype != GV_BF16 && d->dtype != GV_F16) return GV_E_UNSUPPORTED;
+    if ((scale == nullptr) != (shift == nullptr) || z_ld < d->c) return GV_E_BADARG;
+    if (const int rc = pool_train_check(d, d->mode & ~GV_POOL_BWD_STORE, dy_ld, dz_ld, false)) return rc;
+    if (d->dtype == GV_F32) return GV_E_UNSUPPORTED;
     if (d->c % 8 != 0 || z_ld % 8 != 0 || !gv_aligned16(z)) return GV_E_UNSUPPORTED;
     return gvlp::pool2d_bwd_argmax(d, argmax, dy, dy_ld, dz, dz_ld, (hipStream_t)stream, z, z_ld, num_groups, coef_a, coef_b,
                                    coef_c, scale, shift);
@@ -685,12 +691,7 @@ extern "C" int gv_pool2d_bwd_argmax_bn(const gv_pool_desc* d, const uint8_t* arg
 extern "C" int gv_pool2d_bwd_argmax(const gv_pool_desc* d, const uint8_t* argmax, const void* dy, int32_t dy_ld, void* dx,
                                     int32_t dx_ld, void* stream) {
     if (!d || !argmax || !dy || !dx) return GV_E_BADARG;
-    if (d->nb <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->oh <= 0 ||
-        d->ow <= 0 || d->pad_t < 0 || d->pad_l < 0 || dy_ld < d->c || dx_ld < d->c ||
-        (d->mode & ~GV_POOL_BWD_STORE) != GV_POOL_MAX)
-        return GV_E_BADARG;
-    if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;
-    if (d->dtype != GV_F32 && d->dtype != GV_BF16 && d->dtype != GV_F16) return GV_E_UNSUPPORTED;
+    if (const int rc = pool_train_check(d, d->mode & ~GV_POOL_BWD_STORE, dy_ld, dx_ld, false)) return rc;
     return gvlp::pool2d_bwd_argmax(d, argmax, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
 }
 

@@ -87,7 +87,8 @@ extern "C" {
 /* pooling modes */
 #define GV_POOL_MAX 0         /* padding value -inf (slim.max_pool2d) */
 #define GV_POOL_AVG 1         /* divisor = number of VALID taps (slim.avg_pool2d, SAME) */
-#define GV_POOL_BWD_STORE 0x100 /* gv_pool2d_bwd only, OR-ed into mode, 16-bit dtypes: dx = ... instead of dx += ... */
+#define GV_POOL_BWD_STORE 0x100 /* gv_pool2d_bwd and gv_pool2d_bwd_argmax, OR-ed into mode, every dtype: dx = ... instead of
+                                   dx += ... */
 #define GV_POOL_X_P3 0x200    /* OR-ed into mode, GV_F32 only: x is in the three-plane layout of GV_CONV_Y_P3 (x_ld and the
                                  slice offset multiples of 16 channels, c a multiple of 4) */
 #define GV_POOL_Y_P3 0x400    /* OR-ed into mode, GV_F32 only: y is written in that layout */
@@ -874,7 +875,8 @@ int gv_conv2d_wgrad(const gv_conv_desc* d, const void* x, const void* dz, int32_
 int gv_conv2d_wgrad_ws(const gv_conv_desc* d, const void* x, const void* dz, int32_t dz_ld, float* dw_hwio,
                        void* workspace, int64_t workspace_bytes, void* stream);
 /* Pool backward (descriptor of the forward pool): max -> first maximum of each window (tf MaxPoolGrad),
- * avg -> dy / #valid taps.  x is the forward input (max only).  x, dy, dx in d->dtype. */
+ * avg -> dy / #valid taps.  x is the forward input (max only).  x, dy, dx in d->dtype.  GV_E_BADARG: a non-positive
+ * dimension, dy_ld or dx_ld below c, a window without a valid tap. */
 int gv_pool2d_bwd(const gv_pool_desc* d, const void* x, const void* dy, int32_t dy_ld, void* dx,
                   int32_t dx_ld, void* stream);
 /* Max pool for the training step (slim.max_pool2d, nets/inception_v3.py:112,127 / nets/resnet_v2.py:181, under a

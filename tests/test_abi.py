@@ -92,6 +92,21 @@ def test_bad_arguments_return_codes(lib):
     past = _lib.PoolDesc(1, 8, 8, 16, 16, 3, 3, 2, 0, 0, 3, 6, 16, _lib.GV_POOL_MAX, _lib.GV_BF16)
     assert lib.gv_pool2d_fwd_argmax(C.byref(past), 16, 16, 16, None) == -1
     assert lib.gv_pool2d_bwd_argmax(C.byref(past), 16, 16, 16, 16, 16, None) == -1
+    # gv_pool2d_bwd makes the same descriptor checks: a window without a valid tap, a non-positive dimension, a pixel
+    # stride below c, for the max and for the average; a descriptor that passes them is refused for its dtype only
+    for mode in (_lib.GV_POOL_MAX, _lib.GV_POOL_AVG, _lib.GV_POOL_AVG | _lib.GV_POOL_BWD_STORE):
+        past.mode = mode
+        assert lib.gv_pool2d_bwd(C.byref(past), 16, 16, 16, 16, 16, None) == -1
+        wide = _lib.PoolDesc(1, 8, 8, 16, 16, 3, 3, 1, 3, 1, 8, 8, 16, mode, _lib.GV_BF16)        # pad_t = 3 >= kh = 3
+        assert lib.gv_pool2d_bwd(C.byref(wide), 16, 16, 16, 16, 16, None) == -1
+        for field in ("nb", "ih", "iw", "c", "kh", "kw", "stride", "oh", "ow"):
+            good = _lib.PoolDesc(1, 8, 8, 16, 16, 3, 3, 2, 0, 0, 3, 3, 16, mode, 7)
+            assert lib.gv_pool2d_bwd(C.byref(good), 16, 16, 16, 16, 16, None) == -2
+            setattr(good, field, 0)
+            assert lib.gv_pool2d_bwd(C.byref(good), 16, 16, 16, 16, 16, None) == -1, field
+        good = _lib.PoolDesc(1, 8, 8, 16, 16, 3, 3, 2, 0, 0, 3, 3, 16, mode, 7)
+        assert lib.gv_pool2d_bwd(C.byref(good), 16, 16, 15, 16, 16, None) == -1                   # dy_ld < c
+        assert lib.gv_pool2d_bwd(C.byref(good), 16, 16, 16, 16, 15, None) == -1                   # dx_ld < c
     assert lib.gv_group_assign(None, 6, 10, 10, None, None, None, None, None) == -1
     assert lib.gv_group_assign(16, 65, 10, 10, 16, 16, 16, 16, None) == -2        # V > 64
     assert lib.gv_view_pool_fuse_fwd(16, 6, 2, 64, 64, 384, 16, 10, 16, 9, 1.0, None, 16, 0, None) == -1

@@ -423,9 +423,7 @@ def test_max_pool_with_recorded_argmax(dt, tdt, k, stride, padding, c, ld, hw):
     assert torch.equal(arg.cpu(), want)
     dy = torch.zeros(nb, oh, ow, ld, dtype=tdt, device=DEV)
     dy[..., :c] = q(torch.randn(nb, oh, ow, c, generator=g), tdt).to(tdt).to(DEV)
-    for store in (0, _lib.GV_POOL_BWD_STORE):
-        if store and dt == _lib.GV_F32:
-            continue                                     # (gv_pool2d_bwd has the store form for 16-bit storage only)
+    for store in (0, _lib.GV_POOL_BWD_STORE):            # (both entry points have the store form for every storage type)
         d.mode = _lib.GV_POOL_MAX | store
         dx0 = torch.full((nb, ih, iw, ld), 0.25, dtype=tdt, device=DEV)
         dx1 = dx0.clone()
@@ -434,14 +432,6 @@ def test_max_pool_with_recorded_argmax(dt, tdt, k, stride, padding, c, ld, hw):
                    "pool_bwd (argmax)")
         assert torch.equal(dx0[..., :c], dx1[..., :c])
         assert (dx1[..., c:] == 0.25).all()
-    if dt == _lib.GV_F32:                                # the store form exists here for every storage type
-        d.mode = _lib.GV_POOL_MAX | _lib.GV_POOL_BWD_STORE
-        dxs = torch.full((nb, ih, iw, ld), float("nan"), dtype=tdt, device=DEV)
-        _lib.check(lib().gv_pool2d_bwd_argmax(C.byref(d), arg.data_ptr(), dy.data_ptr(), ld, dxs.data_ptr(), ld, st()), "store")
-        d.mode = _lib.GV_POOL_MAX
-        dxz = torch.zeros(nb, ih, iw, ld, dtype=tdt, device=DEV)
-        _lib.check(lib().gv_pool2d_bwd_argmax(C.byref(d), arg.data_ptr(), dy.data_ptr(), ld, dxz.data_ptr(), ld, st()), "add")
-        assert torch.equal(dxs[..., :c], dxz[..., :c])
 
 
 @pytest.mark.parametrize("dt,tdt,eps", TYPES)
