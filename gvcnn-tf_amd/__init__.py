@@ -17,10 +17,10 @@ from .model import (AUTO_REUSE, GVCNN, Explanation, basic, configure, explain_vi
 from . import retrieval  # noqa: E402
 from .retrieval import MetricLearner, ShapeIndex  # noqa: E402,F401
 from . import render  # noqa: E402
-from .render import (MeshBatch, PointBatch, ViewRenderer, load_obj, load_off, load_points, pack_meshes,  # noqa: E402,F401
-                     random_rotations, sample_surface)
+from .render import (MeshBatch, PointBatch, ViewRenderer, estimate_normals, load_obj, load_off, load_points,  # noqa: E402,F401
+                     pack_meshes, random_rotations, sample_surface)
 
 __all__ = ["GVCNN", "gvcnn", "basic", "group_scheme", "group_weight", "view_pooling", "group_fusion",
            "grouping_module", "gvcnn_fused", "configure", "explain_views", "Explanation", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
            "ShapeIndex", "MetricLearner", "render", "MeshBatch", "ViewRenderer", "load_off", "load_obj", "pack_meshes",
-           "random_rotations", "PointBatch", "load_points", "sample_surface"]
+           "random_rotations", "PointBatch", "load_points", "sample_surface", "estimate_normals"]

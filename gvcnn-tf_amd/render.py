@@ -55,6 +55,12 @@ Points in (csrc/render_points.hip; contract: include/gvcnn_hip.h, "points in"; r
   - shading="depth": f = ambient + (1 - ambient) * (1 - Z / (2^24 - 1)), colour = color * f, nearer is brighter;
     shading="normal": the reflection model above on the point's own (rotated) normal, with l_v and m_v as above; a
     normal without a finite positive length takes the depth factor.  One sample per pixel only.
+  - a cloud without normals (a raw scan) gets them on the device: batch.estimate_normals(k=16, orient="outward") or
+    PointBatch(clouds, device, estimate_normals=16) (csrc/point_normals.hip; contract: include/gvcnn_hip.h, "points in",
+    normal estimation; restated in tests/point_normals_oracle.py): per point the exact k nearest neighbours within its
+    cloud (fp32 squared distances, ties to the lower id), their fp64 covariance, its smallest eigenvector by cyclic
+    Jacobi, turned away from the bounding box's centre ("outward"), towards a sensor position ("viewpoint") or so that
+    its largest component is positive ("none").  Bit for bit the same whatever the batch, the grid or the schedule.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
@@ -460,12 +466,49 @@ def pack_points(clouds):
             "normals": None if ns[0] is None else np.concatenate(ns).reshape(-1, 3), "point_offsets": po}
 
 
+NORMALS_MIN_K, NORMALS_MAX_K, NORMALS_MAX_GRID = 3, 32, 128
+NORMALS_ORIENT = {"none": _lib.GV_NORMALS_ORIENT_NONE, "outward": _lib.GV_NORMALS_ORIENT_OUTWARD,
+                  "viewpoint": _lib.GV_NORMALS_ORIENT_VIEWPOINT}
+
+
+def _check_normals_k(k):
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not NORMALS_MIN_K <= k <= NORMALS_MAX_K:
+        raise ValueError("estimate_normals: k must be an integer in [%d, %d]" % (NORMALS_MIN_K, NORMALS_MAX_K))
+    return int(k)
+
+
+def _check_normals_args(k, orient, viewpoint, grid):
+    """(k, GV_NORMALS_ORIENT_* code, viewpoint float32 [3] or None, grid_cells) of estimate_normals, or ValueError."""
+    k = _check_normals_k(k)
+    if not isinstance(orient, str) or orient not in NORMALS_ORIENT:
+        raise ValueError("estimate_normals: orient must be one of %s" % sorted(NORMALS_ORIENT))
+    if (viewpoint is not None) != (orient == "viewpoint"):
+        raise ValueError("estimate_normals: a viewpoint goes with orient='viewpoint', and only with it")
+    if viewpoint is not None:
+        try:
+            with np.errstate(over="ignore"):
+                viewpoint = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float64).astype(np.float32))
+        except (TypeError, ValueError):
+            raise ValueError("estimate_normals: viewpoint must be three finite numbers")
+        if viewpoint.shape != (3,) or not np.isfinite(viewpoint).all():
+            raise ValueError("estimate_normals: viewpoint must be three finite numbers")
+    if grid is None:
+        grid = 0
+    elif isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not 1 <= grid <= NORMALS_MAX_GRID:
+        raise ValueError("estimate_normals: grid must be None (auto) or an integer in [1, %d]" % NORMALS_MAX_GRID)
+    return k, NORMALS_ORIENT[orient], viewpoint, int(grid)
+
+
 class PointBatch:
     """Point clouds packed and uploaded once, as MeshBatch does for meshes.  clouds: a list of points [P, 3] or of
-    (points, normals [P, 3]) tuples."""
+    (points, normals [P, 3]) tuples.  estimate_normals: 0, or the k of estimate_normals(k) for clouds without normals."""
 
-    def __init__(self, clouds, device=None):
+    def __init__(self, clouds, device=None, estimate_normals=0):
         p = pack_points(clouds)
+        if estimate_normals != 0:
+            _check_normals_k(estimate_normals)
+            if p["normals"] is not None:
+                raise ValueError("estimate_normals: the clouds already carry normals")
         self.device = _device(device)
         self.n = len(p["point_offsets"]) - 1
         self.point_offsets_host = p["point_offsets"]
@@ -474,10 +517,13 @@ class PointBatch:
         pts = p["points"] if len(p["points"]) else np.zeros((1, 3), np.float32)
         self.points = torch.from_numpy(np.ascontiguousarray(pts)).to(self.device)
         self.normals = None
+        self.normal_status = None                                # host int32 [N] once estimate_normals has run
         if p["normals"] is not None:
             nr = p["normals"] if len(p["normals"]) else np.zeros((1, 3), np.float32)
             self.normals = torch.from_numpy(np.ascontiguousarray(nr)).to(self.device)
         self.point_offsets = torch.from_numpy(p["point_offsets"]).to(self.device)
+        if estimate_normals:
+            self.estimate_normals(estimate_normals)
 
     def __len__(self):
         return self.n
@@ -492,6 +538,47 @@ class PointBatch:
     def group_normals(self, a):
         """The normals pointer of the group that starts at cloud a (None without normals)."""
         return None if self.normals is None else self.normals.data_ptr() + int(self.point_offsets_host[a]) * 12
+
+    def estimate_normals(self, k=16, orient="outward", viewpoint=None, grid=None, return_neighbors=False,
+                         return_variation=False):
+        """Estimate every point's normal on the device from its k nearest neighbours within its cloud (contract:
+        include/gvcnn_hip.h, "points in", normal estimation) and keep them as the batch's normals, replacing any it had.
+        k: 3..32.  orient: "outward" (away from the centre of the cloud's bounding box), "viewpoint" (towards
+        `viewpoint`, the sensor position, three numbers) or "none" (the largest component positive).  grid: cells per
+        axis of the search grid, 1..128, or None for auto; it changes the speed alone.  Sets normal_status, host int32
+        [N]: GV_RENDER_* of the cloud, with GV_POINTS_DEGENERATE_NORMAL or-ed in when some point's neighbourhood is
+        coincident or collinear (that point's normal is (0, 0, 0): it takes the depth factor).  Returns the batch, or
+        (batch, neighbors int32 [sum P, k] (ids within the cloud by rank, -1 past min(k, P)), variation float32 [sum P]
+        (l0 / (l0 + l1 + l2)), each on request), on the device."""
+        k, orient, viewpoint, grid = _check_normals_args(k, orient, viewpoint, grid)
+        lib = _lib.load()
+        rows = self.points.shape[0]                              # sum P (1 for a batch without points)
+        total = int(self.point_offsets_host[-1])
+        with torch.cuda.device(self.device):
+            ws_bytes = lib.gv_points_normals_workspace_bytes(self.n, total, grid)
+            _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_normals_workspace_bytes")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            normals = torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
+            nb = torch.full((rows, k), -1, dtype=torch.int32, device=self.device) if return_neighbors else None
+            var = torch.zeros(rows, dtype=torch.float32, device=self.device) if return_variation else None
+            status = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            rc = lib.gv_points_estimate_normals(
+                *self.group(0, self.n), k, orient, None if viewpoint is None else viewpoint.ctypes.data, grid,
+                normals.data_ptr(), None if nb is None else nb.data_ptr(), None if var is None else var.data_ptr(),
+                ws.data_ptr(), ws_bytes, status.data_ptr(), _model._st())
+            _lib.check(rc, "gv_points_estimate_normals")
+            self.normal_status = status.cpu().numpy()            # (the workspace is not reused before this sync)
+        self.normals = normals
+        extras = tuple(x for x in (nb, var) if x is not None)
+        return (self,) + extras if extras else self
+
+
+def estimate_normals(points, k=16, orient="outward", viewpoint=None, grid=None, device=None):
+    """The estimated normals float32 [P, 3] of one host cloud points [P, 3]: PointBatch([points]).estimate_normals(...),
+    copied back."""
+    _check_normals_args(k, orient, viewpoint, grid)
+    batch = PointBatch([points], device).estimate_normals(k, orient, viewpoint, grid)
+    return batch.normals.cpu().numpy()[:int(batch.num_points[0])]
 
 
 def random_rotations(n, mode="z", seed=0):

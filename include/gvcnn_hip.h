@@ -785,6 +785,60 @@ int gv_points_draw(const float* points, const int64_t* point_offsets, int32_t n,
                    void* workspace, int64_t workspace_bytes, void* bins, int64_t bins_bytes, int64_t total,
                    int32_t output, void* out, int32_t* point_id, uint32_t* depth, const float* normals,
                    const gv_render_shading* shading, const float* lights, const float* halfs, void* stream);
+/* Normal estimation: the normals "normal" shading needs, for clouds that come without (raw scans): per point the exact
+ * k nearest neighbours within its own cloud, the covariance of that neighbourhood, the eigenvector of its smallest
+ * eigenvalue, a sign convention.  Defined bit for bit: independent of scheduling, of how a batch is split, of the grid
+ * size and of the order of the points in memory (up to the ids that order gives); no floating-point atomics.
+ *  - inputs: points / point_offsets as above (a point's id is its index within its cloud); k in [3, 32]; orient, one of
+ *    GV_NORMALS_ORIENT_*; viewpoint[3], HOST memory, read before the call returns (GV_NORMALS_ORIENT_VIEWPOINT only,
+ *    otherwise it may be NULL); grid_cells: 0 = auto, else 1..128, a hint that only sizes the search grid; max_points
+ *    (the largest P of the batch) only sizes the launches.  Any value of either gives the same results.
+ *  - neighbours of point i of a cloud of P points: k_eff = min(k, P).  fp32, every step rounded on its own (no FMA):
+ *    dx = xj - xi, dy = yj - yi, dz = zj - zi, d2 = (dx*dx + dy*dy) + dz*dz for every j of the cloud, i included
+ *    (d2 = 0).  key = ((uint64)bits(d2) << 32) | j.  The neighbourhood is the k_eff smallest keys in ascending order
+ *    (rank 0 .. k_eff-1): among equal distances the lower id wins.  This is the brute-force answer; the search grid
+ *    only finds it faster.
+ *  - covariance, fp64, every operation rounded on its own, in rank order: d_r = (double)p_r - (double)p_i per
+ *    component; s = d_0 + d_1 + ... (from 0.0, left to right); m = s / (double)k_eff; C starts as 0.0 and for r = 0 ..
+ *    k_eff-1, with e = d_r - m: C00 += e0*e0, C01 += e0*e1, C02 += e0*e2, C11 += e1*e1, C12 += e1*e2, C22 += e2*e2.
+ *  - eigenvectors: cyclic Jacobi on A = C with V = I, fp64, only + - * / and a correctly rounded sqrt.  6 sweeps, each
+ *    the pairs (p, q) = (0,1), (0,2), (1,2) in that order, r the third index.  A pair whose A_pq is exactly 0 is skipped.
+ *    Otherwise theta = (A_qq - A_pp) / (2 * A_pq); t = sgn / (|theta| + sqrt(theta*theta + 1)) with sgn = -1 when
+ *    theta < 0, else 1; c = 1 / sqrt(t*t + 1); s = t * c; h = t * A_pq; A_pp = A_pp - h; A_qq = A_qq + h; A_pq = 0;
+ *    (A_rp, A_rq) = (c*A_rp - s*A_rq, s*A_rp + c*A_rq) from the old pair; and for each row i = 0, 1, 2 of V:
+ *    (V_ip, V_iq) = (c*V_ip - s*V_iq, s*V_ip + c*V_iq).  The eigenvalues are the diagonal of A, ordered l0 <= l1 <= l2
+ *    with ties by column index; the normal is column c0 of V, the column of l0, as it stands (unit up to the rounding
+ *    of the rotations: it is not normalised again).
+ *  - degenerate: k_eff < 3, l2 == 0, or l1 <= 1e-12 * l2 (coincident or collinear neighbourhoods).  Normal (0, 0, 0),
+ *    variation 0, and GV_POINTS_DEGENERATE_NORMAL is set in the cloud's status.  The splatter gives a zero normal the
+ *    depth factor.
+ *  - sign, fp64.  "none" rule: the component of largest magnitude becomes positive (the first of x, y, z on a tie).
+ *    GV_NORMALS_ORIENT_NONE: that rule.  GV_NORMALS_ORIENT_OUTWARD: w = p_i - c with c = 0.5 * ((double)min +
+ *    (double)max) of the cloud's bounding box per component; GV_NORMALS_ORIENT_VIEWPOINT: w = (double)viewpoint - p_i.
+ *    d = (n0*w0 + n1*w1) + n2*w2; the normal is negated when d < 0; d == 0 falls back to the "none" rule.
+ *  - outputs: normals fp32 [sum P, 3], each fp64 component rounded once; neighbours int32 [sum P, k] or NULL: the ids
+ *    in rank order, -1 from k_eff on; variation fp32 [sum P] or NULL: l0 / ((l0 + l1) + l2) in fp64, rounded once;
+ *    status int32 [N], device memory: GV_RENDER_OK, GV_RENDER_EMPTY (no points), GV_RENDER_NONFINITE (a point that is
+ *    not finite, or a bounding box whose extent is not: zero normals, -1 neighbours, variation 0), GV_RENDER_TOO_LARGE
+ *    / GV_RENDER_BAD_OFFSETS (nothing is written for the cloud), with GV_POINTS_DEGENERATE_NORMAL or-ed in.
+ * workspace: gv_points_normals_workspace_bytes(n, total_points, grid_cells) bytes, 16-byte aligned; nothing else is
+ * allocated, and two calls on two streams with two workspaces do not interfere.  GV_E_BADARG before any HIP call: a
+ * NULL points / point_offsets / normals / workspace / status, n <= 0, total_points or max_points < 0, k outside [3, 32],
+ * an unknown orient, GV_NORMALS_ORIENT_VIEWPOINT without a viewpoint or with one that is not finite, grid_cells outside
+ * [0, 128], a workspace smaller than the size query's answer; GV_E_UNSUPPORTED for n > 65535 or max_points > 2^24;
+ * GV_E_ALIGN for a workspace that is not 16-byte aligned, point_offsets not 8-byte aligned or a 4-byte buffer that is
+ * not 4-byte aligned.
+ * Known limit: a cloud with a far outlier has nearly all its points in one cell of the grid; its queries then cost
+ * O(P) each.  The results are the same. */
+#define GV_NORMALS_ORIENT_NONE 0
+#define GV_NORMALS_ORIENT_OUTWARD 1
+#define GV_NORMALS_ORIENT_VIEWPOINT 2
+#define GV_POINTS_DEGENERATE_NORMAL 0x100  /* or-ed into status[m]: some point of cloud m has a degenerate neighbourhood */
+int64_t gv_points_normals_workspace_bytes(int32_t n, int64_t total_points, int32_t grid_cells);
+int gv_points_estimate_normals(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                               int32_t max_points, int32_t k, int32_t orient, const float* viewpoint, int32_t grid_cells,
+                               float* normals, int32_t* neighbours, float* variation, void* workspace,
+                               int64_t workspace_bytes, int32_t* status, void* stream);
 
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
