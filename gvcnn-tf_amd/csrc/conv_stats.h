@@ -37,7 +37,7 @@ constexpr bool stat_has(int s) { return s == STAT_FWD || s == STAT_BWD; }
 // grid of the partial sums: 2^-30 for sum z (totals exact below 2^23), 2^-24 for sum z^2 (2^29); the backward sums
 // are sums of gradients, orders of magnitude smaller: 2^-40 (exact below 2^13)
 constexpr double STAT_Q_FWD0 = 1073741824.0, STAT_Q_FWD1 = 16777216.0, STAT_Q_BWD = 1099511627776.0;
-// fp32 storage (the sums kernels of train_lp.hip; grouped_sums_v8 says why they are finer): 2^-40 for sum z, 2^-36 for
+// fp32 storage (the sums kernel of bn_train.hip, which says why they are finer): 2^-40 for sum z, 2^-36 for
 // sum z^2, 2^-52 for the backward sums
 constexpr double STAT_Q32_FWD0 = 1099511627776.0, STAT_Q32_FWD1 = 68719476736.0, STAT_Q32_BWD = 4503599627370496.0;
 // the grid of sum k (0 or 1) of a sums kernel over storage elements of elem_bytes: forward statistics or backward sums

@@ -1,6 +1,6 @@
 // Why a shape got its class: per-view, per-pixel attribution of one logit through the head above the final tap
 // (view pooling -> group fusion -> global average pool -> Dense), with the grouping held constant as in the backward
-// pass (view_pool_fuse_bwd_t in train_lp.hip: the tie rule and the order of the coefficient's operations are its).
+// pass (view_pool_fuse_bwd_t in train.hip: the tie rule and the order of the coefficient's operations are its).
 //
 //   dlogit_k/dF[n,v,p,c] = sum_{g contains v} ((w_g/W) * (K[c,k]/hw)) / ties_g(p,c)   where F[v] attains the maximum of g
 //                                                                     / |g|            mean pooling

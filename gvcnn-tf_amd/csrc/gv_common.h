@@ -75,6 +75,8 @@ int gv_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... 
         if ((dtype) == GV_F16) { using E = unsigned short; using T = _Float16; CALL; } \
         return GV_E_UNSUPPORTED;                                                      \
     } while (0)
+// a dtype (without GV_ACCUM_* bits) that GV_ST_DISPATCH serves
+static inline bool gv_storage_type(int dtype) { return dtype == GV_F32 || dtype == GV_BF16 || dtype == GV_F16; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

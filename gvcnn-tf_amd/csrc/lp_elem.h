@@ -1,4 +1,4 @@
-// Element helpers of the storage-typed kernels (pool.hip, grouping.hip, train_lp.hip, pool_train.hip): a 16-bit element travels as an
+// Element helpers of the storage-typed kernels (pool.hip, grouping.hip, train.hip, bn_train.hip, pool_train.hip): a 16-bit element travels as an
 // unsigned short, arithmetic is fp32, T = __bf16 or _Float16 selects the encoding; fp32 storage is E = T = float.
 #pragma once
 #include "gv_common.h"

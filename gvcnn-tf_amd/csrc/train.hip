@@ -1,50 +1,99 @@
-// train.hip — kernels that exist only for the training step of the hot path:
-// batch-statistics BatchNorm grouped by view (the reference builds one graph copy per view, so every
-// BN normalises over the N*h*w values of ONE view: nets/model.py:129-141 + slim.batch_norm with
-// is_training=True), the backward of every forward op, the loss (train.py:145) and the Momentum
-// update (train.py:171).  This file holds the extern "C" entry points of the step, the fp32-only kernels (BatchNorm
-// finalize / parameter gradients / moving averages, loss, dense backward, optimizer) and the fp32-MFMA filter gradient.
-// The HBM-bound ops that exist for every storage type (BatchNorm sums and applies, accumulate, the pool and view-pool
-// backward) are checked here and launched by gvlp:: in train_lp.hip and pool_train.hip.  Reductions accumulate in fp64
-// (HBM-bound kernels, the fp64 adds are free) so that per-(view, channel) sums over up to 1.5e5 pixels are reproducible
-// to fp32.
+// train.hip — kernels that exist only for the training step of the hot path: the backward of the
+// forward ops, the loss (train.py:145) and the Momentum update (train.py:171).  This file holds the extern "C" entry
+// points of the step other than the train-mode BatchNorm's (bn_train.hip), the kernels of the small ops (accumulate and
+// the view-pool backward for every storage type; BatchNorm moving averages, loss, dense backward, optimizer in fp32) and
+// the fp32-MFMA filter gradient.  The training pools and the 16-bit filter gradient are checked here and launched by
+// gvlp:: in pool_train.hip, wgrad_lp.hip and wgrad_dma.hip.
 #include <math.h>
 
 #include "gv_common.h"
 #include "lowp.h"
+#include "lp_elem.h"
 
 namespace {
 
-// mean/var (biased) + folded scale/shift per (group, channel)
-__global__ void bn_finalize_grouped(const double* __restrict__ acc, int G, int c, const int* __restrict__ counts,
-                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                    float* __restrict__ mean, float* __restrict__ var, float* __restrict__ inv,
-                                    float* __restrict__ scale, float* __restrict__ shift) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= G * c) return;
-    const int g = i / c, ch = i - g * c;
-    const double m = (double)counts[g];
-    const double mu = acc[(size_t)i * 2] / m;
-    double v = acc[(size_t)i * 2 + 1] / m - mu * mu;
-    if (v < 0.0) v = 0.0;
-    const float iv = (float)(1.0 / sqrt(v + (double)eps));
-    const float ga = gamma ? gamma[ch] : 1.f;
-    mean[i] = (float)mu;
-    var[i] = (float)v;
-    inv[i] = iv;
-    scale[i] = iv * ga;
-    shift[i] = beta[ch] - (float)mu * iv * ga;
+using namespace gvlp_elem;
+
+// One body for every storage type: E is the element type in HBM (float, or unsigned short for the 16-bit types), T the type
+// it stands for (float, __bf16, _Float16): GV_ST_DISPATCH (gv_common.h).
+// dst[p][c] += src[p][c]  (gradient fan-in of the residual add, nets/resnet_v2.py:91); VEC = 16 / sizeof(E) channels per thread (one
+// 16-byte access) where the operands can be walked in quads, else 1
+template <typename E, typename T, int VEC>
+__global__ __launch_bounds__(256) void accumulate_t(const E* __restrict__ src, int src_ld, E* __restrict__ dst, int dst_ld,
+                                                    int64_t npix, int c) {
+    const int cg = c / VEC;
+    const int64_t total = npix * cg;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(idx % cg);
+        const int64_t pix = idx / cg;
+        float a[8], b[8];
+        load_v<T, VEC>(src + pix * src_ld + q * VEC, a);
+        load_v<T, VEC>(dst + pix * dst_ld + q * VEC, b);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) b[e] += a[e];
+        store_v<T, VEC>(dst + pix * dst_ld + q * VEC, b);
+    }
 }
 
-// per-channel parameter gradients: dbeta[c] += sum_g acc[g][c][0], dgamma[c] += sum_g acc[g][c][1]
-__global__ void bn_param_grads(const double* __restrict__ acc, int G, int c, float* __restrict__ dbeta,
-                               float* __restrict__ dgamma) {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    double a = 0.0, b = 0.0;
-    for (int g = 0; g < G; ++g) { a += acc[((size_t)g * c + ch) * 2]; b += acc[((size_t)g * c + ch) * 2 + 1]; }
-    if (dbeta) dbeta[ch] += (float)a;
-    if (dgamma) dgamma[ch] += (float)b;
+// ---- grouping module backward (nets/model.py:44-102) ------------------------------------------------
+// dF[v] += w_g/sum(w) * dS / (#views of g tied at the maximum) for every view of g attaining the maximum
+// (tf.reduce_max splits the gradient equally among ties); mean pooling: w_g/sum(w) * dS / |g|.
+// F and dF in the storage type (SE the element in HBM, T the type it stands for), dS in fp32.
+template <typename SE, typename T>
+__global__ __launch_bounds__(256) void view_pool_fuse_bwd_t(
+    const SE* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
+    int64_t shape_stride, const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode,
+    SE* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
+    __shared__ unsigned long long s_mask[64];
+    __shared__ float s_w[64];
+    __shared__ float s_wsum;
+    const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
+    scheme += (size_t)n * scheme_stride;
+    weight += (size_t)n * weight_stride;
+    for (int g = threadIdx.x; g < G; g += 256) {
+        unsigned long long m = 0;
+        for (int v = 0; v < V; ++v)
+            if (scheme[g * V + v] != 0) m |= 1ull << v;
+        s_mask[g] = m;
+        s_w[g] = weight[g];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ws = 0.f;
+        for (int g = 0; g < G; ++g) ws += s_w[g];
+        s_wsum = ws;
+    }
+    __syncthreads();
+    if (s_wsum == 0.f) return;                      // (per-shape, mean-score weights) S = 0 for this shape: no gradient
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+        const size_t base = (size_t)n * shape_stride + e;
+        const float ds = dS[(size_t)n * E + e];
+        for (int g = 0; g < G; ++g) {
+            const unsigned long long m0 = s_mask[g];
+            if (m0 == 0) continue;
+            const float coef = s_w[g] / s_wsum * ds;
+            if (mode == GV_VIEWPOOL_MEAN) {
+                const float each = coef / (float)__popcll(m0);
+                for (unsigned long long m = m0; m; m &= m - 1) {
+                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
+                    dF[a] = down<T>(up<T>(dF[a]) + each);
+                }
+            } else {
+                float best = -INFINITY;
+                for (unsigned long long m = m0; m; m &= m - 1)
+                    best = fmaxf(best, up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]));
+                int ties = 0;
+                for (unsigned long long m = m0; m; m &= m - 1)
+                    ties += up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]) == best;
+                const float each = coef / (float)ties;
+                for (unsigned long long m = m0; m; m &= m - 1) {
+                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
+                    if (up<T>(F[a]) == best) dF[a] = down<T>(up<T>(dF[a]) + each);
+                }
+            }
+        }
+    }
 }
 
 // dx[b][p][c] += dgap[b][c] / hw
@@ -427,170 +476,6 @@ extern "C" int gv_bn_update_moving_batched(const gv_bn_moving_job* jobs_dev, int
     return GV_OK;
 }
 
-// ---- the HBM-bound ops of the training step: one implementation per op -----------------------------------------------
-// The storage-typed `_t` entry point (dtype GV_F32 | GV_BF16 | GV_F16, for some ops with GV_ACCUM_* bits OR-ed in) is the
-// implementation: it checks the arguments, clears the accumulator, picks the pixel splits and calls gvlp:: (train_lp.hip),
-// which picks the streaming or the scalar kernel of the storage type.  The fp32 entry point passes GV_F32.
-static inline bool storage_type(int dtype) { return dtype == GV_F32 || dtype == GV_BF16 || dtype == GV_F16; }
-
-// pixel splits of a sums launch: 2048 pixels per workgroup on the big layers, but at least ~1024 workgroups in total
-// (down to 128 pixels per workgroup) on the small, latency-bound ones
-static inline int sums_splits(int64_t npix, int cap, int c = 64, int G = 1) {
-    int64_t splits = (npix + 2047) / 2048;
-    const int64_t want = 1024 / ((int64_t)((c + 63) / 64) * G) + 1, most = (npix + 127) / 128;
-    if (splits < want) splits = want < most ? want : most;
-    return (int)(splits > cap ? cap : (splits < 1 ? 1 : splits));
-}
-
-extern "C" int gv_bn_sums_grouped_t(const void* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
-                                    int32_t num_groups, double* accum, int32_t dtype, void* stream) {
-    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;          // the caller keeps a pre-zeroed accumulator per layer
-    dtype &= ~GV_ACCUM_ZEROED;
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!z || !accum) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || z_ld < c || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
-        GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
-    return gvlp::grouped_sums(dtype, 0, z, z_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nb, hw, c,
-                              num_groups, splits, accum, st);
-}
-
-extern "C" int gv_bn_sums_grouped(const float* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
-                                  int32_t num_groups, double* accum, void* stream) {
-    return gv_bn_sums_grouped_t(z, nb, hw, c, z_ld, num_groups, accum, GV_F32, stream);
-}
-
-extern "C" int gv_bn_finalize_grouped(const double* accum, int32_t c, int32_t num_groups, const int32_t* counts,
-                                      const float* gamma, const float* beta, float eps, float* mean, float* var,
-                                      float* inv, float* scale, float* shift, void* stream) {
-    if (!accum || !counts || !beta || !mean || !var || !inv || !scale || !shift || c <= 0 || num_groups <= 0)
-        return GV_E_BADARG;
-    hipLaunchKernelGGL(bn_finalize_grouped, dim3((num_groups * c + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       accum, num_groups, c, counts, gamma, beta, eps, mean, var, inv, scale, shift);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-extern "C" int gv_bn_stats_grouped(const float* z, int32_t nb, int32_t hw, int32_t c, int32_t z_ld,
-                                   int32_t num_groups, const int32_t* counts, const float* gamma,
-                                   const float* beta, float eps, double* accum, float* mean, float* var,
-                                   float* inv, float* scale, float* shift, void* stream) {
-    const int rc = gv_bn_sums_grouped(z, nb, hw, c, z_ld, num_groups, accum, stream);
-    if (rc != GV_OK) return rc;
-    return gv_bn_finalize_grouped(accum, c, num_groups, counts, gamma, beta, eps, mean, var, inv, scale, shift, stream);
-}
-
-extern "C" int gv_scale_shift_act_grouped_t(const void* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
-                                            const float* scale, const float* shift, int32_t num_groups,
-                                            int32_t relu, void* y, int32_t y_ld, int32_t dtype, void* stream) {
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!x || !y || !scale || !shift || nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0)
-        return GV_E_BADARG;
-    // (fp32 storage has always asked for float4 operands here; 16-bit storage takes any shape)
-    if (dtype == GV_F32 && ((c & 3) || (x_ld & 3) || (y_ld & 3) || !gv_aligned16(x) || !gv_aligned16(y) ||
-                            !gv_aligned16(scale) || !gv_aligned16(shift)))
-        return GV_E_ALIGN;
-    return gvlp::scale_shift_act_grouped(dtype, x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld,
-                                         (hipStream_t)stream);
-}
-
-extern "C" int gv_scale_shift_act_grouped(const float* x, int32_t nb, int32_t hw, int32_t c, int32_t x_ld,
-                                          const float* scale, const float* shift, int32_t num_groups,
-                                          int32_t relu, float* y, int32_t y_ld, void* stream) {
-    return gv_scale_shift_act_grouped_t(x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, GV_F32, stream);
-}
-
-extern "C" int gv_bn_finalize_apply_grouped_t(const double* accum, const int32_t* counts, const float* gamma,
-                                              const float* beta, float eps, const void* x, int32_t nb, int32_t hw,
-                                              int32_t c, int32_t x_ld, int32_t num_groups, int32_t relu, void* y,
-                                              int32_t y_ld, float* mean, float* var, float* inv, float* scale,
-                                              float* shift, int32_t dtype, void* stream) {
-    if (!accum || !counts || !beta || !x || !y || !mean || !var || !inv || !scale || !shift) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || x_ld < c || y_ld < c || num_groups <= 0) return GV_E_BADARG;
-    // one fused launch where the shape streams; else the two ops (which also reject an unknown dtype)
-    int rc = gvlp::bn_finalize_apply_grouped(dtype, accum, counts, gamma, beta, eps, x, nb, hw, c, x_ld, num_groups, relu,
-                                             y, y_ld, mean, var, inv, scale, shift, (hipStream_t)stream);
-    if (rc != GV_E_UNSUPPORTED) return rc;
-    rc = gv_bn_finalize_grouped(accum, c, num_groups, counts, gamma, beta, eps, mean, var, inv, scale, shift, stream);
-    if (rc != GV_OK) return rc;
-    return gv_scale_shift_act_grouped_t(x, nb, hw, c, x_ld, scale, shift, num_groups, relu, y, y_ld, dtype, stream);
-}
-
-// scale / shift (both or neither): the ReLU mask is recomputed from z when y was not kept
-extern "C" int gv_bn_relu_bwd_sums_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
-                                             const void* z, int32_t z_ld, const float* mean, const float* inv,
-                                             int32_t nb, int32_t hw, int32_t c, int32_t num_groups, double* accum,
-                                             const float* scale, const float* shift, int32_t dtype, void* stream) {
-    const bool zeroed = (dtype & GV_ACCUM_ZEROED) != 0;
-    dtype &= ~GV_ACCUM_ZEROED;
-    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!dy || !z || !mean || !inv || !accum) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (!zeroed || dtype == GV_F32)                              // (fp32 clears it whatever the bit says)
-        GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)num_groups * c, st));
-    const int splits = sums_splits((int64_t)(nb / num_groups) * hw, 256, c, num_groups);
-    return gvlp::grouped_sums(dtype, 1, z, z_ld, dy, dy_ld, y, y_ld, mean, inv, scale, shift, nb, hw, c, num_groups, splits,
-                              accum, st);
-}
-
-extern "C" int gv_bn_relu_bwd_sums_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
-                                           const float* z, int32_t z_ld, const float* mean, const float* inv,
-                                           int32_t nb, int32_t hw, int32_t c, int32_t num_groups, double* accum,
-                                           void* stream) {
-    return gv_bn_relu_bwd_sums_grouped_t(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, nb, hw, c, num_groups, accum, nullptr,
-                                         nullptr, GV_F32, stream);
-}
-
-extern "C" int gv_bn_relu_bwd_apply_grouped_t(const void* dy, int32_t dy_ld, const void* y, int32_t y_ld,
-                                              const void* z, int32_t z_ld, const float* mean, const float* inv,
-                                              const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
-                                              int32_t c, int32_t num_groups, const double* accum, void* dz,
-                                              int32_t dz_ld, float* dbeta, float* dgamma, const float* scale,
-                                              const float* shift, int32_t accumulate, int32_t dtype, void* stream) {
-    const int raw_z = (dtype & GV_ACCUM_RAW_Z) ? 1 : 0;          // (sum g*z accumulators: 16-bit storage only)
-    dtype &= ~GV_ACCUM_RAW_Z;
-    if ((scale == nullptr) != (shift == nullptr)) return GV_E_BADARG;
-    if (!storage_type(dtype) || (raw_z && dtype == GV_F32)) return GV_E_UNSUPPORTED;
-    if (!dy || !z || !mean || !inv || !counts || !accum || !dz) return GV_E_BADARG;
-    if (nb <= 0 || hw <= 0 || c <= 0 || num_groups <= 0 || nb % num_groups != 0) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    bool done = false;                                           // (the streaming kernel also sums dbeta / dgamma)
-    const int rc = gvlp::bn_bwd_apply_grouped(dtype, dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, accum, counts, scale,
-                                              shift, accumulate, nb, hw, c, num_groups, dz, dz_ld, dbeta, dgamma, &done,
-                                              st, raw_z);
-    if (rc != GV_OK) return rc;
-    if ((dbeta || dgamma) && !done)
-        hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, num_groups, c, dbeta,
-                           dgamma);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-extern "C" int gv_bn_relu_bwd_apply_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
-                                            const float* z, int32_t z_ld, const float* mean, const float* inv,
-                                            const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
-                                            int32_t c, int32_t num_groups, const double* accum, float* dz,
-                                            int32_t dz_ld, float* dbeta, float* dgamma, void* stream) {
-    return gv_bn_relu_bwd_apply_grouped_t(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, counts, nb, hw, c, num_groups,
-                                          accum, dz, dz_ld, dbeta, dgamma, nullptr, nullptr, 1, GV_F32, stream);
-}
-
-extern "C" int gv_bn_relu_bwd_grouped(const float* dy, int32_t dy_ld, const float* y, int32_t y_ld,
-                                      const float* z, int32_t z_ld, const float* mean, const float* inv,
-                                      const float* gamma, const int32_t* counts, int32_t nb, int32_t hw,
-                                      int32_t c, int32_t num_groups, double* accum, float* dz, int32_t dz_ld,
-                                      float* dbeta, float* dgamma, void* stream) {
-    const int rc = gv_bn_relu_bwd_sums_grouped(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, nb, hw, c, num_groups, accum,
-                                               stream);
-    if (rc != GV_OK) return rc;
-    return gv_bn_relu_bwd_apply_grouped(dy, dy_ld, y, y_ld, z, z_ld, mean, inv, gamma, counts, nb, hw, c, num_groups,
-                                        accum, dz, dz_ld, dbeta, dgamma, stream);
-}
-
 __global__ void scale_inplace_f32(float* __restrict__ x, int64_t n, float s) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] *= s;
@@ -605,37 +490,25 @@ extern "C" int gv_scale(float* x, int64_t n, float s, void* stream) {
 
 extern "C" int gv_accumulate_t(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int64_t npix, int32_t c,
                                int32_t dtype, void* stream) {
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!gv_storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!src || !dst || npix <= 0 || c <= 0 || src_ld < c || dst_ld < c) return GV_E_BADARG;
-    return gvlp::accumulate(dtype, src, src_ld, dst, dst_ld, npix, c, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    GV_ST_DISPATCH(dtype, {
+        constexpr int NE = 16 / sizeof(E);
+        if (c % NE == 0 && gv_vec_ok(src, src_ld, NE) && gv_vec_ok(dst, dst_ld, NE))
+            hipLaunchKernelGGL((accumulate_t<E, T, NE>), dim3(gv_grid_for(npix * (c / NE))), dim3(256), 0, st, (const E*)src,
+                               src_ld, (E*)dst, dst_ld, npix, c);
+        else
+            hipLaunchKernelGGL((accumulate_t<E, T, 1>), dim3(gv_grid_for(npix * c)), dim3(256), 0, st, (const E*)src, src_ld,
+                               (E*)dst, dst_ld, npix, c);
+        GV_LAUNCH_CHECK();
+        return GV_OK;
+    });
 }
 
 extern "C" int gv_accumulate(const float* src, int32_t src_ld, float* dst, int32_t dst_ld, int64_t npix,
                              int32_t c, void* stream) {
     return gv_accumulate_t(src, src_ld, dst, dst_ld, npix, c, GV_F32, stream);
-}
-
-extern "C" int gv_bias_grad_t(const void* dz, int32_t dz_ld, int64_t npix, int32_t c, double* accum, float* dbias,
-                              int32_t dtype, void* stream) {
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!dz || !accum || !dbias || npix <= 0 || c <= 0 || dz_ld < c || npix > 0x7fffffff) return GV_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    GV_HIP_CHECK(hipMemsetAsync(accum, 0, sizeof(double) * 2 * (size_t)c, st));
-    // the split count decides the last bits of the sums, so fp32 keeps the rule it has always had: 2048 pixels per
-    // workgroup, without the "at least ~1024 workgroups" term of sums_splits
-    const int most = gv_ceil_div(npix, 2048);
-    const int splits = dtype == GV_F32 ? (most < 1024 ? most : 1024) : sums_splits(npix, 1024);
-    const int rc = gvlp::grouped_sums(dtype, 2, nullptr, 0, dz, dz_ld, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                                      (int)npix, 1, c, 1, splits, accum, st);
-    if (rc != GV_OK) return rc;
-    hipLaunchKernelGGL(bn_param_grads, dim3((c + 255) / 256), dim3(256), 0, st, accum, 1, c, dbias, (float*)nullptr);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
-}
-
-extern "C" int gv_bias_grad(const float* dz, int32_t dz_ld, int64_t npix, int32_t c, double* accum,
-                            float* dbias, void* stream) {
-    return gv_bias_grad_t(dz, dz_ld, npix, c, accum, dbias, GV_F32, stream);
 }
 
 // The descriptor checks of the training pools (pool_train.hip), after an entry point's null pointers: dimensions, the pixel
@@ -647,7 +520,7 @@ static int pool_train_check(const gv_pool_desc* d, int mode, int ld0, int ld1, b
         (mode != GV_POOL_MAX && !(avg_ok && mode == GV_POOL_AVG)))
         return GV_E_BADARG;
     if (!gv_pool_geometry_ok(d)) return GV_E_BADARG;
-    if (!storage_type(d->dtype)) return GV_E_UNSUPPORTED;
+    if (!gv_storage_type(d->dtype)) return GV_E_UNSUPPORTED;
     return GV_OK;
 }
 
@@ -665,14 +538,6 @@ extern "C" int gv_pool2d_fwd_argmax(const gv_pool_desc* d, const void* x, void* 
     if (const int rc = pool_train_check(d, d->mode, d->x_ld, d->y_ld, false)) return rc;
     if (d->kh * d->kw > 255) return GV_E_UNSUPPORTED;               // the tap index is one byte
     return gvlp::pool2d_fwd_argmax(d, x, y, argmax, (hipStream_t)stream);
-}
-
-extern "C" int gv_bn_bwd_coeffs_t(const double* accum, const int32_t* counts, const float* mean, const float* inv,
-                                  const float* gamma, int32_t c, int32_t num_groups, int32_t raw_z, float* coef_a,
-                                  float* coef_b, float* coef_c, float* dbeta, float* dgamma, void* stream) {
-    if (!accum || !counts || !mean || !inv || !coef_a || !coef_b || !coef_c || c <= 0 || num_groups <= 0) return GV_E_BADARG;
-    return gvlp::bn_bwd_coeffs_launch(accum, counts, mean, inv, gamma, c, num_groups, raw_z ? 1 : 0, coef_a, coef_b, coef_c,
-                                      dbeta, dgamma, (hipStream_t)stream);
 }
 
 extern "C" int gv_pool2d_bwd_argmax_bn(const gv_pool_desc* d, const uint8_t* argmax, const void* dy, int32_t dy_ld,
@@ -697,16 +562,23 @@ extern "C" int gv_pool2d_bwd_argmax(const gv_pool_desc* d, const uint8_t* argmax
 
 // per_shape: every shape has its own scheme ([num_groups][num_views]) and weights ([num_groups]); else one for the batch
 extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t num_views, int32_t num_shapes,
-                                       int64_t E, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
+                                       int64_t n_elem, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
                                        int32_t num_groups, const float* weight, int32_t mode, void* dF,
                                        int32_t per_shape, int32_t dtype, void* stream) {
-    if (!storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!gv_storage_type(dtype)) return GV_E_UNSUPPORTED;
     if (!F || !dS || !scheme || !weight || !dF) return GV_E_BADARG;
-    if (num_views <= 0 || num_shapes <= 0 || E <= 0 || num_groups <= 0) return GV_E_BADARG;
+    if (num_views <= 0 || num_shapes <= 0 || n_elem <= 0 || num_groups <= 0) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
     const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
-    return gvlp::view_pool_fuse_bwd(dtype, F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups,
-                                    weight, mode, dF, (hipStream_t)stream, ss, ws);
+    int64_t bx = (n_elem + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    const dim3 grid((unsigned)bx, (unsigned)num_shapes);
+    GV_ST_DISPATCH(dtype, {
+        hipLaunchKernelGGL((view_pool_fuse_bwd_t<E, T>), grid, dim3(256), 0, (hipStream_t)stream, (const E*)F, dS, num_views,
+                           num_shapes, n_elem, view_stride, shape_stride, scheme, num_groups, weight, mode, (E*)dF, ss, ws);
+        GV_LAUNCH_CHECK();
+        return GV_OK;
+    });
 }
 
 extern "C" int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t num_views, int32_t num_shapes,

@@ -2,7 +2,7 @@
 //
 //   dW[tap][ci][co] += sum_m X[shift_tap(m)][ci] * dZ[m][co]          (train_utils.py:217-259)
 //
-// Same decomposition as conv_wgrad_lp (train_lp.hip): one TN GEMM per filter tap, a workgroup owns a (64 TI) x (64 TO)
+// Same decomposition as conv_wgrad_lp (wgrad_lp.hip): one TN GEMM per filter tap, a workgroup owns a (64 TI) x (64 TO)
 // tile of one tap and a slice of the pixels, slices combine with fp32 atomics, 2 x 2 waves of TI x TO accumulators,
 // fragments by ds_read_b64_tr_b16 (the reduction axis — pixels — is the strided one of both operands).  What changes
 // is how the operands reach LDS: global_load_lds_dwordx4 through a ring of ST stages of 32 pixels with counted vmcnt

@@ -1360,21 +1360,12 @@ class TrainGVCNN:
                 self.grads[op["name"] + "/gamma"] += ab[..., 1].sum(0).float()
             ab.zero_()
             dbeta = dgamma = None
-        def apply(flag):
-            return lib.gv_bn_relu_bwd_apply_grouped_t(
-                self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, *_bn_ptrs(st, "mean", "inv"),
-                gamma.data_ptr() if gamma is not None else None,
-                self._count(hw).data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), self._ptr(x, True), x.ld,
-                dbeta, dgamma, sc, sh, acc if self._lazy else 1, self.dt | flag, _st())
-        rc = apply(_lib.GV_ACCUM_RAW_Z if raw else 0)
-        if raw and rc == _lib.GV_E_UNSUPPORTED and self.bn_sync is None:
-            # the apply kernel cannot convert (sum g, sum g*z) for this geometry (its non-vector path): nothing was
-            # written — take the sums from the separate pass after all, and remember it for the next steps
-            accb[:2 * V * x.c].zero_()
-            sums(_lib.GV_ACCUM_ZEROED)
-            op["fused_b"]["_nofuse_b"] = True
-            rc = apply(0)
-        _lib.check(rc, "bn_bwd apply " + op["name"])
+        _lib.check(lib.gv_bn_relu_bwd_apply_grouped_t(
+            self._ptr(y, True), y.ld, yptr, y.ld, self._ptr(x), x.ld, *_bn_ptrs(st, "mean", "inv"),
+            gamma.data_ptr() if gamma is not None else None,
+            self._count(hw).data_ptr(), x.nb, hw, x.c, V, accb.data_ptr(), self._ptr(x, True), x.ld,
+            dbeta, dgamma, sc, sh, acc if self._lazy else 1, self.dt | (_lib.GV_ACCUM_RAW_Z if raw else 0), _st()),
+            "bn_bwd apply " + op["name"])
 
     def _bwd_conv(self, op, zeroed):
         dz = self._ptr(op["y"], True)

@@ -1,5 +1,5 @@
 """The grouping head's kernels over their launch geometries (csrc/grouping.hip, one template per op for every storage type;
-the element-wise ones in csrc/pool.hip, the pooling backward in csrc/train_lp.hip) against tests/head_ref.py: an fp64
+the element-wise ones in csrc/pool.hip, the pooling backward in csrc/train.hip) against tests/head_ref.py: an fp64
 restatement of the stored values, and an ordered fp32 one where the kernel fixes the order of its operations.
 
 Operands are slices of wider flat buffers (tests/slab.py): inputs surrounded by NaN, outputs by a sentinel.  Reductions also

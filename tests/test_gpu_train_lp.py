@@ -1,4 +1,5 @@
-"""Training step on 16-bit storage (BASELINE configs[2]: bf16 forward + backward; csrc/train_lp.hip).
+"""Training step on 16-bit storage (BASELINE configs[2]: bf16 forward + backward; csrc/bn_train.hip, csrc/wgrad_lp.hip,
+csrc/train.hip).
 
 Every storage-typed kernel is checked against torch autograd through the CPU oracle's ops ON THE SAME 16-bit
 representable inputs, so the only differences are the summation order (filter gradient, statistics) and the single
@@ -146,13 +147,16 @@ BN_CASES = {
     "H": (80, 4, 1, 1, 64, 64),        # 1 / 1: hw = 1 with 80 pixels per view: several lane steps of 16 / 32 images on every type
     "D": (40, 2, 2, 2, 72, 80),        # 2 / 2: hw = 4, 80 pixels per block
     "E": (6, 5, 3, 3, 136, 136),       # 1 / 1: hw = 9, five views, ragged third channel block
-    "F": (3, 4, 7, 7, 6, 7),           # 2 / -: no 16-byte walk: the scalar kernels of every type (their apply has a flat grid)
-    "I": (3, 4, 7, 7, 8, 9),           # 2 / -: the channels fill a quad but the leading dimension does not: the scalar kernels again
+    "F": (3, 4, 7, 7, 6, 7),           # 2 / 2: no 16-byte walk: the one-element walk of every type (64 channel threads x 4 pixel lanes)
+    "I": (3, 4, 7, 7, 8, 9),           # 2 / 2: the channels fill a quad but the leading dimension does not: one element again
+    "J": (24, 4, 1, 1, 8, 9),          # 1 / 1: hw = 1 on the one-element walk: every step of its 4 lanes hops images, 6 steps per lane
+    "K": (3, 4, 7, 7, 72, 73),         # 2 / 2: two channel blocks on the one-element walk, the second with 8 channels; two pixel splits
     "G": (2, 12, 25, 32, 2048, 2048),  # 3 / 3: 534 pixels per block (ragged last), block 1 crosses into the next image at
 }                                      #        pixel 800; 16-bit: 17 steps per lane = 4 unrolled trips + 1, the fold at step 12
 # (case, operands start 16 bytes into their buffers, storage); G has 39 M elements: bf16 and fp32 only
 BN_SWEEP = [(case, off, t) for case, off in [("A", 0), ("A", 1), ("B", 0), ("B", 1), ("C", 0), ("H", 0), ("D", 0), ("E", 0),
-                                             ("F", 0), ("I", 0), ("G", 0)] for t in BN_TYPES if (case, t) != ("G", "f16")]
+                                             ("F", 0), ("I", 0), ("J", 0), ("K", 0), ("G", 0)]
+            for t in BN_TYPES if (case, t) != ("G", "f16")]
 
 
 def _hold_totals(tag, what, acc, want0, want1):
@@ -185,21 +189,21 @@ def test_bn_kernels_over_their_launch_geometries_against_fp64(case, off, tname):
     gv_bn_relu_bwd_{sums,apply}_grouped_t on fp32, bf16 and fp16 storage at the geometries of BN_CASES — several pixel splits,
     blocks that start inside an image, several and ragged channel blocks, maps smaller than the pixel-lane count, the unrolled
     loop with its tail and fp32 fold, operands that are channel slices of wider buffers and start 16 bytes into them, the
-    scalar kernels — against the fp64 restatement of tests/bn_ref.py evaluated on the stored values, with and without gamma.
+    one-element walk — against the fp64 restatement of tests/bn_ref.py evaluated on the stored values, with and without gamma.
     The ReLU mask of the backward reference is taken as the kernel defines it (the stored y > 0, or float32(z*scale + shift)
     > 0 with the device's scale / shift).  Accumulators start as garbage (the sums clear them), dz / dbeta / dgamma start
     non-zero where the contract is +=, dz starts as NaN where it is stored, and nothing outside a slice may change.
 
     Measured worst case over all geometries (relative to the tensor's scale; bound):
                      fp32      bf16      fp16
-      mean           4.3e-8    4.4e-8    4.2e-8     (1e-5)
-      var            5.2e-8    7.4e-8    8.8e-8     (1e-5)
+      mean           5.1e-8    4.4e-8    4.2e-8     (1e-5)
+      var            5.2e-8    7.4e-8    9.8e-8     (1e-5)
       y              1.0e-7    3.5e-3    4.2e-4     (1e-5 / 2^-8 = 3.9e-3 / 2^-11 = 4.9e-4: half an ulp at the foot of a binade)
       dz             1.4e-7    3.8e-3    4.6e-4     (1e-4 / 2^-7 = 7.8e-3 / 2^-10 = 9.8e-4)
-      dz, F and I    1.2e-7    3.8e-3    4.3e-4     (the scalar apply of every type: 1 / m once, as the streaming kernel has it)
-      dbeta          8.4e-8    8.3e-8    9.1e-8     (1e-5)
-      dgamma         8.2e-8    1.0e-7    9.6e-8     (1e-4)
-      totals         8.0e-8    9.1e-8    9.2e-8     (1e-6; the backward ones carry the fp32 rounding of zhat)"""
+      dz, F I J K    9.6e-8    3.8e-3    4.3e-4     (the one-element walk of the apply kernel: the same A*g + B*z + C as its quad walk)
+      dbeta          8.4e-8    8.2e-8    9.1e-8     (1e-5)
+      dgamma         8.3e-8    1.0e-7    9.5e-8     (1e-4)
+      totals         8.1e-8    9.9e-8    1.4e-7     (1e-6; the backward ones carry the fp32 rounding of zhat)"""
     dt, tdt, tol_y, tol_dz = BN_TYPES[tname]
     N, V, h, w, c, ld = BN_CASES[case]
     nb, hw, npix = N * V, h * w, N * V * h * w
@@ -347,6 +351,103 @@ def test_bn_split_sums_do_not_depend_on_the_order_of_their_blocks(case, tname):
                                                    stt["shift"].data_ptr(), dt, st()), "bwd sums")
     assert torch.equal(accb[0], accb[1])
     _hold_totals("order %s %s" % (case, tname), "sum g,gzh", accb[0], rz["sum_g"], rz["sum_gzh"])
+
+
+@pytest.mark.parametrize("layout", ["ld9", "off1"])
+@pytest.mark.parametrize("tname", list(BN_TYPES))
+def test_bn_apply_does_not_depend_on_the_width_it_is_walked_at(tname, layout):
+    """The apply does not depend on the width it is walked at: the same stored z and dy, the same accumulators and the same
+    statistics, once in a layout the quad walk takes (c = 8, ld = 8, 16-byte aligned) and once in one it declines (ld = 9, or
+    the base one element off), give the same bits — y of gv_scale_shift_act_grouped_t, y and the five statistics of
+    gv_bn_finalize_apply_grouped_t, and dz (stored and accumulated), dbeta and dgamma of gv_bn_relu_bwd_apply_grouped_t with
+    the kept y, with the recomputed mask and, on 16-bit storage, with GV_ACCUM_RAW_Z accumulators.  Both layouts are fed from
+    ONE sums launch (the sums themselves depend on the thread layout, legitimately).  fp32 storage has no forward apply for
+    the second layout (GV_E_ALIGN), so it covers the backward, with the y of the first."""
+    dt, tdt, _, _ = BN_TYPES[tname]
+    N, V, h, w, c = 3, 4, 7, 7, 8
+    nb, hw, npix = N * V, h * w, N * V * h * w
+    L = lib()
+    g = torch.Generator(device=DEV).manual_seed(11)
+    zv = (torch.randn(npix, c, generator=g, device=DEV) * 2 + 0.5).to(tdt)
+    dyv = torch.randn(npix, c, generator=g, device=DEV).to(tdt)
+    pre = ((torch.rand(npix, c, generator=g, device=DEV) - 0.5) / 2).to(tdt)
+    beta, gamma = torch.randn(c, generator=g, device=DEV), torch.rand(c, generator=g, device=DEV) + 0.5
+    db0, dg0 = torch.randn(c, generator=g, device=DEV), torch.randn(c, generator=g, device=DEV)
+    counts = torch.full((V,), N * hw, dtype=torch.int32, device=DEV)
+    lays = [(8, 0), (9, 0) if layout == "ld9" else (8, 1)]          # (ld, element offset of the base)
+
+    def slab(lay, fill, values=None):
+        return _Slab(npix, c, lay[0], lay[1], tdt, fill, values)
+
+    def garbage():
+        return torch.full((V, c, 2), 1e30, dtype=torch.float64, device=DEV)
+
+    z, dy = [slab(lay, NAN, zv) for lay in lays], [slab(lay, NAN, dyv) for lay in lays]
+    assert z[0].ptr % 16 == 0 and dy[0].ptr % 16 == 0 and (z[1].ptr % 16 != 0 or layout == "ld9")
+    accum, stt = garbage(), _bn_stats(V, c)
+    _lib.check(L.gv_bn_sums_grouped_t(z[0].ptr, nb, hw, c, 8, V, accum.data_ptr(), dt, st()), "sums")
+    _lib.check(L.gv_bn_finalize_grouped(accum.data_ptr(), c, V, counts.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3,
+                                        stt["mean"].data_ptr(), stt["var"].data_ptr(), stt["inv"].data_ptr(),
+                                        stt["scale"].data_ptr(), stt["shift"].data_ptr(), st()), "finalize")
+    mean, inv, scale, shift = (stt[k].data_ptr() for k in ("mean", "inv", "scale", "shift"))
+    # ---- forward
+    ys, fused = [], []
+    for zz, (ld, _) in zip(z, lays):
+        y, y2, st2 = slab((ld, _), SENTINEL), slab((ld, _), SENTINEL), _bn_stats(V, c, 7.0)
+        rc = L.gv_scale_shift_act_grouped_t(zz.ptr, nb, hw, c, ld, scale, shift, V, 1, y.ptr, ld, dt, st())
+        rc2 = L.gv_bn_finalize_apply_grouped_t(accum.data_ptr(), counts.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3,
+                                               zz.ptr, nb, hw, c, ld, V, 1, y2.ptr, ld, st2["mean"].data_ptr(),
+                                               st2["var"].data_ptr(), st2["inv"].data_ptr(), st2["scale"].data_ptr(),
+                                               st2["shift"].data_ptr(), dt, st())
+        if dt == _lib.GV_F32 and zz is z[1]:
+            assert rc == _lib.GV_E_ALIGN and rc2 == _lib.GV_E_ALIGN
+            y.v.copy_(ys[0].v)                                   # (the kept activation of the backward below)
+        else:
+            _lib.check(rc, "apply")
+            _lib.check(rc2, "finalize + apply")
+            assert torch.equal(y2.buf, y.buf) and y.outside_intact()
+        for k in stt:
+            assert torch.equal(st2[k], stt[k]), k
+        ys.append(y)
+        fused.append(y2)
+    assert torch.equal(ys[1].v, ys[0].v)
+    if dt != _lib.GV_F32:
+        assert torch.equal(fused[1].v, fused[0].v)
+    # ---- backward: the sums once, from the first layout
+    acc_y, acc_z = garbage(), garbage()
+    _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy[0].ptr, 8, ys[0].ptr, 8, z[0].ptr, 8, mean, inv, nb, hw, c, V,
+                                               acc_y.data_ptr(), None, None, dt, st()), "bwd sums (kept y)")
+    _lib.check(L.gv_bn_relu_bwd_sums_grouped_t(dy[0].ptr, 8, None, 0, z[0].ptr, 8, mean, inv, nb, hw, c, V,
+                                               acc_z.data_ptr(), scale, shift, dt, st()), "bwd sums (mask from z)")
+    forms = [("kept y", acc_y, True, 0), ("mask from z", acc_z, False, 0)]
+    if dt != _lib.GV_F32:
+        # the raw accumulator a fused data gradient would have produced: sum g, sum g*z (test_gpu_bn_fusion.py)
+        zf, dyf = zv.double().reshape(nb, hw, c), dyv.double().reshape(nb, hw, c)
+        grp = torch.arange(nb, device=DEV) % V
+        gg = dyf * (zf * stt["scale"][grp][:, None, :].double() + stt["shift"][grp][:, None, :].double() > 0).double()
+        raw = torch.zeros(V, c, 2, dtype=torch.float64, device=DEV)
+        for v in range(V):
+            raw[v, :, 0] = gg[grp == v].reshape(-1, c).sum(0)
+            raw[v, :, 1] = (gg * zf)[grp == v].reshape(-1, c).sum(0)
+        forms.append(("raw z", raw, False, _lib.GV_ACCUM_RAW_Z))
+    for name, acc, kept, flag in forms:
+        for accumulate in (0, 1):
+            outs = []
+            for i, (ld, _) in enumerate(lays):
+                dz = slab(lays[i], SENTINEL, pre)
+                if not accumulate:
+                    dz.v.fill_(NAN)
+                dbeta, dgamma = db0.clone(), dg0.clone()
+                _lib.check(L.gv_bn_relu_bwd_apply_grouped_t(
+                    dy[i].ptr, ld, ys[i].ptr if kept else None, ld if kept else 0, z[i].ptr, ld, mean, inv, gamma.data_ptr(),
+                    counts.data_ptr(), nb, hw, c, V, acc.data_ptr(), dz.ptr, ld, dbeta.data_ptr(), dgamma.data_ptr(),
+                    None if kept else scale, None if kept else shift, accumulate, dt | flag, st()), "bwd apply (%s)" % name)
+                assert dz.outside_intact()
+                outs.append((dz.v.clone(), dbeta, dgamma))
+            what = "%s %s %s %s" % (tname, layout, name, "accumulated" if accumulate else "stored")
+            assert torch.equal(outs[1][0], outs[0][0]), "dz " + what          # (equal also says: no NaN left)
+            assert torch.equal(outs[1][1], outs[0][1]) and not torch.equal(outs[0][1], db0), "dbeta " + what
+            assert torch.equal(outs[1][2], outs[0][2]) and not torch.equal(outs[0][2], dg0), "dgamma " + what
 
 
 @pytest.mark.parametrize("dt,tdt,eps", TYPES)

@@ -11,7 +11,7 @@ FAM = [("conv fwd/dgrad, LDS-DMA tiles (conv_dma)", ("conv_dma",)),
        ("filter gradient, LDS-DMA (conv_wgrad_dma)", ("conv_wgrad_dma",)),
        ("filter gradient, tap per workgroup (conv_wgrad_lp)", ("conv_wgrad_lp",)),
        ("filter gradient, strip / stem forms", ("conv_wgrad_strip", "conv_wgrad_stem", "conv_wgrad_direct")),
-       ("BN sums (grouped_sums_v8)", ("grouped_sums",)), ("BN apply (bn_stream_v8)", ("bn_stream",)),
+       ("BN sums (bn_grouped_sums)", ("grouped_sums",)), ("BN apply (bn_stream)", ("bn_stream",)),
        ("max pools (argmax forward / backward, with the BatchNorm tail)", ("maxpool",)), ("other pools", ("pool2d", "avgpool"))]
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
 cnt = collections.defaultdict(int)
