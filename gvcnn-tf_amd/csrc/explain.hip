@@ -1,6 +1,7 @@
 // Why a shape got its class: per-view, per-pixel attribution of one logit through the head above the final tap
 // (view pooling -> group fusion -> global average pool -> Dense), with the grouping held constant as in the backward
-// pass (view_pool_fuse_bwd_t in train.hip: the tie rule and the order of the coefficient's operations are its).
+// pass (view_pool_fuse_bwd_t in grouping.hip: the tie rule and the order of the coefficient's operations are its; the
+// group table is the one both read, group_table.h).
 //
 //   dlogit_k/dF[n,v,p,c] = sum_{g contains v} ((w_g/W) * (K[c,k]/hw)) / ties_g(p,c)   where F[v] attains the maximum of g
 //                                                                     / |g|            mean pooling
@@ -27,6 +28,7 @@
 // exact reads F once; gradcam twice.
 #include <type_traits>
 
+#include "group_table.h"
 #include "lp_elem.h"
 
 namespace {
@@ -55,8 +57,8 @@ struct ExArgs {
     int nchunks;
 };
 
-// group tables in front of the dynamic LDS of explain_maps / explain_alpha: the groups' member masks and w_g / W
-constexpr size_t EX_TABLE_BYTES = 64 * (8 + 4);
+// the group table in front of the dynamic LDS of explain_maps / explain_alpha: masks, weights, W in a 16-byte slot
+constexpr size_t EX_TABLE_BYTES = 64 * (8 + 4) + 16;
 
 // fixed-order sum over the 64 lanes (butterfly: every lane ends with the same bits)
 __device__ __forceinline__ float ex_wave_sum(float x) {
@@ -92,28 +94,13 @@ __global__ void explain_targets(const float* __restrict__ logits, const long lon
     target_out[i] = k;
 }
 
-// Group tables of shape n in LDS: the members of every group as a mask of views, and w_g / W.  False when W == 0 (the
-// forward gives that shape S = 0).  Every thread of the workgroup calls it.
-__device__ __forceinline__ bool ex_groups(const ExArgs& a, int n, unsigned long long* gmask, float* cg) {
-    const int* scheme = a.scheme + (size_t)n * a.scheme_stride;
-    const float* weight = a.weight + (size_t)n * a.weight_stride;
-    for (int g = threadIdx.x; g < 64; g += blockDim.x) {
-        unsigned long long m = 0;
-        float w = 0.f;
-        if (g < a.G) {
-            for (int v = 0; v < a.V; ++v)
-                if (scheme[g * a.V + v] != 0) m |= 1ull << v;
-            w = weight[g];
-        }
-        gmask[g] = m;
-        cg[g] = w;
-    }
-    __syncthreads();
-    float ws = 0.f;
-    for (int g = 0; g < a.G; ++g) ws += cg[g];                  // the order of view_pool_fuse_bwd_t
-    __syncthreads();
+// The group table of shape n with its weights normalised: t.w[g] = w_g / W.  False when W == 0 (the forward gives that
+// shape S = 0; the weights stay as loaded).  Every thread of the workgroup calls it.
+__device__ __forceinline__ bool ex_groups(const ExArgs& a, int n, const GroupTable& t) {
+    group_table_load(t, a.scheme + (size_t)n * a.scheme_stride, a.weight + (size_t)n * a.weight_stride, a.G, a.V, false);
+    const float ws = *t.W;
     if (ws != 0.f)
-        for (int g = threadIdx.x; g < a.G; g += blockDim.x) cg[g] = cg[g] / ws;
+        for (int g = threadIdx.x; g < a.G; g += blockDim.x) t.w[g] = t.w[g] / ws;
     __syncthreads();
     return ws != 0.f;
 }
@@ -277,13 +264,13 @@ __device__ __forceinline__ void ex_column(const ExArgs& a, const unsigned long l
 template <typename E, typename T, int VEC>
 __global__ __launch_bounds__(256) void explain_maps(ExArgs a, int per_shift) {
     extern __shared__ unsigned long long lds64[];                // no static LDS: the dynamic limit may be the CU's whole 160 KB
-    unsigned long long* s_gmask = lds64;
-    float* s_cg = reinterpret_cast<float*>(lds64 + 64);
-    float* lds = s_cg + 64;                                      // (the tables: EX_TABLE_BYTES)
+    float* lds = reinterpret_cast<float*>(lds64 + 64);
+    const GroupTable tab = {lds64, lds, lds + 64};
+    lds += 64 + 4;                                               // (the table: EX_TABLE_BYTES)
     const int p = blockIdx.x, n = blockIdx.y, t = threadIdx.x, ch = blockDim.x;
     float* out = a.maps + ((size_t)n * a.V) * a.hw + p;
     const long long k = a.target[n];
-    const bool live = ex_groups(a, n, s_gmask, s_cg);
+    const bool live = ex_groups(a, n, tab);
     if (k < 0 || !live) {
         for (int v = t; v < a.V; v += ch) out[(size_t)v * a.hw] = 0.f;
         return;
@@ -303,7 +290,7 @@ __global__ __launch_bounds__(256) void explain_maps(ExArgs a, int per_shift) {
             ld.fetch(px + c0 + ch, a.V, a.vs, a.C - c0 - ch, per_shift);
             knext = c0 + ch + t < a.C ? a.K[(size_t)(c0 + ch + t) * a.num_classes + k] : 0.f;
         }
-        ex_column(a, s_gmask, s_cg, kc, slab + t, ch,
+        ex_column(a, tab.mask, tab.w, kc, slab + t, ch,
                   [&](auto b, auto nb, const auto& f, const auto& d) {
                       constexpr int NB = decltype(nb)::value;
                       float o[NB];
@@ -324,16 +311,16 @@ __global__ __launch_bounds__(256) void explain_maps(ExArgs a, int per_shift) {
 template <typename E, typename T, int VEC>
 __global__ __launch_bounds__(256) void explain_alpha(ExArgs a, int per_shift) {
     extern __shared__ unsigned long long lds64[];
-    unsigned long long* s_gmask = lds64;
-    float* s_cg = reinterpret_cast<float*>(lds64 + 64);
-    float* lds = s_cg + 64;                                      // (the tables: EX_TABLE_BYTES)
+    float* lds = reinterpret_cast<float*>(lds64 + 64);
+    const GroupTable tab = {lds64, lds, lds + 64};
+    lds += 64 + 4;                                               // (the table: EX_TABLE_BYTES)
     const int chunk = blockIdx.x, n = blockIdx.y, t = threadIdx.x, ch = blockDim.x;
     const int c0 = chunk * ch;
     const bool mine = c0 + t < a.C;
     float* alpha = a.alpha + ((size_t)n * a.V) * a.C + c0 + t;
     float* part = a.part + ((size_t)n * a.V) * a.nchunks + chunk;
     const long long k = a.target[n];
-    const bool live = ex_groups(a, n, s_gmask, s_cg);
+    const bool live = ex_groups(a, n, tab);
     if (k < 0 || !live) {
         if (mine)
             for (int v = 0; v < a.V; ++v) alpha[(size_t)v * a.C] = 0.f;
@@ -353,7 +340,7 @@ __global__ __launch_bounds__(256) void explain_alpha(ExArgs a, int per_shift) {
         ld.stage(base + (size_t)p * a.C, a.V, a.vs, cw, ch, per_shift, slab);
         __syncthreads();
         if (p + 1 < a.hw) ld.fetch(base + (size_t)(p + 1) * a.C, a.V, a.vs, cw, per_shift);
-        ex_column(a, s_gmask, s_cg, kc, slab + t, ch,
+        ex_column(a, tab.mask, tab.w, kc, slab + t, ch,
                   [&](auto b, auto nb, const auto& f, const auto& d) {
                       constexpr int NB = decltype(nb)::value;
                       float oa[NB], oc[NB];
@@ -412,8 +399,8 @@ __global__ __launch_bounds__(256) void explain_cam(ExArgs a) {
 // zeros there already).  Row V gives baseline[n] = b[k] + sum_{g empty} (w_g/W) * fill * sum_c K[c,k]: every thread sums
 // every 256th entry of the classifier column, the four waves' sums are added in wave order.
 __global__ __launch_bounds__(256) void explain_finish(ExArgs a, int from_part) {
-    __shared__ unsigned long long s_gmask[64];
-    __shared__ float s_cg[64], s_part[4];
+    GROUP_TABLE_SHARED(tab);
+    __shared__ float s_part[4];
     const int n = blockIdx.x, v = blockIdx.y, t = threadIdx.x;
     if (v < a.V) {
         if (t >= 64) return;
@@ -433,7 +420,7 @@ __global__ __launch_bounds__(256) void explain_finish(ExArgs a, int from_part) {
     }
     ksum = ex_wave_sum(ksum);
     if ((t & 63) == 0) s_part[t >> 6] = ksum;
-    const bool live = ex_groups(a, n, s_gmask, s_cg);           // (its barriers publish s_part too)
+    const bool live = ex_groups(a, n, tab);                     // (its barriers publish s_part too)
     if (t == 0) {
         float b = 0.f;
         if (k >= 0) {
@@ -441,7 +428,7 @@ __global__ __launch_bounds__(256) void explain_finish(ExArgs a, int from_part) {
             ksum = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
             if (live)
                 for (int g = 0; g < a.G; ++g)
-                    if (s_gmask[g] == 0) b += s_cg[g] * a.fill * ksum;
+                    if (tab.mask[g] == 0) b += tab.w[g] * a.fill * ksum;
         }
         a.baseline[n] = b;
     }

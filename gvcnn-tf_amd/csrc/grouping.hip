@@ -1,10 +1,10 @@
-// grouping.hip — the grouping module of nets/model.py on device (the scorer partial and the view pool + fusion for every
-// storage type; the rest is fp32).
+// grouping.hip — the grouping module of nets/model.py on device, forward and backward (the scorer partial and the view
+// pool + fusion with its backward for every storage type; the rest is fp32).
 //
 //   scorer            model.py:144-147   GAP -> Dense(1) per view -> batch mean -> sigmoid(log|.|)
 //   group assignment  model.py:16-41     bin = (int)(score * 10f) ; weight = 1 + count
 //   view pooling      model.py:44-74     per group: max over its views, ones when empty
-//   group fusion      model.py:77-102    sum_g w_g D_g / sum_g w_g
+//   group fusion      model.py:77-102    sum_g w_g D_g / sum_g w_g          (the group table and D_g: group_table.h)
 //   classifier        model.py:163-164   GAP -> Dense(C)
 //
 // The reference computes scheme/weight with host numpy between two partial_run calls
@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "gv_common.h"
+#include "group_table.h"
 #include "lp_elem.h"
 
 namespace {
@@ -101,6 +102,12 @@ __global__ __launch_bounds__(256) void view_score_partial(const E* __restrict__ 
     if (threadIdx.x == 0) r_img[b] = (part[0] + part[1] + part[2] + part[3]) / (float)hw + bias[v];
 }
 
+// sigmoid(log|r|) (model.py:147); r == 0 -> log = -inf -> score 0
+__device__ __forceinline__ float view_score(float r) {
+    const float lg = logf(fabsf(r));
+    return 1.0f / (1.0f + expf(-lg));
+}
+
 // score[v] = sigmoid(log(|mean_n r_img[b(n,v)]|)); one thread per view, n ascending.
 __global__ void view_score_finalize_f32(const float* __restrict__ r_img, int num_shapes, int num_views,
                                         int order, float* __restrict__ scores) {
@@ -109,20 +116,31 @@ __global__ void view_score_finalize_f32(const float* __restrict__ r_img, int num
     float s = 0.f;
     for (int n = 0; n < num_shapes; ++n)
         s += r_img[order == GV_ORDER_SHAPE_MAJOR ? n * num_views + v : v * num_shapes + n];
-    const float r = fabsf(s / (float)num_shapes);
-    const float lg = logf(r);                        // r == 0 -> -inf -> score 0
-    scores[v] = 1.0f / (1.0f + expf(-lg));
+    scores[v] = view_score(s / (float)num_shapes);
 }
 
-// One workgroup.  Integer path: must be bit-exact with numpy's int(np.float32(score) * 10).
-__global__ __launch_bounds__(64) void group_assign_kernel(const float* __restrict__ scores, int V, int G,
-                                                          int num_bins, int* __restrict__ gidx,
-                                                          int* __restrict__ scheme,
-                                                          float* __restrict__ weight,
-                                                          int* __restrict__ status) {
+// sigmoid(log|r|) per image (the paper's per-shape scorer; model.py:147 without the batch mean of :146)
+__global__ void view_score_per_shape_f32(const float* __restrict__ r_img, int nb, float* __restrict__ scores) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    scores[b] = view_score(r_img[b]);
+}
+
+// One workgroup per scheme (a batch-level call has one, a per-shape call one per shape).  Integer path: must be bit-exact
+// with numpy's int(np.float32(score) * 10).  Status bits: 1 a bin outside [0, G), 2 a NaN score; or_status: the word was
+// cleared before the launch and every workgroup ORs its bits in, else the one workgroup overwrites it.
+__global__ __launch_bounds__(64) void group_assign_kernel(const float* __restrict__ scores, int V, int G, int num_bins,
+                                                          int weight_mode, int* __restrict__ gidx,
+                                                          int* __restrict__ scheme, float* __restrict__ weight,
+                                                          int* __restrict__ status, int or_status) {
     __shared__ int s_gidx[64];
+    __shared__ float s_score[64];
     __shared__ int s_status;
-    const int t = threadIdx.x;
+    const int n = blockIdx.x, t = threadIdx.x;
+    scores += (size_t)n * V;
+    gidx += (size_t)n * V;
+    scheme += (size_t)n * G * V;
+    weight += (size_t)n * G;
     if (t == 0) s_status = 0;
     __syncthreads();
     if (t < V) {
@@ -132,6 +150,7 @@ __global__ __launch_bounds__(64) void group_assign_kernel(const float* __restric
         if (sc != sc) { atomicOr(&s_status, 2); b = -1; }
         else if (b >= G || b < 0 || prod >= 2147483648.0f) { atomicOr(&s_status, 1); if (prod >= 2147483648.0f) b = 0x7fffffff; }
         s_gidx[t] = b;
+        s_score[t] = sc;
         gidx[t] = b;
     }
     __syncthreads();
@@ -140,11 +159,17 @@ __global__ __launch_bounds__(64) void group_assign_kernel(const float* __restric
         scheme[i] = (s_gidx[v] == g) ? 1 : 0;
     }
     for (int g = t; g < G; g += 64) {
-        int cnt = 1;                                          // model.py:32 `sum = 1`
-        for (int v = 0; v < V; ++v) cnt += (s_gidx[v] == g) ? 1 : 0;
-        weight[g] = (float)cnt;
+        int cnt = 0;
+        float sum = 0.f;
+        for (int v = 0; v < V; ++v)
+            if (s_gidx[v] == g) { ++cnt; sum = __fadd_rn(sum, s_score[v]); }      // view order: reproducible
+        // GV_WEIGHT_COUNT: model.py:32 `sum = 1`
+        weight[g] = weight_mode == GV_WEIGHT_COUNT ? (float)(1 + cnt) : (cnt ? __fdiv_rn(sum, (float)cnt) : 0.f);
     }
-    if (t == 0) *status = s_status;
+    if (t == 0) {
+        if (!or_status) *status = s_status;
+        else if (s_status) atomicOr(status, s_status);
+    }
 }
 
 __global__ void group_weight_kernel(const int* __restrict__ scheme, int G, int V, float* __restrict__ weight) {
@@ -158,8 +183,8 @@ __global__ void group_weight_kernel(const int* __restrict__ scheme, int G, int V
 // Fused view pooling + group fusion.  Thread per (shape n, VEC consecutive descriptor elements).
 // Group membership is turned into per-group 64-bit view masks held in LDS; each view of each
 // group is loaded once, so a one-hot scheme costs exactly V loads per output element.
-// Order of the fp32 operations (numpy float32 reproduces it bit for bit): mean = views added in ascending v, one division
-// by the count; S = fl(w_g * D_g) added in ascending g, one division by wsum (the ascending sum of the weights).  The
+// Order of the fp32 operations (numpy float32 reproduces it bit for bit): D_g and wsum as group_table.h forms them;
+// S = fl(w_g * D_g) added in ascending g, one division by wsum.  The
 // header's __fmul_rn / __fadd_rn are plain operators that hipcc contracts into one FMA by default, wherever they are called
 // from (render.hip), so the kernel body turns contraction off and spells the fusion with plain operators: the product is
 // rounded before it is added, as tf.multiply + tf.add_n round it.
@@ -173,27 +198,10 @@ __global__ __launch_bounds__(256) void view_pool_fuse(const typename A::elem* __
                                                       int64_t scheme_stride, int64_t weight_stride) {
 #pragma clang fp contract(off)
     constexpr int VEC = A::N;
-    __shared__ unsigned long long s_mask[64];
-    __shared__ float s_w[64];
-    __shared__ float s_wsum;
+    GROUP_TABLE_SHARED(tab);
     const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
-    scheme += (size_t)n * scheme_stride;
-    weight += (size_t)n * weight_stride;
-    for (int g = threadIdx.x; g < G; g += 256) {
-        unsigned long long m = 0;
-        for (int v = 0; v < V; ++v)
-            if (scheme[g * V + v] != 0) m |= 1ull << v;
-        s_mask[g] = m;
-        s_w[g] = weight[g];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ws = 0.f;
-        for (int g = 0; g < G; ++g) ws = __fadd_rn(ws, s_w[g]);   // tf.reduce_sum(group_weight_list)
-        s_wsum = ws;
-    }
-    __syncthreads();
-    const float wsum = s_wsum;
+    group_table_load<256>(tab, scheme + (size_t)n * scheme_stride, weight + (size_t)n * weight_stride, G, V, false);
+    const float wsum = *tab.W;
     const int64_t eg = E / VEC;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < eg;
          idx += (int64_t)gridDim.x * blockDim.x) {
@@ -203,32 +211,16 @@ __global__ __launch_bounds__(256) void view_pool_fuse(const typename A::elem* __
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
         for (int g = 0; g < G; ++g) {
-            unsigned long long m = s_mask[g];
+            const unsigned long long m = tab.mask[g];
             float d[VEC];
             if (m == 0) {
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) d[k] = fill;
             } else {
-                const int cnt = __popcll(m);
-                int v = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                A::load(base + (size_t)v * view_stride, 0, 0, 0, d);
-                while (m) {
-                    v = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    float x[VEC];
-                    A::load(base + (size_t)v * view_stride, 0, 0, 0, x);
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) d[k] = mode == GV_VIEWPOOL_MAX ? fmaxf(d[k], x[k]) : d[k] + x[k];
-                }
-                if (mode == GV_VIEWPOOL_MEAN) {
-                    const float c = (float)cnt;
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) d[k] = d[k] / c;
-                }
+                pooled_group<A>(base, view_stride, m, mode, d);
             }
             if (D) A::store(D + ((size_t)g * N + n) * E + e, 0, 0, 0, d);
-            const float w = s_w[g];
+            const float w = tab.w[g];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = acc[k] + w * d[k];   // multiply, add_n: two roundings (contraction is off)
         }
@@ -236,6 +228,50 @@ __global__ __launch_bounds__(256) void view_pool_fuse(const typename A::elem* __
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = wsum != 0.f ? __fdiv_rn(acc[k], wsum) : 0.f;   // tf.div
             A::store(S + (size_t)n * E + e, 0, 0, 0, acc);
+        }
+    }
+}
+
+// The backward of view_pool_fuse (nets/model.py:44-102):
+// dF[v] += w_g/sum(w) * dS / (#views of g tied at the maximum) for every view of g attaining the maximum
+// (tf.reduce_max splits the gradient equally among ties); mean pooling: w_g/sum(w) * dS / |g|.
+// F and dF in the storage type (SE the element in HBM, T the type it stands for), dS in fp32.
+template <typename SE, typename T>
+__global__ __launch_bounds__(256) void view_pool_fuse_bwd_t(
+    const SE* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
+    int64_t shape_stride, const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode,
+    SE* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
+    GROUP_TABLE_SHARED(tab);
+    const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
+    group_table_load<256>(tab, scheme + (size_t)n * scheme_stride, weight + (size_t)n * weight_stride, G, V, false);
+    const float wsum = *tab.W;
+    if (wsum == 0.f) return;                       // (per-shape, mean-score weights) S = 0 for this shape: no gradient
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+        const size_t base = (size_t)n * shape_stride + e;
+        const float ds = dS[(size_t)n * E + e];
+        for (int g = 0; g < G; ++g) {
+            const unsigned long long m0 = tab.mask[g];
+            if (m0 == 0) continue;
+            const float coef = tab.w[g] / wsum * ds;
+            if (mode == GV_VIEWPOOL_MEAN) {
+                const float each = coef / (float)__popcll(m0);
+                for (unsigned long long m = m0; m; m &= m - 1) {
+                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
+                    dF[a] = down<T>(up<T>(dF[a]) + each);
+                }
+            } else {
+                float best = -INFINITY;
+                for (unsigned long long m = m0; m; m &= m - 1)
+                    best = fmaxf(best, up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]));
+                int ties = 0;
+                for (unsigned long long m = m0; m; m &= m - 1)
+                    ties += up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]) == best;
+                const float each = coef / (float)ties;
+                for (unsigned long long m = m0; m; m &= m - 1) {
+                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
+                    if (up<T>(F[a]) == best) dF[a] = down<T>(up<T>(dF[a]) + each);
+                }
+            }
         }
     }
 }
@@ -282,16 +318,22 @@ extern "C" int gv_view_score_finalize(const float* r_img, int32_t num_shapes, in
     return GV_OK;
 }
 
+// the checks of both assign entry points are done: one workgroup per scheme
+static int assign_launch(const float* scores, int num_schemes, int V, int G, int num_bins, int weight_mode, int32_t* gidx,
+                         int32_t* scheme, float* weight, int32_t* status, int or_status, void* stream) {
+    hipLaunchKernelGGL(group_assign_kernel, dim3(num_schemes), dim3(64), 0, (hipStream_t)stream, scores, V, G, num_bins,
+                       weight_mode, gidx, scheme, weight, status, or_status);
+    GV_LAUNCH_CHECK();
+    return GV_OK;
+}
+
 extern "C" int gv_group_assign(const float* scores, int32_t num_views, int32_t num_groups,
                                int32_t num_bins, int32_t* gidx, int32_t* scheme, float* weight,
                                int32_t* status, void* stream) {
     if (!scores || !gidx || !scheme || !weight || !status) return GV_E_BADARG;
     if (num_views <= 0 || num_groups <= 0 || num_bins <= 0) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64) return GV_E_UNSUPPORTED;
-    hipLaunchKernelGGL(group_assign_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scores,
-                       num_views, num_groups, num_bins, gidx, scheme, weight, status);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return assign_launch(scores, 1, num_views, num_groups, num_bins, GV_WEIGHT_COUNT, gidx, scheme, weight, status, 0, stream);
 }
 
 extern "C" int gv_group_weight(const int32_t* scheme, int32_t num_groups, int32_t num_views,
@@ -347,12 +389,41 @@ extern "C" int gv_view_pool_fuse_fwd_per_shape(const void* F, int32_t num_views,
                             empty_fill, D, S, dtype, stream, (int64_t)num_groups * num_views, num_groups);
 }
 
-// sigmoid(log|r|) per image (the paper's per-shape scorer; model.py:147 without the batch mean of :146)
-__global__ void view_score_per_shape_f32(const float* __restrict__ r_img, int nb, float* __restrict__ scores) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    const float lg = logf(fabsf(r_img[b]));
-    scores[b] = 1.0f / (1.0f + expf(-lg));
+// per_shape: every shape has its own scheme ([num_groups][num_views]) and weights ([num_groups]); else one for the batch
+extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t num_views, int32_t num_shapes,
+                                       int64_t n_elem, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
+                                       int32_t num_groups, const float* weight, int32_t mode, void* dF,
+                                       int32_t per_shape, int32_t dtype, void* stream) {
+    if (!gv_storage_type(dtype)) return GV_E_UNSUPPORTED;
+    if (!F || !dS || !scheme || !weight || !dF) return GV_E_BADARG;
+    if (num_views <= 0 || num_shapes <= 0 || n_elem <= 0 || num_groups <= 0) return GV_E_BADARG;
+    if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
+    const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
+    int64_t bx = (n_elem + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    const dim3 grid((unsigned)bx, (unsigned)num_shapes);
+    GV_ST_DISPATCH(dtype, {
+        hipLaunchKernelGGL((view_pool_fuse_bwd_t<E, T>), grid, dim3(256), 0, (hipStream_t)stream, (const E*)F, dS, num_views,
+                           num_shapes, n_elem, view_stride, shape_stride, scheme, num_groups, weight, mode, (E*)dF, ss, ws);
+        GV_LAUNCH_CHECK();
+        return GV_OK;
+    });
+}
+
+extern "C" int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t num_views, int32_t num_shapes,
+                                     int64_t E, int64_t view_stride, int64_t shape_stride,
+                                     const int32_t* scheme, int32_t num_groups, const float* weight,
+                                     int32_t mode, float* dF, void* stream) {
+    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
+                                   mode, dF, 0, GV_F32, stream);
+}
+
+extern "C" int gv_view_pool_fuse_bwd_per_shape(const float* F, const float* dS, int32_t num_views,
+                                               int32_t num_shapes, int64_t E, int64_t view_stride,
+                                               int64_t shape_stride, const int32_t* scheme, int32_t num_groups,
+                                               const float* weight, int32_t mode, float* dF, void* stream) {
+    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
+                                   mode, dF, 1, GV_F32, stream);
 }
 
 extern "C" int gv_view_score_per_shape(const float* r_img, int32_t nb, float* scores, void* stream) {
@@ -363,43 +434,6 @@ extern "C" int gv_view_score_per_shape(const float* r_img, int32_t nb, float* sc
     return GV_OK;
 }
 
-// one workgroup per shape: binning exactly as group_assign_kernel
-__global__ __launch_bounds__(64) void group_assign_per_shape_kernel(const float* __restrict__ scores, int V, int G,
-                                                                    int num_bins, int weight_mode,
-                                                                    int* __restrict__ gidx, int* __restrict__ scheme,
-                                                                    float* __restrict__ weight,
-                                                                    int* __restrict__ status) {
-    __shared__ int s_gidx[64];
-    __shared__ float s_score[64];
-    const int n = blockIdx.x, t = threadIdx.x;
-    scores += (size_t)n * V;
-    gidx += (size_t)n * V;
-    scheme += (size_t)n * G * V;
-    weight += (size_t)n * G;
-    if (t < V) {
-        const float sc = scores[t];
-        const float prod = __fmul_rn(sc, (float)num_bins);
-        int b = (int)prod;
-        if (sc != sc) { atomicOr(status, 2); b = -1; }
-        else if (b >= G || b < 0 || prod >= 2147483648.0f) { atomicOr(status, 1); if (prod >= 2147483648.0f) b = 0x7fffffff; }
-        s_gidx[t] = b;
-        s_score[t] = sc;
-        gidx[t] = b;
-    }
-    __syncthreads();
-    for (int i = t; i < G * V; i += 64) {
-        const int g = i / V, v = i - g * V;
-        scheme[i] = (s_gidx[v] == g) ? 1 : 0;
-    }
-    for (int g = t; g < G; g += 64) {
-        int cnt = 0;
-        float sum = 0.f;
-        for (int v = 0; v < V; ++v)
-            if (s_gidx[v] == g) { ++cnt; sum = __fadd_rn(sum, s_score[v]); }      // view order: reproducible
-        weight[g] = weight_mode == GV_WEIGHT_COUNT ? (float)(1 + cnt) : (cnt ? __fdiv_rn(sum, (float)cnt) : 0.f);
-    }
-}
-
 extern "C" int gv_group_assign_per_shape(const float* scores, int32_t num_shapes, int32_t num_views,
                                          int32_t num_groups, int32_t num_bins, int32_t weight_mode, int32_t* gidx,
                                          int32_t* scheme, float* weight, int32_t* status, void* stream) {
@@ -408,10 +442,8 @@ extern "C" int gv_group_assign_per_shape(const float* scores, int32_t num_shapes
     if (weight_mode != GV_WEIGHT_COUNT && weight_mode != GV_WEIGHT_MEAN_SCORE) return GV_E_BADARG;
     if (num_views > 64 || num_groups > 64) return GV_E_UNSUPPORTED;
     GV_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
-    hipLaunchKernelGGL(group_assign_per_shape_kernel, dim3(num_shapes), dim3(64), 0, (hipStream_t)stream, scores,
-                       num_views, num_groups, num_bins, weight_mode, gidx, scheme, weight, status);
-    GV_LAUNCH_CHECK();
-    return GV_OK;
+    return assign_launch(scores, num_shapes, num_views, num_groups, num_bins, weight_mode, gidx, scheme, weight, status, 1,
+                         stream);
 }
 
 // eval.py:94-99: argmax, correct count, confusion matrix; one thread per shape

@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "gv_common.h"
+#include "group_table.h"
 #include "lp_elem.h"
 
 namespace {
@@ -21,76 +22,37 @@ using namespace gvlp_elem;
 
 constexpr int kGwChunk = 256;                         // element vectors per workgroup of group_weight_bwd (one per thread)
 
-// D_g of one element vector, exactly as view_pool_fuse (grouping.hip) forms it (m != 0)
-template <typename T, int VEC, typename E>
-__device__ __forceinline__ void pooled_group(const E* base, int64_t view_stride, unsigned long long m, int mode,
-                                             float (&d)[8]) {
-    const int cnt = __popcll(m);
-    int v = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    load_v<T, VEC>(base + (size_t)v * view_stride, d);
-    while (m) {
-        v = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        float x[8];
-        load_v<T, VEC>(base + (size_t)v * view_stride, x);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) d[k] = mode == GV_VIEWPOOL_MAX ? fmaxf(d[k], x[k]) : d[k] + x[k];
-    }
-    if (mode == GV_VIEWPOOL_MEAN) {
-        const float c = (float)cnt;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) d[k] = d[k] / c;
-    }
-}
-
 // Workgroup (chunk, n): ws[n][chunk][g] = sum over the chunk's elements of dS_e (D_{g,e} - S_e), S recomputed in
-// registers with the forward kernel's arithmetic (first pass over the groups), D_g formed a second time for the
-// difference (the V vectors of a thread come from cache then).  Empty groups: 0 (their weight is 0 in this form, so
-// the fill value never enters S).
+// registers from the forward kernel's group table and D_g (group_table.h; first pass over the groups), D_g formed a
+// second time for the difference (the V vectors of a thread come from cache then).  Empty groups: 0 (their weight is 0
+// in this form, so the fill value never enters S).
 template <typename T, int VEC, typename E>
 __global__ __launch_bounds__(256) void group_weight_bwd_kernel(const E* __restrict__ F, const float* __restrict__ dS, int V,
                                                                int64_t E_, int64_t view_stride, int64_t shape_stride,
                                                                const int* __restrict__ scheme, int G,
                                                                const float* __restrict__ weight, int mode,
                                                                float* __restrict__ ws) {
-    __shared__ unsigned long long s_mask[64];
-    __shared__ float s_w[64];
-    __shared__ float s_wsum;
+    using A = Px<E, T, VEC>;
+    GROUP_TABLE_SHARED(tab);
     __shared__ float s_part[64][4];
     const int n = blockIdx.y;
-    scheme += (size_t)n * G * V;
-    weight += (size_t)n * G;
-    for (int g = threadIdx.x; g < G; g += 256) {
-        unsigned long long m = 0;
-        for (int v = 0; v < V; ++v)
-            if (scheme[g * V + v] != 0) m |= 1ull << v;
-        s_mask[g] = m;
-        s_w[g] = m ? weight[g] : 0.f;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float w = 0.f;
-        for (int g = 0; g < G; ++g) w = __fadd_rn(w, s_w[g]);
-        s_wsum = w;
-    }
-    __syncthreads();
-    const float wsum = s_wsum;
+    group_table_load<256>(tab, scheme + (size_t)n * G * V, weight + (size_t)n * G, G, V, true);
+    const float wsum = *tab.W;
     const int64_t eg = E_ / VEC;
     const int64_t idx = (int64_t)blockIdx.x * kGwChunk + threadIdx.x;
     const bool live = idx < eg;                                   // (the last chunk is ragged: idle threads add 0)
     const int64_t e = live ? idx * VEC : 0;
     const E* base = F + (size_t)n * shape_stride + e;
-    float s[8], ds[8];
+    float s[VEC], ds[VEC];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = ds[k] = 0.f;
+    for (int k = 0; k < VEC; ++k) s[k] = ds[k] = 0.f;
     if (live) {
         for (int g = 0; g < G; ++g) {
-            const unsigned long long m = s_mask[g];
+            const unsigned long long m = tab.mask[g];
             if (m == 0) continue;
-            float d[8];
-            pooled_group<T, VEC>(base, view_stride, m, mode, d);
-            const float w = s_w[g];
+            float d[VEC];
+            pooled_group<A>(base, view_stride, m, mode, d);
+            const float w = tab.w[g];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) s[k] = __fadd_rn(s[k], __fmul_rn(w, d[k]));
         }
@@ -108,13 +70,13 @@ __global__ __launch_bounds__(256) void group_weight_bwd_kernel(const E* __restri
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int g = 0; g < G; ++g) {                                 // (s_mask is uniform: no divergence around the shuffles)
-        const unsigned long long m = s_mask[g];
+    for (int g = 0; g < G; ++g) {                                 // (the mask is uniform: no divergence around the shuffles)
+        const unsigned long long m = tab.mask[g];
         float t = 0.f;
         if (m != 0) {
             if (live) {
-                float d[8];
-                pooled_group<T, VEC>(base, view_stride, m, mode, d);
+                float d[VEC];
+                pooled_group<A>(base, view_stride, m, mode, d);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) t += ds[k] * (d[k] - s[k]);
             }
@@ -133,26 +95,14 @@ __global__ __launch_bounds__(256) void group_weight_bwd_kernel(const E* __restri
 __global__ __launch_bounds__(64) void group_weight_bwd_finish(const float* __restrict__ ws, int chunks,
                                                               const int* __restrict__ scheme, int V, int G,
                                                               const float* __restrict__ weight, float* __restrict__ dw) {
-    __shared__ float s_w[64];
-    __shared__ float s_wsum;
+    GROUP_TABLE_SHARED(tab);
     const int n = blockIdx.x, g = threadIdx.x;
-    bool member = false;
-    if (g < G) {
-        for (int v = 0; v < V; ++v) member |= scheme[((size_t)n * G + g) * V + v] != 0;
-        s_w[g] = member ? weight[(size_t)n * G + g] : 0.f;
-    }
-    __syncthreads();
-    if (g == 0) {
-        float w = 0.f;
-        for (int i = 0; i < G; ++i) w = __fadd_rn(w, s_w[i]);
-        s_wsum = w;
-    }
-    __syncthreads();
+    group_table_load<64>(tab, scheme + (size_t)n * G * V, weight + (size_t)n * G, G, V, true);
     if (g >= G) return;
-    const float wsum = s_wsum;
+    const float wsum = *tab.W;
     float t = 0.f;
     for (int c = 0; c < chunks; ++c) t += ws[((size_t)n * chunks + c) * G + g];
-    dw[(size_t)n * G + g] = (member && wsum != 0.f) ? t / wsum : 0.f;
+    dw[(size_t)n * G + g] = (tab.mask[g] != 0 && wsum != 0.f) ? t / wsum : 0.f;
 }
 
 // dL/dr of image (n, v): the members of v's group are counted from gidx; a view in no group (gidx outside [0, G):

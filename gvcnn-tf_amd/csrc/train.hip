@@ -1,9 +1,9 @@
 // train.hip — kernels that exist only for the training step of the hot path: the backward of the
 // forward ops, the loss (train.py:145) and the Momentum update (train.py:171).  This file holds the extern "C" entry
-// points of the step other than the train-mode BatchNorm's (bn_train.hip), the kernels of the small ops (accumulate and
-// the view-pool backward for every storage type; BatchNorm moving averages, loss, dense backward, optimizer in fp32) and
-// the fp32-MFMA filter gradient.  The training pools and the 16-bit filter gradient are checked here and launched by
-// gvlp:: in pool_train.hip, wgrad_lp.hip and wgrad_dma.hip.
+// points of the step other than the train-mode BatchNorm's (bn_train.hip) and the view pool's (grouping.hip, next to its
+// forward), the kernels of the small ops (accumulate for every storage type; BatchNorm moving averages, loss, dense
+// backward, optimizer in fp32) and the fp32-MFMA filter gradient.  The training pools and the 16-bit filter gradient are
+// checked here and launched by gvlp:: in pool_train.hip, wgrad_lp.hip and wgrad_dma.hip.
 #include <math.h>
 
 #include "gv_common.h"
@@ -33,66 +33,6 @@ __global__ __launch_bounds__(256) void accumulate_t(const E* __restrict__ src, i
 #pragma unroll
         for (int e = 0; e < VEC; ++e) b[e] += a[e];
         store_v<T, VEC>(dst + pix * dst_ld + q * VEC, b);
-    }
-}
-
-// ---- grouping module backward (nets/model.py:44-102) ------------------------------------------------
-// dF[v] += w_g/sum(w) * dS / (#views of g tied at the maximum) for every view of g attaining the maximum
-// (tf.reduce_max splits the gradient equally among ties); mean pooling: w_g/sum(w) * dS / |g|.
-// F and dF in the storage type (SE the element in HBM, T the type it stands for), dS in fp32.
-template <typename SE, typename T>
-__global__ __launch_bounds__(256) void view_pool_fuse_bwd_t(
-    const SE* __restrict__ F, const float* __restrict__ dS, int V, int N, int64_t E, int64_t view_stride,
-    int64_t shape_stride, const int* __restrict__ scheme, int G, const float* __restrict__ weight, int mode,
-    SE* __restrict__ dF, int64_t scheme_stride, int64_t weight_stride) {
-    __shared__ unsigned long long s_mask[64];
-    __shared__ float s_w[64];
-    __shared__ float s_wsum;
-    const int n = blockIdx.y;                       // one shape per grid row: its own scheme when strides != 0
-    scheme += (size_t)n * scheme_stride;
-    weight += (size_t)n * weight_stride;
-    for (int g = threadIdx.x; g < G; g += 256) {
-        unsigned long long m = 0;
-        for (int v = 0; v < V; ++v)
-            if (scheme[g * V + v] != 0) m |= 1ull << v;
-        s_mask[g] = m;
-        s_w[g] = weight[g];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ws = 0.f;
-        for (int g = 0; g < G; ++g) ws += s_w[g];
-        s_wsum = ws;
-    }
-    __syncthreads();
-    if (s_wsum == 0.f) return;                      // (per-shape, mean-score weights) S = 0 for this shape: no gradient
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-        const size_t base = (size_t)n * shape_stride + e;
-        const float ds = dS[(size_t)n * E + e];
-        for (int g = 0; g < G; ++g) {
-            const unsigned long long m0 = s_mask[g];
-            if (m0 == 0) continue;
-            const float coef = s_w[g] / s_wsum * ds;
-            if (mode == GV_VIEWPOOL_MEAN) {
-                const float each = coef / (float)__popcll(m0);
-                for (unsigned long long m = m0; m; m &= m - 1) {
-                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
-                    dF[a] = down<T>(up<T>(dF[a]) + each);
-                }
-            } else {
-                float best = -INFINITY;
-                for (unsigned long long m = m0; m; m &= m - 1)
-                    best = fmaxf(best, up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]));
-                int ties = 0;
-                for (unsigned long long m = m0; m; m &= m - 1)
-                    ties += up<T>(F[base + (size_t)(__ffsll((long long)m) - 1) * view_stride]) == best;
-                const float each = coef / (float)ties;
-                for (unsigned long long m = m0; m; m &= m - 1) {
-                    const size_t a = base + (size_t)(__ffsll((long long)m) - 1) * view_stride;
-                    if (up<T>(F[a]) == best) dF[a] = down<T>(up<T>(dF[a]) + each);
-                }
-            }
-        }
     }
 }
 
@@ -558,43 +498,6 @@ extern "C" int gv_pool2d_bwd_argmax(const gv_pool_desc* d, const uint8_t* argmax
     if (!d || !argmax || !dy || !dx) return GV_E_BADARG;
     if (const int rc = pool_train_check(d, d->mode & ~GV_POOL_BWD_STORE, dy_ld, dx_ld, false)) return rc;
     return gvlp::pool2d_bwd_argmax(d, argmax, dy, dy_ld, dx, dx_ld, (hipStream_t)stream);
-}
-
-// per_shape: every shape has its own scheme ([num_groups][num_views]) and weights ([num_groups]); else one for the batch
-extern "C" int gv_view_pool_fuse_bwd_t(const void* F, const float* dS, int32_t num_views, int32_t num_shapes,
-                                       int64_t n_elem, int64_t view_stride, int64_t shape_stride, const int32_t* scheme,
-                                       int32_t num_groups, const float* weight, int32_t mode, void* dF,
-                                       int32_t per_shape, int32_t dtype, void* stream) {
-    if (!gv_storage_type(dtype)) return GV_E_UNSUPPORTED;
-    if (!F || !dS || !scheme || !weight || !dF) return GV_E_BADARG;
-    if (num_views <= 0 || num_shapes <= 0 || n_elem <= 0 || num_groups <= 0) return GV_E_BADARG;
-    if (num_views > 64 || num_groups > 64 || num_shapes > 65535) return GV_E_UNSUPPORTED;
-    const int64_t ss = per_shape ? (int64_t)num_groups * num_views : 0, ws = per_shape ? num_groups : 0;
-    int64_t bx = (n_elem + 255) / 256;
-    if (bx > 1024) bx = 1024;
-    const dim3 grid((unsigned)bx, (unsigned)num_shapes);
-    GV_ST_DISPATCH(dtype, {
-        hipLaunchKernelGGL((view_pool_fuse_bwd_t<E, T>), grid, dim3(256), 0, (hipStream_t)stream, (const E*)F, dS, num_views,
-                           num_shapes, n_elem, view_stride, shape_stride, scheme, num_groups, weight, mode, (E*)dF, ss, ws);
-        GV_LAUNCH_CHECK();
-        return GV_OK;
-    });
-}
-
-extern "C" int gv_view_pool_fuse_bwd(const float* F, const float* dS, int32_t num_views, int32_t num_shapes,
-                                     int64_t E, int64_t view_stride, int64_t shape_stride,
-                                     const int32_t* scheme, int32_t num_groups, const float* weight,
-                                     int32_t mode, float* dF, void* stream) {
-    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
-                                   mode, dF, 0, GV_F32, stream);
-}
-
-extern "C" int gv_view_pool_fuse_bwd_per_shape(const float* F, const float* dS, int32_t num_views,
-                                               int32_t num_shapes, int64_t E, int64_t view_stride,
-                                               int64_t shape_stride, const int32_t* scheme, int32_t num_groups,
-                                               const float* weight, int32_t mode, float* dF, void* stream) {
-    return gv_view_pool_fuse_bwd_t(F, dS, num_views, num_shapes, E, view_stride, shape_stride, scheme, num_groups, weight,
-                                   mode, dF, 1, GV_F32, stream);
 }
 
 extern "C" int gv_global_avg_pool_bwd(const float* dgap, int32_t nb, int32_t hw, int32_t c, float* dx,

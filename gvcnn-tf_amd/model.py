@@ -27,10 +27,9 @@ import torch
 from . import _lib
 from . import backbones
 from . import params as _params
+from .head import GroupingHead, POOL_MODES as _POOL_MODES, raise_for_status as _raise_for_status
 
 AUTO_REUSE = "AUTO_REUSE"          # tf.compat.v1.AUTO_REUSE stand-in (model.py:106)
-
-_POOL_MODES = {"max": _lib.GV_VIEWPOOL_MAX, "mean": _lib.GV_VIEWPOOL_MEAN}
 
 
 def _st(stream=None):
@@ -84,14 +83,6 @@ def grouping_module(scores, num_groups, num_bins=10, check=True):
     if check:
         _raise_for_status(int(status.item()), gidx, num_groups)
     return gidx, scheme, weight
-
-
-def _raise_for_status(st, gidx, num_groups):
-    if st & 2:
-        raise ValueError("cannot convert float NaN to integer")
-    if st & 1:
-        bad = [int(b) for b in gidx.tolist() if b >= num_groups or b < 0]
-        raise IndexError("index %d is out of bounds for axis 0 with size %d" % (bad[0], num_groups))
 
 
 def group_scheme(view_discrimination_score, num_group, num_views):
@@ -336,25 +327,12 @@ class GVCNN:
                 head_params = _params.init_head_params(num_views, self.raw.c, self.final.c,
                                                        num_classes, seed=seed + 1)
             self.set_head(head_params)
-            dev, f32, i32 = self.device, torch.float32, torch.int32
-            nb = num_shapes * num_views
-            self.r_img = torch.empty(nb, dtype=f32, device=dev)
-            self.scores = torch.empty(num_views, dtype=f32, device=dev)
-            self.gidx = torch.empty(num_views, dtype=i32, device=dev)
-            self.scheme = torch.empty((num_group, num_views), dtype=i32, device=dev)
-            self.weight = torch.empty(num_group, dtype=f32, device=dev)
-            self.status = torch.zeros(1, dtype=i32, device=dev)
-            f = self.final
-            self.shape_descriptor = torch.empty((num_shapes, f.h, f.w, f.c), dtype=self.tdtype, device=dev)
-            self.gap = torch.empty((num_shapes, f.c), dtype=f32, device=dev)
-            self.logits = torch.empty((num_shapes, num_classes), dtype=f32, device=dev)
-            if self.per_shape:
-                self.scores_ps = torch.empty((num_shapes, num_views), dtype=f32, device=dev)
-                self.gidx_ps = torch.empty((num_shapes, num_views), dtype=i32, device=dev)
-                self.scheme_ps = torch.empty((num_shapes, num_group, num_views), dtype=i32, device=dev)
-                self.weight_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
-            self._all_ones_scheme = torch.ones((1, num_views), dtype=i32, device=dev)
-            self._one = torch.ones(1, dtype=f32, device=dev)
+            self.head = GroupingHead(self, self.device, num_shapes, num_views, num_group, num_bins, self.final, num_classes,
+                                     dtype=self.dtype, tdtype=self.tdtype, pool_mode=_POOL_MODES[pool],
+                                     empty_fill=empty_fill, per_shape=self.per_shape, weight_mode=self.weight_mode)
+            self.head.alias_onto("shape_descriptor")
+            self._all_ones_scheme = torch.ones((1, num_views), dtype=torch.int32, device=self.device)
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
 
     # -- parameters -------------------------------------------------------------------------------
     def set_head(self, H):
@@ -388,20 +366,11 @@ class GVCNN:
 
     def compute_scores(self):
         """r_img from the raw-descriptor tap, then the V scores (model.py:144-147)."""
-        lib, r = self.lib, self.raw
-        raw_ptr = self.plan.view(r).data_ptr()
-        _lib.check(lib.gv_view_score_partial(raw_ptr, r.nb, r.h * r.w, r.c, r.ld,
-                                             self.score_kernel.data_ptr(), self.score_bias.data_ptr(),
-                                             self.V, _lib.GV_ORDER_SHAPE_MAJOR, self.r_img.data_ptr(),
-                                             self.dtype, _st()), "gv_view_score_partial")
-        self.finalize_scores(self.r_img, self.N)
-        return self.scores
+        self.head.respond(self.plan.view(self.raw).data_ptr(), self.raw, self.score_kernel, self.score_bias)
+        return self.head.finalize_scores()
 
     def finalize_scores(self, r_img, num_shapes, order=_lib.GV_ORDER_SHAPE_MAJOR):
-        _lib.check(self.lib.gv_view_score_finalize(r_img.data_ptr(), num_shapes, self.V, order,
-                                                   self.scores.data_ptr(), _st()),
-                   "gv_view_score_finalize")
-        return self.scores
+        return self.head.finalize_scores(r_img, num_shapes, order)
 
     def forward_phase1(self, views):
         """Returns the V view discrimination scores (device tensor [V]); descriptors stay on device."""
@@ -410,16 +379,10 @@ class GVCNN:
 
     # -- phase 2: pooling + fusion + classifier (train.py:281-288) -------------------------------
     def assign_groups(self, check=True):
-        _lib.check(self.lib.gv_group_assign(self.scores.data_ptr(), self.V, self.G, self.num_bins,
-                                            self.gidx.data_ptr(), self.scheme.data_ptr(),
-                                            self.weight.data_ptr(), self.status.data_ptr(), _st()),
-                   "gv_group_assign")
-        if check:
-            self.check_status()
-        return self.scheme, self.weight
+        return self.head.assign(check)
 
     def check_status(self):
-        _raise_for_status(int(self.status.item()), self.gidx, self.G)
+        self.head.check_status()
 
     def final_view_descriptors(self):
         """[N, V, h, w, C] view of the final-descriptor tap (shape-major image order)."""
@@ -433,30 +396,15 @@ class GVCNN:
     def pool_fuse_classify(self, scheme, weight, F=None, num_shapes=None, out=None):
         """view_pooling + group_fusion + GAP + Dense (model.py:154-164) on device.
         F: optional descriptor tensor [N', V, h, w, C] (defaults to this engine's tap)."""
-        lib, f = self.lib, self.final
-        E = f.h * f.w * f.c
         if F is None:
-            assert f.ld == f.c
-            F_ptr, N = self.plan.view(f).data_ptr(), self.N
-            S, gap, logits = self.shape_descriptor, self.gap, self.logits
-        else:
-            F = F.to(self.tdtype).contiguous()
-            N = F.shape[0]
-            F_ptr = F.data_ptr()
-            S = torch.empty((N, f.h, f.w, f.c), dtype=self.tdtype, device=self.device)
-            gap = torch.empty((N, f.c), dtype=torch.float32, device=self.device)
-            logits = torch.empty((N, self.num_classes), dtype=torch.float32, device=self.device)
-        G = scheme.shape[0]
-        _lib.check(lib.gv_view_pool_fuse_fwd(F_ptr, self.V, N, E, E, self.V * E, scheme.data_ptr(), G,
-                                             weight.data_ptr(), _POOL_MODES[self.pool], self.empty_fill,
-                                             None, S.data_ptr(), self.dtype, _st()),
-                   "gv_view_pool_fuse_fwd")
-        _lib.check(lib.gv_global_avg_pool(S.data_ptr(), N, f.h * f.w, f.c, f.c, gap.data_ptr(),
-                                          self.dtype, _st()), "gv_global_avg_pool")
-        _lib.check(lib.gv_dense_fwd(gap.data_ptr(), N, f.c, self.cls_kernel.data_ptr(),
-                                    self.cls_bias.data_ptr(), self.num_classes, logits.data_ptr(),
-                                    _st()), "gv_dense_fwd")
-        return S, logits
+            return self._classify(scheme=scheme, weight=weight)
+        F = F.to(self.tdtype).contiguous()
+        return self.head.classify(F.data_ptr(), self.cls_kernel, self.cls_bias, scheme, weight, num_shapes=F.shape[0])
+
+    def _classify(self, **kw):
+        """The head's classify on this engine's final tap and classifier."""
+        assert self.final.ld == self.final.c
+        return self.head.classify(self.plan.view(self.final).data_ptr(), self.cls_kernel, self.cls_bias, **kw)
 
     def forward_phase2(self, g_scheme=None, g_weight=None):
         """Feed scheme/weight (host arrays like train.py:281-288, or device tensors); None = use the
@@ -471,42 +419,20 @@ class GVCNN:
     def forward_per_shape(self, views, check=True):
         """Per-shape grouping: (scores [N,V], shape_descriptor, logits).  Nothing couples the shapes
         of the batch, so a shape-sharded job needs no exchange."""
-        lib, f = self.lib, self.final
-        self.forward_phase1(views)                     # fills r_img (the batch-mean scores are not used)
-        _lib.check(lib.gv_view_score_per_shape(self.r_img.data_ptr(), self.N * self.V, self.scores_ps.data_ptr(),
-                                               _st()), "gv_view_score_per_shape")
-        _lib.check(lib.gv_group_assign_per_shape(self.scores_ps.data_ptr(), self.N, self.V, self.G, self.num_bins,
-                                                 self.weight_mode, self.gidx_ps.data_ptr(), self.scheme_ps.data_ptr(),
-                                                 self.weight_ps.data_ptr(), self.status.data_ptr(), _st()),
-                   "gv_group_assign_per_shape")
-        E = f.h * f.w * f.c
-        S = self.shape_descriptor
-        _lib.check(lib.gv_view_pool_fuse_fwd_per_shape(self.plan.view(f).data_ptr(), self.V, self.N, E, E, self.V * E,
-                                                       self.scheme_ps.data_ptr(), self.G, self.weight_ps.data_ptr(),
-                                                       _POOL_MODES[self.pool], self.empty_fill, None, S.data_ptr(),
-                                                       self.dtype, _st()), "gv_view_pool_fuse_fwd_per_shape")
-        _lib.check(lib.gv_global_avg_pool(S.data_ptr(), self.N, f.h * f.w, f.c, f.c, self.gap.data_ptr(),
-                                          self.dtype, _st()), "gv_global_avg_pool")
-        _lib.check(lib.gv_dense_fwd(self.gap.data_ptr(), self.N, f.c, self.cls_kernel.data_ptr(),
-                                    self.cls_bias.data_ptr(), self.num_classes, self.logits.data_ptr(), _st()),
-                   "gv_dense_fwd")
-        if check:
-            st = int(self.status.item())
-            if st:
-                _raise_for_status(st, self.gidx_ps.reshape(-1), self.G)
-        return self.scores_ps, S, self.logits
+        assert self.per_shape
+        return self.forward(views, check)
 
     def forward(self, views, check=True):
         """Fused forward: (scores [V], shape_descriptor [N,h,w,C], logits [N,num_classes]), all on
         device; the only host interaction is the optional status read (check=True)."""
-        if self.per_shape:
-            return self.forward_per_shape(views, check)
         self.forward_phase1(views)
-        self.assign_groups(check=False)
-        S, logits = self.pool_fuse_classify(self.scheme, self.weight)
+        if self.per_shape:                             # phase 1 filled r_img (its batch-mean scores are not used)
+            self.head.score()
+        self.head.assign(check=False)
+        S, logits = self._classify()
         if check:
-            self.check_status()
-        return self.scores, S, logits
+            self.head.check_status()
+        return self.head.scores, S, logits
 
     # -- hipGraph replay (small batches are launch-bound) ---------------------------------------------------
     def capture(self, views):
@@ -533,7 +459,7 @@ class GVCNN:
         def replay():
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.gv_graph_launch(handle, _st()), "gv_graph_launch")
-            return (self.scores_ps if self.per_shape else self.scores), self.shape_descriptor, self.logits
+            return self.head.scores, self.shape_descriptor, self.logits
         replay.close = self.close_graphs
         return replay
 
@@ -553,19 +479,8 @@ class GVCNN:
     def forward_basic(self, views):
         """nets/model.py:169-206 (MVCNN baseline): max over all views -> GAP -> Dense."""
         self.run_backbone(views)
-        lib, f = self.lib, self.final
-        E = f.h * f.w * f.c
-        S = self.shape_descriptor
-        _lib.check(lib.gv_view_pool_fuse_fwd(self.plan.view(f).data_ptr(), self.V, self.N, E, E,
-                                             self.V * E, self._all_ones_scheme.data_ptr(), 1,
-                                             self._one.data_ptr(), _lib.GV_VIEWPOOL_MAX, 1.0, None,
-                                             S.data_ptr(), self.dtype, _st()), "gv_view_pool_fuse_fwd")
-        _lib.check(lib.gv_global_avg_pool(S.data_ptr(), self.N, f.h * f.w, f.c, f.c,
-                                          self.gap.data_ptr(), self.dtype, _st()), "gv_global_avg_pool")
-        _lib.check(lib.gv_dense_fwd(self.gap.data_ptr(), self.N, f.c, self.cls_kernel.data_ptr(),
-                                    self.cls_bias.data_ptr(), self.num_classes,
-                                    self.logits.data_ptr(), _st()), "gv_dense_fwd")
-        return S, self.logits
+        return self._classify(scheme=self._all_ones_scheme, weight=self._one, pool_mode=_lib.GV_VIEWPOOL_MAX,
+                              empty_fill=1.0)
 
     def embed(self, views, check=True, basic=False):
         """The shape descriptor retrieval ranks on: forward (forward_basic when basic=True), then a copy of `gap`
@@ -636,10 +551,7 @@ class GVCNN:
         f = self.final
         assert f.ld == f.c
         self.forward(views, check=check)
-        if self.per_shape:
-            scheme, weight, scores, gidx = self.scheme_ps, self.weight_ps, self.scores_ps, self.gidx_ps
-        else:
-            scheme, weight, scores, gidx = self.scheme, self.weight, self.scores, self.gidx
+        scheme, weight, scores, gidx = self.head.scheme, self.head.weight, self.head.scores, self.head.gidx
         E = f.h * f.w * f.c
         tgt, base, contrib, maps, _ = _explain_launch(
             self.plan.view(f).data_ptr(), self.dtype, self.N, self.V, f.h, f.w, f.c, E, self.V * E, scheme, weight,

@@ -465,11 +465,7 @@ class ShardedTrainGVCNN:
         eng.forward_backbone(views_local)
         r_all = gather_scores(eng.score_partial(), self.group)              # [P*N_l*V], global shape-major order
         # batch-mean scores over the GLOBAL batch (identical on every rank), then the local head
-        _lib_scores = eng.lib.gv_view_score_finalize
-        from . import _lib
-        from .model import _st
-        _lib.check(_lib_scores(r_all.data_ptr(), eng.N * self.world, eng.V, _lib.GV_ORDER_SHAPE_MAJOR,
-                               eng.scores.data_ptr(), _st()), "score finalize (global)")
+        eng.head.finalize_scores(r_all, eng.N * self.world)
         eng.forward_head(labels_local, check=check, r_img=None, scores_ready=True)
         eng.backward_head()
         red = self._filter_reducer(self.group)
@@ -486,8 +482,6 @@ class ShardedTrainGVCNN:
     def _train_step_hybrid(self, views_local, labels_local, lr, mu, weight_decay, check):
         """views_local [N / shape_shards, V / view_groups, H, W, 3]: this rank's views of this rank's shapes; labels_local
         [N / shape_shards]."""
-        from . import _lib
-        from .model import _st
         eng = self.eng
         f = eng.final
         n_l, v_l, V = eng.N, eng.V, eng.Vh
@@ -495,8 +489,7 @@ class ShardedTrainGVCNN:
         r_loc = eng.score_partial().view(n_l, v_l)
         r_views = gather_views(r_loc, self.view_group, V) if self.vg > 1 else r_loc                    # [N_l, V]
         r_all = _all_gather_flat(r_views, self.shape_group) if self.sh > 1 else r_views               # [N, V], shape order
-        _lib.check(eng.lib.gv_view_score_finalize(r_all.data_ptr(), n_l * self.sh, V, _lib.GV_ORDER_SHAPE_MAJOR,
-                                                  eng.scores.data_ptr(), _st()), "score finalize (global)")
+        eng.head.finalize_scores(r_all, n_l * self.sh)
         F_loc = eng.view(f).view(n_l, v_l, f.h, f.w, f.c)
         F_all = gather_views(F_loc, self.view_group, V) if self.vg > 1 else F_loc
         eng.forward_head(labels_local, check=check, F=F_all if self.vg > 1 else None, r_img=r_views.reshape(-1),

@@ -67,14 +67,9 @@ class Trainer:
             # the group-assignment status word of THIS step, in the same synchronising readback: a score of exactly
             # 1.0 (bin == num_group) or NaN leaves a view in no group with a finite loss; the reference's host
             # group_scheme raises IndexError / ValueError there (nets/model.py:23, train.py:277)
-            eng = self._engine()
-            st = getattr(eng, "status", None)
-            if st is not None and not getattr(eng, "per_shape", False):
-                from .model import _raise_for_status
-                _raise_for_status(int(st.item()), eng.gidx, eng.G)
-            elif st is not None and int(st.item()):
-                from .model import _raise_for_status
-                _raise_for_status(int(st.item()), eng.gidx_ps.reshape(-1), eng.G)
+            head = getattr(self._engine(), "head", None)          # (both engines have one; a stand-in without it has
+            if head is not None:                                  # no assignment to check)
+                head.check_status()
         return loss
 
     # -- checkpoints (tf.train.Saver: train.py:225-234 restores, train.py:297-302 saves) -------------------------------

@@ -24,7 +24,8 @@ from . import _lib
 from . import backbones
 from . import params as _params
 from .backbones import _out_size
-from .model import _st, _dev, _raise_for_status, pin_device
+from .head import GroupingHead, POOL_MODES
+from .model import _st, _dev, pin_device
 from ._train_layout import flat_layout, pick_tile, s2_parity_classes
 
 _BN_STAT_KEYS = ("mean", "var", "inv", "scale", "shift")
@@ -214,7 +215,7 @@ class TrainGVCNN:
         self.backbone = backbone
         self.N, self.V, self.H, self.W = num_shapes, num_views, height, width
         self.num_classes, self.G, self.num_bins = num_classes, num_group, num_bins
-        self.pool_mode = {"max": _lib.GV_VIEWPOOL_MAX, "mean": _lib.GV_VIEWPOOL_MEAN}[pool]
+        self.pool_mode = POOL_MODES[pool]
         self.empty_fill = float(empty_fill)
         self.math_mode = backbones.MATH_MODES[math]
         if self.math_mode == _lib.GV_MATH_F32:
@@ -383,19 +384,12 @@ class TrainGVCNN:
                         op["s2"] = [dict(c_, tile=0, w=packed(c_["th"], c_["tw"], cout, cin)) for c_ in cls]
 
     def _alloc_head(self):
-        """Buffers of the grouping head, the classifier and the loss."""
+        """The grouping head over the Vh views (head.py) and the buffers of its backward and the loss."""
         dev, f32, num_shapes, num_group = self.device, torch.float32, self.N, self.G
-        self.r_img = torch.empty(self.N * self.V, dtype=f32, device=dev)
-        self.scores = torch.empty(self.Vh, dtype=f32, device=dev)
-        self.gidx = torch.empty(self.Vh, dtype=torch.int32, device=dev)
-        self.scheme = torch.empty((num_group, self.Vh), dtype=torch.int32, device=dev)
-        self.weight = torch.empty(num_group, dtype=f32, device=dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        if self.per_shape:
-            self.scores_ps = torch.empty((num_shapes, self.Vh), dtype=f32, device=dev)
-            self.gidx_ps = torch.empty((num_shapes, self.Vh), dtype=torch.int32, device=dev)
-            self.scheme_ps = torch.empty((num_shapes, num_group, self.Vh), dtype=torch.int32, device=dev)
-            self.weight_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
+        self.head = GroupingHead(self, dev, num_shapes, self.Vh, num_group, self.num_bins, self.final, self.num_classes,
+                                 dtype=self.dt, tdtype=self.tdt, pool_mode=self.pool_mode, empty_fill=self.empty_fill,
+                                 per_shape=self.per_shape, weight_mode=self.weight_mode, own_views=self.V)
+        self.head.alias_onto("S")
         if self.train_scorer:
             self.dw_ps = torch.empty((num_shapes, num_group), dtype=f32, device=dev)
             nws = self.lib.gv_group_weight_bwd_workspace_bytes(num_shapes, self.final.h * self.final.w * self.final.c,
@@ -403,12 +397,8 @@ class TrainGVCNN:
             if nws < 0:
                 _lib.check(int(nws), "gv_group_weight_bwd_workspace_bytes")
             self._gw_ws = torch.empty(int(nws), dtype=torch.uint8, device=dev)
-        f = self.final
-        self.S = torch.empty((num_shapes, f.h, f.w, f.c), dtype=self.tdt, device=dev)
-        self.dS = torch.empty((num_shapes, f.h, f.w, f.c), dtype=f32, device=dev)
-        self.gap = torch.empty((num_shapes, f.c), dtype=f32, device=dev)
+        self.dS = torch.empty(self.S.shape, dtype=f32, device=dev)
         self.dgap = torch.empty_like(self.gap)
-        self.logits = torch.empty((num_shapes, self.num_classes), dtype=f32, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         self.loss = torch.zeros(1, dtype=f32, device=dev)
 
@@ -1139,75 +1129,36 @@ class TrainGVCNN:
         """Scorer responses r_img [N*V] of this engine's views (model.py:144-145); no gradient flows through the
         scorer: the scores leave the graph in partial_run #1.  (train_scorer=True: backward_head computes the gradient
         the per-shape mean_score weights carry, see _backward_scorer.)"""
-        r = self.raw
-        _lib.check(self.lib.gv_view_score_partial(self._ptr(r), r.nb, r.h * r.w, r.c, r.ld,
-                                                  self.score_kernel.data_ptr(), self.score_bias.data_ptr(), self.V,
-                                                  _lib.GV_ORDER_SHAPE_MAJOR, self.r_img.data_ptr(), self.dt,
-                                                  _st()), "score")
-        return self.r_img
+        return self.head.respond(self._ptr(self.raw), self.raw, self.score_kernel, self.score_bias)
 
     def forward_head(self, labels=None, g_scheme=None, g_weight=None, check=True, F=None, r_img=None,
                      scores_ready=False):
         """Scores -> scheme/weight -> view pooling + fusion -> classifier -> loss, over self.Vh views.
         F [N, Vh, h, w, C] / r_img [N*Vh]: the gathered descriptors / scorer responses of a view-sharded job
         (default: this engine's own taps)."""
-        lib, V = self.lib, self.Vh
+        h = self.head
         r_img = self.r_img if r_img is None else r_img
-        assert r_img.numel() == self.N * V
+        assert r_img.numel() == self.N * h.V
         self._F = F
-        f = self.final
-        E = f.h * f.w * f.c
-        F_ptr = self._ptr(f) if F is None else F.data_ptr()
         if self.per_shape:
             assert g_scheme is None, "per-shape grouping derives its schemes on the device"
-            _lib.check(lib.gv_view_score_per_shape(r_img.data_ptr(), self.N * V, self.scores_ps.data_ptr(), _st()),
-                       "score per shape")
-            _lib.check(lib.gv_group_assign_per_shape(self.scores_ps.data_ptr(), self.N, V, self.G, self.num_bins,
-                                                     self.weight_mode, self.gidx_ps.data_ptr(),
-                                                     self.scheme_ps.data_ptr(), self.weight_ps.data_ptr(),
-                                                     self.status.data_ptr(), _st()), "assign per shape")
-            if check:
-                st_ = int(self.status.item())
-                if st_:
-                    _raise_for_status(st_, self.gidx_ps.reshape(-1), self.G)
-            _lib.check(lib.gv_view_pool_fuse_fwd_per_shape(F_ptr, V, self.N, E, E, V * E, self.scheme_ps.data_ptr(),
-                                                           self.G, self.weight_ps.data_ptr(), self.pool_mode,
-                                                           self.empty_fill, None, self.S.data_ptr(), self.dt,
-                                                           _st()), "pool_fuse per shape")
-            return self._classify_and_loss(labels, self.scores_ps)
-        if not scores_ready:                              # (shape-sharded jobs finalise the scores over the global batch)
-            _lib.check(lib.gv_view_score_finalize(r_img.data_ptr(), self.N, V, _lib.GV_ORDER_SHAPE_MAJOR,
-                                                  self.scores.data_ptr(), _st()), "score finalize")
+        if self.per_shape or not scores_ready:            # (shape-sharded jobs finalise the scores over the global batch)
+            h.score(r_img)
         if g_scheme is None:
-            _lib.check(lib.gv_group_assign(self.scores.data_ptr(), V, self.G, self.num_bins, self.gidx.data_ptr(),
-                                           self.scheme.data_ptr(), self.weight.data_ptr(), self.status.data_ptr(),
-                                           _st()), "assign")
-            if check:
-                _raise_for_status(int(self.status.item()), self.gidx, self.G)
+            h.assign(check)
         else:
-            self.scheme.copy_(torch.as_tensor(np.asarray(g_scheme), dtype=torch.int32))
-            self.weight.copy_(torch.as_tensor(np.asarray(g_weight), dtype=torch.float32))
-        _lib.check(lib.gv_view_pool_fuse_fwd(F_ptr, V, self.N, E, E, V * E, self.scheme.data_ptr(), self.G,
-                                             self.weight.data_ptr(), self.pool_mode, self.empty_fill, None,
-                                             self.S.data_ptr(), self.dt, _st()), "pool_fuse")
-        return self._classify_and_loss(labels, self.scores)
-
-    def _classify_and_loss(self, labels, scores):
-        lib, f = self.lib, self.final
-        _lib.check(lib.gv_global_avg_pool(self.S.data_ptr(), self.N, f.h * f.w, f.c, f.c, self.gap.data_ptr(),
-                                          self.dt, _st()), "gap")
+            h.scheme.copy_(torch.as_tensor(np.asarray(g_scheme), dtype=torch.int32))
+            h.weight.copy_(torch.as_tensor(np.asarray(g_weight), dtype=torch.float32))
         kn, bn = self.cls_names
-        _lib.check(lib.gv_dense_fwd(self.gap.data_ptr(), self.N, f.c, self.params[kn].data_ptr(),
-                                    self.params[bn].data_ptr(), self.num_classes, self.logits.data_ptr(), _st()),
-                   "dense")
+        h.classify(self._ptr(self.final) if F is None else F.data_ptr(), self.params[kn], self.params[bn])
         if labels is not None:
             self._labels = labels.to(device=self.device, dtype=torch.int64).contiguous()
-            _lib.check(lib.gv_softmax_ce(self.logits.data_ptr(), self._labels.data_ptr(), self.N, self.num_classes,
-                                         self.loss.data_ptr(), self.dlogits.data_ptr(), _st()), "softmax_ce")
+            _lib.check(self.lib.gv_softmax_ce(self.logits.data_ptr(), self._labels.data_ptr(), self.N, self.num_classes,
+                                              self.loss.data_ptr(), self.dlogits.data_ptr(), _st()), "softmax_ce")
             if self.shape_world > 1:                      # the loss is the mean over the GLOBAL batch
-                _lib.check(lib.gv_scale(self.dlogits.data_ptr(), self.dlogits.numel(), 1.0 / self.shape_world, _st()),
-                           "gv_scale")
-        return scores, self.S, self.logits, self.loss
+                _lib.check(self.lib.gv_scale(self.dlogits.data_ptr(), self.dlogits.numel(), 1.0 / self.shape_world,
+                                             _st()), "gv_scale")
+        return h.scores, self.S, self.logits, self.loss
 
     # -- backward ----------------------------------------------------------------------------------------
     def backward(self):
@@ -1238,9 +1189,8 @@ class TrainGVCNN:
                                               _st()), "gap_bwd")
         F_ptr = self._ptr(f) if self._F is None else self._F.data_ptr()
         dF_ptr = self._ptr(f, grad=True) if dF is None else dF.data_ptr()
-        scheme, weight = (self.scheme_ps, self.weight_ps) if self.per_shape else (self.scheme, self.weight)
-        _lib.check(lib.gv_view_pool_fuse_bwd_t(F_ptr, self.dS.data_ptr(), V, self.N, E, E, V * E, scheme.data_ptr(),
-                                               self.G, weight.data_ptr(), self.pool_mode, dF_ptr, int(self.per_shape),
+        _lib.check(lib.gv_view_pool_fuse_bwd_t(F_ptr, self.dS.data_ptr(), V, self.N, E, E, V * E, self.head.scheme.data_ptr(),
+                                               self.G, self.head.weight.data_ptr(), self.pool_mode, dF_ptr, int(self.per_shape),
                                                self.dt, _st()), "pool_fuse_bwd")
         if self.train_scorer:
             self._backward_scorer(F_ptr, E)

@@ -313,6 +313,40 @@ def test_group_assign_at_every_bin_edge_bit_for_bit():
         _assign_equal("assign V1", outs, HR.group_assign_f32(one.cpu().numpy(), G, B), 1, 1, G)
 
 
+def test_group_assign_entry_points_agree_and_own_the_status_word():
+    """One kernel behind both entry points: on the same row gv_group_assign and gv_group_assign_per_shape (N = 1, count
+    weights) give identical gidx, scheme, weight and status, at V = 64, G = 64 and at V = 1, on a clean row, a row with a NaN
+    and a row with an out-of-range score.  A stale status word (3) is overwritten to 0 by a clean batch-level call and
+    cleared by a clean per-shape call with N = 3."""
+    G = B = 64
+    clean = np.random.RandomState(2).uniform(0, 0.999, size=64).astype(F32)
+    with_nan, outside = clean.copy(), clean.copy()
+    with_nan[[0, 31, 63]] = np.nan
+    outside[[5, 63]] = [1.0, -0.5]
+    rows = [(clean, 0), (with_nan, 2), (outside, 1), (clean[:1], 0), (with_nan[:1], 2), (outside[5:6], 1)]
+    for row, st_want in rows:
+        V = len(row)
+        sd = torch.from_numpy(row).to(DEV)
+        a, b = _assign_outputs(1, V, G), _assign_outputs(1, V, G)
+        _lib.check(lib().gv_group_assign(sd.data_ptr(), V, G, B, a[0].ptr, a[1].ptr, a[2].ptr, a[3].data_ptr(), st()), "assign")
+        _lib.check(lib().gv_group_assign_per_shape(sd.data_ptr(), 1, V, G, B, _lib.GV_WEIGHT_COUNT, b[0].ptr, b[1].ptr,
+                                                   b[2].ptr, b[3].data_ptr(), st()), "assign per shape")
+        assert int(a[3].item()) == int(b[3].item()) == st_want, (V, st_want)
+        for x, y in zip(a[:3], b[:3]):
+            assert x.v.cpu().numpy().tobytes() == y.v.cpu().numpy().tobytes() and x.outside_intact() and y.outside_intact()
+    sd = torch.from_numpy(np.stack([clean, clean[::-1], clean])).to(DEV)
+    for N in (1, 3):
+        outs = _assign_outputs(N, 64, G)
+        outs[3].fill_(3)
+        if N == 1:
+            _lib.check(lib().gv_group_assign(sd.data_ptr(), 64, G, B, outs[0].ptr, outs[1].ptr, outs[2].ptr,
+                                             outs[3].data_ptr(), st()), "assign")
+        else:
+            _lib.check(lib().gv_group_assign_per_shape(sd.data_ptr(), N, 64, G, B, _lib.GV_WEIGHT_COUNT, outs[0].ptr,
+                                                       outs[1].ptr, outs[2].ptr, outs[3].data_ptr(), st()), "assign per shape")
+        assert int(outs[3].item()) == 0, N
+
+
 # ---- view_pool_fuse_fwd, _per_shape -------------------------------------------------------------------------------------
 def _scheme_bits(G, V=64):
     """Views 31, 32 and 63 in use; a group of all 64 views; rows that overlap (view 31 in groups 0, 1 and 2); empty groups."""
@@ -485,6 +519,65 @@ def test_view_pool_fuse_backward_over_the_mask_edges(case, tname, mode):
     want = Fr.grad.reshape(N * V, E)
     _within(tag, "dF %s" % tname, dF.v, want, tol * float(want.abs().max()))
     assert dF.outside_intact() and dS.outside_intact(), tag
+
+
+# ---- the four readers of one group table ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["max", "mean"])
+@pytest.mark.parametrize("E", [8, 9])                                 # the vector and the scalar walk
+def test_a_shape_whose_weights_sum_to_zero_in_every_reader_of_the_group_table(E, mode):
+    """Per-shape grouping with mean_score weights, N = 2, V = 3, G = 4: every score of shape 0 is 0, so its weights sum to 0;
+    shape 1 is an ordinary one.  The forward, its backward, the weight gradient and explain each load the group table of
+    their shape and must agree on shape 0: S = 0, dF untouched, dw = 0, maps and view_contrib 0 with baseline = bias[k].
+    Shape 1: S equals the ordered fp32 restatement bit for bit, dF is within 1e-5 of the tensor's scale of fp64 autograd,
+    dw within 1e-5 of its absolute-term sum (scorer_ref.group_weight_grad), explain within (n + 8) 2^-24 of its
+    absolute-term sum (explain_ref)."""
+    import explain_ref as XR                                          # tests/explain_ref.py
+    import scorer_ref as SR                                           # tests/scorer_ref.py
+    N, V, G, nc = 2, 3, 4, 5
+    pm = _lib.GV_VIEWPOOL_MAX if mode == "max" else _lib.GV_VIEWPOOL_MEAN
+    g = _gen(E, N, V, G)
+    scores = torch.tensor([[0.0, 0.0, 0.0], [0.15, 0.17, 0.62]], device=DEV)
+    gidx, scheme, weight, status = (torch.empty(N, V, dtype=torch.int32, device=DEV),
+                                    torch.empty(N, G, V, dtype=torch.int32, device=DEV), torch.empty(N, G, device=DEV),
+                                    torch.zeros(1, dtype=torch.int32, device=DEV))
+    _lib.check(lib().gv_group_assign_per_shape(scores.data_ptr(), N, V, G, G, _lib.GV_WEIGHT_MEAN_SCORE, gidx.data_ptr(),
+                                               scheme.data_ptr(), weight.data_ptr(), status.data_ptr(), st()), "assign")
+    sch, wt = scheme.cpu().numpy(), weight.cpu().numpy()
+    assert int(status.item()) == 0 and not wt[0].any() and sch[0, 0].all() and float(wt[1].sum()) > 0
+    F, dS = _randn(g, N, V, E), _randn(g, N, E)
+    S = torch.full((N, E), SENTINEL, device=DEV)
+    _lib.check(lib().gv_view_pool_fuse_fwd_per_shape(F.data_ptr(), V, N, E, E, V * E, scheme.data_ptr(), G, weight.data_ptr(),
+                                                     pm, 1.0, None, S.data_ptr(), _lib.GV_F32, st()), "fuse")
+    _, S32 = HR.pool_fuse_f32(F.cpu().numpy(), sch, wt, mode, 1.0)
+    assert not S[0].any() and S[1].cpu().numpy().tobytes() == S32[1].tobytes() and S32[1].any()
+    dF0 = _randn(g, N, V, E)
+    dF = dF0.clone()
+    _lib.check(lib().gv_view_pool_fuse_bwd_t(F.data_ptr(), dS.data_ptr(), V, N, E, E, V * E, scheme.data_ptr(), G,
+                                             weight.data_ptr(), pm, dF.data_ptr(), 1, _lib.GV_F32, st()), "fuse bwd")
+    Fr = F.double().requires_grad_(True)
+    HR.pool_fuse(Fr, sch, wt, mode, 1.0)[1].backward(dS.double())
+    assert torch.equal(dF[0], dF0[0])
+    _within("zero-sum", "dF of shape 1", dF[1] - dF0[1], Fr.grad[1], 1e-5 * float(Fr.grad[1].abs().max()))
+    nws = lib().gv_group_weight_bwd_workspace_bytes(N, E, G)
+    ws, dw = torch.full((nws // 4,), SENTINEL, device=DEV), torch.full((N, G), SENTINEL, device=DEV)
+    _lib.check(lib().gv_group_weight_bwd_per_shape(F.data_ptr(), dS.data_ptr(), V, N, E, E, V * E, scheme.data_ptr(), G,
+                                                   weight.data_ptr(), pm, dw.data_ptr(), ws.data_ptr(), nws, _lib.GV_F32, st()),
+               "group_weight_bwd")
+    ref, A = SR.group_weight_grad(F.cpu().double(), dS.cpu().double(), gidx.cpu(), weight.cpu().double(), G, mode)
+    assert not dw[0].any() and float(dw[1].abs().max()) > 0
+    assert bool(((dw[1].cpu().double() - ref[1]).abs() <= 1e-5 * A[1]).all()), (dw[1], ref[1])
+    K, b, tg = _randn(g, E, nc), _randn(g, nc), np.array([1, 3])
+    import gvcnn_tf_amd as gv
+    for kind in ("exact", "gradcam"):
+        ex = gv.explain_views(F.reshape(N, V, 1, 1, E), scheme, weight, K, b, target=tg, pool=mode, empty_fill=1.0, kind=kind)
+        want = XR.explain(F.cpu().numpy().reshape(N, V, 1, E), sch, wt, K.cpu().numpy(), b.cpu().numpy(), tg, mode, 1.0, kind)
+        got = dict(maps=ex.maps.reshape(N, V, 1), view_contrib=ex.view_contrib, baseline=ex.baseline)
+        assert not got["maps"][0].any() and not got["view_contrib"][0].any() and float(ex.baseline[0]) == float(b[tg[0]])
+        for name, t in got.items():
+            val, n, T = (x[1] for x in want[name])
+            err = np.abs(t[1].cpu().numpy().astype(np.float64) - val)
+            assert (err <= 1.01 * (n + 8) * U * T).all(), (kind, name, err, T)
+        assert kind == "gradcam" or got["maps"][1].any()          # (gradcam clips at 0: a single pixel may well be 0)
 
 
 # ---- scale_shift_act ----------------------------------------------------------------------------------------------------
