@@ -39,6 +39,7 @@ GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RE
     0, 1, 2, 3, 4, 5
 GV_NORMALS_ORIENT_NONE, GV_NORMALS_ORIENT_OUTWARD, GV_NORMALS_ORIENT_VIEWPOINT = 0, 1, 2
 GV_POINTS_DEGENERATE_NORMAL = 0x100
+GV_POINTS_CLEAN_PASSTHROUGH, GV_POINTS_CLEAN_TABLE_FULL = 0x200, 0x400
 GV_PNG_STATUS = ("OK", "TRUNCATED", "BAD_HEADER", "BAD_BLOCK", "BAD_CODES", "BAD_DISTANCE", "TOO_LONG", "TOO_SHORT",
                  "BAD_CHECKSUM", "BAD_FILTER", "BAD_PALETTE_INDEX")      # GV_PNG_* of the header, by value
 (GV_PNG_OK, GV_PNG_TRUNCATED, GV_PNG_BAD_HEADER, GV_PNG_BAD_BLOCK, GV_PNG_BAD_CODES, GV_PNG_BAD_DISTANCE, GV_PNG_TOO_LONG,
@@ -182,6 +183,10 @@ SIGNATURES = {
                                  _P, C.POINTER(RenderShading), _P, _P, _P]),
     "gv_points_normals_workspace_bytes": (_L, [_I, _L, _I]),
     "gv_points_estimate_normals": (C.c_int, [_P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P]),
+    "gv_points_clean_workspace_bytes": (_L, [_I, _L, _I]),
+    "gv_points_outlier_select": (C.c_int, [_P, _P, _I, _L, _I, _I, _F, _I, _P, _P, _P, _P, _L, _P, _P]),
+    "gv_points_voxel_select": (C.c_int, [_P, _P, _I, _L, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _P]),
+    "gv_points_compact": (C.c_int, [_P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),

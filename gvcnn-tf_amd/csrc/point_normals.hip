@@ -2,224 +2,30 @@
 // covariance of the neighbourhood, its smallest eigenvector by cyclic Jacobi, a sign convention (the contract is in
 // include/gvcnn_hip.h, "points in", normal estimation; tests/point_normals_oracle.py restates it in numpy).
 //
-//   gv_points_estimate_normals   bbox_kernel        one workgroup per cloud: offsets check, bounding box, cells per axis G.
-//                                cell_base_kernel   one workgroup: exclusive scan of the clouds' G^3 -> where each cloud's
-//                                                   cells start in the workspace.
-//                                bin_kernel<false>  a thread per point: its cell's counter + 1 (integer atomics).
-//                                alloc_kernel       a thread per cell: takes count slots of its cloud's id range from the
-//                                                   cloud's cursor (an integer atomic: WHERE a cell's ids lie is arbitrary).
-//                                bin_kernel<true>   a thread per point: its id into its cell's range.
+//   gv_points_estimate_normals   build_grid         bounding boxes, statuses and the binned ids of the batch (point_grid.h,
+//                                                   shared with point_clean.hip: five launches).
 //                                query_kernel<K>    a thread per point, in cell order (neighbouring lanes walk the same
-//                                                   cells): Chebyshev rings of cells around the point's own, the k_eff
-//                                                   smallest keys (bits(d2) << 32 | id) kept sorted in an LDS column of the
-//                                                   thread; then covariance, Jacobi and the sign in fp64 registers.
+//                                                   cells): ring_walk over Chebyshev rings of cells around the point's own,
+//                                                   the k_eff smallest keys (bits(d2) << 32 | id) kept sorted in an LDS
+//                                                   column of the thread; then covariance, Jacobi and the sign in fp64
+//                                                   registers.
 //
 // Nothing in the result depends on the grid: keys are unique, so the k_eff smallest are the same set in the same order
 // whatever the order candidates arrive in, and a ring walk stops only when every point it has not seen is PROVABLY
-// farther than the k-th key (ring_bound below; ties included).  No floating-point atomics anywhere.
-#include <math.h>
-
-#include "gv_common.h"
-
-// every step of the contract's arithmetic rounds on its own (fp32 distances, fp64 covariance and Jacobi)
-#pragma clang fp contract(off)
+// farther than the k-th key (ring_bound in point_grid.h; ties included).  No floating-point atomics anywhere.
+#include "point_grid.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int NT = 256;                                          // threads of every kernel but the scan
-constexpr int SCAN_T = 1024;
-constexpr int MAX_CLOUD = 1 << 24;                               // points of a cloud: ids fit the splatter's 24 bits
-constexpr int MAX_G = 128;                                       // cells per axis
-constexpr int MAX_GRID_X = 2048;                                 // workgroups along x; the loops stride the rest
 constexpr int SWEEPS = 6;                                        // Jacobi sweeps (contract)
-constexpr u64 NO_KEY = ~0ull;
 
-struct CloudGrid {                                               // per cloud, written by bbox_kernel (64 bytes)
-    float mn[3], mx[3];                                          // bounding box
-    float inv[3];                                                // cells per unit length, 0 on an axis without extent
-    int G;                                                       // cells per axis
-    int status;                                                  // GV_RENDER_*
-    int cursor;                                                  // next free slot of the cloud's id range (alloc_kernel)
-    long long cell_base;                                         // first cell in cell_count / cell_end
-};
-
-// largest g with g^3 <= x, at most MAX_G
-__host__ __device__ inline int icbrt(long long x) {
-    int g = 0;
-    while (g < MAX_G && (long long)(g + 1) * (g + 1) * (g + 1) <= x) ++g;
-    return g;
-}
-
-// Cells per axis of a cloud of P points.  Auto: about two points per cell by volume, G^3 <= max(P / 2, 1).  A hint h:
-// min(h, the largest G with G^3 <= max(4 P, 1)), which keeps the cells of a batch within 4 * total_points + n whatever h.
-__host__ __device__ inline int cells_per_axis(long long P, int hint) {
-    const int g = icbrt(hint <= 0 ? P / 2 : 4 * P), g1 = g < 1 ? 1 : g;
-    return hint <= 0 || g1 < hint ? g1 : hint;
-}
-
-// the cells a batch can need: the workspace holds two int32 per cell
-inline int64_t cell_capacity(int32_t n, int64_t total_points, int32_t hint) {
-    if (hint <= 0) return total_points / 2 + n;
-    const int64_t by_hint = (int64_t)n * hint * hint * hint, by_points = 4 * total_points + n;
-    return by_hint < by_points ? by_hint : by_points;
-}
-
-struct NormalsWs {
-    int64_t grids, ids, cell_count, cell_end, cells, bytes;      // byte offsets; cells: capacity in cells
-};
-
-inline int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
-
-NormalsWs ws_layout(int32_t n, int64_t total_points, int32_t hint) {
-    NormalsWs L;
-    L.cells = cell_capacity(n, total_points, hint);
-    L.grids = 0;
-    L.ids = round16((int64_t)n * (int64_t)sizeof(CloudGrid));
-    L.cell_count = L.ids + round16(total_points * 4);
-    L.cell_end = L.cell_count + round16(L.cells * 4);
-    L.bytes = L.cell_end + round16(L.cells * 4);
-    return L;
-}
-
-struct NArgs {
-    const float* pts;
-    const long long* poff;
-    CloudGrid* grid;
-    int* ids;                                                    // [total_points]: a cloud's ids, cell by cell
-    int* cell_count;
-    int* cell_end;                                               // after scatter_kernel: one past the cell's last slot
-    int* status;
-    long long total_points, cells;
-    int n, k, orient, hint;
+struct NArgs : GridArgs {
+    int k, orient;
     double vp[3];
     float* normals;
     int* neighbours;
     float* variation;
 };
-
-// the cell of coordinate x on an axis: monotone in x (each step is), the same wherever it is computed
-__device__ __forceinline__ int cell_of(float x, float mn, float inv, int G) {
-    return min((int)((x - mn) * inv), G - 1);
-}
-
-__device__ __forceinline__ void cell3(const CloudGrid& g, const float* p, int c[3]) {
-    for (int a = 0; a < 3; ++a) c[a] = cell_of(p[a], g.mn[a], g.inv[a], g.G);
-}
-
-// ---- bounding box, grid size ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void bbox_kernel(NArgs a) {
-    __shared__ float s_red[6][NT];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const long long v0 = a.poff[m] - a.poff[0], v1 = a.poff[m + 1] - a.poff[0];
-    int st = GV_RENDER_OK;
-    if (v0 < 0 || v1 < v0 || v1 > a.total_points) st = GV_RENDER_BAD_OFFSETS;
-    else if (v1 - v0 > MAX_CLOUD) st = GV_RENDER_TOO_LARGE;
-    else if (v1 == v0) st = GV_RENDER_EMPTY;
-    CloudGrid g = {};
-    if (st == GV_RENDER_OK) {                                    // (uniform)
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (long long i = v0 + tid; i < v1; i += NT)
-            for (int c = 0; c < 3; ++c) {
-                const float p = a.pts[i * 3 + c];
-                mn[c] = fminf(mn[c], p);
-                mx[c] = p != p ? INFINITY : fmaxf(mx[c], p);     // (fmaxf would drop a NaN: it must not pass unseen)
-            }
-        for (int c = 0; c < 3; ++c) {
-            s_red[c][tid] = mn[c];
-            s_red[3 + c][tid] = mx[c];
-        }
-        __syncthreads();
-        for (int s = NT / 2; s > 0; s >>= 1) {
-            if (tid < s)
-                for (int c = 0; c < 3; ++c) {
-                    s_red[c][tid] = fminf(s_red[c][tid], s_red[c][tid + s]);
-                    s_red[3 + c][tid] = fmaxf(s_red[3 + c][tid], s_red[3 + c][tid + s]);
-                }
-            __syncthreads();
-        }
-        g.G = cells_per_axis(v1 - v0, a.hint);
-        for (int c = 0; c < 3; ++c) {
-            g.mn[c] = s_red[c][0];
-            g.mx[c] = s_red[3 + c][0];
-            const float ext = g.mx[c] - g.mn[c];
-            if (!(ext >= 0.0f && ext < INFINITY)) st = GV_RENDER_NONFINITE;      // a NaN / inf point, or a box past fp32
-            const float inv = ext > 0.0f ? (float)g.G / ext : 0.0f;
-            g.inv[c] = inv < INFINITY ? inv : 0.0f;              // (an extent in the denormals: one cell on this axis)
-        }
-    }
-    if (st != GV_RENDER_OK) g.G = 0;
-    g.status = st;
-    if (tid == 0) {
-        a.grid[m] = g;
-        a.status[m] = st;
-    }
-}
-
-// exclusive scan of the clouds' cell counts (one workgroup).  A cloud whose cells would pass the workspace's capacity
-// (offsets that overlap: the clouds then hold more than total_points points) is refused as GV_RENDER_BAD_OFFSETS.
-__global__ __launch_bounds__(SCAN_T) void cell_base_kernel(NArgs a) {
-    __shared__ long long s[SCAN_T];
-    const int tid = threadIdx.x;
-    long long carry = 0;
-    for (int b = 0; b < a.n; b += SCAN_T) {
-        const int i = b + tid;
-        long long v = 0;
-        if (i < a.n) {
-            const long long G = a.grid[i].G;
-            v = G * G * G;
-        }
-        s[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < SCAN_T; o <<= 1) {
-            const long long add = tid >= o ? s[tid - o] : 0;
-            __syncthreads();
-            s[tid] += add;
-            __syncthreads();
-        }
-        if (i < a.n) {
-            const long long base = carry + s[tid] - v;
-            a.grid[i].cell_base = base;
-            if (base + v > a.cells) {
-                a.grid[i].G = 0;
-                a.grid[i].status = GV_RENDER_BAD_OFFSETS;
-                a.status[i] = GV_RENDER_BAD_OFFSETS;
-            }
-        }
-        carry += s[SCAN_T - 1];
-        __syncthreads();
-    }
-}
-
-// ---- binning --------------------------------------------------------------------------------------------------------
-template <bool SCATTER>
-__global__ __launch_bounds__(NT) void bin_kernel(NArgs a) {
-    const int m = blockIdx.y;
-    const CloudGrid g = a.grid[m];
-    if (g.status != GV_RENDER_OK) return;
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
-    for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
-        int c[3];
-        cell3(g, a.pts + (v0 + i) * 3, c);
-        const long long cell = g.cell_base + ((long long)c[2] * g.G + c[1]) * g.G + c[0];
-        if (SCATTER) a.ids[v0 + atomicAdd(&a.cell_end[cell], 1)] = i;
-        else atomicAdd(&a.cell_count[cell], 1);
-    }
-}
-
-// every non-empty cell takes its slots from the cloud's cursor: cell_end starts as the cell's first slot
-__global__ __launch_bounds__(NT) void alloc_kernel(NArgs a) {
-    const int m = blockIdx.y;
-    CloudGrid& g = a.grid[m];
-    if (g.status != GV_RENDER_OK) return;
-    const long long cells = (long long)g.G * g.G * g.G;
-    for (long long c = (long long)blockIdx.x * NT + threadIdx.x; c < cells; c += (long long)gridDim.x * NT) {
-        const int cnt = a.cell_count[g.cell_base + c];
-        a.cell_end[g.cell_base + c] = cnt ? atomicAdd(&g.cursor, cnt) : 0;
-    }
-}
 
 // ---- covariance, Jacobi, sign ---------------------------------------------------------------------------------------
 // one Jacobi rotation of the pair (p, q) of a symmetric 3x3; r the third index.  Contract formulas, in their order.
@@ -312,21 +118,6 @@ __device__ __forceinline__ bool normal_of(const NArgs& a, const CloudGrid& g, lo
 }
 
 // ---- query ----------------------------------------------------------------------------------------------------------
-// A lower bound of the squared distance from point p (cell c) to any point in a cell outside the block of Chebyshev
-// radius r around c; +inf when the block holds the whole grid.  A point in a cell >= h on an axis has fl(fl(x - mn) *
-// inv) >= h, so x - mn >= (h / inv) (1 - 2^-23) in real numbers; a point in a cell <= l has x - mn < ((l + 1) / inv)
-// (1 + 2^-23).  The margin taken is 2^-18, in fp64 from the exact u = x_p - mn.
-__device__ __forceinline__ double ring_bound(const CloudGrid& g, const float* p, const int c[3], int r) {
-    double D = INFINITY;
-    for (int a = 0; a < 3; ++a) {
-        if (g.inv[a] == 0.0f) continue;                          // one occupied cell on this axis: nothing beyond it
-        const double u = (double)p[a] - (double)g.mn[a], cs = 1.0 / (double)g.inv[a];
-        if (c[a] + r + 1 <= g.G - 1) D = fmin(D, fmax((double)(c[a] + r + 1) * cs * (1.0 - 0x1p-18) - u, 0.0));
-        if (c[a] - r - 1 >= 0) D = fmin(D, fmax(u - (double)(c[a] - r) * cs * (1.0 + 0x1p-18), 0.0));
-    }
-    return D * D;
-}
-
 template <int K>
 __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
     __shared__ u64 s_keys[K * NT];                               // rank-major: a thread's column is s_keys[r * NT + tid]
@@ -335,7 +126,7 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
     if (g.status != GV_RENDER_OK && g.status != GV_RENDER_NONFINITE) return;     // no points, or none that can be trusted
     const long long v0 = a.poff[m] - a.poff[0];
     const int P = (int)(a.poff[m + 1] - a.poff[m]);
-    const int keff = min(a.k, P), G = g.G;
+    const int keff = min(a.k, P);
     u64* keys = s_keys + tid;
     bool degenerate = false;
     for (int s = blockIdx.x * NT + tid; s < P; s += gridDim.x * NT) {
@@ -346,50 +137,12 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
             i = a.ids[v0 + s];
             const float* pp = a.pts + (v0 + i) * 3;
             const float pi[3] = {pp[0], pp[1], pp[2]};
-            int c[3];
-            cell3(g, pi, c);
             for (int r = 0; r < keff; ++r) keys[r * NT] = NO_KEY;
             u64 worst = NO_KEY;
-            auto visit = [&](long long cell) {                  // every point of a cell against the k_eff best so far
-                const int end = a.cell_end[cell], beg = end - a.cell_count[cell];
-                for (int q = beg; q < end; ++q) {
-                    const int j = a.ids[v0 + q];
-                    const float* pj = a.pts + (v0 + j) * 3;
-                    const float dx = pj[0] - pi[0], dy = pj[1] - pi[1], dz = pj[2] - pi[2];
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    const u64 key = ((u64)__float_as_uint(d2) << 32) | (unsigned)j;
-                    if (key >= worst) continue;
-                    int t = keff - 1;                            // sorted insert from the end
-                    while (t > 0) {
-                        const u64 prev = keys[(t - 1) * NT];
-                        if (prev < key) break;
-                        keys[t * NT] = prev;
-                        --t;
-                    }
-                    keys[t * NT] = key;
-                    worst = keys[(keff - 1) * NT];
-                }
-            };
-            for (int r = 0;; ++r) {                              // the shell of Chebyshev radius r, clipped to the grid
-                const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G - 1);
-                const int xl = c[0] - r, xh = c[0] + r;
-                for (int z = z0; z <= z1; ++z)
-                    for (int y = y0; y <= y1; ++y) {
-                        const long long row = g.cell_base + ((long long)z * G + y) * G;
-                        if (abs(z - c[2]) == r || abs(y - c[1]) == r) {          // a row of the shell's z or y faces: whole
-                            for (int x = max(xl, 0); x <= min(xh, G - 1); ++x) visit(row + x);
-                        } else {                                                 // any other (r >= 1): its two ends
-                            if (xl >= 0) visit(row + xl);
-                            if (xh <= G - 1) visit(row + xh);
-                        }
-                    }
-                const double B = ring_bound(g, pi, c, r);
-                if (B == INFINITY) break;                        // every cell has been seen
-                // fp32 d2 of an unseen point >= B (1 - 2^-22) unless B is near the underflow of a square; the strict <
-                // leaves a tie with the k-th key to the next ring
-                if (worst != NO_KEY && B > 1e-30 && (double)__uint_as_float((unsigned)(worst >> 32)) < B * (1.0 - 0x1p-18))
-                    break;
-            }
+            ring_walk(
+                a, g, v0, pi,
+                [&](int j, float d2) { insert_key(keys, keff, ((u64)__float_as_uint(d2) << 32) | (unsigned)j, worst); },
+                [&]() { return worst; });
             ok = normal_of(a, g, v0, pi, keys, keff, nf, var);
             degenerate |= !ok;
         }
@@ -405,17 +158,12 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
     if (degenerate) atomicOr(&a.status[m], GV_POINTS_DEGENERATE_NORMAL);
 }
 
-unsigned grid_x(long long items) {
-    const long long b = (items + NT - 1) / NT;
-    return (unsigned)(b < 1 ? 1 : b > MAX_GRID_X ? MAX_GRID_X : b);
-}
-
 }  // namespace
 
 extern "C" int64_t gv_points_normals_workspace_bytes(int32_t n, int64_t total_points, int32_t grid_cells) {
     if (n <= 0 || total_points < 0 || grid_cells < 0 || grid_cells > MAX_G) return GV_E_BADARG;
     if (n > 65535) return GV_E_UNSUPPORTED;
-    return ws_layout(n, total_points, grid_cells).bytes;
+    return grid_ws_layout(n, total_points, grid_cells).bytes;
 }
 
 extern "C" int gv_points_estimate_normals(const float* points, const int64_t* point_offsets, int32_t n,
@@ -432,45 +180,23 @@ extern "C" int gv_points_estimate_normals(const float* points, const int64_t* po
         !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return GV_E_BADARG;
     if (n > 65535 || max_points > MAX_CLOUD) return GV_E_UNSUPPORTED;
-    const NormalsWs L = ws_layout(n, total_points, grid_cells);
+    const GridWs L = grid_ws_layout(n, total_points, grid_cells);
     if (workspace_bytes < L.bytes) return GV_E_BADARG;
     if (!gv_aligned16(workspace) || ((uintptr_t)point_offsets & 7u) ||
         (((uintptr_t)points | (uintptr_t)normals | (uintptr_t)neighbours | (uintptr_t)variation | (uintptr_t)status) & 3u))
         return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
     NArgs a;
-    a.pts = points;
-    a.poff = (const long long*)point_offsets;
-    a.grid = reinterpret_cast<CloudGrid*>(ws + L.grids);
-    a.ids = reinterpret_cast<int*>(ws + L.ids);
-    a.cell_count = reinterpret_cast<int*>(ws + L.cell_count);
-    a.cell_end = reinterpret_cast<int*>(ws + L.cell_end);
-    a.status = status;
-    a.total_points = total_points;
-    a.cells = L.cells;
-    a.n = n;
+    grid_args(a, points, point_offsets, n, total_points, grid_cells, workspace, L, status);
     a.k = k;
     a.orient = orient;
-    a.hint = grid_cells;
     for (int c = 0; c < 3; ++c) a.vp[c] = orient == GV_NORMALS_ORIENT_VIEWPOINT ? (double)viewpoint[c] : 0.0;
     a.normals = normals;
     a.neighbours = neighbours;
     a.variation = variation;
-    // max_points sizes the launches only: every kernel strides what its grid does not cover
-    const long long G = cells_per_axis(max_points, grid_cells);
-    const dim3 by_point(grid_x(max_points), (unsigned)n), by_cell(grid_x(G * G * G), (unsigned)n);
-    GV_HIP_CHECK(hipMemsetAsync(a.cell_count, 0, (size_t)L.cells * 4, st));
-    hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)n), dim3(NT), 0, st, a);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cell_base_kernel, dim3(1), dim3(SCAN_T), 0, st, a);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bin_kernel<false>, by_point, dim3(NT), 0, st, a);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(alloc_kernel, by_cell, dim3(NT), 0, st, a);
-    GV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bin_kernel<true>, by_point, dim3(NT), 0, st, a);
-    GV_LAUNCH_CHECK();
+    const int rc = build_grid(a, max_points, st);
+    if (rc != GV_OK) return rc;
+    const dim3 by_point(grid_x(max_points), (unsigned)n);
     if (k <= 8) hipLaunchKernelGGL(query_kernel<8>, by_point, dim3(NT), 0, st, a);
     else if (k <= 16) hipLaunchKernelGGL(query_kernel<16>, by_point, dim3(NT), 0, st, a);
     else hipLaunchKernelGGL(query_kernel<32>, by_point, dim3(NT), 0, st, a);

@@ -61,6 +61,11 @@ Points in (csrc/render_points.hip; contract: include/gvcnn_hip.h, "points in"; r
     cloud (fp32 squared distances, ties to the lower id), their fp64 covariance, its smallest eigenvector by cyclic
     Jacobi, turned away from the bounding box's centre ("outward"), towards a sensor position ("viewpoint") or so that
     its largest component is positive ("none").  Bit for bit the same whatever the batch, the grid or the schedule.
+  - a raw scan is cleaned on the device first: batch.voxel_downsample(voxel) keeps the centroid of every occupied voxel,
+    batch.remove_outliers(k=16, std_ratio=2.0) drops the points whose mean distance to their k nearest neighbours lies
+    more than std_ratio standard deviations above the cloud's mean (csrc/point_clean.hip; contract: include/gvcnn_hip.h,
+    "points in", cleaning; restated in tests/points_clean_oracle.py).  Each returns a new PointBatch that every call
+    above takes; PointBatch.from_device wraps tensors that are on the device already.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
@@ -498,6 +503,47 @@ def _check_normals_args(k, orient, viewpoint, grid):
         raise ValueError("estimate_normals: grid must be None (auto) or an integer in [1, %d]" % NORMALS_MAX_GRID)
     return k, NORMALS_ORIENT[orient], viewpoint, int(grid)
 
+CLEAN_MIN_K, CLEAN_MAX_K = 1, 32
+
+
+def _check_grid(grid, what):
+    if grid is None:
+        return 0
+    if isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not 1 <= grid <= NORMALS_MAX_GRID:
+        raise ValueError("%s: grid must be None (auto) or an integer in [1, %d]" % (what, NORMALS_MAX_GRID))
+    return int(grid)
+
+
+def _check_outlier_args(k, std_ratio, grid):
+    """(k, std_ratio as float32, grid_cells) of remove_outliers, or ValueError."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not CLEAN_MIN_K <= k <= CLEAN_MAX_K:
+        raise ValueError("remove_outliers: k must be an integer in [%d, %d]" % (CLEAN_MIN_K, CLEAN_MAX_K))
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, numbers.Real):
+        raise ValueError("remove_outliers: std_ratio must be a finite number >= 0")
+    with np.errstate(over="ignore"):
+        ratio = np.float32(std_ratio)
+    if not (np.isfinite(ratio) and ratio >= 0):
+        raise ValueError("remove_outliers: std_ratio must be a finite number >= 0")
+    return int(k), ratio, _check_grid(grid, "remove_outliers")
+
+
+def _check_voxel_args(voxel, relative, n):
+    """(voxel float32 [n], relative 0 / 1) of voxel_downsample, or ValueError.  A size is a finite number > 0: the
+    passthrough clauses of the contract are for sizes that turn bad on the device (relative to a cloud without extent)."""
+    if not isinstance(relative, (bool, np.bool_)):
+        raise ValueError("voxel_downsample: relative must be True or False")
+    try:
+        with np.errstate(over="ignore"):
+            v = np.asarray(voxel, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("voxel_downsample: voxel must be a number or one number per cloud")
+    if isinstance(voxel, (bool, np.bool_)) or v.ndim > 1 or (v.ndim == 1 and len(v) != n):
+        raise ValueError("voxel_downsample: voxel must be a number or one number per cloud (%d)" % n)
+    v = np.ascontiguousarray(np.broadcast_to(v, (n,)))
+    if not (np.isfinite(v).all() and (v > 0).all()):
+        raise ValueError("voxel_downsample: a voxel size must be finite and > 0")
+    return v, int(bool(relative))
+
 
 class PointBatch:
     """Point clouds packed and uploaded once, as MeshBatch does for meshes.  clouds: a list of points [P, 3] or of
@@ -518,6 +564,7 @@ class PointBatch:
         self.points = torch.from_numpy(np.ascontiguousarray(pts)).to(self.device)
         self.normals = None
         self.normal_status = None                                # host int32 [N] once estimate_normals has run
+        self.clean_status = None                                 # host int32 [N] on the result of a cleaning call
         if p["normals"] is not None:
             nr = p["normals"] if len(p["normals"]) else np.zeros((1, 3), np.float32)
             self.normals = torch.from_numpy(np.ascontiguousarray(nr)).to(self.device)
@@ -538,6 +585,117 @@ class PointBatch:
     def group_normals(self, a):
         """The normals pointer of the group that starts at cloud a (None without normals)."""
         return None if self.normals is None else self.normals.data_ptr() + int(self.point_offsets_host[a]) * 12
+
+    @classmethod
+    def from_device(cls, points, point_offsets_host, normals=None):
+        """A batch from tensors that are on the device already, with no host round trip: points float32 [sum P, 3]
+        (contiguous), point_offsets_host int64 [N + 1] on the host (from 0, non-decreasing, ending at sum P), normals
+        float32 [sum P, 3] or None.  The points are not read: what pack_points checks on the host (finite values) is the
+        device's per-cloud status here."""
+        po = np.ascontiguousarray(np.asarray(point_offsets_host, dtype=np.int64))
+        if po.ndim != 1 or len(po) < 2 or po[0] != 0 or (np.diff(po) < 0).any():
+            raise ValueError("from_device: point_offsets must be [N + 1], start at 0 and not decrease")
+        if np.diff(po).max() > MAX_POINTS:
+            raise ValueError("from_device: a cloud has more than 2^24 points")
+        for name, t in (("points", points), ("normals", normals)):
+            if t is None and name == "normals":
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2
+                    and t.shape[1] == 3 and t.is_contiguous() and t.shape[0] >= max(int(po[-1]), 1)):
+                raise ValueError("from_device: %s must be a contiguous float32 device tensor [sum P, 3]" % name)
+        if normals is not None and normals.device != points.device:
+            raise ValueError("from_device: points and normals are on different devices")
+        self = cls.__new__(cls)
+        self.device = points.device
+        self.n = len(po) - 1
+        self.point_offsets_host = po
+        self.num_points = np.diff(po)
+        self.points = points
+        self.normals = normals
+        self.normal_status = None
+        self.clean_status = None
+        self.point_offsets = torch.from_numpy(po).to(self.device)
+        return self
+
+    def _compact(self, lib, keep, selected, index, status, ws, ws_bytes, with_normals):
+        """gv_points_compact on a selection -> (new batch, out_index); only the counts are read back."""
+        rows = self.points.shape[0]
+        out_points = torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
+        out_normals = torch.zeros((rows, 3), dtype=torch.float32, device=self.device) if with_normals else None
+        out_index = torch.zeros(rows, dtype=torch.int32, device=self.device)
+        out_offsets = torch.zeros(self.n + 1, dtype=torch.int64, device=self.device)
+        counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        rc = lib.gv_points_compact(
+            *self.group(0, self.n), keep.data_ptr(), None if selected is None else selected.data_ptr(),
+            None if index is None else index.data_ptr(), self.group_normals(0) if with_normals else None,
+            status.data_ptr(), out_points.data_ptr(), None if out_normals is None else out_normals.data_ptr(),
+            out_index.data_ptr(), out_offsets.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws_bytes, _model._st())
+        _lib.check(rc, "gv_points_compact")
+        po = np.zeros(self.n + 1, np.int64)
+        po[1:] = np.cumsum(counts.cpu().numpy().astype(np.int64))        # (the workspace is not reused before this sync)
+        new = PointBatch.from_device(out_points, po, out_normals)
+        new.point_offsets = out_offsets
+        return new, out_index
+
+    def _clean_workspace(self, lib, grid):
+        total = int(self.point_offsets_host[-1])
+        ws_bytes = lib.gv_points_clean_workspace_bytes(self.n, total, grid)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_clean_workspace_bytes")
+        return torch.empty(ws_bytes, dtype=torch.uint8, device=self.device), ws_bytes
+
+    def remove_outliers(self, k=16, std_ratio=2.0, grid=None, return_index=False, return_stats=False):
+        """Statistical outlier removal on the device (contract: include/gvcnn_hip.h, "points in", cleaning): a point
+        goes when the mean distance to its k nearest neighbours (k: 1..32) exceeds the cloud's mean of that figure by
+        more than std_ratio (>= 0) standard deviations.  Returns a NEW batch of the kept points in their order; normals
+        and normal_status are carried along.  grid: as for estimate_normals, it changes the speed alone.  Sets
+        clean_status on the result, host int32 [N]: GV_RENDER_* of the cloud, with GV_POINTS_CLEAN_PASSTHROUGH when it
+        went through unchanged.  Only the counts are read back.  Returns the batch, or (batch, index int32 [new sum P]
+        (ids within the original cloud), (mean_dist float32 [old sum P], stats float64 [N, 3] = mu, sigma, threshold),
+        each on request), on the device."""
+        k, ratio, grid = _check_outlier_args(k, std_ratio, grid)
+        lib = _lib.load()
+        rows = self.points.shape[0]
+        with torch.cuda.device(self.device):
+            ws, ws_bytes = self._clean_workspace(lib, grid)
+            keep = torch.zeros(rows, dtype=torch.int32, device=self.device)
+            md = torch.zeros(rows, dtype=torch.float32, device=self.device) if return_stats else None
+            stats = torch.zeros((self.n, 3), dtype=torch.float64, device=self.device) if return_stats else None
+            status = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            rc = lib.gv_points_outlier_select(
+                *self.group(0, self.n), k, float(ratio), grid, keep.data_ptr(), None if md is None else md.data_ptr(),
+                None if stats is None else stats.data_ptr(), ws.data_ptr(), ws_bytes, status.data_ptr(), _model._st())
+            _lib.check(rc, "gv_points_outlier_select")
+            new, index = self._compact(lib, keep, None, None, status, ws, ws_bytes, self.normals is not None)
+            new.clean_status = status.cpu().numpy()
+        new.normal_status = None if self.normal_status is None else self.normal_status.copy()
+        extras = ((index,) if return_index else ()) + (((md, stats),) if return_stats else ())
+        return (new,) + extras if extras else new
+
+    def voxel_downsample(self, voxel, relative=False, return_index=False):
+        """Voxel downsampling on the device (contract: include/gvcnn_hip.h, "points in", cleaning): one point per
+        occupied voxel, the centroid of the voxel's points, in the order of each voxel's first point.  voxel: the edge
+        length, a number or one number per cloud, in the clouds' units, or with relative=True as a fraction of the
+        cloud's largest bounding-box extent.  Returns a NEW batch; a batch with normals gives each centroid the normal
+        of the voxel's point nearest to it (normals are not averaged), and normal_status becomes None.  Sets
+        clean_status on the result, host int32 [N], as remove_outliers does (GV_POINTS_CLEAN_PASSTHROUGH: a voxel size
+        that is not > 0 on the device, or below 2^-21 of the extent).  Returns the batch, or (batch, index int32 [new
+        sum P]: the id within the original cloud of that nearest point), on the device."""
+        voxel, relative = _check_voxel_args(voxel, relative, self.n)
+        lib = _lib.load()
+        rows = self.points.shape[0]
+        with torch.cuda.device(self.device):
+            ws, ws_bytes = self._clean_workspace(lib, 0)
+            keep = torch.zeros(rows, dtype=torch.int32, device=self.device)
+            centroids = torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
+            index = torch.full((rows,), -1, dtype=torch.int32, device=self.device)
+            status = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            rc = lib.gv_points_voxel_select(
+                *self.group(0, self.n), voxel.ctypes.data, relative, 0, keep.data_ptr(), centroids.data_ptr(),
+                index.data_ptr(), ws.data_ptr(), ws_bytes, status.data_ptr(), _model._st())
+            _lib.check(rc, "gv_points_voxel_select")
+            new, out_index = self._compact(lib, keep, centroids, index, status, ws, ws_bytes, self.normals is not None)
+            new.clean_status = status.cpu().numpy()              # (voxel, a host array, stays alive past its copy)
+        return (new, out_index) if return_index else new
 
     def estimate_normals(self, k=16, orient="outward", viewpoint=None, grid=None, return_neighbors=False,
                          return_variation=False):
@@ -579,6 +737,25 @@ def estimate_normals(points, k=16, orient="outward", viewpoint=None, grid=None, 
     _check_normals_args(k, orient, viewpoint, grid)
     batch = PointBatch([points], device).estimate_normals(k, orient, viewpoint, grid)
     return batch.normals.cpu().numpy()[:int(batch.num_points[0])]
+
+
+def _kept(batch, index):
+    n = int(batch.num_points[0])
+    return batch.points.cpu().numpy()[:n], index.cpu().numpy()[:n]
+
+
+def remove_outliers(points, k=16, std_ratio=2.0, grid=None, device=None):
+    """(kept points float32 [P', 3], index int32 [P'] into `points`) of one host cloud points [P, 3]:
+    PointBatch([points]).remove_outliers(...), copied back."""
+    _check_outlier_args(k, std_ratio, grid)
+    return _kept(*PointBatch([points], device).remove_outliers(k, std_ratio, grid, return_index=True))
+
+
+def voxel_downsample(points, voxel, relative=False, device=None):
+    """(centroids float32 [P', 3], index int32 [P']: the point of `points` nearest to each centroid within its voxel) of
+    one host cloud points [P, 3]: PointBatch([points]).voxel_downsample(...), copied back."""
+    _check_voxel_args(voxel, relative, 1)
+    return _kept(*PointBatch([points], device).voxel_downsample(voxel, relative, return_index=True))
 
 
 def random_rotations(n, mode="z", seed=0):

@@ -839,6 +839,69 @@ int gv_points_estimate_normals(const float* points, const int64_t* point_offsets
                                int32_t max_points, int32_t k, int32_t orient, const float* viewpoint, int32_t grid_cells,
                                float* normals, int32_t* neighbours, float* variation, void* workspace,
                                int64_t workspace_bytes, int32_t* status, void* stream);
+/* Cleaning: what a raw scan needs before its normals are estimated and before the normalisation above may trust every
+ * point: statistical outlier selection, voxel selection, and the one compaction that turns either selection into a new
+ * batch.  Defined bit for bit, under the discipline of the normals call: independent of scheduling, of how a batch is
+ * split, of grid_cells / max_points and of the order of the points in memory (up to the ids that order gives); no
+ * floating-point atomics; every step rounded on its own (no FMA).
+ *  - inputs: points / point_offsets / max_points / grid_cells as for the normals call.  The per-cloud status [N] (device
+ *    memory) comes from the same bounding-box pass.  GV_RENDER_EMPTY, GV_RENDER_TOO_LARGE and GV_RENDER_BAD_OFFSETS:
+ *    nothing is written for the cloud and its output count is 0.  GV_RENDER_NONFINITE: the cloud passes through unchanged
+ *    (every keep flag 1, centroid = the point, index = its id, mean_dist 0, stats 0) with GV_POINTS_CLEAN_PASSTHROUGH
+ *    or-ed into its status.
+ *  - gv_points_outlier_select: k in [1, 32], std_ratio finite and >= 0.  Neighbours of point i of a cloud of P points: the
+ *    fp32 d2 and the keys (bits(d2) << 32) | j of the normals contract over every j != i; the neighbourhood is the k_eff =
+ *    min(k, P - 1) smallest keys in ascending order.  Mean distance, fp64, every step rounded: m_i = (sqrt((double)d2_0)
+ *    + ... + sqrt((double)d2_{k_eff-1})) / (double)k_eff, summed from 0.0 left to right in rank order, sqrt correctly
+ *    rounded.  Sums over a cloud are the tree sum T(a): a_0 .. a_{P-1} padded with +0.0 to the next power of two, then
+ *    level by level b_t = a_{2t} + a_{2t+1} until one value is left (a fixed tree over ids).  mu = T(m) / (double)P; e_i =
+ *    m_i - mu; sigma = sqrt(T(e*e) / (double)(P - 1)); T = mu + (double)std_ratio * sigma; keep_i = (m_i <= T).  P < 2:
+ *    every point is kept, m_i = 0 and the stats are 0.  Outputs: keep int32 [sum P] (1 / 0); mean_dist fp32 [sum P] or
+ *    NULL: m_i rounded once; stats fp64 [N, 3] or NULL: (mu, sigma, T), zeros for a cloud without a selection.
+ *  - gv_points_voxel_select: voxel fp32 [N], HOST memory (copied into the workspace on the stream: keep it alive until
+ *    the stream has passed that copy); relative 0 / 1.  Per cloud, with mn / ext the bounding box's minimum and fp32
+ *    extent per axis: h = voxel_m, or fl(voxel_m * max(ext_x, ext_y, ext_z)) when relative.  An h that is not finite or
+ *    not > 0, or fl(ext_a / h) >= 2097152 on some axis: the cloud passes through unchanged with
+ *    GV_POINTS_CLEAN_PASSTHROUGH.  Cell of a point per axis: t = x - mn, q = t / h (a correctly rounded fp32 division),
+ *    c = (int)q; the voxel key is (c2 << 42) | (c1 << 21) | c0.  Centroid through integers, so that no order enters:
+ *    frexpf(max ext) = f * 2^E and s = 2^(29 - E) as a double (s = 1 when the largest extent is 0); F = llrint((double)t
+ *    * s) per axis (the product is exact; ties to even); S = the int64 sum of F over the voxel's n_v members (at most
+ *    2^53); centroid = (float)((double)mn + ((double)S / (double)n_v) / s), each fp64 step rounded, one rounding to
+ *    fp32.  Representative member: the smallest key (bits(d2) << 32) | id over the members, d = p - centroid per
+ *    component in fp32 and d2 = (dx*dx + dy*dy) + dz*dz.  Outputs at the voxel's LOWEST member id: keep 1, centroids
+ *    [sum P, 3] the centroid, index int32 [sum P] the representative's id; at every other member: keep 0, centroid
+ *    (0, 0, 0), index -1.  GV_POINTS_CLEAN_TABLE_FULL in a status says the voxel table overflowed: a defect, never a
+ *    property of the input (the table holds more slots than the cloud has points).
+ *  - gv_points_compact: per cloud the exclusive scan of keep in id order; counts int32 [N] and the new point_offsets
+ *    int64 [N + 1] (from 0), both device memory; out_points [new sum P, 3] = selected (the centroids) or, with selected
+ *    NULL, the points themselves; out_index int32 [new sum P] = index or, with index NULL, the point's own id: ids within
+ *    the ORIGINAL cloud; out_normals = normals[out_index], with normals NULL none (both or neither).  The kept points of
+ *    a cloud stay in ascending id order, so voxels come in the order of their lowest member.  status: the selection's,
+ *    read on the device.  Output buffers are caller-allocated at the old sum P.
+ * workspace: gv_points_clean_workspace_bytes(n, total_points, grid_cells) bytes, 16-byte aligned, serves all three calls
+ * (the compaction with any grid_cells).  The argument errors are those of the normals call, before any HIP call:
+ * GV_E_BADARG for a NULL required pointer, n <= 0, total_points or max_points < 0, k outside [1, 32], a std_ratio that is
+ * not finite or < 0, relative outside {0, 1}, grid_cells outside [0, 128], normals without out_normals or the reverse, a
+ * workspace smaller than the size query's answer; GV_E_UNSUPPORTED for n > 65535 or max_points > 2^24; GV_E_ALIGN for a
+ * workspace that is not 16-byte aligned, an 8-byte buffer (point_offsets, stats, out_offsets) that is not 8-byte aligned
+ * or a 4-byte buffer that is not 4-byte aligned.
+ * Not here: radius-count outlier removal, normals averaged over a voxel, voxel sizes below 2^-21 of the extent. */
+#define GV_POINTS_CLEAN_PASSTHROUGH 0x200  /* or-ed into status[m]: cloud m went through unchanged */
+#define GV_POINTS_CLEAN_TABLE_FULL 0x400   /* or-ed into status[m]: the voxel table of cloud m overflowed (a defect) */
+int64_t gv_points_clean_workspace_bytes(int32_t n, int64_t total_points, int32_t grid_cells);
+int gv_points_outlier_select(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                             int32_t max_points, int32_t k, float std_ratio, int32_t grid_cells, int32_t* keep,
+                             float* mean_dist, double* stats, void* workspace, int64_t workspace_bytes, int32_t* status,
+                             void* stream);
+int gv_points_voxel_select(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                           int32_t max_points, const float* voxel, int32_t relative, int32_t grid_cells, int32_t* keep,
+                           float* centroids, int32_t* index, void* workspace, int64_t workspace_bytes, int32_t* status,
+                           void* stream);
+int gv_points_compact(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
+                      int32_t max_points, const int32_t* keep, const float* selected, const int32_t* index,
+                      const float* normals, const int32_t* status, float* out_points, float* out_normals,
+                      int32_t* out_index, int64_t* out_offsets, int32_t* counts, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
