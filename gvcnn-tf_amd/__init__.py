@@ -18,10 +18,10 @@ from . import retrieval  # noqa: E402
 from .retrieval import MetricLearner, ShapeIndex  # noqa: E402,F401
 from . import render  # noqa: E402
 from .render import (MeshBatch, PointBatch, ViewRenderer, estimate_normals, load_obj, load_off, load_points,  # noqa: E402,F401
-                     pack_meshes, random_rotations, remove_outliers, sample_surface, voxel_downsample)
+                     pack_meshes, random_rotations, register, remove_outliers, sample_surface, voxel_downsample)
 
 __all__ = ["GVCNN", "gvcnn", "basic", "group_scheme", "group_weight", "view_pooling", "group_fusion",
            "grouping_module", "gvcnn_fused", "configure", "explain_views", "Explanation", "AUTO_REUSE", "backbones", "params", "model", "retrieval",
            "ShapeIndex", "MetricLearner", "render", "MeshBatch", "ViewRenderer", "load_off", "load_obj", "pack_meshes",
            "random_rotations", "PointBatch", "load_points", "sample_surface", "estimate_normals", "remove_outliers",
-           "voxel_downsample"]
+           "voxel_downsample", "register"]

@@ -40,6 +40,7 @@ GV_RENDER_OK, GV_RENDER_EMPTY, GV_RENDER_ZERO_RADIUS, GV_RENDER_NONFINITE, GV_RE
 GV_NORMALS_ORIENT_NONE, GV_NORMALS_ORIENT_OUTWARD, GV_NORMALS_ORIENT_VIEWPOINT = 0, 1, 2
 GV_POINTS_DEGENERATE_NORMAL = 0x100
 GV_POINTS_CLEAN_PASSTHROUGH, GV_POINTS_CLEAN_TABLE_FULL = 0x200, 0x400
+GV_POINTS_ICP_CONVERGED, GV_POINTS_ICP_FEW_PAIRS, GV_POINTS_ICP_NONFINITE = 0x800, 0x1000, 0x2000
 GV_PNG_STATUS = ("OK", "TRUNCATED", "BAD_HEADER", "BAD_BLOCK", "BAD_CODES", "BAD_DISTANCE", "TOO_LONG", "TOO_SHORT",
                  "BAD_CHECKSUM", "BAD_FILTER", "BAD_PALETTE_INDEX")      # GV_PNG_* of the header, by value
 (GV_PNG_OK, GV_PNG_TRUNCATED, GV_PNG_BAD_HEADER, GV_PNG_BAD_BLOCK, GV_PNG_BAD_CODES, GV_PNG_BAD_DISTANCE, GV_PNG_TOO_LONG,
@@ -187,6 +188,9 @@ SIGNATURES = {
     "gv_points_outlier_select": (C.c_int, [_P, _P, _I, _L, _I, _I, _F, _I, _P, _P, _P, _P, _L, _P, _P]),
     "gv_points_voxel_select": (C.c_int, [_P, _P, _I, _L, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _P]),
     "gv_points_compact": (C.c_int, [_P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "gv_points_register_workspace_bytes": (_L, [_I, _L, _L, _I]),
+    "gv_points_register": (C.c_int, [_P, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _I, _F, C.c_double, _I, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _L, _P, _P]),
     "gv_dense_fwd": (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gv_bn_stats_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
     "gv_bn_sums_grouped": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
@@ -265,6 +269,7 @@ TUNING = {
     "gv_conv2d_wgrad_num_cfgs": (C.c_int, [C.c_int]),
     "gv_conv2d_wgrad_set_strip_taps": (None, [C.c_int]),
     "gv_pool2d_set_rows": (None, [C.c_int]),
+    "gv_points_register_set_cell_order": (None, [C.c_int]),      # nearest kernel: source points by cell (1) or by id (0)
 }
 # gv_conv2d_set_debug bits that tests may use: each selects another CORRECT product path (gvconv::Probe, csrc/conv_probe.h)
 PROBE_TAP_MAJOR = 128               # conv_dma: k-tiles tap-major where channel-chunk-major would be taken

@@ -17,7 +17,7 @@ PT = os.environ.get("GV_PHASE_TIMES") == "1"
 LIB = os.path.join(HERE, "libgvcnn_hip_pt.so" if PT else "libgvcnn_hip.so")
 BUILD = "build_pt" if PT else "build"
 SOURCES = ["conv_igemm.hip", "conv_bf16s.hip", "conv_lp.hip", "conv_dma.hip", "conv_ws.hip", "conv_ws_x3.hip", "conv_chain.hip", "pool.hip", "grouping.hip", "plan.hip", "train.hip", "bn_train.hip", "wgrad_lp.hip", "pool_train.hip", "wgrad_dma.hip",
-           "retrieval.hip", "render.hip", "render_points.hip", "point_normals.hip", "point_clean.hip", "metric.hip", "scorer_bwd.hip", "png.hip", "png_enc.hip", "explain.hip"]
+           "retrieval.hip", "render.hip", "render_points.hip", "point_normals.hip", "point_clean.hip", "point_register.hip", "metric.hip", "scorer_bwd.hip", "png.hip", "png_enc.hip", "explain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + (["-DGV_PHASE_TIMES"] if PT else [])
 

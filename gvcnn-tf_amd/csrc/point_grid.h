@@ -1,5 +1,6 @@
 // point_grid.h — the uniform search grid over a batch of point clouds and the exact k-nearest walk through it, shared by
-// point_normals.hip (normal estimation) and point_clean.hip (outlier selection, voxel selection, compaction).
+// point_normals.hip (normal estimation), point_clean.hip (outlier selection, voxel selection, compaction) and
+// point_register.hip (the nearest target point of a moved source point).
 //
 //   build_grid   bbox_kernel        one workgroup per cloud: offsets check, bounding box, cells per axis G.
 //                cell_base_kernel   one workgroup: exclusive scan of the clouds' G^3 -> where each cloud's cells start in
@@ -10,7 +11,8 @@
 //                bin_kernel<true>   a thread per point: its id into its cell's range.
 //   ring_walk    Chebyshev rings of cells around a point's own; every candidate goes to visit(j, d2); the walk stops
 //                only when every point it has not seen is PROVABLY farther than the caller's k-th key (ring_bound; ties
-//                included), so the k smallest keys never depend on the grid.
+//                included), so the k smallest keys never depend on the grid.  ring_walk_from: the same walk around a
+//                cell the caller names (cell3_clamped: a query that may lie outside the cloud's box).
 //   insert_key   the k smallest keys (bits(d2) << 32 | id) kept sorted in an LDS column of the thread.
 //
 #pragma once
@@ -114,6 +116,17 @@ __device__ __forceinline__ int cell_of(float x, float mn, float inv, int G) {
 
 __device__ __forceinline__ void cell3(const CloudGrid& g, const float* p, int c[3]) {
     for (int a = 0; a < 3; ++a) c[a] = cell_of(p[a], g.mn[a], g.inv[a], g.G);
+}
+
+// cell_of for a coordinate that may lie outside the cloud's box (a query from another cloud): the nearest cell of the
+// axis.  The clamp is in float, before the conversion, so neither a negative nor a huge (x - mn) * inv reaches the cast
+// (fmaxf turns the NaN of inf * 0 into 0).  Inside the box it is cell_of: min((int)t, G - 1) == (int)min(t, G - 1), t >= 0.
+__device__ __forceinline__ int cell_of_clamped(float x, float mn, float inv, int G) {
+    return (int)fminf(fmaxf((x - mn) * inv, 0.0f), (float)(G - 1));
+}
+
+__device__ __forceinline__ void cell3_clamped(const CloudGrid& g, const float* p, int c[3]) {
+    for (int a = 0; a < 3; ++a) c[a] = cell_of_clamped(p[a], g.mn[a], g.inv[a], g.G);
 }
 
 // ---- bounding box, grid size ----------------------------------------------------------------------------------------
@@ -258,6 +271,9 @@ inline int build_grid(const GridArgs& a, int32_t max_points, hipStream_t st) {
 // radius r around c; +inf when the block holds the whole grid.  A point in a cell >= h on an axis has fl(fl(x - mn) *
 // inv) >= h, so x - mn >= (h / inv) (1 - 2^-23) in real numbers; a point in a cell <= l has x - mn < ((l + 1) / inv)
 // (1 + 2^-23).  The margin taken is 2^-18, in fp64 from the exact u = x_p - mn.
+// Neither inequality speaks of p, so the bound holds for ANY cell c, p's own or not, and for a p outside the box with its
+// clamped cell: beyond the upper face c = G - 1 and the first branch is skipped, while in the second u only grew past
+// the box (a larger, still true, bound); beyond the lower face c = 0, the second is skipped and -u > 0 adds to the first.
 __device__ __forceinline__ double ring_bound(const CloudGrid& g, const float* p, const int c[3], int r) {
     double D = INFINITY;
     for (int a = 0; a < 3; ++a) {
@@ -285,12 +301,11 @@ __device__ __forceinline__ void insert_key(u64* keys, int keff, u64 key, u64& wo
 
 // Every point j of the cloud that can be among the nearest of point pi, ring by ring: visit(j, d2) with the contract's
 // fp32 d2 (pi itself included, d2 = 0).  kth() is the caller's k-th smallest key so far, NO_KEY while it has fewer.
+// c: the cell the rings are centred on, any cell of the grid (ring_bound holds for each; the nearest is the fastest).
 template <class Visit, class Kth>
-__device__ __forceinline__ void ring_walk(const GridArgs& a, const CloudGrid& g, long long v0, const float pi[3], Visit visit,
-                                          Kth kth) {
+__device__ __forceinline__ void ring_walk_from(const GridArgs& a, const CloudGrid& g, long long v0, const float pi[3],
+                                               const int c[3], Visit visit, Kth kth) {
     const int G = g.G;
-    int c[3];
-    cell3(g, pi, c);
     auto cell_points = [&](long long cell) {
         const int end = a.cell_end[cell], beg = end - a.cell_count[cell];
         for (int q = beg; q < end; ++q) {
@@ -320,6 +335,15 @@ __device__ __forceinline__ void ring_walk(const GridArgs& a, const CloudGrid& g,
         const u64 worst = kth();
         if (worst != NO_KEY && B > 1e-30 && (double)__uint_as_float((unsigned)(worst >> 32)) < B * (1.0 - 0x1p-18)) break;
     }
+}
+
+// the walk of a point of the cloud itself, around its own cell
+template <class Visit, class Kth>
+__device__ __forceinline__ void ring_walk(const GridArgs& a, const CloudGrid& g, long long v0, const float pi[3], Visit visit,
+                                          Kth kth) {
+    int c[3];
+    cell3(g, pi, c);
+    ring_walk_from(a, g, v0, pi, c, visit, kth);
 }
 
 }  // namespace

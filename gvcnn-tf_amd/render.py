@@ -66,6 +66,11 @@ Points in (csrc/render_points.hip; contract: include/gvcnn_hip.h, "points in"; r
     more than std_ratio standard deviations above the cloud's mean (csrc/point_clean.hip; contract: include/gvcnn_hip.h,
     "points in", cleaning; restated in tests/points_clean_oracle.py).  Each returns a new PointBatch that every call
     above takes; PointBatch.from_device wraps tensors that are on the device already.
+  - a scan that comes as several partial clouds is put together on the device first: moved = piece.register(first) aligns
+    cloud m of one batch to cloud m of another by point-to-point ICP (csrc/point_register.hip; contract: include/gvcnn_hip.h,
+    "points in", registration; restated in tests/points_register_oracle.py): the exact nearest target point of every moved
+    source point, fp64 tree sums, Horn's quaternion by cyclic Jacobi, no read-back between rounds;
+    PointBatch.merged(first, moved) concatenates pair by pair, and voxel_downsample removes the doubled points.
 The defaults are the reference's renders (data_utils/obj2png.py): 8 views at azimuth 45 * (i + 1) there, C0 blue
 (31, 119, 180) / 255 on white, the light of LightSource(azdeg=225, altdeg=19.4712).
 """
@@ -545,6 +550,35 @@ def _check_voxel_args(voxel, relative, n):
     return v, int(bool(relative))
 
 
+def _check_register_args(n, iterations, max_distance, tolerance, init, grid):
+    """(iterations, max_distance as float32, tolerance as float, init float64 [n, 4, 4] or None, grid_cells) of register,
+    or ValueError."""
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or not 1 <= iterations < 2 ** 31:
+        raise ValueError("register: iterations must be an integer >= 1")
+    if max_distance is None:
+        md = np.float32(np.inf)
+    else:
+        if isinstance(max_distance, bool) or not isinstance(max_distance, numbers.Real):
+            raise ValueError("register: max_distance must be None or a number >= 0")
+        with np.errstate(over="ignore"):
+            md = np.float32(max_distance)
+        if not md >= 0:
+            raise ValueError("register: max_distance must be None or a number >= 0")
+    if isinstance(tolerance, bool) or not isinstance(tolerance, numbers.Real) or not float(tolerance) >= 0:
+        raise ValueError("register: tolerance must be a number >= 0")
+    if init is not None:
+        try:
+            init = np.asarray(init.detach().cpu().numpy() if torch.is_tensor(init) else init, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("register: init must be [4, 4] or [%d, 4, 4] finite numbers" % n)
+        if init.shape == (4, 4):
+            init = np.broadcast_to(init, (n, 4, 4))
+        if init.shape != (n, 4, 4) or not np.isfinite(init).all():
+            raise ValueError("register: init must be [4, 4] or [%d, 4, 4] finite numbers, got %s" % (n, init.shape))
+        init = np.ascontiguousarray(init)
+    return int(iterations), md, float(tolerance), init, _check_grid(grid, "register")
+
+
 class PointBatch:
     """Point clouds packed and uploaded once, as MeshBatch does for meshes.  clouds: a list of points [P, 3] or of
     (points, normals [P, 3]) tuples.  estimate_normals: 0, or the k of estimate_normals(k) for clouds without normals."""
@@ -565,6 +599,7 @@ class PointBatch:
         self.normals = None
         self.normal_status = None                                # host int32 [N] once estimate_normals has run
         self.clean_status = None                                 # host int32 [N] on the result of a cleaning call
+        self.register_status = None                              # host int32 [N] on the result of register
         if p["normals"] is not None:
             nr = p["normals"] if len(p["normals"]) else np.zeros((1, 3), np.float32)
             self.normals = torch.from_numpy(np.ascontiguousarray(nr)).to(self.device)
@@ -614,8 +649,92 @@ class PointBatch:
         self.normals = normals
         self.normal_status = None
         self.clean_status = None
+        self.register_status = None
         self.point_offsets = torch.from_numpy(po).to(self.device)
         return self
+
+    def register(self, target, iterations=30, max_distance=None, tolerance=0.0, init=None, grid=None, return_info=False,
+                 return_correspondence=False):
+        """Rigid registration on the device (contract: include/gvcnn_hip.h, "points in", registration): point-to-point
+        ICP of cloud m of this batch (the source) onto cloud m of `target`, a PointBatch of the same length on the same
+        device.  Every round matches each moved source point to its exact nearest target point (ties to the lower id),
+        keeps the pairs within max_distance (None: all of them) and solves for the rigid motion of the original source
+        onto its matches (Horn's quaternion); at most `iterations` rounds, a pair stops earlier once its rmse changes by
+        no more than `tolerance` between two rounds (0: an exact fixed point only).  init: a [4, 4] or [N, 4, 4] float64
+        starting transform (the identity without).  grid: as for estimate_normals, it changes the speed alone.  Returns
+        a NEW batch of the moved source, normals rotated, normal_status carried along, with register_status host int32
+        [N]: GV_RENDER_* of the pair (the source's, else the target's) with GV_POINTS_ICP_CONVERGED / _FEW_PAIRS /
+        _NONFINITE or-ed in.  Only that status is read back.  Returns the batch, or (batch, transforms float64 [N, 4, 4],
+        (rmse float64 [N], inliers int32 [N], rounds used int32 [N]) with return_info, correspondence int32 [sum P] (the
+        matched target id of the last round, -1 for a rejected point) with return_correspondence), on the device."""
+        if not isinstance(target, PointBatch):
+            raise ValueError("register: target must be a PointBatch")
+        if target.n != self.n:
+            raise ValueError("register: %d source clouds but %d target clouds" % (self.n, target.n))
+        if target.device != self.device:
+            raise ValueError("register: source on %s but target on %s" % (self.device, target.device))
+        iterations, md, tol, init, grid = _check_register_args(self.n, iterations, max_distance, tolerance, init, grid)
+        lib = _lib.load()
+        rows = self.points.shape[0]
+        total_s, total_t = int(self.point_offsets_host[-1]), int(target.point_offsets_host[-1])
+        with torch.cuda.device(self.device):
+            ws_bytes = lib.gv_points_register_workspace_bytes(self.n, total_s, total_t, grid)
+            _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_register_workspace_bytes")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            transforms = torch.zeros((self.n, 4, 4), dtype=torch.float64, device=self.device)
+            rmse = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+            inliers = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+            used = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+            corr = torch.full((rows,), -1, dtype=torch.int32, device=self.device) if return_correspondence else None
+            moved = torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
+            moved_normals = None if self.normals is None else torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
+            status = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            s, t = self.group(0, self.n), target.group(0, self.n)
+            rc = lib.gv_points_register(
+                s[0], s[1], t[0], t[1], self.n, total_s, total_t, s[4], t[4], self.group_normals(0),
+                None if init is None else init.ctypes.data, iterations, float(md), tol, grid, transforms.data_ptr(),
+                rmse.data_ptr(), inliers.data_ptr(), used.data_ptr(), None if corr is None else corr.data_ptr(),
+                moved.data_ptr(), None if moved_normals is None else moved_normals.data_ptr(), ws.data_ptr(), ws_bytes,
+                status.data_ptr(), _model._st())
+            _lib.check(rc, "gv_points_register")
+            st = status.cpu().numpy()                            # (init, a host array, stays alive past its copy)
+        new = PointBatch.from_device(moved, self.point_offsets_host, moved_normals)
+        new.point_offsets = self.point_offsets
+        new.normal_status = None if self.normal_status is None else self.normal_status.copy()
+        new.register_status = st
+        extras = ((transforms, (rmse, inliers, used)) if return_info else ()) + ((corr,) if return_correspondence else ())
+        return (new,) + extras if extras else new
+
+    @staticmethod
+    def merged(*batches):
+        """Pair by pair, the clouds of several batches as one: cloud m of the result is cloud m of the first batch followed
+        by cloud m of the second, and so on (what register leaves to do before voxel_downsample removes the doubled
+        points of the overlap).  The batches have the same length, are on the same device and are all with normals or
+        all without.  The points never leave the device: one concatenation and one gather by an index built from the
+        host offsets.  normal_status, clean_status and register_status are None on the result."""
+        if not batches or not all(isinstance(b, PointBatch) for b in batches):
+            raise ValueError("merged: one PointBatch at least, and PointBatches only")
+        first = batches[0]
+        for b in batches[1:]:
+            if b.n != first.n:
+                raise ValueError("merged: batches of %d and %d clouds" % (first.n, b.n))
+            if b.device != first.device:
+                raise ValueError("merged: batches on %s and %s" % (first.device, b.device))
+            if (b.normals is None) != (first.normals is None):
+                raise ValueError("merged: normals are all or none across the batches")
+        base = np.concatenate([[0], np.cumsum([b.points.shape[0] for b in batches])])
+        rows = [np.arange(b.point_offsets_host[m], b.point_offsets_host[m + 1], dtype=np.int64) + base[k]
+                for m in range(first.n) for k, b in enumerate(batches)]
+        po = np.zeros(first.n + 1, np.int64)
+        po[1:] = np.cumsum(np.sum([b.num_points for b in batches], axis=0))
+        if np.diff(po).max() > MAX_POINTS:
+            raise ValueError("merged: a cloud has more than 2^24 points")
+        index = np.concatenate(rows) if int(po[-1]) else np.zeros(1, np.int64)      # (one row at least, as everywhere)
+        with torch.cuda.device(first.device):
+            idx = torch.from_numpy(index).to(first.device)
+            points = torch.cat([b.points for b in batches]).index_select(0, idx)
+            normals = None if first.normals is None else torch.cat([b.normals for b in batches]).index_select(0, idx)
+        return PointBatch.from_device(points, po, normals)
 
     def _compact(self, lib, keep, selected, index, status, ws, ws_bytes, with_normals):
         """gv_points_compact on a selection -> (new batch, out_index); only the counts are read back."""
@@ -756,6 +875,15 @@ def voxel_downsample(points, voxel, relative=False, device=None):
     one host cloud points [P, 3]: PointBatch([points]).voxel_downsample(...), copied back."""
     _check_voxel_args(voxel, relative, 1)
     return _kept(*PointBatch([points], device).voxel_downsample(voxel, relative, return_index=True))
+
+
+def register(source, target, iterations=30, max_distance=None, tolerance=0.0, init=None, grid=None, device=None):
+    """(moved points float32 [P, 3], transform float64 [4, 4]) of one host pair: source [P, 3] registered onto target
+    [Q, 3]: PointBatch([source]).register(PointBatch([target]), ...), copied back."""
+    _check_register_args(1, iterations, max_distance, tolerance, init, grid)
+    batch, transforms, _ = PointBatch([source], device).register(PointBatch([target], device), iterations, max_distance,
+                                                                 tolerance, init, grid, return_info=True)
+    return batch.points.cpu().numpy()[:int(batch.num_points[0])], transforms.cpu().numpy()[0]
 
 
 def random_rotations(n, mode="z", seed=0):

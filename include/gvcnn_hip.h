@@ -902,6 +902,76 @@ int gv_points_compact(const float* points, const int64_t* point_offsets, int32_t
                       const float* normals, const int32_t* status, float* out_points, float* out_normals,
                       int32_t* out_index, int64_t* out_offsets, int32_t* counts, void* workspace,
                       int64_t workspace_bytes, void* stream);
+/* Registration: rigid point-to-point ICP (iterative closest point) for a batch of N pairs (source cloud m, target cloud
+ * m): the rotation R and translation t that carry the source onto the target, found by repeating "nearest target point
+ * of every moved source point, then the best rigid motion for those matches".  Everything runs on the stream with no
+ * read-back between rounds.  Defined bit for bit, under the discipline of the calls above: independent of scheduling, of
+ * how a batch is split, of grid_cells / max_source / max_target; no floating-point atomics; every step rounded on its own
+ * (no FMA); fp64 uses only + - * / and a correctly rounded sqrt.  (The order of the SOURCE points fixes the order of the
+ * sums; the order of the target points enters through ties alone.)
+ *  - inputs: source / source_offsets and target / target_offsets, two batches of N clouds laid out as above; a point's id
+ *    is its index within its cloud.  source_normals fp32 [sum Ps, 3] or NULL.  init fp64 [N, 4, 4] row-major, HOST memory
+ *    (copied into the workspace on the stream: keep it alive until the stream has passed that copy), or NULL for the
+ *    identity: T = (R | t) is its upper three rows, whatever they hold (no check that R is a rotation); its last row is
+ *    not read.  iterations >= 1; max_distance fp32 >= 0, +inf for none; tolerance fp64 >= 0; grid_cells as above.
+ *  - status byte of pair m: the source cloud's GV_RENDER_* from the bounding-box pass (EMPTY, NONFINITE, TOO_LARGE,
+ *    BAD_OFFSETS); where that is GV_RENDER_OK, the target cloud's.  A pair whose byte is not GV_RENDER_OK runs no round:
+ *    T stays the initial transform, used = 0, inliers = 0, rmse = 0.
+ *  - move, the one formula for a point p under T (here and in the final apply): per component c, in fp64,
+ *    q_c = ((R_c0 * (double)p_0 + R_c1 * (double)p_1) + R_c2 * (double)p_2) + t_c, rounded once to fp32.
+ *  - round k = 1 .. iterations of a pair that has not stopped, T the pair's current transform:
+ *    1. every source point p_i is moved to q_i.  If some component of some q_i is not finite: GV_POINTS_ICP_NONFINITE
+ *       is set, the pair stops with used = k, inliers = 0, rmse = 0 and every correspondence -1; T is kept.
+ *    2. match: over every target point y_j of the pair, fp32, dx = y_j0 - q_i0, dy, dz likewise, d2 = (dx*dx + dy*dy) +
+ *       dz*dz, key = ((uint64)bits(d2) << 32) | j; the match of i is the smallest key: the nearest target point, the
+ *       lower id among equal distances.  This is the brute-force answer; the grid over the target only finds it faster.
+ *    3. i is an inlier when d2_i <= max_d2 with max_d2 = max_distance * max_distance in fp32 (the boundary included;
+ *       +inf stays +inf).  Sums over the source ids are the tree sum T(a) of the cleaning contract, over a_0 .. a_{Ps-1}
+ *       with a_i = +0.0 at every i that is no inlier.  First pass: c = T(1.0), Sp = T((double)p_i) (the ORIGINAL source
+ *       points), Sy = T((double)y_match(i)) per component, Sd = T((double)d2_i).  used = k, inliers = c.
+ *    4. c < 3: GV_POINTS_ICP_FEW_PAIRS is set, rmse = sqrt(Sd / c) (0 when c = 0), T is kept and the pair stops.
+ *    5. rmse = sqrt(Sd / c).  From round 2 on: |rmse_prev - rmse| <= tolerance (false for a NaN) sets
+ *       GV_POINTS_ICP_CONVERGED; T is kept (it is the transform the matches of this round were found under) and the pair
+ *       stops.  Otherwise rmse_prev = rmse.
+ *    6. cp = Sp / c, cy = Sy / c per component.  Second pass: H_ab = T(((double)p_ia - cp_a) * ((double)y_ib - cy_b)) for
+ *       a, b in 0..2, y_i the match of i.
+ *    7. Horn's closed form.  The symmetric 4x4 matrix A: A00 = (H00 + H11) + H22; A11 = (H00 - H11) - H22; A22 = (H11 -
+ *       H00) - H22; A33 = (H22 - H00) - H11; A01 = H12 - H21; A02 = H20 - H02; A03 = H01 - H10; A12 = H01 + H10; A13 = H20
+ *       + H02; A23 = H12 + H21.  Cyclic Jacobi on A with V = I: 8 sweeps, each the pairs (p, q) = (0,1), (0,2), (0,3),
+ *       (1,2), (1,3), (2,3) in that order, with the rotation formulas of the normals contract (a pair whose A_pq is
+ *       exactly 0 is skipped; theta, t, c, s, h; A_pp, A_qq, A_pq; then (A_rp, A_rq) = (c*A_rp - s*A_rq, s*A_rp + c*A_rq)
+ *       for the two other indices r in ascending order, kept symmetric; then rows i = 0..3 of V).  The eigenvalues are
+ *       the diagonal; e = column of V of the largest, the lower column on a tie.  e is negated when its first non-zero
+ *       component is negative; nn = ((e0*e0 + e1*e1) + e2*e2) + e3*e3; (w, x, y, z) = e / sqrt(nn) per component.
+ *    8. R00 = ((w*w + x*x) - y*y) - z*z; R01 = 2 * (x*y - w*z); R02 = 2 * (x*z + w*y); R10 = 2 * (x*y + w*z); R11 = ((w*w
+ *       - x*x) + y*y) - z*z; R12 = 2 * (y*z - w*x); R20 = 2 * (x*z - w*y); R21 = 2 * (y*z + w*x); R22 = ((w*w - x*x) -
+ *       y*y) + z*z; t_c = cy_c - ((R_c0 * cp_0 + R_c1 * cp_1) + R_c2 * cp_2).  This (R, t) replaces T whole: it maps the
+ *       original source points onto their matches, nothing is composed from round to round.  A unit quaternion always
+ *       gives a proper rotation: there is no reflection case.
+ *  - outputs, device memory: transforms fp64 [N, 4, 4] (T over the row 0 0 0 1); rmse fp64 [N], inliers int32 [N] and
+ *    used int32 [N] (each or NULL): those of the last round the pair ran, so rmse describes the transform that ENTERED
+ *    that round; correspondence int32 [sum Ps] or NULL: the match of the last round run, -1 where i was no inlier or
+ *    no round ran; moved fp32 [sum Ps, 3]: the source points under the final T; moved_normals fp32 [sum Ps, 3] (with
+ *    source_normals, both or neither): ((R_c0 * (double)g_0 + R_c1 * (double)g_1) + R_c2 * (double)g_2), rounded once;
+ *    status int32 [N]: the pair's byte with GV_POINTS_ICP_* or-ed in.  Nothing is written to correspondence, moved or
+ *    moved_normals for a pair whose SOURCE is EMPTY, TOO_LARGE or BAD_OFFSETS.
+ * workspace: gv_points_register_workspace_bytes(n, total_source, total_target, grid_cells) bytes, 16-byte aligned.
+ * GV_E_BADARG before any HIP call: a NULL source / source_offsets / target / target_offsets / transforms / moved /
+ * workspace / status, source_normals without moved_normals or the reverse, n <= 0, a total or max below 0, iterations
+ * < 1, a max_distance or tolerance that is negative or NaN, grid_cells outside [0, 128], a workspace smaller than the size
+ * query's answer; GV_E_UNSUPPORTED for n > 65535 or a max above 2^24; GV_E_ALIGN as for the cleaning calls.
+ * Not here: point-to-plane ICP, a trimmed fraction of the pairs, a global (initial-pose-free) alignment, more than two
+ * clouds in one solve.  Known limit: a source point far outside the target's box walks most of the grid. */
+#define GV_POINTS_ICP_CONVERGED 0x800   /* or-ed into status[m]: pair m stopped on the tolerance */
+#define GV_POINTS_ICP_FEW_PAIRS 0x1000  /* or-ed into status[m]: a round of pair m had fewer than 3 inliers */
+#define GV_POINTS_ICP_NONFINITE 0x2000  /* or-ed into status[m]: a moved source point of pair m was not finite */
+int64_t gv_points_register_workspace_bytes(int32_t n, int64_t total_source, int64_t total_target, int32_t grid_cells);
+int gv_points_register(const float* source, const int64_t* source_offsets, const float* target,
+                       const int64_t* target_offsets, int32_t n, int64_t total_source, int64_t total_target,
+                       int32_t max_source, int32_t max_target, const float* source_normals, const double* init,
+                       int32_t iterations, float max_distance, double tolerance, int32_t grid_cells, double* transforms,
+                       double* rmse, int32_t* inliers, int32_t* used, int32_t* correspondence, float* moved,
+                       float* moved_normals, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
 
 /* ---- training step (train.py:145,166-187, utils/train_utils.py:217-259) -----------
  * fp32.  Gradient outputs ACCUMULATE (+=) into caller-zeroed buffers, because a tensor that feeds several
