@@ -1,13 +1,12 @@
 // point_clean.hip — cleaning a batch of raw point clouds on the device: statistical outlier selection, voxel selection
 // and the one compaction both feed (the contract is in include/gvcnn_hip.h, "points in", cleaning;
-// tests/points_clean_oracle.py restates it in numpy).  The search grid and the exact k-nearest walk are point_grid.h's,
-// shared with point_normals.hip.
+// tests/points_clean_oracle.py restates it in numpy).  The search grid, the exact k-nearest collector and the call
+// prologue are point_grid.h's; the tree sum and the block scan are point_math.h's.
 //
 //   gv_points_outlier_select   build_grid          bounding boxes, statuses, binned ids (point_grid.h).
-//                              mean_kernel<K>      a thread per point, in cell order: the k_eff smallest keys over j != i
-//                                                  in an LDS column, then the fp64 mean of their distances in rank order.
-//                              tree_kernel x 6     the tree sum T(a) in three levels of aligned 256-blocks with adjacent
-//                                                  pairing: first over m (-> mu), then over (m - mu)^2 (-> sigma, T).
+//                              mean_kernel<K>      a thread per point, in cell order: nearest_keys over j != i, then the
+//                                                  fp64 mean of their distances in rank order.
+//                              tree_kernel x 6     tree_level<1> with the leaves m (-> mu), then (m - mu)^2 (-> sigma, T).
 //                              keep_kernel         a thread per point: m_i <= T; the cloud's stats.
 //   gv_points_voxel_select     bbox + cell_base    (the same bounding-box pass; the grid itself is not needed)
 //                              voxel_setup_kernel  a thread per cloud: voxel size, passthrough clauses, fixed-point scale.
@@ -18,7 +17,7 @@
 //                              voxel_best_kernel   a thread per point: smallest key (bits(d2 to the centroid) << 32 | id).
 //                              voxel_final_kernel  a thread per point: keep / centroid / index at the lowest member id.
 //   gv_points_compact          scan_kernel         one workgroup per cloud: exclusive scan of keep in id order, counts.
-//                              offsets_kernel      one workgroup: the new point_offsets.
+//                              offsets_kernel      one workgroup: the new point_offsets (both: block_exclusive_scan).
 //                              gather_kernel       a thread per point: points (or centroids), normals[index], index.
 //
 // No floating-point atomics anywhere; nothing in a result depends on the grid, the batch or the schedule.
@@ -26,7 +25,6 @@
 
 namespace {
 
-constexpr int TB = 256;                                          // leaves of one workgroup tree (= NT)
 constexpr u64 GOLD = 0x9E3779B97F4A7C15ull;
 constexpr float TOO_FINE = 2097152.0f;                           // 2^21 cells on an axis
 
@@ -54,8 +52,7 @@ CleanWs clean_layout(int32_t n, int64_t total_points, int32_t hint) {
     L.extra = L.grid.bytes;
     L.mean = L.extra;
     L.part1 = L.mean + round16(total_points * 8);
-    L.part2 = L.part1 + round16((total_points / TB + n + 2) * 8);
-    L.cstat = L.part2 + round16((int64_t)n * TB * 8);
+    L.cstat = tree_layout(L.part1, n, total_points, 1, L.part2);
     const int64_t outlier_end = L.cstat + round16((int64_t)n * 4 * 8);
     L.slots = 4 * total_points;                                  // a cloud of P points: slots [4 v0, 4 v0 + capacity)
     L.vcloud = L.extra;
@@ -71,18 +68,13 @@ CleanWs clean_layout(int32_t n, int64_t total_points, int32_t hint) {
     return L;
 }
 
-__device__ __forceinline__ bool no_points(int st) {              // the statuses whose output count is 0
-    st &= 0xFF;
-    return st == GV_RENDER_EMPTY || st == GV_RENDER_TOO_LARGE || st == GV_RENDER_BAD_OFFSETS;
-}
-
 // ---- statistical outlier selection ----------------------------------------------------------------------------------
 struct OArgs : GridArgs {
     int k;
     double ratio;                                                // (double)std_ratio
     double* mean;                                                // [total_points], by id
-    double* part1;                                               // cloud m: from (v0 >> 8) + m
-    double* part2;                                               // cloud m: from m * TB
+    double* part1;                                               // the tree's partials (tree_layout, one channel)
+    double* part2;
     double* cstat;                                               // [n, 4]: -, mu, sigma, T
     int* keep;
     float* mean_dist;
@@ -95,8 +87,7 @@ __global__ __launch_bounds__(NT) void mean_kernel(OArgs a) {
     const int m = blockIdx.y, tid = threadIdx.x;
     const CloudGrid g = a.grid[m];
     if (g.status != GV_RENDER_OK) return;
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
     const int keff = min(a.k, P - 1);
     u64* keys = s_keys + tid;
     for (int s = blockIdx.x * NT + tid; s < P; s += gridDim.x * NT) {
@@ -105,14 +96,7 @@ __global__ __launch_bounds__(NT) void mean_kernel(OArgs a) {
         if (keff > 0) {                                          // (uniform)
             const float* pp = a.pts + (v0 + i) * 3;
             const float pi[3] = {pp[0], pp[1], pp[2]};
-            for (int r = 0; r < keff; ++r) keys[r * NT] = NO_KEY;
-            u64 worst = NO_KEY;
-            ring_walk(
-                a, g, v0, pi,
-                [&](int j, float d2) {
-                    if (j != i) insert_key(keys, keff, ((u64)__float_as_uint(d2) << 32) | (unsigned)j, worst);
-                },
-                [&]() { return worst; });
+            nearest_keys<true>(a, g, v0, i, pi, keys, keff);
             for (int r = 0; r < keff; ++r)
                 mi = mi + __builtin_sqrt((double)__uint_as_float((unsigned)(keys[r * NT] >> 32)));
             mi = mi / (double)keff;
@@ -122,55 +106,31 @@ __global__ __launch_bounds__(NT) void mean_kernel(OArgs a) {
     }
 }
 
-__device__ __forceinline__ int blocks_of(int x) { return (x + TB - 1) / TB; }
-
-// One level of the tree sum T(a) of cloud m: aligned blocks of TB values, adjacent pairs level by level (b_t = a_2t +
-// a_2t+1, zeros past the end), one partial per block.  level 0 reads the means (mode 1: (m_i - mu)^2), level 1 the
-// partials of level 0, level 2 those of level 1 (at most TB: one block) and finishes the statistic.
-__global__ __launch_bounds__(TB) void tree_kernel(OArgs a, int level, int mode) {
+// one level (point_math.h) of the tree sums of cloud m: mode 0 T(m) -> mu = T / P, mode 1 T((m - mu)^2) -> sigma, threshold
+__global__ __launch_bounds__(TB) void tree_kernel(OArgs a, int mode, int level) {
     __shared__ double s[TB];
-    const int m = blockIdx.y, tid = threadIdx.x;
-    const CloudGrid& g = a.grid[m];
-    if (g.status != GV_RENDER_OK) return;
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
-    if (P < 2) return;
-    const int c1 = blocks_of(P), c2 = blocks_of(c1);
-    const int count = level == 0 ? P : level == 1 ? c1 : c2;
-    double* p1 = a.part1 + (v0 >> 8) + m;
-    double* p2 = a.part2 + (long long)m * TB;
-    const double* in = level == 0 ? a.mean + v0 : level == 1 ? p1 : p2;
-    double* out = level == 0 ? p1 : level == 1 ? p2 : a.cstat + m * 4;
-    const double mu = a.cstat[m * 4 + 1];
-    for (int b = blockIdx.x; b < blocks_of(count); b += gridDim.x) {
-        const int idx = b * TB + tid;
-        double x = 0.0;
-        if (idx < count) {
-            x = in[idx];
-            if (level == 0 && mode == 1) {
-                const double e = x - mu;
-                x = e * e;
-            }
-        }
-        s[tid] = x;
-        __syncthreads();
-        for (int stride = 1; stride < TB; stride <<= 1) {
-            if ((tid & (2 * stride - 1)) == 0) s[tid] = s[tid] + s[tid + stride];
-            __syncthreads();
-        }
-        if (tid == 0) {
-            if (level < 2) {
-                out[b] = s[0];
-            } else if (mode == 0) {
-                out[1] = s[0] / (double)P;
+    const int m = blockIdx.y;
+    if (a.grid[m].status != GV_RENDER_OK) return;
+    const CloudSpan sp = cloud_span(a.poff, m);
+    if (sp.P < 2) return;
+    const double* mean = a.mean + sp.v0;
+    double* out = a.cstat + m * 4;                               // -, mu, sigma, T
+    const double mu = out[1];
+    tree_level<1>(
+        level, m, sp.v0, sp.P, a.part1, 0, a.part2, s,                  // (one channel: no plane stride)
+        [&](int i, double x[1]) {
+            const double e = mean[i] - mu;                       // (mode 0: mu is still 0)
+            x[0] = mode == 0 ? mean[i] : e * e;
+        },
+        [&](int, double total) {
+            if (mode == 0) {
+                out[1] = total / (double)sp.P;
             } else {
-                const double sigma = __builtin_sqrt(s[0] / (double)(P - 1));
+                const double sigma = __builtin_sqrt(total / (double)(sp.P - 1));
                 out[2] = sigma;
                 out[3] = mu + a.ratio * sigma;
             }
-        }
-        __syncthreads();
-    }
+        });
 }
 
 __global__ __launch_bounds__(NT) void keep_kernel(OArgs a) {
@@ -181,8 +141,7 @@ __global__ __launch_bounds__(NT) void keep_kernel(OArgs a) {
         if (first && a.stats) a.stats[m * 3] = a.stats[m * 3 + 1] = a.stats[m * 3 + 2] = 0.0;
         return;
     }
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
     const bool select = g.status == GV_RENDER_OK && P >= 2;
     const double T = a.cstat[m * 4 + 3];
     if (first) {
@@ -220,7 +179,7 @@ __global__ __launch_bounds__(NT) void voxel_setup_kernel(VArgs a) {
     VoxelCloud vc = {};
     if (g.status == GV_RENDER_NONFINITE) vc.pass = 1;
     if (g.status == GV_RENDER_OK) {
-        const int P = (int)(a.poff[m + 1] - a.poff[m]);
+        const int P = cloud_span(a.poff, m).P;
         float ext[3], big = 0.0f;
         for (int c = 0; c < 3; ++c) {
             ext[c] = g.mx[c] - g.mn[c];
@@ -258,8 +217,8 @@ __global__ __launch_bounds__(NT) void voxel_insert_kernel(VArgs a) {
     const CloudGrid g = a.grid[m];
     const VoxelCloud vc = a.vcloud[m];
     if (g.status != GV_RENDER_OK || vc.pass) return;
-    const long long v0 = a.poff[m] - a.poff[0], base = 4 * v0;
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
+    const long long base = 4 * v0;
     for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
         const float* p = a.pts + (v0 + i) * 3;
         float t[3];
@@ -295,8 +254,8 @@ __global__ __launch_bounds__(NT) void voxel_best_kernel(VArgs a) {
     const CloudGrid g = a.grid[m];
     const VoxelCloud vc = a.vcloud[m];
     if (g.status != GV_RENDER_OK || vc.pass) return;
-    const long long v0 = a.poff[m] - a.poff[0], base = 4 * v0;
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
+    const long long base = 4 * v0;
     for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
         const int s = a.slot[v0 + i];
         if (s < 0) continue;
@@ -314,8 +273,8 @@ __global__ __launch_bounds__(NT) void voxel_final_kernel(VArgs a) {
     const CloudGrid g = a.grid[m];
     const VoxelCloud vc = a.vcloud[m];
     if (g.status != GV_RENDER_OK && g.status != GV_RENDER_NONFINITE) return;
-    const long long v0 = a.poff[m] - a.poff[0], base = 4 * v0;
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
+    const long long base = 4 * v0;
     for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
         const long long o = v0 + i;
         const float* p = a.pts + o * 3;
@@ -376,17 +335,10 @@ __global__ __launch_bounds__(NT) void scan_kernel(CArgs a) {
     cloud_range(a, m, v0, P);                                    // (P = 0 without output)
     for (int b = 0; b < P; b += NT) {
         const int i = b + tid, k = i < P && a.keep[v0 + i] != 0;
-        s[tid] = k;
-        __syncthreads();
-        for (int o = 1; o < NT; o <<= 1) {
-            const int add = tid >= o ? s[tid - o] : 0;
-            __syncthreads();
-            s[tid] += add;
-            __syncthreads();
-        }
-        if (i < P) a.rank[v0 + i] = carry + s[tid] - k;
-        carry += s[NT - 1];
-        __syncthreads();
+        int total;
+        const int before = block_exclusive_scan<int, NT>(s, k, total);
+        if (i < P) a.rank[v0 + i] = carry + before;
+        carry += total;
     }
     if (tid == 0) a.counts[m] = carry;
 }
@@ -398,17 +350,10 @@ __global__ __launch_bounds__(SCAN_T) void offsets_kernel(CArgs a) {
     for (int b = 0; b < a.n; b += SCAN_T) {
         const int i = b + tid;
         const long long v = i < a.n ? a.counts[i] : 0;
-        s[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < SCAN_T; o <<= 1) {
-            const long long add = tid >= o ? s[tid - o] : 0;
-            __syncthreads();
-            s[tid] += add;
-            __syncthreads();
-        }
-        if (i < a.n) a.out_offsets[i] = carry + s[tid] - v;
-        carry += s[SCAN_T - 1];
-        __syncthreads();
+        long long total;
+        const long long before = block_exclusive_scan<long long, SCAN_T>(s, v, total);
+        if (i < a.n) a.out_offsets[i] = carry + before;
+        carry += total;
     }
     if (tid == 0) a.out_offsets[a.n] = carry;
 }
@@ -439,25 +384,11 @@ __global__ __launch_bounds__(NT) void gather_kernel(CArgs a) {
     }
 }
 
-// the argument clauses every call shares, in the order of the normals call
-int check_common(const void* points, const void* point_offsets, int32_t n, int64_t total_points, int32_t max_points,
-                 int32_t grid_cells, const void* workspace, int64_t workspace_bytes, bool compaction) {
-    if (!points || !point_offsets || !workspace) return GV_E_BADARG;
-    if (n <= 0 || total_points < 0 || max_points < 0 || grid_cells < 0 || grid_cells > MAX_G) return GV_E_BADARG;
-    if (n > 65535 || max_points > MAX_CLOUD) return GV_E_UNSUPPORTED;
-    // (the compaction keeps one int32 per point: less than the size query answers for any grid_cells)
-    if (workspace_bytes < (compaction ? round16(total_points * 4) : clean_layout(n, total_points, grid_cells).bytes))
-        return GV_E_BADARG;
-    if (!gv_aligned16(workspace) || ((uintptr_t)point_offsets & 7u) || ((uintptr_t)points & 3u)) return GV_E_ALIGN;
-    return GV_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t gv_points_clean_workspace_bytes(int32_t n, int64_t total_points, int32_t grid_cells) {
-    if (n <= 0 || total_points < 0 || grid_cells < 0 || grid_cells > MAX_G) return GV_E_BADARG;
-    if (n > 65535) return GV_E_UNSUPPORTED;
-    return clean_layout(n, total_points, grid_cells).bytes;
+    const int rc = check_sizes(n, total_points, 0, grid_cells);
+    return rc != GV_OK ? rc : clean_layout(n, total_points, grid_cells).bytes;
 }
 
 extern "C" int gv_points_outlier_select(const float* points, const int64_t* point_offsets, int32_t n, int64_t total_points,
@@ -466,11 +397,11 @@ extern "C" int gv_points_outlier_select(const float* points, const int64_t* poin
                                         int32_t* status, void* stream) {
     if (!keep || !status) return GV_E_BADARG;
     if (k < 1 || k > 32 || !(std_ratio >= 0.0f && std_ratio < INFINITY)) return GV_E_BADARG;
-    const int rc = check_common(points, point_offsets, n, total_points, max_points, grid_cells, workspace, workspace_bytes, false);
+    const CleanWs L = clean_layout(n, total_points, grid_cells);
+    const int rc = check_common(points, point_offsets, n, total_points, max_points, grid_cells, workspace, workspace_bytes, L.bytes);
     if (rc != GV_OK) return rc;
     if ((((uintptr_t)keep | (uintptr_t)mean_dist | (uintptr_t)status) & 3u) || ((uintptr_t)stats & 7u)) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
-    const CleanWs L = clean_layout(n, total_points, grid_cells);
     char* ws = static_cast<char*>(workspace);
     OArgs a;
     grid_args(a, points, point_offsets, n, total_points, grid_cells, workspace, L.grid, status);
@@ -487,17 +418,10 @@ extern "C" int gv_points_outlier_select(const float* points, const int64_t* poin
     if (g != GV_OK) return g;
     GV_HIP_CHECK(hipMemsetAsync(a.cstat, 0, (size_t)n * 4 * 8, st));
     const dim3 by_point(grid_x(max_points), (unsigned)n);
-    if (k <= 8) hipLaunchKernelGGL(mean_kernel<8>, by_point, dim3(NT), 0, st, a);
-    else if (k <= 16) hipLaunchKernelGGL(mean_kernel<16>, by_point, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(mean_kernel<32>, by_point, dim3(NT), 0, st, a);
+    GV_LAUNCH_BY_K(mean_kernel, k, by_point, st, a);
     GV_LAUNCH_CHECK();
-    const long long b1 = ((long long)max_points + TB - 1) / TB, b2 = (b1 + TB - 1) / TB;
     for (int mode = 0; mode < 2; ++mode) {
-        hipLaunchKernelGGL(tree_kernel, dim3(grid_x(b1 * NT), (unsigned)n), dim3(TB), 0, st, a, 0, mode);
-        GV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(tree_kernel, dim3(grid_x(b2 * NT), (unsigned)n), dim3(TB), 0, st, a, 1, mode);
-        GV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(tree_kernel, dim3(1, (unsigned)n), dim3(TB), 0, st, a, 2, mode);
+        launch_tree<tree_kernel>(n, max_points, st, a, mode);
         GV_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(keep_kernel, by_point, dim3(NT), 0, st, a);
@@ -511,11 +435,11 @@ extern "C" int gv_points_voxel_select(const float* points, const int64_t* point_
                                       int64_t workspace_bytes, int32_t* status, void* stream) {
     if (!voxel || !keep || !centroids || !index || !status) return GV_E_BADARG;
     if (relative != 0 && relative != 1) return GV_E_BADARG;
-    const int rc = check_common(points, point_offsets, n, total_points, max_points, grid_cells, workspace, workspace_bytes, false);
+    const CleanWs L = clean_layout(n, total_points, grid_cells);
+    const int rc = check_common(points, point_offsets, n, total_points, max_points, grid_cells, workspace, workspace_bytes, L.bytes);
     if (rc != GV_OK) return rc;
     if (((uintptr_t)keep | (uintptr_t)centroids | (uintptr_t)index | (uintptr_t)status) & 3u) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
-    const CleanWs L = clean_layout(n, total_points, grid_cells);
     char* ws = static_cast<char*>(workspace);
     VArgs a;
     grid_args(a, points, point_offsets, n, total_points, grid_cells, workspace, L.grid, status);
@@ -561,7 +485,9 @@ extern "C" int gv_points_compact(const float* points, const int64_t* point_offse
                                  int64_t workspace_bytes, void* stream) {
     if (!keep || !status || !out_points || !out_index || !out_offsets || !counts) return GV_E_BADARG;
     if ((normals != nullptr) != (out_normals != nullptr)) return GV_E_BADARG;
-    const int rc = check_common(points, point_offsets, n, total_points, max_points, 0, workspace, workspace_bytes, true);
+    // (one int32 per point: less than the size query answers for any grid_cells)
+    const int rc = check_common(points, point_offsets, n, total_points, max_points, 0, workspace, workspace_bytes,
+                                round16(total_points * 4));
     if (rc != GV_OK) return rc;
     if ((((uintptr_t)keep | (uintptr_t)selected | (uintptr_t)index | (uintptr_t)normals | (uintptr_t)status |
           (uintptr_t)out_points | (uintptr_t)out_normals | (uintptr_t)out_index | (uintptr_t)counts) & 3u) ||

@@ -1,6 +1,7 @@
 // point_grid.h — the uniform search grid over a batch of point clouds and the exact k-nearest walk through it, shared by
 // point_normals.hip (normal estimation), point_clean.hip (outlier selection, voxel selection, compaction) and
-// point_register.hip (the nearest target point of a moved source point).
+// point_register.hip (the nearest target point of a moved source point).  What they share that is not the grid (the block
+// scan, the tree sum, the Jacobi rotation) is point_math.h's.
 //
 //   build_grid   bbox_kernel        one workgroup per cloud: offsets check, bounding box, cells per axis G.
 //                cell_base_kernel   one workgroup: exclusive scan of the clouds' G^3 -> where each cloud's cells start in
@@ -14,24 +15,18 @@
 //                included), so the k smallest keys never depend on the grid.  ring_walk_from: the same walk around a
 //                cell the caller names (cell3_clamped: a query that may lie outside the cloud's box).
 //   insert_key   the k smallest keys (bits(d2) << 32 | id) kept sorted in an LDS column of the thread.
-//
+//   nearest_keys the k_eff smallest keys of a point of the cloud, itself included or not (GV_LAUNCH_BY_K: the kernel<K>).
+//   check_common, check_sizes   the argument clauses the entry points and the size queries share, in the ABI's order.
 #pragma once
-#include <math.h>
-
-#include "gv_common.h"
-
-// every step of the contracts' arithmetic rounds on its own, here and in the file that includes this one
-#pragma clang fp contract(off)
+#include "point_math.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int NT = 256;                                          // threads of every kernel but the scan
 constexpr int SCAN_T = 1024;
 constexpr int MAX_CLOUD = 1 << 24;                               // points of a cloud: ids fit the splatter's 24 bits
 constexpr int MAX_G = 128;                                       // cells per axis
-constexpr int MAX_GRID_X = 2048;                                 // workgroups along x; the loops stride the rest
 constexpr u64 NO_KEY = ~0ull;
 
 struct CloudGrid {                                               // per cloud, written by bbox_kernel (64 bytes)
@@ -59,7 +54,7 @@ __host__ __device__ inline int cells_per_axis(long long P, int hint) {
 
 // the cells a batch can need: the workspace holds two int32 per cell
 inline int64_t cell_capacity(int32_t n, int64_t total_points, int32_t hint) {
-    if (hint <= 0) return total_points / 2 + n;
+    if (hint <= 0 || hint > MAX_G) return total_points / 2 + n;  // (a hint out of range is refused: the layout stays defined)
     const int64_t by_hint = (int64_t)n * hint * hint * hint, by_points = 4 * total_points + n;
     return by_hint < by_points ? by_hint : by_points;
 }
@@ -67,8 +62,6 @@ inline int64_t cell_capacity(int32_t n, int64_t total_points, int32_t hint) {
 struct GridWs {
     int64_t grids, ids, cell_count, cell_end, cells, bytes;      // byte offsets; cells: capacity in cells
 };
-
-inline int64_t round16(int64_t x) { return (x + 15) / 16 * 16; }
 
 inline GridWs grid_ws_layout(int32_t n, int64_t total_points, int32_t hint) {
     GridWs L;
@@ -107,6 +100,38 @@ inline void grid_args(GridArgs& a, const float* points, const int64_t* point_off
     a.cells = L.cells;
     a.n = n;
     a.hint = hint;
+}
+
+// the clauses of the sizes (all a size query has), in the ABI's order; total_b, max_b: the target batch of a registration
+inline int check_sizes(int32_t n, int64_t total, int32_t max_points, int32_t grid_cells, int64_t total_b = 0, int32_t max_b = 0) {
+    if (n <= 0 || total < 0 || max_points < 0 || grid_cells < 0 || grid_cells > MAX_G || total_b < 0 || max_b < 0)
+        return GV_E_BADARG;
+    return n > 65535 || max_points > MAX_CLOUD || max_b > MAX_CLOUD ? GV_E_UNSUPPORTED : GV_OK;
+}
+
+// The argument clauses every call shares, in the ABI's order: null pointers and sizes (GV_E_BADARG), limits
+// (GV_E_UNSUPPORTED), the workspace's size (GV_E_BADARG; need: what the call's layout asks for), alignment (GV_E_ALIGN).
+// A call checks its own values before (registration: that its target is there) and the alignment of its own pointers after.
+inline int check_common(const void* points, const void* offsets, int32_t n, int64_t total, int32_t max_points,
+                        int32_t grid_cells, const void* workspace, int64_t workspace_bytes, int64_t need,
+                        const void* points_b = nullptr, const void* offsets_b = nullptr, int64_t total_b = 0, int32_t max_b = 0) {
+    if (!points || !offsets || !workspace) return GV_E_BADARG;
+    const int rc = check_sizes(n, total, max_points, grid_cells, total_b, max_b);
+    if (rc != GV_OK) return rc;
+    if (workspace_bytes < need) return GV_E_BADARG;
+    const uintptr_t by8 = (uintptr_t)offsets | (uintptr_t)offsets_b, by4 = (uintptr_t)points | (uintptr_t)points_b;
+    return !gv_aligned16(workspace) || (by8 & 7u) || (by4 & 3u) ? GV_E_ALIGN : GV_OK;
+}
+
+struct CloudSpan { long long v0; int P; };                       // a cloud's first point in the packed arrays, its points
+
+__device__ __forceinline__ CloudSpan cloud_span(const long long* poff, int m) {
+    return {poff[m] - poff[0], (int)(poff[m + 1] - poff[m])};
+}
+
+__device__ __forceinline__ bool no_points(int st) {              // the statuses whose cloud has no output
+    st &= 0xFF;
+    return st == GV_RENDER_EMPTY || st == GV_RENDER_TOO_LARGE || st == GV_RENDER_BAD_OFFSETS;
 }
 
 // the cell of coordinate x on an axis: monotone in x (each step is), the same wherever it is computed
@@ -191,16 +216,10 @@ __global__ __launch_bounds__(SCAN_T) void cell_base_kernel(GridArgs a) {
             const long long G = a.grid[i].G;
             v = G * G * G;
         }
-        s[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < SCAN_T; o <<= 1) {
-            const long long add = tid >= o ? s[tid - o] : 0;
-            __syncthreads();
-            s[tid] += add;
-            __syncthreads();
-        }
+        long long total;
+        const long long before = block_exclusive_scan<long long, SCAN_T>(s, v, total);
         if (i < a.n) {
-            const long long base = carry + s[tid] - v;
+            const long long base = carry + before;
             a.grid[i].cell_base = base;
             if (base + v > a.cells) {
                 a.grid[i].G = 0;
@@ -208,8 +227,7 @@ __global__ __launch_bounds__(SCAN_T) void cell_base_kernel(GridArgs a) {
                 a.status[i] = GV_RENDER_BAD_OFFSETS;
             }
         }
-        carry += s[SCAN_T - 1];
-        __syncthreads();
+        carry += total;
     }
 }
 
@@ -219,8 +237,7 @@ __global__ __launch_bounds__(NT) void bin_kernel(GridArgs a) {
     const int m = blockIdx.y;
     const CloudGrid g = a.grid[m];
     if (g.status != GV_RENDER_OK) return;
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
     for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
         int c[3];
         cell3(g, a.pts + (v0 + i) * 3, c);
@@ -240,11 +257,6 @@ __global__ __launch_bounds__(NT) void alloc_kernel(GridArgs a) {
         const int cnt = a.cell_count[g.cell_base + c];
         a.cell_end[g.cell_base + c] = cnt ? atomicAdd(&g.cursor, cnt) : 0;
     }
-}
-
-inline unsigned grid_x(long long items) {
-    const long long b = (items + NT - 1) / NT;
-    return (unsigned)(b < 1 ? 1 : b > MAX_GRID_X ? MAX_GRID_X : b);
 }
 
 // bounding boxes, statuses and the binned ids of the batch.  max_points sizes the launches only: every kernel strides
@@ -345,5 +357,23 @@ __device__ __forceinline__ void ring_walk(const GridArgs& a, const CloudGrid& g,
     cell3(g, pi, c);
     ring_walk_from(a, g, v0, pi, c, visit, kth);
 }
+
+// the keff smallest keys of point pi (id i) of the cloud into the thread's column; SKIP_SELF: over j != i
+template <bool SKIP_SELF>
+__device__ __forceinline__ void nearest_keys(const GridArgs& a, const CloudGrid& g, long long v0, int i, const float pi[3],
+                                             u64* keys, int keff) {
+    for (int r = 0; r < keff; ++r) keys[r * NT] = NO_KEY;
+    u64 worst = NO_KEY;
+    ring_walk(
+        a, g, v0, pi,
+        [&](int j, float d2) {
+            if (!SKIP_SELF || j != i) insert_key(keys, keff, ((u64)__float_as_uint(d2) << 32) | (unsigned)j, worst);
+        },
+        [&]() { return worst; });
+}
+
+// kernel<K>(args) for the smallest K in 8 / 16 / 32 that holds k keys (K sizes the LDS columns), a thread per point
+#define GV_LAUNCH_BY_K(kernel, k, by_point, st, args) \
+    hipLaunchKernelGGL(((k) <= 8 ? kernel<8> : (k) <= 16 ? kernel<16> : kernel<32>), by_point, dim3(NT), 0, st, args)
 
 }  // namespace

@@ -3,12 +3,11 @@
 // include/gvcnn_hip.h, "points in", normal estimation; tests/point_normals_oracle.py restates it in numpy).
 //
 //   gv_points_estimate_normals   build_grid         bounding boxes, statuses and the binned ids of the batch (point_grid.h,
-//                                                   shared with point_clean.hip: five launches).
+//                                                   shared with point_clean.hip and point_register.hip: five launches).
 //                                query_kernel<K>    a thread per point, in cell order (neighbouring lanes walk the same
-//                                                   cells): ring_walk over Chebyshev rings of cells around the point's own,
-//                                                   the k_eff smallest keys (bits(d2) << 32 | id) kept sorted in an LDS
-//                                                   column of the thread; then covariance, Jacobi and the sign in fp64
-//                                                   registers.
+//                                                   cells): nearest_keys (point_grid.h), the k_eff smallest keys (bits(d2)
+//                                                   << 32 | id) sorted in an LDS column of the thread; then covariance,
+//                                                   Jacobi (the rotation is point_math.h's) and the sign in fp64 registers.
 //
 // Nothing in the result depends on the grid: keys are unique, so the k_eff smallest are the same set in the same order
 // whatever the order candidates arrive in, and a ring walk stops only when every point it has not seen is PROVABLY
@@ -28,30 +27,19 @@ struct NArgs : GridArgs {
 };
 
 // ---- covariance, Jacobi, sign ---------------------------------------------------------------------------------------
-// one Jacobi rotation of the pair (p, q) of a symmetric 3x3; r the third index.  Contract formulas, in their order.
+// one Jacobi rotation (point_math.h) of the pair (p, q) of a symmetric 3x3; r the third index
 __device__ __forceinline__ void rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
                                        double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
     if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + __builtin_sqrt(theta * theta + 1.0));
-    const double c = 1.0 / __builtin_sqrt(t * t + 1.0);
-    const double s = t * c;
-    const double h = t * apq;
+    double c, s, h;
+    jacobi_csh(app, aqq, apq, c, s, h);
     app = app - h;
     aqq = aqq + h;
     apq = 0.0;
-    double x = arp, y = arq;
-    arp = c * x - s * y;
-    arq = s * x + c * y;
-    x = v0p, y = v0q;
-    v0p = c * x - s * y;
-    v0q = s * x + c * y;
-    x = v1p, y = v1q;
-    v1p = c * x - s * y;
-    v1q = s * x + c * y;
-    x = v2p, y = v2q;
-    v2p = c * x - s * y;
-    v2q = s * x + c * y;
+    rotate_pair(c, s, arp, arq);
+    rotate_pair(c, s, v0p, v0q);
+    rotate_pair(c, s, v1p, v1q);
+    rotate_pair(c, s, v2p, v2q);
 }
 
 // the "none" rule: the component of largest magnitude becomes positive (the first of x, y, z on a tie)
@@ -124,8 +112,7 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
     const int m = blockIdx.y, tid = threadIdx.x;
     const CloudGrid g = a.grid[m];
     if (g.status != GV_RENDER_OK && g.status != GV_RENDER_NONFINITE) return;     // no points, or none that can be trusted
-    const long long v0 = a.poff[m] - a.poff[0];
-    const int P = (int)(a.poff[m + 1] - a.poff[m]);
+    const auto [v0, P] = cloud_span(a.poff, m);
     const int keff = min(a.k, P);
     u64* keys = s_keys + tid;
     bool degenerate = false;
@@ -137,12 +124,7 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
             i = a.ids[v0 + s];
             const float* pp = a.pts + (v0 + i) * 3;
             const float pi[3] = {pp[0], pp[1], pp[2]};
-            for (int r = 0; r < keff; ++r) keys[r * NT] = NO_KEY;
-            u64 worst = NO_KEY;
-            ring_walk(
-                a, g, v0, pi,
-                [&](int j, float d2) { insert_key(keys, keff, ((u64)__float_as_uint(d2) << 32) | (unsigned)j, worst); },
-                [&]() { return worst; });
+            nearest_keys<false>(a, g, v0, i, pi, keys, keff);
             ok = normal_of(a, g, v0, pi, keys, keff, nf, var);
             degenerate |= !ok;
         }
@@ -161,9 +143,8 @@ __global__ __launch_bounds__(NT) void query_kernel(NArgs a) {
 }  // namespace
 
 extern "C" int64_t gv_points_normals_workspace_bytes(int32_t n, int64_t total_points, int32_t grid_cells) {
-    if (n <= 0 || total_points < 0 || grid_cells < 0 || grid_cells > MAX_G) return GV_E_BADARG;
-    if (n > 65535) return GV_E_UNSUPPORTED;
-    return grid_ws_layout(n, total_points, grid_cells).bytes;
+    const int rc = check_sizes(n, total_points, 0, grid_cells);
+    return rc != GV_OK ? rc : grid_ws_layout(n, total_points, grid_cells).bytes;
 }
 
 extern "C" int gv_points_estimate_normals(const float* points, const int64_t* point_offsets, int32_t n,
@@ -171,20 +152,16 @@ extern "C" int gv_points_estimate_normals(const float* points, const int64_t* po
                                           const float* viewpoint, int32_t grid_cells, float* normals, int32_t* neighbours,
                                           float* variation, void* workspace, int64_t workspace_bytes, int32_t* status,
                                           void* stream) {
-    if (!points || !point_offsets || !normals || !workspace || !status) return GV_E_BADARG;
-    if (n <= 0 || total_points < 0 || max_points < 0 || k < 3 || k > 32 || grid_cells < 0 || grid_cells > MAX_G)
-        return GV_E_BADARG;
+    if (!normals || !status || k < 3 || k > 32) return GV_E_BADARG;
     if (orient != GV_NORMALS_ORIENT_NONE && orient != GV_NORMALS_ORIENT_OUTWARD && orient != GV_NORMALS_ORIENT_VIEWPOINT)
         return GV_E_BADARG;
     if (orient == GV_NORMALS_ORIENT_VIEWPOINT &&
         !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return GV_E_BADARG;
-    if (n > 65535 || max_points > MAX_CLOUD) return GV_E_UNSUPPORTED;
     const GridWs L = grid_ws_layout(n, total_points, grid_cells);
-    if (workspace_bytes < L.bytes) return GV_E_BADARG;
-    if (!gv_aligned16(workspace) || ((uintptr_t)point_offsets & 7u) ||
-        (((uintptr_t)points | (uintptr_t)normals | (uintptr_t)neighbours | (uintptr_t)variation | (uintptr_t)status) & 3u))
-        return GV_E_ALIGN;
+    const int rc0 = check_common(points, point_offsets, n, total_points, max_points, grid_cells, workspace, workspace_bytes, L.bytes);
+    if (rc0 != GV_OK) return rc0;
+    if (((uintptr_t)normals | (uintptr_t)neighbours | (uintptr_t)variation | (uintptr_t)status) & 3u) return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
     NArgs a;
     grid_args(a, points, point_offsets, n, total_points, grid_cells, workspace, L, status);
@@ -197,9 +174,7 @@ extern "C" int gv_points_estimate_normals(const float* points, const int64_t* po
     const int rc = build_grid(a, max_points, st);
     if (rc != GV_OK) return rc;
     const dim3 by_point(grid_x(max_points), (unsigned)n);
-    if (k <= 8) hipLaunchKernelGGL(query_kernel<8>, by_point, dim3(NT), 0, st, a);
-    else if (k <= 16) hipLaunchKernelGGL(query_kernel<16>, by_point, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(query_kernel<32>, by_point, dim3(NT), 0, st, a);
+    GV_LAUNCH_BY_K(query_kernel, k, by_point, st, a);
     GV_LAUNCH_CHECK();
     return GV_OK;
 }

@@ -1,7 +1,7 @@
 // point_register.hip — rigid point-to-point ICP for a batch of (source cloud, target cloud) pairs, entirely on the stream
 // (the contract is in include/gvcnn_hip.h, "points in", registration; tests/points_register_oracle.py restates it in
-// numpy).  The grid and the exact nearest walk are point_grid.h's; the sums are the cleaning's tree (aligned 256-blocks,
-// adjacent pairing, zeros for rejected pairs and past the end), several channels to a workgroup.
+// numpy).  The grid, the exact nearest walk and the call prologue are point_grid.h's; the tree sum (zeros for rejected
+// pairs), several channels to a workgroup, and the Jacobi rotation are point_math.h's, shared with the cleaning and the normals.
 //
 //   gv_points_register   build_grid x 2        the target's grid (it does not move: built once) and the source's (its
 //                                              status, and the cell order the nearest kernel visits the points in).
@@ -9,7 +9,7 @@
 //     per round          nearest_kernel        a thread per source point: moved by the pair's (R, t) in fp64, rounded
 //                                              once; ring_walk_from around the clamped cell in the TARGET's grid; the one
 //                                              smallest key (bits(d2) << 32 | id) in a register.
-//                        sum_kernel<8> x 3     count, sum p, sum y, sum d2 over the inliers (three levels of the tree).
+//                        sum_kernel<8> x 3     count, sum p, sum y, sum d2 over the inliers (tree_level<8>, three levels).
 //                        decide_kernel         a thread per pair: non-finite / few pairs / rmse / converged; centroids.
 //                        sum_kernel<9> x 3     H = sum (p - cp)(y - cy)^T about those centroids.
 //                        solve_kernel          a thread per pair: Horn's 4x4 matrix, cyclic Jacobi, quaternion -> (R, t).
@@ -20,11 +20,8 @@
 // atomics anywhere; nothing in a result depends on the grid, the batch or the schedule.
 #include "point_grid.h"
 
-#pragma clang fp contract(off)
-
 namespace {
 
-constexpr int TB = 256;                                          // leaves of one workgroup tree (= NT)
 constexpr int SWEEPS = 8;                                        // Jacobi sweeps of the 4x4 (contract)
 constexpr int C1 = 8, C2 = 9, CMAX = 9;                          // channels of the two passes
 
@@ -39,7 +36,7 @@ struct PairState {                                               // per pair
 struct RegWs {
     GridWs tgrid, sgrid;
     int64_t t0, s0;                                              // where the two grids start
-    int64_t state, init, sstatus, tstatus, match, d2, part1, part2, tot, plane, bytes;
+    int64_t state, init, sstatus, tstatus, match, d2, part1, part2, tot, bytes;
 };
 
 RegWs reg_layout(int32_t n, int64_t total_source, int64_t total_target, int32_t hint) {
@@ -54,10 +51,8 @@ RegWs reg_layout(int32_t n, int64_t total_source, int64_t total_target, int32_t 
     L.tstatus = L.sstatus + round16((int64_t)n * 4);
     L.match = L.tstatus + round16((int64_t)n * 4);
     L.d2 = L.match + round16(total_source * 4);
-    L.plane = total_source / TB + n + 2;                         // level-0 partials of one channel: cloud m from (v0 >> 8) + m
     L.part1 = L.d2 + round16(total_source * 4);
-    L.part2 = L.part1 + round16(L.plane * CMAX * 8);
-    L.tot = L.part2 + round16((int64_t)n * TB * CMAX * 8);
+    L.tot = tree_layout(L.part1, n, total_source, CMAX, L.part2);
     L.bytes = L.tot + round16((int64_t)n * CMAX * 8);
     return L;
 }
@@ -113,8 +108,8 @@ __global__ __launch_bounds__(NT) void nearest_kernel(RArgs a) {
     const CloudGrid g = a.t.grid[m];
     double T[12];
     for (int c = 0; c < 12; ++c) T[c] = ps.T[c];
-    const long long vs = a.s.poff[m] - a.s.poff[0], vt = a.t.poff[m] - a.t.poff[0];
-    const int P = (int)(a.s.poff[m + 1] - a.s.poff[m]);
+    const auto [vs, P] = cloud_span(a.s.poff, m);
+    const long long vt = cloud_span(a.t.poff, m).v0;
     bool bad = false;
     for (int s = blockIdx.x * NT + threadIdx.x; s < P; s += gridDim.x * NT) {
         // the cell order of the source at its ORIGINAL positions: a rigid motion keeps neighbours neighbours
@@ -144,12 +139,9 @@ __global__ __launch_bounds__(NT) void nearest_kernel(RArgs a) {
 }
 
 // ---- sums -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int blocks_of(int x) { return (x + TB - 1) / TB; }
-
-// the leaf values of source id i of pair m: zeros unless i is an inlier
+// the leaf values of source id i of pair m, written over the zeros x arrives with (tree_level): left alone unless i is an inlier
 template <int C>
 __device__ __forceinline__ void leaf(const RArgs& a, const PairState& ps, long long vs, long long vt, int i, double x[C]) {
-    for (int c = 0; c < C; ++c) x[c] = 0.0;
     const float d2 = a.d2[vs + i];
     if (!(d2 <= a.max_d2)) return;
     const float* p = a.s.pts + (vs + i) * 3;
@@ -172,45 +164,18 @@ __device__ __forceinline__ void leaf(const RArgs& a, const PairState& ps, long l
     }
 }
 
-// One level of the tree sums of pair m, C channels at once: aligned blocks of TB values, adjacent pairs level by level,
-// zeros past the end, one partial per block and channel.  level 0 reads the leaves, level 1 the partials of level 0,
-// level 2 those of level 1 (at most TB: one block) and writes the totals.
+// one level (point_math.h) of the tree sums of pair m over its source points, C channels at once
 template <int C>
 __global__ __launch_bounds__(TB) void sum_kernel(RArgs a, int level) {
-    __shared__ double sh[C][TB];
-    const int m = blockIdx.y, tid = threadIdx.x;
+    __shared__ double sh[C * TB];
+    const int m = blockIdx.y;
     const PairState& ps = a.state[m];
     if (ps.done) return;                                         // (uniform)
-    const long long vs = a.s.poff[m] - a.s.poff[0], vt = a.t.poff[m] - a.t.poff[0];
-    const int P = (int)(a.s.poff[m + 1] - a.s.poff[m]);
-    const int c1 = blocks_of(P), c2 = blocks_of(c1);
-    const int count = level == 0 ? P : level == 1 ? c1 : c2;
-    double* p1 = a.part1 + (vs >> 8) + m;                        // channel c: + c * plane
-    double* p2 = a.part2 + (long long)m * C * TB;                // channel c: + c * TB
-    for (int b = blockIdx.x; b < blocks_of(count); b += gridDim.x) {
-        const int idx = b * TB + tid;
-        double x[C];
-        for (int c = 0; c < C; ++c) x[c] = 0.0;
-        if (idx < count) {
-            if (level == 0) leaf<C>(a, ps, vs, vt, idx, x);
-            else
-                for (int c = 0; c < C; ++c) x[c] = level == 1 ? p1[c * a.plane + idx] : p2[c * TB + idx];
-        }
-        for (int c = 0; c < C; ++c) sh[c][tid] = x[c];
-        __syncthreads();
-        for (int stride = 1; stride < TB; stride <<= 1) {
-            if ((tid & (2 * stride - 1)) == 0)
-                for (int c = 0; c < C; ++c) sh[c][tid] = sh[c][tid] + sh[c][tid + stride];
-            __syncthreads();
-        }
-        if (tid < C) {
-            const double v = sh[tid][0];
-            if (level == 0) p1[tid * a.plane + b] = v;
-            else if (level == 1) p2[tid * TB + b] = v;
-            else a.tot[m * CMAX + tid] = v;
-        }
-        __syncthreads();
-    }
+    const CloudSpan sp = cloud_span(a.s.poff, m);
+    const long long vt = cloud_span(a.t.poff, m).v0;
+    tree_level<C>(
+        level, m, sp.v0, sp.P, a.part1, a.plane, a.part2, sh, [&](int i, double x[C]) { leaf<C>(a, ps, sp.v0, vt, i, x); },
+        [&](int c, double total) { a.tot[m * CMAX + c] = total; });
 }
 
 // ---- the round's decision -------------------------------------------------------------------------------------------
@@ -247,32 +212,25 @@ __global__ __launch_bounds__(NT) void decide_kernel(RArgs a, int round) {
 }
 
 // ---- Horn's closed form ---------------------------------------------------------------------------------------------
-// one Jacobi rotation of the pair (P, Q) of the symmetric 4x4 A (both triangles kept) and of V: the normals' formulas
+// one Jacobi rotation (point_math.h) of the pair (P, Q) of the symmetric 4x4 A (both triangles kept) and of V
 template <int P, int Q>
 __device__ __forceinline__ void rotate4(double (&A)[4][4], double (&V)[4][4]) {
     const double apq = A[P][Q];
     if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + __builtin_sqrt(theta * theta + 1.0));
-    const double c = 1.0 / __builtin_sqrt(t * t + 1.0);
-    const double s = t * c;
-    const double h = t * apq;
+    double c, s, h;
+    jacobi_csh(A[P][P], A[Q][Q], apq, c, s, h);
     A[P][P] = A[P][P] - h;
     A[Q][Q] = A[Q][Q] + h;
     A[P][Q] = A[Q][P] = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         if (r == P || r == Q) continue;
-        const double x = A[r][P], y = A[r][Q];
-        A[r][P] = A[P][r] = c * x - s * y;
-        A[r][Q] = A[Q][r] = s * x + c * y;
+        rotate_pair(c, s, A[r][P], A[r][Q]);
+        A[P][r] = A[r][P];
+        A[Q][r] = A[r][Q];
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double x = V[i][P], y = V[i][Q];
-        V[i][P] = c * x - s * y;
-        V[i][Q] = s * x + c * y;
-    }
+    for (int i = 0; i < 4; ++i) rotate_pair(c, s, V[i][P], V[i][Q]);
 }
 
 __global__ __launch_bounds__(NT) void solve_kernel(RArgs a) {
@@ -353,19 +311,14 @@ __global__ __launch_bounds__(NT) void finish_kernel(RArgs a) {
     a.status[m] = ps.byte | ps.flags;
 }
 
-__device__ __forceinline__ bool no_source(int st) {
-    return st == GV_RENDER_EMPTY || st == GV_RENDER_TOO_LARGE || st == GV_RENDER_BAD_OFFSETS;
-}
-
 __global__ __launch_bounds__(NT) void apply_kernel(RArgs a) {
     const int m = blockIdx.y;
-    if (no_source(a.s.grid[m].status)) return;                   // (its offsets cannot be trusted, or it has no points)
+    if (no_points(a.s.grid[m].status)) return;                   // (its offsets cannot be trusted, or it has no points)
     const PairState& ps = a.state[m];
     double T[12];
     for (int c = 0; c < 12; ++c) T[c] = ps.T[c];
     const bool matched = ps.used > 0 && !(ps.flags & GV_POINTS_ICP_NONFINITE);
-    const long long vs = a.s.poff[m] - a.s.poff[0];
-    const int P = (int)(a.s.poff[m + 1] - a.s.poff[m]);
+    const auto [vs, P] = cloud_span(a.s.poff, m);
     for (int i = blockIdx.x * NT + threadIdx.x; i < P; i += gridDim.x * NT) {
         const long long o = vs + i;
         float q[3];
@@ -389,9 +342,8 @@ __global__ __launch_bounds__(NT) void apply_kernel(RArgs a) {
 extern "C" void gv_points_register_set_cell_order(int on) { g_cell_order = on != 0; }
 
 extern "C" int64_t gv_points_register_workspace_bytes(int32_t n, int64_t total_source, int64_t total_target, int32_t grid_cells) {
-    if (n <= 0 || total_source < 0 || total_target < 0 || grid_cells < 0 || grid_cells > MAX_G) return GV_E_BADARG;
-    if (n > 65535) return GV_E_UNSUPPORTED;
-    return reg_layout(n, total_source, total_target, grid_cells).bytes;
+    const int rc = check_sizes(n, total_source, 0, grid_cells, total_target, 0);
+    return rc != GV_OK ? rc : reg_layout(n, total_source, total_target, grid_cells).bytes;
 }
 
 extern "C" int gv_points_register(const float* source, const int64_t* source_offsets, const float* target,
@@ -401,19 +353,16 @@ extern "C" int gv_points_register(const float* source, const int64_t* source_off
                                   double* transforms, double* rmse, int32_t* inliers, int32_t* used, int32_t* correspondence,
                                   float* moved, float* moved_normals, void* workspace, int64_t workspace_bytes,
                                   int32_t* status, void* stream) {
-    if (!source || !source_offsets || !target || !target_offsets || !transforms || !moved || !workspace || !status)
-        return GV_E_BADARG;
+    if (!target || !target_offsets || !transforms || !moved || !status) return GV_E_BADARG;
     if ((source_normals != nullptr) != (moved_normals != nullptr)) return GV_E_BADARG;
-    if (n <= 0 || total_source < 0 || total_target < 0 || max_source < 0 || max_target < 0 || iterations < 1 ||
-        !(max_distance >= 0.0f) || !(tolerance >= 0.0) || grid_cells < 0 || grid_cells > MAX_G)
-        return GV_E_BADARG;
-    if (n > 65535 || max_source > MAX_CLOUD || max_target > MAX_CLOUD) return GV_E_UNSUPPORTED;
+    if (iterations < 1 || !(max_distance >= 0.0f) || !(tolerance >= 0.0)) return GV_E_BADARG;
     const RegWs L = reg_layout(n, total_source, total_target, grid_cells);
-    if (workspace_bytes < L.bytes) return GV_E_BADARG;
-    if (!gv_aligned16(workspace) ||
-        (((uintptr_t)source_offsets | (uintptr_t)target_offsets | (uintptr_t)init | (uintptr_t)transforms | (uintptr_t)rmse) & 7u) ||
-        (((uintptr_t)source | (uintptr_t)target | (uintptr_t)source_normals | (uintptr_t)inliers | (uintptr_t)used |
-          (uintptr_t)correspondence | (uintptr_t)moved | (uintptr_t)moved_normals | (uintptr_t)status) & 3u))
+    const int rc0 = check_common(source, source_offsets, n, total_source, max_source, grid_cells, workspace, workspace_bytes, L.bytes,
+                                 target, target_offsets, total_target, max_target);
+    if (rc0 != GV_OK) return rc0;
+    if ((((uintptr_t)init | (uintptr_t)transforms | (uintptr_t)rmse) & 7u) ||
+        (((uintptr_t)source_normals | (uintptr_t)inliers | (uintptr_t)used | (uintptr_t)correspondence | (uintptr_t)moved |
+          (uintptr_t)moved_normals | (uintptr_t)status) & 3u))
         return GV_E_ALIGN;
     const hipStream_t st = (hipStream_t)stream;
     char* ws = static_cast<char*>(workspace);
@@ -428,7 +377,7 @@ extern "C" int gv_points_register(const float* source, const int64_t* source_off
     a.part1 = reinterpret_cast<double*>(ws + L.part1);
     a.part2 = reinterpret_cast<double*>(ws + L.part2);
     a.tot = reinterpret_cast<double*>(ws + L.tot);
-    a.plane = L.plane;
+    a.plane = tree_plane(n, total_source);
     a.max_d2 = max_distance * max_distance;
     a.tol = tolerance;
     a.cell_order = g_cell_order;
@@ -446,22 +395,16 @@ extern "C" int gv_points_register(const float* source, const int64_t* source_off
     rc = build_grid(a.s, max_source, st);
     if (rc != GV_OK) return rc;
     const dim3 by_pair((unsigned)((n + NT - 1) / NT)), by_point(grid_x(max_source), (unsigned)n);
-    const long long b1 = ((long long)max_source + TB - 1) / TB, b2 = (b1 + TB - 1) / TB;
-    const dim3 level0(grid_x(b1 * NT), (unsigned)n), level1(grid_x(b2 * NT), (unsigned)n), level2(1, (unsigned)n);
     hipLaunchKernelGGL(begin_kernel, by_pair, dim3(NT), 0, st, a);
     GV_LAUNCH_CHECK();
     for (int round = 1; round <= iterations; ++round) {
         hipLaunchKernelGGL(nearest_kernel, by_point, dim3(NT), 0, st, a);
         GV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sum_kernel<C1>, level0, dim3(TB), 0, st, a, 0);
-        hipLaunchKernelGGL(sum_kernel<C1>, level1, dim3(TB), 0, st, a, 1);
-        hipLaunchKernelGGL(sum_kernel<C1>, level2, dim3(TB), 0, st, a, 2);
+        launch_tree<sum_kernel<C1>>(n, max_source, st, a);
         GV_LAUNCH_CHECK();
         hipLaunchKernelGGL(decide_kernel, by_pair, dim3(NT), 0, st, a, round);
         GV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sum_kernel<C2>, level0, dim3(TB), 0, st, a, 0);
-        hipLaunchKernelGGL(sum_kernel<C2>, level1, dim3(TB), 0, st, a, 1);
-        hipLaunchKernelGGL(sum_kernel<C2>, level2, dim3(TB), 0, st, a, 2);
+        launch_tree<sum_kernel<C2>>(n, max_source, st, a);
         GV_LAUNCH_CHECK();
         hipLaunchKernelGGL(solve_kernel, by_pair, dim3(NT), 0, st, a);
         GV_LAUNCH_CHECK();

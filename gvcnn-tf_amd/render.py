@@ -481,10 +481,22 @@ NORMALS_ORIENT = {"none": _lib.GV_NORMALS_ORIENT_NONE, "outward": _lib.GV_NORMAL
                   "viewpoint": _lib.GV_NORMALS_ORIENT_VIEWPOINT}
 
 
-def _check_normals_k(k):
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not NORMALS_MIN_K <= k <= NORMALS_MAX_K:
-        raise ValueError("estimate_normals: k must be an integer in [%d, %d]" % (NORMALS_MIN_K, NORMALS_MAX_K))
+def _check_k(k, lo, hi, what):
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not lo <= k <= hi:
+        raise ValueError("%s: k must be an integer in [%d, %d]" % (what, lo, hi))
     return int(k)
+
+
+def _check_normals_k(k):
+    return _check_k(k, NORMALS_MIN_K, NORMALS_MAX_K, "estimate_normals")
+
+
+def _check_grid(grid, what):
+    if grid is None:
+        return 0
+    if isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not 1 <= grid <= NORMALS_MAX_GRID:
+        raise ValueError("%s: grid must be None (auto) or an integer in [1, %d]" % (what, NORMALS_MAX_GRID))
+    return int(grid)
 
 
 def _check_normals_args(k, orient, viewpoint, grid):
@@ -502,27 +514,15 @@ def _check_normals_args(k, orient, viewpoint, grid):
             raise ValueError("estimate_normals: viewpoint must be three finite numbers")
         if viewpoint.shape != (3,) or not np.isfinite(viewpoint).all():
             raise ValueError("estimate_normals: viewpoint must be three finite numbers")
-    if grid is None:
-        grid = 0
-    elif isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not 1 <= grid <= NORMALS_MAX_GRID:
-        raise ValueError("estimate_normals: grid must be None (auto) or an integer in [1, %d]" % NORMALS_MAX_GRID)
-    return k, NORMALS_ORIENT[orient], viewpoint, int(grid)
+    return k, NORMALS_ORIENT[orient], viewpoint, _check_grid(grid, "estimate_normals")
+
 
 CLEAN_MIN_K, CLEAN_MAX_K = 1, 32
 
 
-def _check_grid(grid, what):
-    if grid is None:
-        return 0
-    if isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not 1 <= grid <= NORMALS_MAX_GRID:
-        raise ValueError("%s: grid must be None (auto) or an integer in [1, %d]" % (what, NORMALS_MAX_GRID))
-    return int(grid)
-
-
 def _check_outlier_args(k, std_ratio, grid):
     """(k, std_ratio as float32, grid_cells) of remove_outliers, or ValueError."""
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not CLEAN_MIN_K <= k <= CLEAN_MAX_K:
-        raise ValueError("remove_outliers: k must be an integer in [%d, %d]" % (CLEAN_MIN_K, CLEAN_MAX_K))
+    k = _check_k(k, CLEAN_MIN_K, CLEAN_MAX_K, "remove_outliers")
     if isinstance(std_ratio, bool) or not isinstance(std_ratio, numbers.Real):
         raise ValueError("remove_outliers: std_ratio must be a finite number >= 0")
     with np.errstate(over="ignore"):
@@ -678,9 +678,7 @@ class PointBatch:
         rows = self.points.shape[0]
         total_s, total_t = int(self.point_offsets_host[-1]), int(target.point_offsets_host[-1])
         with torch.cuda.device(self.device):
-            ws_bytes = lib.gv_points_register_workspace_bytes(self.n, total_s, total_t, grid)
-            _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_register_workspace_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            ws, ws_bytes = self._workspace(lib, "gv_points_register_workspace_bytes", total_s, total_t, grid)
             transforms = torch.zeros((self.n, 4, 4), dtype=torch.float64, device=self.device)
             rmse = torch.zeros(self.n, dtype=torch.float64, device=self.device)
             inliers = torch.zeros(self.n, dtype=torch.int32, device=self.device)
@@ -756,11 +754,14 @@ class PointBatch:
         new.point_offsets = out_offsets
         return new, out_index
 
-    def _clean_workspace(self, lib, grid):
-        total = int(self.point_offsets_host[-1])
-        ws_bytes = lib.gv_points_clean_workspace_bytes(self.n, total, grid)
-        _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_clean_workspace_bytes")
+    def _workspace(self, lib, query, *sizes):
+        """(workspace, its bytes) as the size query `query` of the library asks for this batch: (n, *sizes)."""
+        ws_bytes = getattr(lib, query)(self.n, *sizes)
+        _lib.check(ws_bytes if ws_bytes < 0 else 0, query)
         return torch.empty(ws_bytes, dtype=torch.uint8, device=self.device), ws_bytes
+
+    def _clean_workspace(self, lib, grid):
+        return self._workspace(lib, "gv_points_clean_workspace_bytes", int(self.point_offsets_host[-1]), grid)
 
     def remove_outliers(self, k=16, std_ratio=2.0, grid=None, return_index=False, return_stats=False):
         """Statistical outlier removal on the device (contract: include/gvcnn_hip.h, "points in", cleaning): a point
@@ -832,9 +833,7 @@ class PointBatch:
         rows = self.points.shape[0]                              # sum P (1 for a batch without points)
         total = int(self.point_offsets_host[-1])
         with torch.cuda.device(self.device):
-            ws_bytes = lib.gv_points_normals_workspace_bytes(self.n, total, grid)
-            _lib.check(ws_bytes if ws_bytes < 0 else 0, "gv_points_normals_workspace_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            ws, ws_bytes = self._workspace(lib, "gv_points_normals_workspace_bytes", total, grid)
             normals = torch.zeros((rows, 3), dtype=torch.float32, device=self.device)
             nb = torch.full((rows, k), -1, dtype=torch.int32, device=self.device) if return_neighbors else None
             var = torch.zeros(rows, dtype=torch.float32, device=self.device) if return_variation else None

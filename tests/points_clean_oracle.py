@@ -40,6 +40,42 @@ def key_table(points, k):
     return out
 
 
+def line_cloud(P, seed):
+    """(points float32 [P, 3], perm): P points on the x axis whose k = 1 key table costs O(P) (line_key_table), for clouds
+    too large for key_table.  x: the cumulative sum of integer gaps in [1, 64) times 2^-8, exact in fp32 up to 2^24; the ids
+    are a random permutation of the line order: id t holds the perm[t]-th point of the line."""
+    rng = np.random.RandomState(seed)
+    steps = np.cumsum(rng.randint(1, 64, size=P).astype(np.int64))
+    assert steps[-1] < 1 << 24
+    perm = rng.permutation(P)
+    pts = np.zeros((P, 3), np.float32)
+    pts[:, 0] = (steps[perm].astype(np.float64) / 256.0).astype(np.float32)
+    return pts, perm
+
+
+def line_key_table(points, perm):
+    """key_table(points, 1) of a line_cloud from the two line neighbours of each point: a gap is at most 63 / 256, so d2 is
+    exact in fp32 and grows strictly with the distance along the line; a tie between the two goes to the lower id, as the
+    smaller key."""
+    x = np.ascontiguousarray(points, dtype=np.float32)[:, 0]
+    P = len(x)
+    ids = np.empty(P, np.int64)
+    ids[perm] = np.arange(P)                                       # ids[s]: the id of the s-th point of the line
+    xs = x[ids]
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    side = []
+    for nb, at in ((slice(0, P - 1), slice(1, P)), (slice(1, P), slice(0, P - 1))):    # the left, then the right neighbour
+        dx = xs[nb] - xs[at]
+        d2 = (dx * dx + np.float32(0.0)) + np.float32(0.0)
+        assert d2.dtype == np.float32
+        keys = np.full(P, none, np.uint64)
+        keys[at] = (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | ids[nb].astype(np.uint64)
+        side.append(keys)
+    out = np.empty((P, 1), np.uint64)
+    out[ids, 0] = np.minimum(side[0], side[1])
+    return out
+
+
 def mean_distances(keys):
     """m_i float64 [P]: (sqrt((double)d2_0) + ... ) / k_eff from 0.0, left to right in rank order."""
     P, keff = keys.shape

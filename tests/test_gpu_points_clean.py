@@ -127,6 +127,32 @@ def test_outlier_removal_equals_oracle(k, ratio):
         assert 1500 not in kept.tolist() and len(kept) >= 1400
 
 
+_large = {}
+
+
+def large_clouds():
+    """A cloud needs more than 65 536 points before level 1 of the tree sum has a second block and level 2 reads more
+    than one partial: 65 536 (one full level-1 block) and 65 537 (one value into the second), behind a small cloud so that
+    their first point is no multiple of 256.  Line clouds: the k = 1 table in O(P) (CO.line_key_table)."""
+    if not _large:
+        small = sized(300, 9)
+        lines = [CO.line_cloud(65536, 21), CO.line_cloud(65537, 22)]
+        _large["clouds"] = [small] + [pts for pts, _ in lines]
+        tables = [CO.key_table(small, 1)] + [CO.line_key_table(pts, perm) for pts, perm in lines]
+        _large["want"] = CO.remove_outliers(_large["clouds"], 1, 1.0, tables=tables)
+    return _large["clouds"], _large["want"]
+
+
+@pytest.mark.parametrize("grid", [None, 128])
+def test_outlier_removal_past_65536_points_equals_oracle(grid):
+    """the third level of the tree sum, and the scan and the gather past 256 blocks of a cloud"""
+    clouds, want = large_clouds()
+    got = device_outliers(clouds, 1, 1.0, grid=grid)
+    assert_same(got, want, OUTLIER_KEYS, "grid %s" % grid)
+    assert got["status"].tolist() == [0, 0, 0]
+    assert all(0.5 * len(c) < n < len(c) for c, n in zip(clouds, got["counts"].tolist()))       # some go, most stay
+
+
 VOXELS = {"rel_0.05": (0.05, True), "rel_0.25": (0.25, True), "rel_1.0": (1.0, True), "abs_0.3": (0.3, False),
           "per_cloud": (None, True)}
 

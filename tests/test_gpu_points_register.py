@@ -105,17 +105,22 @@ def oracle(case, lo=0, hi=len(ORDER)):
     return _want[key]
 
 
-def device_register(case, lo=0, hi=len(ORDER), grid=None, targets=None):
+def device_register_of(sources, normals, targets, init, case, grid=None):
     it, md, tol = case
-    src = R.PointBatch(list(zip(SOURCES[lo:hi], NORMALS[lo:hi])), DEV)
-    tgt = R.PointBatch(TARGETS[lo:hi] if targets is None else targets, DEV)
-    new, transforms, (rmse, inliers, used), corr = src.register(tgt, it, md, tol, INIT[lo:hi], grid, return_info=True,
+    src = R.PointBatch(list(zip(sources, normals)), DEV)
+    tgt = R.PointBatch(targets, DEV)
+    new, transforms, (rmse, inliers, used), corr = src.register(tgt, it, md, tol, init, grid, return_info=True,
                                                                 return_correspondence=True)
     total = int(src.point_offsets_host[-1])
     assert new.point_offsets_host.tolist() == src.point_offsets_host.tolist() and new.normal_status is None
     return {"transforms": host(transforms), "rmse": host(rmse), "inliers": host(inliers), "used": host(used),
             "correspondence": host(corr)[:total], "moved": host(new.points)[:total],
             "moved_normals": host(new.normals)[:total], "status": new.register_status.copy()}
+
+
+def device_register(case, lo=0, hi=len(ORDER), grid=None, targets=None):
+    return device_register_of(SOURCES[lo:hi], NORMALS[lo:hi], TARGETS[lo:hi] if targets is None else targets, INIT[lo:hi],
+                              case, grid)
 
 
 def assert_same(got, want, what=""):
@@ -159,6 +164,39 @@ def test_register_equals_oracle(case):
     Rm = got["transforms"][:, :3, :3]
     ok = np.array([k not in ("far",) for k in ORDER])
     assert np.abs(Rm[ok] @ Rm[ok].transpose(0, 2, 1) - np.eye(3)).max() < 1e-9 and (np.linalg.det(Rm[ok]) > 0.999).all()
+
+
+# Sources past 65 536 points: level 1 of the tree sums has a second block and level 2 reads more than one partial.  The
+# sums run over the source alone, so targets of 64 points keep the brute-force oracle quick; a small pair goes first so
+# that the large sources do not start at a multiple of 256.  LARGE_MD = 0.5 rejects some pairs and keeps most of the tree
+# busy: on the oracle the two large pairs have 29 674 / 30 860, 29 707 / 30 905 and 29 711 / 30 933 inliers in rounds 1 to 3.
+LARGE_MD = 0.5
+_large = {}
+
+
+def large_pairs():
+    if not _large:
+        small = sized(140, 40)
+        _large["sources"] = [posed(small, 8.0, (0.05, -0.03, 0.02), 40, 0.01, take=100), sized(65536, 41), sized(65537, 42)]
+        _large["targets"] = [small, sized(64, 43), sized(64, 44)]
+        _large["normals"] = [np.random.RandomState(80 + i).normal(size=s.shape).astype(F)
+                             for i, s in enumerate(_large["sources"])]
+    return _large["sources"], _large["normals"], _large["targets"]
+
+
+@pytest.mark.parametrize("md", [None, LARGE_MD])
+def test_register_past_65536_source_points_equals_oracle(md):
+    sources, normals, targets = large_pairs()
+    case = (3, md, 0.0)
+    want = RO.register(sources, targets, None, 3, md, 0.0, normals)
+    assert want["used"].tolist() == [3, 3, 3] and want["status"].tolist() == [0, 0, 0]
+    rounds = [RO.register(sources[1:], targets[1:], None, it, md, 0.0)["inliers"].tolist() for it in (1, 2)]
+    for inliers in rounds + [want["inliers"][1:].tolist()]:         # every round: some pairs rejected, never too few
+        for i in (0, 1):
+            assert (3 <= inliers[i] < len(sources[1 + i])) if md else (inliers[i] == len(sources[1 + i]))
+    if md:
+        assert rounds == [[29674, 30860], [29707, 30905]] and want["inliers"][1:].tolist() == [29711, 30933]
+    assert_same(device_register_of(sources, normals, targets, None, case), want, str(case))
 
 
 # ---- nothing but speed depends on the grid or the batch ----------------------------------------------------------------

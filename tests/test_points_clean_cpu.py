@@ -55,6 +55,15 @@ def test_key_table_is_the_brute_force_answer_without_self():
         assert ((keys[i] >> np.uint64(32)).astype(np.uint32).view(F) == d2[i, want]).all()
 
 
+def test_line_key_table_is_the_key_table_of_a_line_cloud():
+    """the O(P) table the device tests use past 65 536 points, against the brute-force one; equal gaps do occur (ties)"""
+    pts, perm = CO.line_cloud(300, 5)
+    want = CO.key_table(pts, 1)
+    assert CO.line_key_table(pts, perm).tobytes() == want.tobytes()
+    x = np.sort(pts[:, 0])
+    assert (pts[:, 1:] == 0).all() and len(np.unique(x)) == 300 and (np.diff(x)[1:] == np.diff(x)[:-1]).any()
+
+
 def test_mean_distances_against_float64_norms():
     pts = planted(400, 0, 7)
     m = CO.mean_distances(CO.key_table(pts, 8))
